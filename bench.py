@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- (user,item) pairs/s of the DeepCoNN review-encoder train step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
+
+A plain run sets up, runs W warm-up steps, times EXACTLY K steps, writes the outputs of the timed step when --dump-outputs
+is given (see below) and prints the headline line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+Everything else below -- the repeated-block statistics, the secondary variants, the HIP-event kernel pass, the rooflines,
+the forward-only rate, the other BASELINE configs and the CPU baseline -- is measured only with --full.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts its own ranks BEFORE touching the GPU: a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -13,15 +18,25 @@ documents per pair, 300-d embeddings, conv widths 3/5/7 x 50 channels, latent 32
 fp32, synthetic Zipf token ids (tests/golden/synth.py).  One step = the reference trainer's step
 (trainer/train_deepconn_pp.py:161-168): zero_grad -> forward -> MSELoss -> backward ->
 [N>1: RCCL gradient exchange] -> clip_grad_norm_(5.0) -> Adam(lr=2e-3).  Inputs are resident in
-HBM before the timed region.  Weak scaling: every rank processes its own 256 pairs.
+HBM before the timed region.  Weak scaling: every rank processes its own 256 pairs.  Parameters, batches and dropout draws are seeded:
+with the same arguments every run sees the same inputs.
 
 Timing.  The step is recorded into hipGraphs (train_step.GraphedTrainStep) and replayed.  Every step takes the next of
 --batches (default 4) DISTINCT resident batches; each batch sits in its own input slot of the step (one recorded graph per
 slot: a loader stages batch i + 1 into the next slot while slot i runs), so a step starts with no copy of its inputs.
 `copy_per_step` is the one-slot form of earlier rounds (one device-to-device copy into the single input block inside the
-timed region).  A timed block is EXACTLY --steps steps between
-barrier + synchronize on both sides, max over ranks; the block is repeated until >= 0.5 s of timed region and
-`ms_per_step` / `value` are the MEDIAN block (`ms_per_step_min`, `repeats` beside them).  Secondary results, same step:
+timed region).  The headline is ONE block of exactly --steps steps after --warmup steps, barrier + synchronize on both
+sides, max over ranks: `ms_per_step` = block / steps, `value` = pairs/s of that block.
+
+--dump-outputs DIR: after the timed block, parameters and optimizer state are put back to their (seeded) initial values and
+the timed path's step -- the same recorded graph, on the last timed step's batch -- runs once more; rank 0 writes what it
+handed back, `loss`, `grad_norm`, `pred`, and every parameter as its update left it (`param.<name>`; the 50 002 x 300 word
+table as `param.<name>.rows_sample`: 8192 rows picked by a fixed seed), float32 .npy files, about 11 MB in all.  Its inputs
+are identical in every run, so two runs agree to rounding.  The state the timed steps train is not: several gradient sums
+are float atomics, and Adam lets their rounding grow from step to step.
+
+--full only.  `median_block`: the headline's step from the initial model again, blocks of --steps steps repeated until
+>= 0.5 s of timed region, the MEDIAN block (`ms_per_step_min`, `repeats` beside it).  Secondary results, same step:
 `single_batch_replay` (one batch resident in the input block, no copy: round 1's number), `uniform_ids` (token ids
 uniform over the vocabulary) and `all_distinct` (every vocabulary entry occurs: distinct tokens = min(V, positions)),
 each with its distinct-token count -- the token-product conv's cost follows that count.
@@ -100,6 +115,37 @@ def build_model(cfg, device):
         m = DeepCoNNpp(cfg["U"], cfg["I"], cfg["V"], cfg["kz"], cfg["D"], cfg["H"], cfg["K"], cfg["L"], None, 0.5)
     m.load_state_dict(synth.deepconn_params(cfg, 0))
     return m.to(device)
+
+
+DUMP_TABLE_ROWS = 8192          # rows of a large parameter that --dump-outputs writes (fixed seed)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, last):
+    """--dump-outputs: the (loss, gnorm, pred) the dumped step returned and the parameters its update left, as float32
+    (float64 stays float64) .npy files in out_dir.  A parameter of more than 1 M elements (the word table) is written as
+    DUMP_TABLE_ROWS of its rows, chosen by a fixed seed; every other one whole."""
+    import numpy as np
+
+    def host(t):
+        a = torch.as_tensor(t).detach().cpu().numpy()
+        return a if a.dtype == np.float64 else a.astype(np.float32)
+
+    loss, gnorm, pred = last
+    arrays = {"loss": host(loss), "grad_norm": host(gnorm), "pred": host(pred)}
+    for name, p in model.named_parameters():
+        if p.numel() > (1 << 20) and p.dim() >= 2 and p.shape[0] > DUMP_TABLE_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(p.shape[0], DUMP_TABLE_ROWS, replace=False))
+            arrays[f"param.{name}.rows_sample"] = host(p.detach()[torch.from_numpy(rows).to(p.device)])
+        else:
+            arrays[f"param.{name}"] = host(p)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def batch_on(cfg, seed, device, ids="zipf"):
@@ -640,6 +686,12 @@ def main():
     ap.add_argument("--batches", type=int, default=4, help="distinct resident batches rotated through the step's input block")
     ap.add_argument("--one-slot", action="store_true",
                     help="record ONE step graph and copy every batch into its input block (the copy_per_step form) instead of one graph per resident batch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, run the timed step once more from the initial state on the last timed batch and write "
+                         "its outputs (loss, grad norm, predictions, updated parameters) as .npy files")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: repeated blocks, variants, kernel pass, rooflines, "
+                         "forward-only rate, the other BASELINE configs and the CPU baseline (the --no-* options below apply to it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="skip the single-batch / uniform-id / all-distinct secondary results")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from Python instead of replaying a hipGraph")
@@ -657,6 +709,8 @@ def main():
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the `configs` object (cfg2 in the bf16 class, NARRE cfg3 in both classes, D-ATT cfg4)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a))          # nothing above this line has initialised HIP
@@ -667,7 +721,16 @@ def main():
     if world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}")
     if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
+        msg = "bench.py needs an MI355X: the HIP path has no CPU fallback"
+        if world > 1:
+            # torch.distributed.run stops every rank as soon as one exits: each rank reports, then they meet on the CPU
+            print(msg, file=sys.stderr, flush=True)
+            import torch.distributed as dist
+            dist.init_process_group("gloo")
+            dist.barrier()
+            dist.destroy_process_group()
+            raise SystemExit(1)
+        raise SystemExit(msg)
 
     from review_based_recommender_amd import _lib
     from review_based_recommender_amd import functional as RF
@@ -683,6 +746,9 @@ def main():
     backend = os.environ.get("RBR_BENCH_BACKEND", "nccl")
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
+    # the dropout draws are keyed by the device generator's seed (functional._drop_rng), which torch otherwise picks at random
+    # per process: fixed here, so that the same arguments give the same outputs (--dump-outputs)
+    torch.manual_seed(rank)
     cfg = synth.DEEPCONN_CFGS[WORKLOAD]
 
     grad_sync = None
@@ -783,6 +849,57 @@ def main():
                     if torch.is_tensor(v):
                         v.zero_()
         torch.cuda.synchronize()
+
+    # The headline: --warmup steps, then exactly --steps steps in ONE block.
+    reset_model()
+    run = make_runner(batches)
+    for i in range(a.warmup):
+        run(i)
+    barrier()
+    t0 = time.perf_counter()
+    for i in range(a.steps):
+        run(i)
+    barrier()
+    step_s = max_over_ranks(time.perf_counter() - t0) / a.steps
+    if a.dump_outputs:
+        # What the timed path computes, from inputs that are the same in every run: the model trained by the W + N steps above
+        # is not (several gradient sums are float atomics, and Adam lets their rounding grow step after step), so the step is
+        # replayed once more, outside the timed region, from the initial parameters and optimizer state on the last timed
+        # step's batch.
+        reset_model()
+        last = run(a.steps - 1)
+        barrier()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, model, last)
+    head = {
+        "metric": "(user,item) pairs/sec, DeepCoNN train step (fwd+MSE+bwd+clip+Adam), bsz256 2x512tok",
+        "value": round(cfg["B"] * world / step_s, 1), "unit": "pairs/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(1e3 * step_s, 4), "timed_region_s": round(step_s * a.steps, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16" if precision == "bf16" else "f32", "data": "synthetic",
+        "ranks_seen": dist.get_world_size() if world > 1 else 1, "backend": dist.get_backend() if world > 1 else None,
+        "config": {"workload": "DeepCoNN cfg2: batch 256 pairs/GPU, 2x512-token docs, D=300, conv widths 3/5/7 x 50, "
+                               "latent 32, V=50002, fp32, Zipf ids", "global_batch": cfg["B"] * world,
+                   "parallelism": f"dp{world}", "launch": launch_note or (("hipGraph replay, one recorded step per resident input slot (no per-step input copy)"
+                                              if stepper.slots > 1 else "hipGraph replay") if use_graph else "eager"),
+                   "resident_batches": nb,
+                   "conv_arithmetic": {"f32": "f32 MFMA (v_mfma_f32_32x32x2_f32)",
+                                       "bf16x3": "f32 operands split exactly into 3 bf16 planes, 6 plane products per product on "
+                                                 "v_mfma_f32_32x32x16_bf16, f32 accumulate (f32-class accuracy: parity tests at 1e-4)",
+                                       "bf16x2": "2 bf16 planes, 3 plane products, f32 accumulate",
+                                       "bf16": "operands rounded to bf16, f32 accumulate (reduced precision)"}[precision],
+                   "optimizer": "torch clip_grad_norm_ + fused Adam" if a.torch_optim else
+                                "HipClipAdam (clip + Adam, 2 launches; word-table gradient in compact row form)",
+                   "grad_exchange": None if world == 1 else (exchange_note or f"RCCL all-reduce, {a.comm_dtype} wire format, before the clip")},
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     reset_model()
     headline = timed_blocks(make_runner(batches), max_repeats=2000)
@@ -892,33 +1009,18 @@ def main():
         flops = conv_fwd_flops(cfg)
         masks = torch.cat([args[2], args[3]])
         dense_mode = "textcnn_conv_fwd" in ksum
-        out = {
-            "metric": "(user,item) pairs/sec, DeepCoNN train step (fwd+MSE+bwd+clip+Adam), bsz256 2x512tok",
-            "value": round(cfg["B"] * world * a.steps / med, 1), "unit": "pairs/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(1e3 * med / a.steps, 4), "ms_per_step_min": round(1e3 * best / a.steps, 4),
-            "repeats": len(headline), "timed_region_s": round(sum(headline), 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16" if precision == "bf16" else "f32", "data": "synthetic",
-            "ranks_seen": dist.get_world_size() if world > 1 else 1, "backend": dist.get_backend() if world > 1 else None,
-            "config": {"workload": "DeepCoNN cfg2: batch 256 pairs/GPU, 2x512-token docs, D=300, conv widths 3/5/7 x 50, "
-                                   "latent 32, V=50002, fp32, Zipf ids", "global_batch": cfg["B"] * world,
-                       "parallelism": f"dp{world}", "launch": launch_note or (("hipGraph replay, one recorded step per resident input slot (no per-step input copy)"
-                                                  if stepper.slots > 1 else "hipGraph replay") if use_graph else "eager"),
-                       "resident_batches": nb,
-                       "conv_arithmetic": {"f32": "f32 MFMA (v_mfma_f32_32x32x2_f32)",
-                                           "bf16x3": "f32 operands split exactly into 3 bf16 planes, 6 plane products per product on "
-                                                     "v_mfma_f32_32x32x16_bf16, f32 accumulate (f32-class accuracy: parity tests at 1e-4)",
-                                           "bf16x2": "2 bf16 planes, 3 plane products, f32 accumulate",
-                                           "bf16": "operands rounded to bf16, f32 accumulate (reduced precision)"}[precision],
-                       "optimizer": "torch clip_grad_norm_ + fused Adam" if a.torch_optim else
-                                    "HipClipAdam (clip + Adam, 2 launches; word-table gradient in compact row form)",
-                       "grad_exchange": None if world == 1 else (exchange_note or f"RCCL all-reduce, {a.comm_dtype} wire format, before the clip")},
+        out = dict(head)
+        out.update({
+            "median_block": {"ms_per_step": round(1e3 * med / a.steps, 4), "ms_per_step_min": round(1e3 * best / a.steps, 4),
+                             "pairs_per_s": round(cfg["B"] * world * a.steps / med, 1), "repeats": len(headline),
+                             "timed_region_s": round(sum(headline), 3),
+                             "note": "the headline's step from the initial model again, blocks of --steps steps until >= 0.5 s, "
+                                     "median block"},
             "fwd_only_pairs_per_s": round(cfg["B"] / fwd_s, 1),
             "fwd_only_graph_pairs_per_s": None if fwd_graph_s is None else round(cfg["B"] / fwd_graph_s, 1),
             "kernels_ms": {k: round(v[1], 4) for k, v in ksum.items()},
             "kernel_timing": "HIP events around the C-ABI launches, eager pass over the same steps after the timed region",
-        }
+        })
         out.update(variants)
         ids_all = torch.cat([args[0], args[1]])
         n_distinct = int(torch.unique(ids_all[masks]).numel())

@@ -27,6 +27,18 @@ import torch.nn.functional as F
 Params = Mapping[str, torch.Tensor]
 
 
+def _pin_ieee_fp32() -> None:
+    """The oracle is IEEE fp32 arithmetic: a host or process setting that lets oneDNN run fp32 convolutions / matmuls in a
+    reduced-precision math mode (bf16, tf32) would move it by ~1e-3 and fail every fp32 tolerance that trusts it."""
+    for op in ("conv", "matmul", "rnn"):
+        backend = getattr(torch.backends.mkldnn, op, None)
+        if backend is not None and hasattr(backend, "fp32_precision"):
+            backend.fp32_precision = "ieee"
+
+
+_pin_ieee_fp32()
+
+
 # --------------------------------------------------------------------------- layers
 def word_embedding(table: torch.Tensor, ids: torch.Tensor, padding_idx: int = 0) -> torch.Tensor:
     """models/deepconn/layers.py:9-24 -- nn.Embedding(V, D, padding_idx=0) row gather.

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/r03; mkdir -p $O
 export TMPDIR=/tmp
 # 1. the driver's bench command, unprofiled: the line
-timeout -k 10 400 python bench.py > $O/bench_line.log 2>&1; tail -1 $O/bench_line.log > $O/r03_bench_line.json; echo "bench rc=$?"
+timeout -k 10 400 python bench.py --full > $O/bench_line.log 2>&1; tail -1 $O/bench_line.log > $O/r03_bench_line.json; echo "bench rc=$?"
 # 2. kernel stats of the same step
 rm -rf $O/ks; timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o r -- python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-variants > $O/ks.log 2>&1
 cp $(find $O/ks -name '*kernel_stats.csv' | head -1) $O/r03_bench_kernel_stats.csv 2>/dev/null; rm -rf $O/ks
@@ -20,7 +20,7 @@ for k in clip_adam grad_sqnorm g_times_w gather_pool dw_partial4 prod_gemm_b16 b
 done
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_TCC_HIT_sum_TCC_MISS_sum
 # 4. the bf16 class (BASELINE configs 3 and 5 name it)
-timeout -k 10 300 python bench.py --precision bf16 --no-cpu-baseline --no-variants > $O/bench_bf16.log 2>&1; tail -1 $O/bench_bf16.log > $O/r03_bench_line_bf16.json
+timeout -k 10 300 python bench.py --full --precision bf16 --no-cpu-baseline --no-variants > $O/bench_bf16.log 2>&1; tail -1 $O/bench_bf16.log > $O/r03_bench_line_bf16.json
 # 5. secondary models
 for m in narre datt siamese; do
   timeout -k 10 300 python tools/bench_models.py $m > $O/models_$m.log 2>&1; grep '^{' $O/models_$m.log | tail -1 > $O/r03_${m}_bench_line.json
