@@ -543,6 +543,19 @@ int rbr_dedup_rows(int32_t B, int32_t L, const int64_t* u_ids, const int64_t* i_
  * ADDED onto row first[r] and cleared, so the encoder's backward, which skips the blanked documents, sees the whole gradient. */
 int rbr_dedup_fold_rows(int32_t n_rows, int32_t H, const int64_t* first, float* d_rows, void* stream);
 
+/* ---- id-fed doc-split batch.  Replaces the reference's host collate of the doc split
+ *      (trainer/train_deepconn_pp.py:281-292, train_dual_att.py:273-280: LongTensor(u_docs / i_docs) + get_mask, utils.py:30-42)
+ *      with ONE launch over device-resident int32 tables: the documents of an example are meta.pkl's per-id documents
+ *      (preprocess/divide_and_create_example_doc.py:261-262), so the batch is fully determined by its ids.
+ *      docs_out [2B, L] int64: row r < B = user_docs[u_ids[r]], row B + r = item_docs[i_ids[r]] (stacked, user rows first);
+ *      masks_out [2B, L] = (docs_out != pad_token) or NULL; ids_out [2B] = the checked ids (u then i) or NULL.
+ *      An id outside [0, U) / [0, I) is never read: row `replace_id` (0 <= replace_id < min(U, I)) stands in for its document,
+ *      ids_out gets replace_id, and err (the int64[4] record of rbr_sanitize_ids) is updated with the same meaning (set 0 =
+ *      u_ids, set 1 = i_ids).  Tables are [U, L] / [I, L] int32.  No sync, static shapes: graph-capturable.          ---- */
+int rbr_doc_gather(int32_t B, int32_t L, const int64_t* u_ids, const int64_t* i_ids, const int32_t* user_docs, int32_t U,
+                   const int32_t* item_docs, int32_t I, int64_t pad_token, int64_t replace_id, int64_t* docs_out,
+                   uint8_t* masks_out, int64_t* ids_out, int64_t* err, void* stream);
+
 /* ---- NgramFeat arch="HierPooling" (deepconn/layers.py:62-98,110-114): pooled[doc,d] =
  *      max_l mean_{j<k} x[doc,l+j,d] over l in [0, L-k], x = mask * table[ids]; relu != 0 applies the
  *      trailing ReLU when there is no projection layer.  argmax[doc,d] = first maximising window start.

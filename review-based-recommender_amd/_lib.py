@@ -207,6 +207,8 @@ SIGNATURES = {
     "rbr_sanitize_ids": (C.c_int, [i32, C.POINTER(IdSet), C.c_void_p, c_stream]),
     "rbr_dedup_ws_bytes": (C.c_size_t, [i32, i32]),
     "rbr_dedup_rows": (C.c_int, [i32, i32, c_i64p, c_i64p, i32, i32, c_u8p, C.c_void_p, c_i64p, c_u8p, c_stream]),
+    "rbr_doc_gather": (C.c_int, [i32, i32, c_i64p, c_i64p, c_i32p, i32, c_i32p, i32, C.c_int64, C.c_int64, c_i64p, c_u8p, c_i64p,
+                                 c_i64p, c_stream]),
     "rbr_embedding_fwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, c_f32p, c_stream]),
     "rbr_embedding_bwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, i32, c_f32p, c_stream]),
     "rbr_hier_pool_fwd": (C.c_int, [i32, i32, i32, i32, c_i64p, c_u8p, c_f32p, i32, c_f32p, c_i32p, c_stream]),

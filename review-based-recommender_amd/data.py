@@ -107,17 +107,32 @@ def _rows(mapping, n, what):
 
 
 class DocDataset(torch.utils.data.Dataset):
-    """doc split (DeepCoNN / D-ATT): examples are [u_id, i_id, rating, u_doc, i_doc]."""
+    """doc split (DeepCoNN / D-ATT): examples are [u_id, i_id, rating, u_doc, i_doc].
 
-    def __init__(self, data_dir: str, set_name: str, with_ids: bool = True):
+    feed="docs" (the reference's): a batch carries its documents (collate_fn, train_deepconn_pp.py:281-292).
+    feed="ids": a batch is (u_ids int64, i_ids int64, ratings f32) -- also for the D-ATT split (with_ids=False), whose
+    documents are then gathered by id -- and the documents come from meta.pkl's per-id tables on the device
+    (DeviceDocCache.gather).  That is only the same batch when every example's documents ARE meta's documents for its ids
+    (preprocess/divide_and_create_example_doc.py:261-262 builds them so); the id feed checks it once, at load time, and
+    refuses a split that differs (ValueError naming the first such example)."""
+
+    FEEDS = ("docs", "ids")
+
+    def __init__(self, data_dir: str, set_name: str, with_ids: bool = True, feed: str = "docs"):
+        if feed not in self.FEEDS:
+            raise ValueError(f"feed must be one of {self.FEEDS}, got {feed!r}")
         meta = load_pickle(os.path.join(data_dir, "meta.pkl"))
         self.user_num, self.item_num = meta["user_num"], meta["item_num"]
         self.doc_len = meta["doc_len"]
         self.vocab_size = vocab_size_of(meta["indexlizer"])
         self.user_docs, self.item_docs = meta["user_docs"], meta["item_docs"]
         self.examples = load_pickle(os.path.join(data_dir, f"{set_name}_exmaples.pkl"))
+        self.set_name = set_name
         self.with_ids = with_ids
+        self.feed = feed
         self.validate_ranges()
+        if feed == "ids":
+            self.check_documents_match_meta()
 
     def validate_ranges(self) -> None:
         """Every token / user / item id of the split against its table, once at load time: the IndexError nn.Embedding
@@ -128,20 +143,40 @@ class DocDataset(torch.utils.data.Dataset):
         _check_range([e[3] for e in self.examples], self.vocab_size, "user document tokens")
         _check_range([e[4] for e in self.examples], self.vocab_size, "item document tokens")
 
+    def check_documents_match_meta(self) -> None:
+        """The id feed's precondition: example k's u_doc / i_doc equal meta's user_docs[u_id] / item_docs[i_id]."""
+        urows = _rows(self.user_docs, self.user_num, "user_docs")
+        irows = _rows(self.item_docs, self.item_num, "item_docs")
+        for k, e in enumerate(self.examples):
+            for side, rows, idx, doc in (("u_doc", urows, int(e[0]), e[3]), ("i_doc", irows, int(e[1]), e[4])):
+                if list(doc) != list(rows[idx]):
+                    which = "user_docs" if side == "u_doc" else "item_docs"
+                    raise ValueError(f"{self.set_name} example {k}: its {side} is not meta.pkl's {which}[{idx}], so the id feed "
+                                     "would train on other documents than the example's (use feed='docs')")
+
     def __len__(self):
         return len(self.examples)
 
     def __getitem__(self, i):
-        return self.examples[i][:5]
+        return self.examples[i][:3] if self.feed == "ids" else self.examples[i][:5]
 
     def collate_fn(self, batch):
-        """train_deepconn_pp.py:281-292 (with ids) / train_dual_att.py:273-280 (docs and ratings only)."""
+        """train_deepconn_pp.py:281-292 (with ids) / train_dual_att.py:273-280 (docs and ratings only); the id feed's batch
+        is id_collate_fn's."""
+        if self.feed == "ids":
+            return self.id_collate_fn(batch)
         u_ids, i_ids, ratings, u_docs, i_docs = zip(*batch)
         u_docs, i_docs = torch.LongTensor(u_docs), torch.LongTensor(i_docs)
         ratings = torch.FloatTensor(ratings)
         if not self.with_ids:
             return u_docs, i_docs, ratings
         return (u_docs, i_docs, get_mask(u_docs), get_mask(i_docs), torch.LongTensor(u_ids), torch.LongTensor(i_ids), ratings)
+
+    @staticmethod
+    def id_collate_fn(batch):
+        """(u_ids int64 [B], i_ids int64 [B], ratings f32 [B]) of examples (or their first three fields)."""
+        u_ids, i_ids, ratings = zip(*[e[:3] for e in batch])
+        return torch.LongTensor(u_ids), torch.LongTensor(i_ids), torch.FloatTensor(ratings)
 
 
 class ReviewDataset(torch.utils.data.Dataset):
@@ -183,10 +218,15 @@ class DeviceDocCache:
     """All user / item documents resident on the GPU, so a batch is a pair of id vectors gathered ON DEVICE
     instead of 2 x doc_len token ids per pair shipped from the DataLoader workers.
 
-    doc split: user_docs [U, L], item_docs [I, L];  review split: reviews [U, R, T] plus counterpart ids [U, R].
+    doc split: user_docs [U, L], item_docs [I, L] int32 (half the bytes of int64; every token was range-checked against the
+    vocabulary once, here, so a gathered batch needs no per-step token check); review split: reviews [U, R, T] plus
+    counterpart ids [U, R], int64.
     The reference trains on the examples' own copies (train_deepconn_pp.py:276); for the doc split those are
-    the same per-id documents, so gathering by id is equivalent.  (For NARRE's train split the reference blanks
-    the target review inside each example, divide_and_create_example_word.py:262-288 -- use the examples there.)"""
+    the same per-id documents (DocDataset.check_documents_match_meta), so gathering by id is equivalent.  (For NARRE's train
+    split the reference blanks the target review inside each example, divide_and_create_example_word.py:262-288 -- use the
+    examples there.)"""
+
+    PAD = 0          # get_mask's padding id (utils.py:30-42)
 
     def __init__(self, ds, device):
         self.device = torch.device(device)
@@ -196,17 +236,70 @@ class DeviceDocCache:
             self.user_rids = torch.tensor(_rows(ds.user_rids, ds.user_num, "user_rids"), dtype=torch.int64, device=self.device)
             self.item_rids = torch.tensor(_rows(ds.item_rids, ds.item_num, "item_rids"), dtype=torch.int64, device=self.device)
         else:
-            self.user = torch.tensor(_rows(ds.user_docs, ds.user_num, "user_docs"), dtype=torch.int64, device=self.device)
-            self.item = torch.tensor(_rows(ds.item_docs, ds.item_num, "item_docs"), dtype=torch.int64, device=self.device)
+            user = torch.tensor(_rows(ds.user_docs, ds.user_num, "user_docs"), dtype=torch.int64)
+            item = torch.tensor(_rows(ds.item_docs, ds.item_num, "item_docs"), dtype=torch.int64)
+            _check_range(user, ds.vocab_size, "meta.pkl user_docs tokens")
+            _check_range(item, ds.vocab_size, "meta.pkl item_docs tokens")
+            self.user = user.to(torch.int32).to(self.device)
+            self.item = item.to(torch.int32).to(self.device)
             self.user_rids = self.item_rids = None
+            self.doc_len = self.user.shape[1]
+
+    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None, masks: bool = True, ids: bool = True):
+        """The documents of the pairs (u_ids[b], i_ids[b]) on the device (functional.doc_gather, one launch): stacked
+        (docs [2B, L] int64, masks [2B, L] bool or None, ids [2B] int64 or None), user rows first.  `out`: a doc-fed batch to
+        write into instead -- (u_docs, i_docs) or (u_docs, i_docs, u_masks, i_masks, u_ids, i_ids), each pair adjacent in one
+        allocation (the input views of a recorded step); its length decides masks / ids.  An id outside its table gets the
+        all-pad row 0 and an IndexError at functional.check_id_errors()."""
+        from . import functional as RF
+        if self.user_rids is not None:
+            raise RuntimeError("gather is the doc split's id feed (the review split's examples are not per-id data)")
+        u_ids = u_ids.to(self.device, non_blocking=True)
+        i_ids = i_ids.to(self.device, non_blocking=True)
+        if out is None:
+            return RF.doc_gather(u_ids, i_ids, self.user, self.item, self.PAD, 0, masks=masks, ids=ids)
+        if len(out) not in (2, 6):
+            raise RuntimeError("out must be (u_docs, i_docs) or (u_docs, i_docs, u_masks, i_masks, u_ids, i_ids)")
+        stacked = [_adjacent(out[k], out[k + 1]) for k in range(0, len(out), 2)] + [None, None]
+        return RF.doc_gather(u_ids, i_ids, self.user, self.item, self.PAD, 0, docs=stacked[0], masks=stacked[1], ids=stacked[2])
+
+    def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
+        """The model's doc-fed arguments for the pairs: (u_docs, i_docs, u_masks, i_masks, u_ids, i_ids) for DeepCoNN++, or
+        (u_docs, i_docs) for D-ATT (with_ids=False) -- views of one gather."""
+        B = u_ids.shape[0]
+        docs, masks, ids = self.gather(u_ids, i_ids, masks=with_ids, ids=with_ids)
+        if not with_ids:
+            return docs[:B], docs[B:]
+        return docs[:B], docs[B:], masks[:B], masks[B:], ids[:B], ids[B:]
+
+    def empty_inputs(self, B: int, with_ids: bool = True):
+        """Zeroed tensors of inputs()' shapes and dtypes for B pairs (what a recorded step lays its input block out by)."""
+        L = self.user.shape[1]
+        docs = [torch.zeros(B, L, dtype=torch.int64, device=self.device) for _ in range(2)]
+        if not with_ids:
+            return tuple(docs)
+        masks = [torch.zeros(B, L, dtype=torch.bool, device=self.device) for _ in range(2)]
+        ids = [torch.zeros(B, dtype=torch.int64, device=self.device) for _ in range(2)]
+        return (*docs, *masks, *ids)
 
     def doc_batch(self, u_ids: torch.Tensor, i_ids: torch.Tensor):
-        u_ids, i_ids = u_ids.to(self.device), i_ids.to(self.device)
-        u_docs, i_docs = self.user.index_select(0, u_ids), self.item.index_select(0, i_ids)
-        return u_docs, i_docs, get_mask(u_docs), get_mask(i_docs), u_ids, i_ids
+        if self.device.type != "cuda":
+            u_ids, i_ids = u_ids.to(self.device), i_ids.to(self.device)
+            u_docs, i_docs = self.user.index_select(0, u_ids).long(), self.item.index_select(0, i_ids).long()
+            return u_docs, i_docs, get_mask(u_docs), get_mask(i_docs), u_ids, i_ids
+        return self.inputs(u_ids, i_ids, with_ids=True)
 
     def review_batch(self, u_ids: torch.Tensor, i_ids: torch.Tensor):
         u_ids, i_ids = u_ids.to(self.device), i_ids.to(self.device)
         u, i = self.user.index_select(0, u_ids), self.item.index_select(0, i_ids)
         return (u, i, get_mask(u), get_mask(i), u_ids, i_ids, self.user_rids.index_select(0, u_ids),
                 self.item_rids.index_select(0, i_ids))
+
+
+def _adjacent(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """[a; b] as ONE view when b directly follows a in the same allocation (a write through it lands in a and b)."""
+    if not (a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype and a.shape == b.shape and a.device == b.device
+            and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+            and b.storage_offset() == a.storage_offset() + a.numel()):
+        raise RuntimeError("the output pair must be adjacent halves of one allocation (see train_step._flat_layout)")
+    return a.as_strided((2 * a.shape[0], *a.shape[1:]), a.stride(), a.storage_offset())

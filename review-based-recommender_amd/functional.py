@@ -148,6 +148,49 @@ def dedup_rows(u_ids: torch.Tensor, i_ids: torch.Tensor, user_size: int, item_si
     return first, out.view(torch.bool)
 
 
+def doc_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_docs: torch.Tensor, item_docs: torch.Tensor, pad_token: int = 0,
+               replace_id: int = 0, docs: Optional[torch.Tensor] = None, masks=True, ids=True):
+    """The id-fed doc-split batch (rbr_doc_gather, one launch): returns (docs2 [2B, L] int64, masks2 [2B, L] bool or None,
+    ids2 [2B] int64 or None), user rows first -- docs2[:B] / docs2[B:] are the u_docs / i_docs that DocDataset.collate_fn builds
+    for the same ids, masks2 = docs2 != pad_token, ids2 the checked ids.  user_docs / item_docs: [U, L] / [I, L] int32 tables.
+
+    An id outside its table reads row `replace_id` instead (the all-pad row 0 of meta.pkl's tables) and is recorded like
+    sanitize_ids() records it: check_id_errors() raises nn.Embedding's IndexError at the caller's next synchronisation point.
+    (The doc-fed path keeps the document the caller sent for a bad id; here no document exists for it.)
+
+    `docs` / `masks` / `ids`: stacked output tensors to write into (a recorded step's input views), True to allocate, or
+    None / False to leave out (masks / ids; D-ATT takes the documents only).  No autograd, no sync: graph-capturable."""
+    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
+        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+    B, L = u_ids.shape[0], user_docs.shape[1]
+    if user_docs.dim() != 2 or item_docs.dim() != 2 or item_docs.shape[1] != L:
+        raise RuntimeError(f"tables must be [U, L] / [I, L], got {tuple(user_docs.shape)} / {tuple(item_docs.shape)}")
+    dev = u_ids.device
+    if docs is None:
+        docs = torch.empty(2 * B, L, dtype=I64, device=dev)
+    if masks is True:
+        masks = torch.empty(2 * B, L, dtype=torch.bool, device=dev)
+    elif masks is False:
+        masks = None
+    if ids is True:
+        ids = torch.empty(2 * B, dtype=I64, device=dev)
+    elif ids is False:
+        ids = None
+    if docs.shape != (2 * B, L) or (masks is not None and masks.shape != (2 * B, L)) or (ids is not None and ids.shape != (2 * B,)):
+        raise RuntimeError(f"outputs must be docs [{2 * B}, {L}], masks [{2 * B}, {L}], ids [{2 * B}]")
+    if masks is not None and masks.dtype != torch.bool:
+        raise RuntimeError(f"masks must be bool, got {masks.dtype}")
+    if B == 0:
+        return docs, masks, ids
+    check(_lib.lib().rbr_doc_gather(B, L, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),
+                                    dev_ptr(user_docs, I32, "user_docs"), user_docs.shape[0],
+                                    dev_ptr(item_docs, I32, "item_docs"), item_docs.shape[0], int(pad_token), int(replace_id),
+                                    dev_ptr(docs, I64, "docs"), dev_ptr(None if masks is None else masks.view(U8), U8, "masks"),
+                                    dev_ptr(ids, I64, "ids"),
+                                    _id_err(dev).data_ptr(), current_stream()), "rbr_doc_gather")
+    return docs, masks, ids
+
+
 def set_tap_sink(sink, table: Optional[torch.Tensor] = None) -> None:
     """Installs `sink` for the word table it exchanges (sink.table); set_tap_sink(None, table) removes that table's sink,
     set_tap_sink(None) removes all of them."""

@@ -333,13 +333,26 @@ class GraphedForward:
     fixed batch shape (the trainers' validation loops, trainer/train_deepconn_pp.py:171-196: ~25 short kernels whose eager
     launches leave the GPU waiting on Python).  The model's train/eval mode at construction is what the graph holds -- put
     the model in eval() first.  __call__ copies a batch of the same shapes into the static input block (one copy when it was
-    pack()ed) and replays; the returned prediction tensor is static: overwritten by the next replay."""
+    pack()ed) and replays; the returned prediction tensor is static: overwritten by the next replay.
 
-    def __init__(self, model: nn.Module, batch, warmup: int = 2, capture_error_mode: str = "global"):
+    `feed` (a data.DeviceDocCache; from_ids()): the batch is (u_ids, i_ids) and the graph starts with the gather of their
+    documents into the model's input block (with_ids=False: documents only, D-ATT's forward)."""
+
+    def __init__(self, model: nn.Module, batch, warmup: int = 2, capture_error_mode: str = "global", feed=None,
+                 with_ids: bool = True):
         batch = list(batch)
         if not batch or not batch[0].is_cuda:
             raise RuntimeError("GraphedForward needs HIP tensors")
         self.model = model
+        self._feed, self._with_ids = feed, with_ids
+        self.ids = None
+        if feed is not None:
+            self._id_layout = _flat_layout(batch)
+            self._id_flat = torch.empty(self._id_layout[-1], dtype=torch.uint8, device=batch[0].device)
+            self.ids = tuple(_flat_views(self._id_flat, self._id_layout, batch))
+            for v, src in zip(self.ids, batch):
+                v.copy_(src)
+            batch = list(feed.empty_inputs(batch[0].shape[0], with_ids))
         self._layout = _flat_layout(batch)
         self._flat = torch.empty(self._layout[-1], dtype=torch.uint8, device=batch[0].device)
         views = _flat_views(self._flat, self._layout, batch)
@@ -350,6 +363,7 @@ class GraphedForward:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():      # warm-up off the default stream (allocator, lazy module state)
             for _ in range(warmup):
+                self._prologue()
                 model(*self.batch)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
@@ -357,28 +371,44 @@ class GraphedForward:
         self._capture_stream = _capture_stream(batch[0].device)
         with torch.no_grad(), _lib_mod().capture_guard(self._capture_stream), \
                 torch.cuda.graph(self.graph, stream=self._capture_stream, capture_error_mode=capture_error_mode):
+            self._prologue()
             out = model(*self.batch)
         self.pred = out[0] if isinstance(out, tuple) else out
 
+    @classmethod
+    def from_ids(cls, model: nn.Module, cache, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True, **kw):
+        """The id-fed forward: replays gather (cache.gather) + model; __call__((u_ids, i_ids))."""
+        return cls(model, (u_ids, i_ids), feed=cache, with_ids=with_ids, **kw)
+
+    def _prologue(self):
+        if self._feed is not None:
+            self._feed.gather(self.ids[0], self.ids[1], out=self.batch)
+
+    def _inputs(self):
+        return (self.ids, self._id_flat, self._id_layout) if self._feed is not None else (self.batch, self._flat, self._layout)
+
     def matches(self, batch) -> bool:
         """True when `batch` has the shapes and dtypes the graph was recorded with (a ragged last batch does not)."""
-        return len(batch) == len(self.batch) and all(a.shape == b.shape and a.dtype == b.dtype for a, b in zip(batch, self.batch))
+        ref = self._inputs()[0]
+        return len(batch) == len(ref) and all(a.shape == b.shape and a.dtype == b.dtype for a, b in zip(batch, ref))
 
     def pack(self, batch) -> torch.Tensor:
-        blob = torch.empty_like(self._flat)
-        for v, src in zip(_flat_views(blob, self._layout, list(batch)), batch):
+        _, flat, layout = self._inputs()
+        blob = torch.empty_like(flat)
+        for v, src in zip(_flat_views(blob, layout, list(batch)), batch):
             v.copy_(src)
         return blob
 
     def __call__(self, batch=None, packed: torch.Tensor | None = None) -> torch.Tensor:
+        dsts, flat, _ = self._inputs()
         if packed is not None:
-            if packed.shape != self._flat.shape or packed.dtype != torch.uint8:
+            if packed.shape != flat.shape or packed.dtype != torch.uint8:
                 raise RuntimeError("packed batch does not match the forward's input layout (use GraphedForward.pack)")
-            self._flat.copy_(packed, non_blocking=True)
+            flat.copy_(packed, non_blocking=True)
         if batch is not None:
             if not self.matches(batch):
                 raise RuntimeError("batch shapes differ from the recorded forward's (run ragged batches eagerly)")
-            for dst, src in zip(self.batch, batch):
+            for dst, src in zip(dsts, batch):
                 if dst is not src:
                     dst.copy_(src, non_blocking=True)
         self.graph.replay()
@@ -407,7 +437,7 @@ def _count_kernel_nodes(graph: torch.cuda.CUDAGraph) -> int:
 
 class _StepSlot:
     """One input block of a GraphedTrainStep and the graph(s) recorded over it."""
-    __slots__ = ("flat", "batch", "ratings", "g_fwd_bwd", "g_update", "static_grads", "loss", "gnorm", "pred")
+    __slots__ = ("flat", "batch", "ratings", "ids", "id_flat", "g_fwd_bwd", "g_update", "static_grads", "loss", "gnorm", "pred")
 
 
 class GraphedTrainStep:
@@ -425,28 +455,50 @@ class GraphedTrainStep:
     and the step itself starts with no device-to-device copy of its inputs (`__call__(slot=k)`).  Parameters,
     optimizer state and the optimizer's own buffers are shared by the slots; every slot keeps its own graph memory.
 
-    The optimizer must have been built with make_optimizer(..., capturable=True)."""
+    The optimizer must have been built with make_optimizer(..., capturable=True).
+
+    `feed` (a data.DeviceDocCache; from_ids()): the id-fed step.  `batch` is then (u_ids, i_ids); a slot stages only
+    (u_ids, i_ids, ratings) -- one small block, `stage` / `slot_inputs` -- and its graph starts with the gather of the
+    documents into the slot's document block (cache.gather: documents, masks and checked ids for DeepCoNN++; documents
+    only with with_ids=False, D-ATT), followed by the unchanged step."""
 
     def __init__(self, model: nn.Module, optimizer: torch.optim.Optimizer, batch, ratings: torch.Tensor,
                  max_grad_norm: float = MAX_GRAD_NORM, grad_sync=None, warmup: int = 3, capture_error_mode: str | None = None,
-                 slots: int = 1, keep_graph: bool = False):
+                 slots: int = 1, keep_graph: bool = False, feed=None, with_ids: bool = True):
         if not ratings.is_cuda:
             raise RuntimeError("GraphedTrainStep needs HIP tensors")
         if slots < 1:
             raise ValueError("slots must be >= 1")
         self.model, self.optimizer, self.grad_sync, self.max_grad_norm = model, optimizer, grad_sync, max_grad_norm
         self._keep_graph = bool(keep_graph)      # keeps the hipGraph_t behind the executable: kernel_launches() can count its nodes
+        self._feed, self._with_ids = feed, with_ids
+        id_block = None
+        if feed is not None:          # the loader's block is (u_ids, i_ids, ratings); the documents are gathered on the device
+            id_block = list(batch) + [ratings]
+            self._id_layout = _flat_layout(id_block)
+            inputs = list(feed.empty_inputs(batch[0].shape[0], with_ids))
+        else:
+            inputs = list(batch) + [ratings]
         # every input of the step lives in ONE block (`flat`): a loader hands over a batch with a single device-to-device
         # (or host-to-device) copy, and the two towers' inputs are neighbours, so the models stack them as a view
-        self._layout = _flat_layout(list(batch) + [ratings])
+        self._layout = _flat_layout(inputs)
         self._slots = []
         for _ in range(slots):
             sl = _StepSlot()
             sl.flat = torch.empty(self._layout[-1], dtype=torch.uint8, device=ratings.device)
-            views = _flat_views(sl.flat, self._layout, list(batch) + [ratings])
-            for v, src in zip(views, list(batch) + [ratings]):
+            views = _flat_views(sl.flat, self._layout, inputs)
+            for v, src in zip(views, inputs):
                 v.copy_(src)
-            sl.batch, sl.ratings = tuple(views[:-1]), views[-1]
+            if id_block is None:
+                sl.batch, sl.ratings = tuple(views[:-1]), views[-1]
+                sl.ids = sl.id_flat = None
+            else:
+                sl.batch = tuple(views)
+                sl.id_flat = torch.empty(self._id_layout[-1], dtype=torch.uint8, device=ratings.device)
+                idv = _flat_views(sl.id_flat, self._id_layout, id_block)
+                for v, src in zip(idv, id_block):
+                    v.copy_(src)
+                sl.ids, sl.ratings = tuple(idv[:-1]), idv[-1]
             sl.g_update = sl.static_grads = None
             self._slots.append(sl)
         first = self._slots[0]
@@ -459,6 +511,7 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):      # warm-up off the default stream: allocator, lazy optimizer state, occupancy queries
             for _ in range(warmup):
+                self._prologue(first)
                 train_step(model, optimizer, first.batch, first.ratings, max_grad_norm, grad_sync)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
@@ -472,10 +525,12 @@ class GraphedTrainStep:
             sl.g_fwd_bwd = torch.cuda.CUDAGraph(keep_graph=True) if self._keep_graph else torch.cuda.CUDAGraph()
             if grad_sync is None:
                 with _lib_mod().capture_guard(cs), torch.cuda.graph(sl.g_fwd_bwd, stream=cs, capture_error_mode=mode):
+                    self._prologue(sl)
                     sl.loss, sl.gnorm, sl.pred = train_step(model, optimizer, sl.batch, sl.ratings, max_grad_norm)
                 sl.static_grads = [(p, p.grad) for p in model.parameters()]
             else:
                 with _lib_mod().capture_guard(cs), torch.cuda.graph(sl.g_fwd_bwd, stream=cs, capture_error_mode=mode):
+                    self._prologue(sl)
                     optimizer.zero_grad()
                     pred, loss = _forward_loss_backward(model, sl.batch, sl.ratings)
                     sl.loss, sl.pred = loss.detach(), pred.detach()
@@ -498,6 +553,18 @@ class GraphedTrainStep:
         if self._slots[-1].static_grads is not None:
             for p, g in first.static_grads:
                 p.grad = g
+
+    @classmethod
+    def from_ids(cls, model: nn.Module, optimizer: torch.optim.Optimizer, cache, u_ids: torch.Tensor, i_ids: torch.Tensor,
+                 ratings: torch.Tensor, max_grad_norm: float = MAX_GRAD_NORM, grad_sync=None, with_ids: bool = True, **kw):
+        """The id-fed step over `cache` (data.DeviceDocCache): each replay gathers the staged ids' documents, then steps.
+        with_ids=False: the model takes (u_docs, i_docs) only (D-ATT)."""
+        return cls(model, optimizer, (u_ids, i_ids), ratings, max_grad_norm, grad_sync, feed=cache, with_ids=with_ids, **kw)
+
+    def _prologue(self, sl) -> None:
+        """What a slot's graph runs in front of the step: the id feed's gather (nothing without a feed)."""
+        if self._feed is not None:
+            self._feed.gather(sl.ids[0], sl.ids[1], out=sl.batch)
 
     # slot 0 under the names the one-slot step has always had
     batch = property(lambda self: self._slots[0].batch)
@@ -523,27 +590,57 @@ class GraphedTrainStep:
             return None
 
     def slot_inputs(self, slot: int = 0):
-        """(batch views, ratings view, the whole block as uint8) of input slot `slot`: what a loader writes into."""
+        """(batch views, ratings view, the whole block as uint8) of input slot `slot`: what a loader writes into.  With an id
+        feed: ((u_ids, i_ids) views, ratings view, the id block) -- slot_batch() has the gathered documents."""
         sl = self._slots[slot]
+        if self._feed is not None:
+            return sl.ids, sl.ratings, sl.id_flat
         return sl.batch, sl.ratings, sl.flat
+
+    def slot_batch(self, slot: int = 0):
+        """The model's input views of slot `slot` (with an id feed: what the recorded gather writes)."""
+        return self._slots[slot].batch
 
     def pack(self, batch, ratings: torch.Tensor) -> torch.Tensor:
         """`batch` + `ratings` as one block in the layout of the step's input buffers (what a loader would stage on the
-        device); hand it to __call__(packed=...)."""
-        blob = torch.empty_like(self._slots[0].flat)
-        for v, src in zip(_flat_views(blob, self._layout, list(batch) + [ratings]), list(batch) + [ratings]):
+        device); hand it to __call__(packed=...).  With an id feed `batch` is (u_ids, i_ids) and the block is the id block."""
+        flat, layout = (self._slots[0].id_flat, self._id_layout) if self._feed is not None else (self._slots[0].flat, self._layout)
+        blob = torch.empty_like(flat)
+        for v, src in zip(_flat_views(blob, layout, list(batch) + [ratings]), list(batch) + [ratings]):
             v.copy_(src)
         return blob
 
     def stage(self, slot: int, batch=None, ratings: torch.Tensor | None = None, packed: torch.Tensor | None = None) -> None:
-        """Copies a batch into input slot `slot` on the current stream (no replay)."""
+        """Copies a batch into input slot `slot` on the current stream (no replay).  With an id feed `batch` is (u_ids, i_ids):
+        host tensors together with host ratings go over in ONE host-to-device copy of the id block."""
         sl = self._slots[slot]
+        if self._feed is not None:
+            return self._stage_ids(sl, batch, ratings, packed)
         if packed is not None:
             if packed.shape != sl.flat.shape or packed.dtype != torch.uint8:
                 raise RuntimeError("packed batch does not match the step's input layout (use GraphedTrainStep.pack)")
             sl.flat.copy_(packed, non_blocking=True)      # one copy launch for all inputs
         if batch is not None:
             for dst, src in zip(sl.batch, batch):
+                if dst is not src:
+                    dst.copy_(src, non_blocking=True)
+        if ratings is not None and ratings is not sl.ratings:
+            sl.ratings.copy_(ratings, non_blocking=True)
+
+    def _stage_ids(self, sl, batch, ratings, packed) -> None:
+        if packed is not None:
+            if packed.shape != sl.id_flat.shape or packed.dtype != torch.uint8:
+                raise RuntimeError("packed ids do not match the step's id block (use GraphedTrainStep.pack)")
+            sl.id_flat.copy_(packed, non_blocking=True)
+        if batch is not None and ratings is not None and not ratings.is_cuda and not any(t.is_cuda for t in batch):
+            blob = torch.empty(sl.id_flat.shape, dtype=torch.uint8)       # packed on the host: one copy
+            srcs = list(batch) + [ratings]
+            for v, src in zip(_flat_views(blob, self._id_layout, srcs), srcs):
+                v.copy_(src)
+            sl.id_flat.copy_(blob, non_blocking=True)
+            return
+        if batch is not None:
+            for dst, src in zip(sl.ids, batch):
                 if dst is not src:
                     dst.copy_(src, non_blocking=True)
         if ratings is not None and ratings is not sl.ratings:

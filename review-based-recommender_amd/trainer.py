@@ -19,7 +19,9 @@ GLOBAL batch, split evenly over the ranks (train_deepconn_pp.py:130 scatters eac
 draws a new permutation (sampler.set_epoch), and validation shards the examples without padding so each one counts
 once in the all-reduced RMSE; running loss / gnorm are accumulated on
 the device and read back only at log lines (the reference calls loss.item() twice per step); the config key
-`fast_step: true` switches to HipClipAdam and hipGraph replay of the step (train_step.py).
+`fast_step: true` switches to HipClipAdam and hipGraph replay of the step (train_step.py); `device_cache: true` (DeepCoNN++ and
+D-ATT) keeps meta.pkl's documents on the GPU and feeds the step (u_id, i_id, rating) batches whose documents are gathered
+there (data.DeviceDocCache; the loaders check once that every example's documents are meta's for its ids).
 """
 from __future__ import annotations
 
@@ -56,7 +58,7 @@ class EarlyStop(Exception):
 
 DEFAULTS = dict(log_dir="logs", dataset="dataset", log=True, log_idx=500, verbose=False, parallel=False, epochs=64,
                 batch_size=50, lr=0.002, max_grad_norm=5.0, patience=5, dropout=0.5, arch="CNN", use_pretrain=False,
-                num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False)
+                num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False)
 
 
 class _ShardSampler(torch.utils.data.Sampler):
@@ -109,6 +111,11 @@ class ReviewExperiment:
         if getattr(args, "use_pretrain", False):
             raise RuntimeError("use_pretrain needs gensim + a word2vec file (train_deepconn_pp.py:105-119): pass "
                                "pretrained rows through the model's `pretrained_embeddings` argument instead")
+        if bool(args.device_cache) and kind not in ("deepconn", "dual_att"):
+            # the review split's training examples are not per-id data: the reference drops the target pair's own review from
+            # the user's and the item's lists before truncating (preprocess/divide_and_create_example_word.py:263-285)
+            raise ValueError(f"device_cache is valid for --model deepconn and dual_att, not {kind}: the review split's examples "
+                             "are not per-id documents")
         self.kind, self.args, self.quirks = kind, args, reference_quirks
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -126,8 +133,12 @@ class ReviewExperiment:
         review_split = kind in ("narre", "simple_siamese")
         cls = D.ReviewDataset if review_split else D.DocDataset
         kw = {} if review_split else {"with_ids": kind == "deepconn"}
+        if args.device_cache:
+            kw["feed"] = "ids"
         self.train_set = cls(args.data_dir, "train", **kw)
         self.valid_set = cls(args.data_dir, "valid", **kw)
+        # device_cache: meta.pkl's documents resident on this GPU (train and valid share meta.pkl, so one cache serves both)
+        self.cache = D.DeviceDocCache(self.train_set, self.device) if args.device_cache else None
         self._make_dir()
         self.build_model()
         # both splits were range-checked against their tables when they were loaded (data.validate_ranges): the per-forward
@@ -255,6 +266,8 @@ class ReviewExperiment:
             staged = self._step_from_host(batch)
             if staged is not None:
                 loss, gnorm, ratings = staged
+            elif self.cache is not None:
+                loss, gnorm, ratings = self._id_step(batch)
             else:
                 inputs, ratings = self._to_device(batch)
                 loss, gnorm = self._step(inputs, ratings)
@@ -307,6 +320,43 @@ class ReviewExperiment:
         loss, gnorm, _ = train_step(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync)
         return loss, gnorm
 
+    def _id_step(self, batch):
+        """device_cache: one step on a (u_ids, i_ids, ratings) batch.  With `fast_step` the id-fed step recorded for this batch
+        shape (gather + step) is replayed; otherwise, and for a ragged last batch, the documents are gathered eagerly and
+        train_step runs on them."""
+        a = self.args
+        u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
+        with_ids = self.kind == "deepconn"
+        if a.fast_step:
+            key = tuple((t.shape, t.dtype) for t in batch)
+            if self._graphed is None:
+                self._graphed = GraphedTrainStep.from_ids(self.model, self.optimizer, self.cache, u_ids, i_ids, ratings,
+                                                          a.max_grad_norm, self.grad_sync, with_ids=with_ids)
+                self._graphed_key = key
+            if key == self._graphed_key:
+                loss, gnorm, _ = self._graphed((u_ids, i_ids), ratings)
+                return loss.clone(), gnorm.clone(), ratings
+        inputs = self.cache.inputs(u_ids, i_ids, with_ids=with_ids)
+        loss, gnorm, _ = train_step(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync)
+        return loss, gnorm, ratings
+
+    def _eval_forward_ids(self, u_ids, i_ids):
+        """device_cache: the eval forward of an id batch -- gather + forward replayed from a hipGraph for the loader's regular
+        batch shape with `fast_step`, eager otherwise."""
+        with_ids = self.kind == "deepconn"
+        if self.args.fast_step:
+            g = getattr(self, "_graphed_eval", None)
+            if g is None:
+                try:
+                    g = self._graphed_eval = GraphedForward.from_ids(self.model, self.cache, u_ids, i_ids, with_ids=with_ids)
+                except Exception as e:          # a capture the runtime refuses costs the speed-up, not the validation
+                    self.print_write_to_log(f"eval forward not graphed ({type(e).__name__}: {str(e)[:100]})")
+                    g = self._graphed_eval = False
+            if g and g.matches((u_ids, i_ids)):
+                return g((u_ids, i_ids))
+        out = self.model(*self.cache.inputs(u_ids, i_ids, with_ids=with_ids))
+        return out[0] if isinstance(out, tuple) else out
+
     def _eval_forward(self, inputs):
         """The eval forward: replayed from a hipGraph for the loader's regular batch shape (recorded at first use; the
         parameters are read in place, so training steps in between need no re-recording), eager for any other shape
@@ -333,8 +383,12 @@ class ReviewExperiment:
         self.model.eval()
         with torch.no_grad():
             for batch in loader:
-                inputs, ratings = self._to_device(batch)
-                pred = self._eval_forward(inputs)
+                if self.cache is not None:
+                    u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
+                    pred = self._eval_forward_ids(u_ids, i_ids)
+                else:
+                    inputs, ratings = self._to_device(batch)
+                    pred = self._eval_forward(inputs)
                 loss = self.loss_func(pred, ratings)
                 sq_err += loss.double() * ratings.size(0)
                 loss_sum += loss.double()
