@@ -206,7 +206,8 @@ int rbr_textcnn_bwd_dw(const rbr_textcnn_desc* d, const int64_t* ids, const uint
 int rbr_textcnn_bwd_dtable(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* gate,
                            const float* table, const float* packed, const float* feat, const int32_t* argmax,
                            const float* d_feat, float* dtable, float* dgate, void* stream);
-/* Table (and gate) gradient through the token-product formulation (same maths as rbr_textcnn_bwd_dtable; with a gate,
+/* Table (and gate) gradient through the token-product formulation, rbr_textcnn_bwd_dtable_prod_ex below (same maths as
+ * rbr_textcnn_bwd_dtable; with a gate,
  * dgate[doc,p] is OVERWRITTEN -- zeroed by the call, then summed from the forward's product table T, which must still be
  * intact in `fwd_ws`):
  * G[token][tap, channel] = sum of g over the argmax windows touching that token, for the DISTINCT tokens the
@@ -225,23 +226,13 @@ size_t rbr_textcnn_bwd_dtable_list_ws_bytes(const rbr_textcnn_desc* d);
 int rbr_textcnn_bwd_dtable_list(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* const* W,
                                 const float* feat, const int32_t* argmax, const float* d_feat, void* ws, float* dtable,
                                 void* stream);
-int rbr_textcnn_bwd_dtable_prod(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* gate,
-                                const float* feat, const int32_t* argmax, const float* d_feat, void* fwd_ws, void* bwd_ws,
-                                float* dtable, float* dgate, void* stream);
-/* rbr_textcnn_bwd_dtable_prod with the rows added to dtable instead of the whole [V,D] gradient being overwritten (see
- * `accumulate` of the D-ATT gate backwards). */
-int rbr_textcnn_bwd_dtable_prod_acc(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* gate,
-                                    const float* feat, const int32_t* argmax, const float* d_feat, void* fwd_ws, void* bwd_ws,
-                                    float* dtable, float* dgate, void* stream);
-/* The two halves of rbr_textcnn_bwd_dtable_prod as separate calls (G is always built; dgate as above): for a caller that
- * runs other consumers of G -- rbr_textcnn_bwd_dw_from_g -- beside the product, on another stream. */
-int rbr_textcnn_bwd_g_build(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* gate,
-                            const float* feat, const int32_t* argmax, const float* d_feat, void* fwd_ws, void* bwd_ws,
-                            float* dgate, void* stream);
-int rbr_textcnn_bwd_g_product(const rbr_textcnn_desc* d, void* fwd_ws, void* bwd_ws, float* dtable, void* stream);
-/* Every form of the token-product table gradient behind one entry (the four calls above are fixed-flag forms of it):
- *   RBR_G_BUILD | RBR_G_PRODUCT  the phases to run (G from the argmax windows; dtable = G @ Wprod^T);
- *   RBR_G_ACCUMULATE             the batch's rows are ADDED to the dense dtable [V, D];
+/* The token-product table gradient described above, every form of it behind one entry:
+ *   RBR_G_BUILD | RBR_G_PRODUCT  the phases to run (G from the argmax windows, G is always built; dtable = G @ Wprod^T): both in
+ *                                one call, or one call each for a caller that runs other consumers of G --
+ *                                rbr_textcnn_bwd_dw_from_g -- beside the product, on another stream.  RBR_G_PRODUCT alone reads
+ *                                fwd_ws, bwd_ws, dtable (and sq_part) only: the other pointers may be NULL;
+ *   RBR_G_ACCUMULATE             the batch's rows are ADDED to the dense dtable [V, D] instead of the whole gradient being
+ *                                overwritten (see `accumulate` of the D-ATT gate backwards);
  *   RBR_G_ROWS                   `dtable` is the gradient in COMPACT form [list rows, D]: row r belongs to token tok_of_row[r]
  *                                of the forward's list (rbr_textcnn_token_list), tokens the batch does not hold have no row
  *                                (their gradient is zero and is never written: at cfg2 that is 57 % of embedding_dense_backward's
@@ -249,7 +240,7 @@ int rbr_textcnn_bwd_g_product(const rbr_textcnn_desc* d, void* fwd_ws, void* bwd
  *                                per-workgroup sums of squares of the rows in a fixed order (the table's share of
  *                                clip_grad_norm_'s norm).  Consumers: rbr_clip_adam_step_rows, rbr_row_grad_to_dense;
  *   RBR_G_ZEROED                 G's rows are already zero (a caller that cleared `bwd_ws` itself): no zero launch here.
- * sq_part is only read with RBR_G_ROWS; dgate as for rbr_textcnn_bwd_dtable_prod. */
+ * sq_part is only read with RBR_G_ROWS; dgate (RBR_G_BUILD) as described above. */
 #define RBR_G_BUILD 1
 #define RBR_G_PRODUCT 2
 #define RBR_G_ACCUMULATE 4
@@ -267,7 +258,7 @@ int rbr_textcnn_token_list(const rbr_textcnn_desc* d, void* fwd_ws, const int32_
 /* Conv weight / bias gradients from the G the call above left in `bwd_ws` (dW = G^T @ table[distinct tokens] on the f32
  * MFMA pipe, split over token ranges, fixed-order reduce).  For many short documents (NARRE's reviews) this replaces
  * rbr_textcnn_bwd_dw; rbr_textcnn_bwd_dw_from_g_ws_floats(d) == 0 means "use rbr_textcnn_bwd_dw".  Needs the SAME fwd_ws /
- * bwd_ws as the rbr_textcnn_bwd_dtable_prod call that ran just before it (with dtable != NULL). */
+ * bwd_ws as the rbr_textcnn_bwd_dtable_prod_ex call (RBR_G_BUILD) that ran just before it. */
 size_t rbr_textcnn_bwd_dw_from_g_ws_floats(const rbr_textcnn_desc* d);
 int rbr_textcnn_bwd_dw_from_g(const rbr_textcnn_desc* d, const float* table, const float* feat, const float* d_feat,
                               void* fwd_ws, void* bwd_ws, float* const* dW, float* const* dbias, float* ws, void* stream);

@@ -107,13 +107,6 @@ SIGNATURES = {
     "rbr_textcnn_bwd_dtable": (C.c_int, [_DESC, c_i64p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p,
                                          c_f32p, c_stream]),
     "rbr_textcnn_bwd_prod_ws_bytes": (C.c_size_t, [_DESC]),
-    "rbr_textcnn_bwd_dtable_prod": (C.c_int, [_DESC, c_i64p, c_u8p, c_f32p, c_f32p, c_i32p, c_f32p, C.c_void_p, C.c_void_p,
-                                              c_f32p, c_f32p, c_stream]),
-    "rbr_textcnn_bwd_dtable_prod_acc": (C.c_int, [_DESC, c_i64p, c_u8p, c_f32p, c_f32p, c_i32p, c_f32p, C.c_void_p, C.c_void_p,
-                                                  c_f32p, c_f32p, c_stream]),
-    "rbr_textcnn_bwd_g_build": (C.c_int, [_DESC, c_i64p, c_u8p, c_f32p, c_f32p, c_i32p, c_f32p, C.c_void_p, C.c_void_p, c_f32p,
-                                          c_stream]),
-    "rbr_textcnn_bwd_g_product": (C.c_int, [_DESC, C.c_void_p, C.c_void_p, c_f32p, c_stream]),
     "rbr_textcnn_bwd_dtable_prod_ex": (C.c_int, [_DESC, c_i64p, c_u8p, c_f32p, c_f32p, c_i32p, c_f32p, C.c_void_p, C.c_void_p,
                                                  c_f32p, c_f32p, c_f32p, i32, c_stream]),
     "rbr_textcnn_row_grad_partials": (C.c_size_t, [_DESC]),

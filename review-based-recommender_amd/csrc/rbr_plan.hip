@@ -202,5 +202,5 @@ extern "C" int rbr_pair_end(int32_t* n_paired, int32_t* n_single) {
     return rc;
 }
 
-extern "C" int rbr_version(void) { return 1; }
+extern "C" int rbr_version(void) { return 2; }      // 2: the fixed-flag forms of rbr_textcnn_bwd_dtable_prod_ex are gone
 extern "C" const char* rbr_last_error(void) { return rbr::g_err; }

@@ -18,7 +18,7 @@
 //                                      of the dense path, run over the token list as one long document, store epilogue)
 //   5. gather_pool                   : per 32-position wave-tile, sum the kz rows of T, running max / first argmax
 //   then pool_finalize as for the dense path.
-// Backward (rbr_textcnn_bwd_dtable_prod): zero_g_rows, build_g (G[token][(tap, channel)] += g, d(gate) from T),
+// Backward (rbr_textcnn_bwd_dtable_prod_ex): zero_g_rows, build_g (G[token][(tap, channel)] += g, d(gate) from T),
 //   g_times_w (dtable[token, :] = G[token, :] @ Wprod^T as a sparse row product; absent tokens' rows zeroed).
 #include "rbr_common.h"
 #include "textcnn_b16.h"
@@ -1292,58 +1292,13 @@ static int dtable_through_list(const rbr_textcnn_desc* d, const ConvPlan* plans,
                                const float* feat, const int32_t* argmax, const float* d_feat, void* fwd_ws, void* bwd_ws,
                                float* dtable, float* dgate, hipStream_t st, int phases = kGBuild | kGProduct, float* sq_part = nullptr);
 
-extern "C" int rbr_textcnn_bwd_dtable_prod(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* gate,
-                                           const float* feat, const int32_t* argmax, const float* d_feat, void* fwd_ws,
-                                           void* bwd_ws, float* dtable, float* dgate, void* stream) {
-    ConvPlan plans[kMaxGroups];
-    if (!build_plans(d, plans)) return RBR_ERR_BAD_ARG;
-    if (dgate != nullptr && gate == nullptr) dgate = nullptr;
-    if (dtable == nullptr && dgate == nullptr) return 0;
-    if (!ids || !feat || !argmax || !d_feat || !fwd_ws || !bwd_ws) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    if (!prod_applicable(d)) { set_error("token-product path does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
-    return dtable_through_list(d, plans, ids, mask, gate, feat, argmax, d_feat, fwd_ws, bwd_ws, dtable, dgate, (hipStream_t)stream);
-}
-
-// rbr_textcnn_bwd_dtable_prod with the table rows ADDED to `dtable` (a gradient buffer shared by several producers that run
-// one after the other on the same stream: functional.table_fanout) instead of the whole [V, D] gradient being overwritten.
-extern "C" int rbr_textcnn_bwd_dtable_prod_acc(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* gate,
-                                               const float* feat, const int32_t* argmax, const float* d_feat, void* fwd_ws,
-                                               void* bwd_ws, float* dtable, float* dgate, void* stream) {
-    ConvPlan plans[kMaxGroups];
-    if (!build_plans(d, plans)) return RBR_ERR_BAD_ARG;
-    if (dgate != nullptr && gate == nullptr) dgate = nullptr;
-    if (!ids || !feat || !argmax || !d_feat || !fwd_ws || !bwd_ws || !dtable) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    if (!prod_applicable(d)) { set_error("token-product path does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
-    return dtable_through_list(d, plans, ids, mask, gate, feat, argmax, d_feat, fwd_ws, bwd_ws, dtable, dgate, (hipStream_t)stream,
-                               kGBuild | kGProduct | kGAccumulate);
-}
-
-// The two halves of rbr_textcnn_bwd_dtable_prod as separate calls, for callers that put work between them or beside the
-// second one (functional: NARRE's dW = G^T @ table rows runs on a second stream while the product runs on the first).
-extern "C" int rbr_textcnn_bwd_g_build(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* gate,
-                                       const float* feat, const int32_t* argmax, const float* d_feat, void* fwd_ws, void* bwd_ws,
-                                       float* dgate, void* stream) {
-    ConvPlan plans[kMaxGroups];
-    if (!build_plans(d, plans)) return RBR_ERR_BAD_ARG;
-    if (dgate != nullptr && gate == nullptr) dgate = nullptr;
-    if (!ids || !feat || !argmax || !d_feat || !fwd_ws || !bwd_ws) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    if (!prod_applicable(d)) { set_error("token-product path does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
-    return dtable_through_list(d, plans, ids, mask, gate, feat, argmax, d_feat, fwd_ws, bwd_ws, nullptr, dgate, (hipStream_t)stream,
-                               kGBuild);
-}
-
-extern "C" int rbr_textcnn_bwd_g_product(const rbr_textcnn_desc* d, void* fwd_ws, void* bwd_ws, float* dtable, void* stream) {
-    ConvPlan plans[kMaxGroups];
-    if (!build_plans(d, plans)) return RBR_ERR_BAD_ARG;
-    if (!fwd_ws || !bwd_ws || !dtable) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    if (!prod_applicable(d)) { set_error("token-product path does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
-    return dtable_through_list(d, plans, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, fwd_ws, bwd_ws, dtable, nullptr,
-                               (hipStream_t)stream, kGProduct);
-}
-
-// Every form of the token-product table gradient behind one entry (the calls above are its fixed-flag forms):
-//   RBR_G_BUILD | RBR_G_PRODUCT   the phases to run;
-//   RBR_G_ACCUMULATE              the rows are added to the dense `dtable`;
+// Every form of the token-product table gradient behind one entry:
+//   RBR_G_BUILD | RBR_G_PRODUCT   the phases to run -- in one call, or as two for callers that put work between them or beside
+//                                 the second one (functional: NARRE's dW = G^T @ table rows runs on a second stream while the
+//                                 product runs on the first);
+//   RBR_G_ACCUMULATE              the rows are ADDED to the dense `dtable` (a gradient buffer shared by several producers that
+//                                 run one after the other on the same stream: functional.table_fanout) instead of the whole
+//                                 [V, D] gradient being overwritten;
 //   RBR_G_ROWS                    `dtable` is the COMPACT gradient [list rows, D] (row r = token tok_of_row[r]; absent tokens have
 //                                 no row) and sq_part[rbr_textcnn_row_grad_partials(d)] receives per-workgroup sums of squares;
 //   RBR_G_ZEROED                  G's rows are zero already (a caller that cleared bwd_ws itself).
@@ -1417,7 +1372,7 @@ static int dtable_through_list(const rbr_textcnn_desc* d, const ConvPlan* plans,
         A.kz[w] = d->kz[w]; A.ch[w] = d->ch[w]; A.ch_off[w] = plans[0].ch_off[w];
         A.poff[w] = cp_real; cp_real += d->kz[w] * d->ch[w];
     }
-    // kGBuild alone (rbr_textcnn_bwd_g_build) always builds G: its caller multiplies it out later (rbr_textcnn_bwd_g_product)
+    // kGBuild alone (RBR_G_BUILD) always builds G: its caller multiplies it out later (a second call with RBR_G_PRODUCT)
     const bool want_g = dtable != nullptr || !(phases & kGProduct);
     if (phases & kGBuild) {
         if ((want_g && !(phases & kGZeroed)) || dgate != nullptr || B.rows_gemm) {      // dgate is zeroed here: the caller hands it over uninitialised
@@ -1650,7 +1605,7 @@ extern "C" int rbr_textcnn_prod_pool(const rbr_textcnn_desc* d, const int64_t* i
     return 0;
 }
 
-// ---- conv weight / bias gradient from G (see dw_from_g_kernel): after rbr_textcnn_bwd_dtable_prod built G in `bwd_ws`
+// ---- conv weight / bias gradient from G (see dw_from_g_kernel): after rbr_textcnn_bwd_dtable_prod_ex built G in `bwd_ws`
 static bool dw_from_g_applicable(const rbr_textcnn_desc* d) {
     // the shapes the document-centric dW kernel serves (textcnn_bwd.hip): many short documents
     long cp = 0;

@@ -25,6 +25,25 @@ def _mask_u8(mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     raise RuntimeError(f"mask must be bool or uint8, got {mask.dtype}")
 
 
+def _call(key: Optional[str], fn, *args) -> None:
+    """check(fn(*args)) for the C-ABI entry `fn`, bracketed by a pair of TIMER events recorded under `key` while bench.py's
+    kernel-timing pass is on.  key None: never bracketed (inside a D-ATT pair region an event pair would be a stream operation
+    ahead of the recorded launches)."""
+    ev = TIMER.record(key) if key is not None else None
+    check(fn(*args), fn.__name__)
+    if ev is not None:
+        ev.record()
+
+
+@contextlib.contextmanager
+def _timed(key: str):
+    """The same bracket around a block of several calls."""
+    ev = TIMER.record(key)
+    yield
+    if ev is not None:
+        ev.record()
+
+
 # Data-parallel tap exchange (distributed.TapExchange): when a sink is installed, the backward of an un-gated conv over the
 # sink's word table emits its (token, value) taps instead of the dense table gradient; the sink rebuilds the averaged
 # gradient of all ranks after an all-gather of the taps (rbr_textcnn_bwd_taps / rbr_textcnn_dtable_from_taps).
@@ -102,7 +121,7 @@ def sanitize_ids(sets, stack_first_two: bool = False):
         o += t.numel()
         rep = 0 if rep is None or rep < 0 else int(rep)
         arr[k] = _lib.IdSet(t.data_ptr() if t.numel() else None, v.data_ptr() if t.numel() else None, t.numel(), int(rows), rep)
-    check(_lib.lib().rbr_sanitize_ids(len(tens), arr, _id_err(dev).data_ptr(), current_stream()), "rbr_sanitize_ids")
+    _call(None, _lib.lib().rbr_sanitize_ids, len(tens), arr, _id_err(dev).data_ptr(), current_stream())
     if stack_first_two:
         a, b = tens[0], tens[1]
         if a.shape != b.shape:
@@ -142,9 +161,9 @@ def dedup_rows(u_ids: torch.Tensor, i_ids: torch.Tensor, user_size: int, item_si
     ws = torch.empty(L_.rbr_dedup_ws_bytes(int(user_size), int(item_size)), dtype=torch.uint8, device=dev)
     first = torch.empty(2 * B, dtype=I64, device=dev)
     out = torch.empty(2 * B, L, dtype=torch.uint8, device=dev)
-    check(L_.rbr_dedup_rows(B, int(L), dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"), int(user_size), int(item_size),
-                            dev_ptr(mask8, U8, "mask"), ws.data_ptr(), dev_ptr(first, I64, "first"), dev_ptr(out, U8, "mask_out"),
-                            current_stream()), "rbr_dedup_rows")
+    _call(None, L_.rbr_dedup_rows, B, int(L), dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"), int(user_size),
+          int(item_size), dev_ptr(mask8, U8, "mask"), ws.data_ptr(), dev_ptr(first, I64, "first"), dev_ptr(out, U8, "mask_out"),
+          current_stream())
     return first, out.view(torch.bool)
 
 
@@ -182,12 +201,11 @@ def doc_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_docs: torch.Tensor
         raise RuntimeError(f"masks must be bool, got {masks.dtype}")
     if B == 0:
         return docs, masks, ids
-    check(_lib.lib().rbr_doc_gather(B, L, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),
-                                    dev_ptr(user_docs, I32, "user_docs"), user_docs.shape[0],
-                                    dev_ptr(item_docs, I32, "item_docs"), item_docs.shape[0], int(pad_token), int(replace_id),
-                                    dev_ptr(docs, I64, "docs"), dev_ptr(None if masks is None else masks.view(U8), U8, "masks"),
-                                    dev_ptr(ids, I64, "ids"),
-                                    _id_err(dev).data_ptr(), current_stream()), "rbr_doc_gather")
+    _call(None, _lib.lib().rbr_doc_gather, B, L, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),
+          dev_ptr(user_docs, I32, "user_docs"), user_docs.shape[0], dev_ptr(item_docs, I32, "item_docs"), item_docs.shape[0],
+          int(pad_token), int(replace_id), dev_ptr(docs, I64, "docs"),
+          dev_ptr(None if masks is None else masks.view(U8), U8, "masks"), dev_ptr(ids, I64, "ids"), _id_err(dev).data_ptr(),
+          current_stream())
     return docs, masks, ids
 
 
@@ -250,6 +268,78 @@ def table_fanout(table: torch.Tensor, n: int):
     return _TableFanout.apply(table, n)
 
 
+class _ConvSaved:
+    """What a conv forward allocates (_conv_fwd_buffers) and what it leaves for its backward (a plain record: the fused encoder +
+    head function shares the backward, D-ATT keeps one per tower)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _conv_desc(table, n_docs, L, ws, pad_mode, act, padding_idx, flags: int = 0):
+    """Descriptor of the conv with the weights `ws` ([C_w, D, kz_w] each) over [n_docs, L] ids into `table`."""
+    V, D = table.shape
+    return _lib.make_desc(n_docs, L, D, V, [int(w.shape[2]) for w in ws], [int(w.shape[0]) for w in ws], pad_mode, act, padding_idx,
+                          flags)
+
+
+def _conv_operands(table, ids, mask, weights, pad_mode, act, padding_idx, flags: int = 0):
+    """What every conv entry starts with: contiguous operands, the device / dtype gate before anything touches HIP, the mask
+    check and the descriptor.  Returns (table_c, ids, mask8, ws, desc)."""
+    table_c = table.contiguous()
+    dev_ptr(table_c, F32, "word table")
+    if ids.dim() != 2:
+        raise RuntimeError("ids must be [n_docs, L]")
+    ids = ids.contiguous()
+    mask8 = _mask_u8(mask)
+    if mask8 is not None and mask8.shape != ids.shape:
+        raise AssertionError("inputs.shape[:-1] == masks.shape")   # deepconn/utils.py:58
+    ws = [w.contiguous() for w in weights]
+    return table_c, ids, mask8, ws, _conv_desc(table_c, ids.shape[0], ids.shape[1], ws, pad_mode, act, padding_idx, flags)
+
+
+def _conv_fwd_buffers(rec, desc, dev, feat=None, argmax=None):
+    """Plan queries and output buffers of a conv forward, left on the record `rec` -- allocations only, nothing launches: pval /
+    pidx (the pool's per-slab partials), feat / argmax [n_docs, C] (or the caller's views) and prod_ws, the workspace of the
+    token-product formulation (None: it does not apply to this shape, the dense formulation runs)."""
+    L_ = _lib.lib()
+    n_part = L_.rbr_textcnn_partial_elems(C.byref(desc))
+    if not n_part:
+        check(-1, "rbr_textcnn plan")
+    ws_bytes = L_.rbr_textcnn_fwd_ws_bytes(C.byref(desc))      # > 0: the token-product formulation will run
+    Ctot = sum(desc.ch[:desc.n_widths])
+    rec.pval = torch.empty(n_part, dtype=F32, device=dev)
+    rec.pidx = torch.empty(n_part, dtype=I32, device=dev)
+    rec.feat = feat if feat is not None else torch.empty(desc.n_docs, Ctot, dtype=F32, device=dev)
+    rec.argmax = argmax if argmax is not None else torch.empty(desc.n_docs, Ctot, dtype=I32, device=dev)
+    rec.prod_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    return rec
+
+
+def _prod_forward(desc, rec, table, ids, mask8, gate, ws, st, *, id_sets=None, prepare_key="textcnn_prod_prepare"):
+    """The token-product forward, stage by stage (each stage is what rbr_textcnn_conv_fwd would run): prepare -> table -> pool,
+    into rec.pval / rec.pidx (_conv_fwd_buffers).  Library calls only, so that D-ATT can issue it inside a pair region (where its
+    prepare stage has never been bracketed: prepare_key None).  id_sets = (n, IdSet array, error record): the range check of
+    the raw id tensors rides in the prepare stage's first launch (rbr_textcnn_prod_prepare_ids)."""
+    L_ = _lib.lib()
+    d, wsp = C.byref(desc), rec.prod_ws.data_ptr()
+    ids_p, mask_p, pidx_p = dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"), dev_ptr(rec.pidx, I32, "pidx")
+    if id_sets is not None:
+        _call(prepare_key, L_.rbr_textcnn_prod_prepare_ids, d, *id_sets, ids_p, mask_p, ptr_array(ws, F32, "conv weight"), pidx_p,
+              wsp, st)
+    else:
+        _call(prepare_key, L_.rbr_textcnn_prod_prepare, d, ids_p, mask_p, ptr_array(ws, F32, "conv weight"), pidx_p, wsp, st)
+    _call("textcnn_prod_table", L_.rbr_textcnn_prod_table, d, dev_ptr(table, F32, "word table"), wsp, st)
+    _call("textcnn_prod_pool", L_.rbr_textcnn_prod_pool, d, ids_p, mask_p, dev_ptr(gate, F32, "gate"), dev_ptr(rec.pval, F32, "pval"),
+          pidx_p, wsp, st)
+
+
+def _pool_finalize(desc, rec, bs, st):
+    """feat / argmax from the pool's partials (either formulation) and the conv biases."""
+    _call(None, _lib.lib().rbr_textcnn_pool_finalize, C.byref(desc), dev_ptr(rec.pval, F32, "pval"), dev_ptr(rec.pidx, I32, "pidx"),
+          ptr_array(bs, F32, "conv bias"), dev_ptr(rec.feat, F32, "feat"), dev_ptr(rec.argmax, I32, "argmax"), st)
+
+
 class _TextCNN(torch.autograd.Function):
     """feat[n_docs, C] = pool(act(conv(mask * gate * table[ids])))  -- see rbr_textcnn_* in rbr_hip.h."""
 
@@ -258,80 +348,34 @@ class _TextCNN(torch.autograd.Function):
         ctx.fanout_acc = _fanout_acc(table)
         n = len(kernel_sizes)
         weights, biases = wb[:n], wb[n:]
-        dev_ptr(table.contiguous(), F32, "word table")   # device / dtype gate before anything touches HIP
-        if ids.dim() != 2:
-            raise RuntimeError("ids must be [n_docs, L]")
-        n_docs, L = ids.shape
-        V, D = table.shape
+        table_c, ids, mask8, ws, desc = _conv_operands(table, ids, mask, weights, pad_mode, act, padding_idx, conv_flags)
         for k, w, b in zip(kernel_sizes, weights, biases):
-            assert w.shape[1] == D and w.shape[2] == k and b.shape[0] == w.shape[0]
-        channels = [w.shape[0] for w in weights]
-        Ctot = sum(channels)
-        desc = _lib.make_desc(n_docs, L, D, V, kernel_sizes, channels, pad_mode, act, padding_idx, conv_flags)
-        L_ = _lib.lib()
-        dev = table.device
-        ids = ids.contiguous()
-        mask8 = _mask_u8(mask)
-        if mask8 is not None and mask8.shape != ids.shape:
-            raise AssertionError("inputs.shape[:-1] == masks.shape")   # deepconn/utils.py:58
+            assert w.shape[1] == table.shape[1] and w.shape[2] == k and b.shape[0] == w.shape[0]
+        bs = [b.contiguous() for b in biases]
         if gate is not None:
             gate = gate.contiguous()
-        table_c = table.contiguous()
-        ws = [w.contiguous() for w in weights]
-        bs = [b.contiguous() for b in biases]
-
+        L_ = _lib.lib()
+        dev = table.device
         n_packed = L_.rbr_textcnn_packed_floats(C.byref(desc))
-        n_part = L_.rbr_textcnn_partial_elems(C.byref(desc))
-        if n_packed == 0 or n_part == 0:
+        if not n_packed:
             check(-1, "rbr_textcnn plan")
-        pval = torch.empty(n_part, dtype=F32, device=dev)
-        pidx = torch.empty(n_part, dtype=I32, device=dev)
-        feat = torch.empty(n_docs, Ctot, dtype=F32, device=dev)
-        argmax = torch.empty(n_docs, Ctot, dtype=I32, device=dev)
+        buf = _conv_fwd_buffers(_ConvSaved(), desc, dev)
         st = current_stream()
-
-        ws_bytes = L_.rbr_textcnn_fwd_ws_bytes(C.byref(desc))      # > 0: the token-product formulation will run
-        prod_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
         packed = None         # MFMA tile image of the conv weights: the dense forward and the scatter backward read it
-        if prod_ws is None:
-            packed = _TextCNN._pack(L_, desc, ws, n_packed, dev, st)
-        if prod_ws is not None:
-            # token-product formulation, stage by stage (each stage is what rbr_textcnn_conv_fwd would run)
-            wsp = prod_ws.data_ptr()
-            ev = TIMER.record("textcnn_prod_prepare")
-            check(L_.rbr_textcnn_prod_prepare(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                              ptr_array(ws, F32, "conv weight"), dev_ptr(pidx, I32, "pidx"), wsp, st),
-                  "rbr_textcnn_prod_prepare")
-            if ev is not None:
-                ev.record()
-            ev = TIMER.record("textcnn_prod_table")
-            check(L_.rbr_textcnn_prod_table(C.byref(desc), dev_ptr(table_c, F32, "word table"), wsp, st),
-                  "rbr_textcnn_prod_table")
-            if ev is not None:
-                ev.record()
-            ev = TIMER.record("textcnn_prod_pool")
-            check(L_.rbr_textcnn_prod_pool(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                           dev_ptr(gate, F32, "gate"), dev_ptr(pval, F32, "pval"), dev_ptr(pidx, I32, "pidx"),
-                                           wsp, st), "rbr_textcnn_prod_pool")
-            if ev is not None:
-                ev.record()
+        if buf.prod_ws is not None:
+            _prod_forward(desc, buf, table_c, ids, mask8, gate, ws, st)
         else:
-            ev = TIMER.record("textcnn_conv_fwd")
-            check(L_.rbr_textcnn_conv_fwd(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                          dev_ptr(gate, F32, "gate"), dev_ptr(table_c, F32, "word table"),
-                                          ptr_array(ws, F32, "conv weight"), dev_ptr(packed, F32, "packed"),
-                                          dev_ptr(pval, F32, "pval"), dev_ptr(pidx, I32, "pidx"), None, st),
-                  "rbr_textcnn_conv_fwd")
-            if ev is not None:
-                ev.record()
-        check(L_.rbr_textcnn_pool_finalize(C.byref(desc), dev_ptr(pval, F32, "pval"), dev_ptr(pidx, I32, "pidx"),
-                                           ptr_array(bs, F32, "conv bias"), dev_ptr(feat, F32, "feat"),
-                                           dev_ptr(argmax, I32, "argmax"), st), "rbr_textcnn_pool_finalize")
+            packed = _TextCNN._pack(L_, desc, ws, n_packed, dev, st)
+            _call("textcnn_conv_fwd", L_.rbr_textcnn_conv_fwd, C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
+                  dev_ptr(gate, F32, "gate"), dev_ptr(table_c, F32, "word table"), ptr_array(ws, F32, "conv weight"),
+                  dev_ptr(packed, F32, "packed"), dev_ptr(buf.pval, F32, "pval"), dev_ptr(buf.pidx, I32, "pidx"), None, st)
+        _pool_finalize(desc, buf, bs, st)
+        feat, argmax = buf.feat, buf.argmax
         ctx.desc = desc
         ctx.n = n
         ctx.has_gate = gate is not None
         ctx.has_mask = mask8 is not None
-        ctx.prod_ws = prod_ws          # distinct-token list of the batch, reused by the table-gradient GEMM
+        ctx.prod_ws = buf.prod_ws      # distinct-token list of the batch, reused by the table-gradient GEMM
         ctx.save_for_backward(table_c, ids, packed, feat, argmax, *([mask8] if mask8 is not None else []),
                               *([gate] if gate is not None else []), *ws)
         ctx.mark_non_differentiable(argmax)
@@ -341,8 +385,7 @@ class _TextCNN(torch.autograd.Function):
     @staticmethod
     def _pack(L_, desc, ws, n_packed, dev, st):
         packed = torch.empty(n_packed, dtype=F32, device=dev)
-        check(L_.rbr_textcnn_pack(C.byref(desc), ptr_array(ws, F32, "conv weight"), dev_ptr(packed, F32, "packed"), st),
-              "rbr_textcnn_pack")
+        _call(None, L_.rbr_textcnn_pack, C.byref(desc), ptr_array(ws, F32, "conv weight"), dev_ptr(packed, F32, "packed"), st)
         return packed
 
     @staticmethod
@@ -357,232 +400,237 @@ class _TextCNN(torch.autograd.Function):
         if ctx.has_gate:
             gate = saved[k]; k += 1
         S = _ConvSaved(table=table, ids=ids, packed=packed, feat=feat, argmax=argmax, mask8=mask8, gate=gate, ws=list(saved[k:]),
-                       desc=ctx.desc, prod_ws=ctx.prod_ws, fanout_acc=ctx.fanout_acc, bws=None)
+                       desc=ctx.desc, prod_ws=ctx.prod_ws, fanout_acc=ctx.fanout_acc)
         dtable, dgate, dWs, dbs = _textcnn_backward(S, d_feat, ctx.needs_input_grad[0], ctx.has_gate and ctx.needs_input_grad[1])
         return (dtable, dgate, None, None, None, None, None, None, None, *dWs, *dbs)
 
 
-class _ConvSaved:
-    """What a conv forward leaves for its backward (a plain record: the fused encoder + head function shares the backward)."""
+# ---- backward of the fused encoder: one dispatcher, one function per table-gradient strategy, the weight-gradient chain ------
+class _Fork:
+    """The second stream of `dev` (_side_stream), forked from the current stream HERE: the event is recorded at construction.
+    `with fork:` -- now or after more work has been enqueued on the current stream -- runs its body on the second stream behind
+    the fork point; fork.join() makes the current stream wait for that body.  Inside a captured graph the two become parallel
+    branches.  on=False, or RBR_BWD_OVERLAP=0: the body runs inline on the current stream."""
 
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
+    def __init__(self, dev, on: bool = True):
+        self.side = _side_stream(dev) if on else None
+        self.done = None
+        if self.side is not None:
+            self.forked = torch.cuda.Event()
+            self.forked.record()
+
+    def __enter__(self):
+        if self.side is not None:
+            self.side.wait_event(self.forked)
+            self._ctx = torch.cuda.stream(self.side)
+            self._ctx.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        if self.side is not None:
+            if exc[0] is None:
+                self.done = torch.cuda.Event()
+                self.done.record()
+            self._ctx.__exit__(*exc)
+        return False
+
+    def join(self) -> None:
+        _join(self.done)
+
+
+def _g_chain(key, flags, st, desc, operands, fwd_ws, bws, dtable, dgate, sq):
+    """rbr_textcnn_bwd_dtable_prod_ex on the raw stream `st`: the token-product table gradient over the forward's distinct-token
+    list in `fwd_ws`.  flags: the phases -- G_BUILD (G in `bws`, and dgate, from operands = (ids, mask8, gate, feat, argmax,
+    d_feat)), G_PRODUCT (dtable [, sq] = G @ Wprod^T) -- plus G_ACCUMULATE / G_ROWS for the product.  What a phase that is not
+    asked for would read or write is passed as NULL.  key: the TIMER key of the call, or None."""
+    build, product = flags & _lib.G_BUILD, flags & _lib.G_PRODUCT
+    ids, mask8, gate, feat, argmax, d_feat = operands if build else (None,) * 6
+    _call(key, _lib.lib().rbr_textcnn_bwd_dtable_prod_ex, C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
+          dev_ptr(gate, F32, "gate"), dev_ptr(feat, F32, "feat"), dev_ptr(argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"),
+          fwd_ws.data_ptr(), bws.data_ptr(), dev_ptr(dtable if product else None, F32, "dtable"),
+          dev_ptr(dgate if build else None, F32, "dgate"), dev_ptr(sq if product else None, F32, "sq_part"), flags, st)
 
 
 def _textcnn_backward(S, d_feat, need_table: bool, need_gate: bool):
     """Backward of the fused encoder from d_feat [n_docs, C]: returns (dtable, dgate, dWs, dbs).  dtable is None when the table
     gradient left through a side channel instead: the data-parallel tap sink, or -- compact row form -- the optimizer that
-    registered for it (set_row_grad_sink).  S.bws: the G workspace the forward allocated and cleared (or None)."""
-    table, ids, packed, feat, argmax, mask8, gate, ws, desc = (S.table, S.ids, S.packed, S.feat, S.argmax, S.mask8, S.gate,
-                                                               S.ws, S.desc)
-    if d_feat is None:
-        d_feat = torch.zeros_like(feat)
+    registered for it (set_row_grad_sink).  Picks the table-gradient strategy; each one also runs the weight-gradient chain.
+    Precedence: tap sink (one that accepts the call wins over fixed mode), fixed point, token product, token list, window scatter."""
     L_ = _lib.lib()
+    table, gate, desc = S.table, S.gate, S.desc
     dev = table.device
-    d_feat = d_feat.contiguous()
-    dWs = [torch.empty_like(w) for w in ws]
-    dbs = [torch.empty(w.shape[0], dtype=F32, device=dev) for w in ws]
+    d_feat = (torch.zeros_like(S.feat) if d_feat is None else d_feat).contiguous()
+    dWs = [torch.empty_like(w) for w in S.ws]
+    dbs = [torch.empty(w.shape[0], dtype=F32, device=dev) for w in S.ws]
+    plain = need_table and gate is None          # the tap and token-list forms of the table gradient serve un-gated convs only
     sink = _TAP_SINKS.get(table.data_ptr())          # only the sink installed for THIS table ever sees the call
-    use_taps = (sink is not None and need_table and gate is None and sink.accepts(table, desc, L_))
-    if use_taps:
-        need_table = False          # table.grad is produced by the exchange, after the all-gather of the taps
-    fixed_dtable = None
-    if need_table and gate is None and _dtable_fixed():
-        fixed_bytes = L_.rbr_textcnn_dtable_from_taps_ws_bytes(C.byref(desc), 1)
-        if fixed_bytes:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("RBR_DTABLE_MODE=fixed sorts with rocPRIM and cannot be recorded into a hipGraph: run the step eagerly")
-            n_taps = L_.rbr_textcnn_taps_count(C.byref(desc))
-            tok = torch.empty(n_taps, dtype=I32, device=dev)
-            val = torch.empty(n_taps, dtype=F32, device=dev)
-            tws = torch.empty(fixed_bytes, dtype=torch.uint8, device=dev)
-            fixed_dtable = torch.empty_like(table)
-            check(L_.rbr_textcnn_bwd_taps(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"), dev_ptr(feat, F32, "feat"),
-                                          dev_ptr(argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"), dev_ptr(tok, I32, "tap tokens"),
-                                          dev_ptr(val, F32, "tap values"), current_stream()), "rbr_textcnn_bwd_taps")
-            check(L_.rbr_textcnn_dtable_from_taps(C.byref(desc), 1, dev_ptr(tok, I32, "tap tokens"), dev_ptr(val, F32, "tap values"),
-                                                  ptr_array(ws, F32, "conv weight"), tws.data_ptr(), dev_ptr(fixed_dtable, F32, "dtable"),
-                                                  current_stream()), "rbr_textcnn_dtable_from_taps")
-            need_table = False
-    bws_bytes = L_.rbr_textcnn_bwd_prod_ws_bytes(C.byref(desc)) if S.prod_ws is not None else 0
-    # dense forward (no token list of its own), un-gated: the table gradient still goes through a distinct-token list built
-    # here (16 us) instead of the window scatter's row of f32 atomics per (document, channel, tap)
-    list_bytes = (L_.rbr_textcnn_bwd_dtable_list_ws_bytes(C.byref(desc))
-                  if (need_table and not bws_bytes and gate is None) else 0)
-    acc = _table_acc(S.fanout_acc, dev) if (need_table and bws_bytes) else None
+    if plain and sink is not None and sink.accepts(table, desc, L_):
+        dtable, dgate = _bwd_tap_sink(S, d_feat, sink, dWs, dbs)
+    elif plain and _dtable_fixed() and (fixed_bytes := L_.rbr_textcnn_dtable_from_taps_ws_bytes(C.byref(desc), 1)):
+        dtable, dgate = _bwd_fixed(S, d_feat, fixed_bytes, dWs, dbs)
+    elif (need_table or need_gate) and S.prod_ws is not None and (bws_bytes := L_.rbr_textcnn_bwd_prod_ws_bytes(C.byref(desc))):
+        dtable, dgate = _bwd_token_product(S, d_feat, need_table, need_gate, bws_bytes, dWs, dbs)
+    elif plain and (list_bytes := L_.rbr_textcnn_bwd_dtable_list_ws_bytes(C.byref(desc))):
+        dtable, dgate = _bwd_token_list(S, d_feat, list_bytes, dWs, dbs)
+    else:
+        dtable, dgate = _bwd_window_scatter(S, d_feat, need_table, need_gate, dWs, dbs)
+    return dtable, dgate, dWs, dbs
+
+
+def _bwd_dw(S, d_feat, dWs, dbs, fork) -> None:
+    """The weight-gradient chain (rbr_textcnn_bwd_dw) on `fork`'s stream, joined before returning.  The weight-gradient kernels
+    and the table-gradient kernels both start from d_feat and share nothing else: the former go to a second stream, so the two
+    chains overlap -- also inside a captured graph, where the fork becomes two parallel branches.  A strategy forks BEFORE its
+    table-gradient chain and calls this AFTER it: in a replayed graph the branch captured first keeps the queue of the nodes
+    before and after the fork, and the join of the other branch into that queue costs ~10 us -- so the longer (table) branch goes
+    first and the step's next kernel follows it without a gap."""
+    L_ = _lib.lib()
+    wsb = torch.empty(max(L_.rbr_textcnn_bwd_ws_floats(C.byref(S.desc)), 1), dtype=F32, device=S.table.device)
+    with fork:
+        _call("textcnn_bwd_dw", L_.rbr_textcnn_bwd_dw, C.byref(S.desc), dev_ptr(S.ids, I64, "ids"), dev_ptr(S.mask8, U8, "mask"),
+              dev_ptr(S.gate, F32, "gate"), dev_ptr(S.table, F32, "table"), dev_ptr(S.feat, F32, "feat"),
+              dev_ptr(S.argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"), ptr_array(dWs, F32, "dW"),
+              ptr_array(dbs, F32, "dbias"), dev_ptr(wsb, F32, "ws"), current_stream())
+    fork.join()
+
+
+def _bwd_taps(key, S, d_feat, tok, val) -> None:
+    """(token, value) taps of an un-gated conv's table gradient: rbr_textcnn_bwd_taps."""
+    _call(key, _lib.lib().rbr_textcnn_bwd_taps, C.byref(S.desc), dev_ptr(S.ids, I64, "ids"), dev_ptr(S.mask8, U8, "mask"),
+          dev_ptr(S.feat, F32, "feat"), dev_ptr(S.argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"),
+          dev_ptr(tok, I32, "tap tokens"), dev_ptr(val, F32, "tap values"), current_stream())
+
+
+def _bwd_tap_sink(S, d_feat, sink, dWs, dbs):
+    """Data-parallel tap sink: the taps go to the exchange, which produces table.grad after the all-gather -- no dtable here."""
+    dev = S.table.device
+    fork = _Fork(dev)
+    tok, val = sink.local_buffers(_lib.lib().rbr_textcnn_taps_count(C.byref(S.desc)), dev)
+    _bwd_taps("textcnn_bwd_dtable", S, d_feat, tok, val)
+    sink.record(S.desc, list(S.ws))
+    _bwd_dw(S, d_feat, dWs, dbs, fork)
+    return None, None
+
+
+def _bwd_fixed(S, d_feat, fixed_bytes, dWs, dbs):
+    """set_dtable_mode("fixed"): order-free fixed-point sums, the data-parallel tap rebuild run on this rank's taps alone.  The
+    weight gradient follows on the same stream."""
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("RBR_DTABLE_MODE=fixed sorts with rocPRIM and cannot be recorded into a hipGraph: run the step eagerly")
+    L_ = _lib.lib()
+    dev = S.table.device
+    n_taps = L_.rbr_textcnn_taps_count(C.byref(S.desc))
+    tok = torch.empty(n_taps, dtype=I32, device=dev)
+    val = torch.empty(n_taps, dtype=F32, device=dev)
+    tws = torch.empty(fixed_bytes, dtype=torch.uint8, device=dev)
+    dtable = torch.empty_like(S.table)
+    _bwd_taps(None, S, d_feat, tok, val)
+    _call(None, L_.rbr_textcnn_dtable_from_taps, C.byref(S.desc), 1, dev_ptr(tok, I32, "tap tokens"), dev_ptr(val, F32, "tap values"),
+          ptr_array(S.ws, F32, "conv weight"), tws.data_ptr(), dev_ptr(dtable, F32, "dtable"), current_stream())
+    _bwd_dw(S, d_feat, dWs, dbs, _Fork(dev, on=False))
+    return dtable, None
+
+
+def _bwd_token_product(S, d_feat, need_table, need_gate, bws_bytes, dWs, dbs):
+    """Token-product backward: dtable = G @ Wprod^T over the forward's distinct-token list (no atomics on the table); d(gate) of
+    gated convs (D-ATT) is read off the forward's product table.  Returns (dtable, dgate); dtable is None when the rows went to
+    the optimizer's row sink."""
+    L_ = _lib.lib()
+    table, desc = S.table, S.desc
+    dev = table.device
+    st = current_stream()
+    # many short documents (NARRE's reviews): dW = G^T @ table[distinct tokens] on the MFMA pipe, from the G the
+    # table-gradient call builds anyway (0 floats of workspace = not this shape: the window-row kernels of _bwd_dw)
+    dwg_floats = L_.rbr_textcnn_bwd_dw_from_g_ws_floats(C.byref(desc)) if need_table else 0
+    acc = _table_acc(S.fanout_acc, dev) if need_table else None
     # compact row gradient: the optimizer that asked for it takes the rows of the batch's tokens, nobody writes (or later
     # reads) the zero rows of a dense [V, D] gradient
-    row_sink = _row_grad_sink_for(table) if (need_table and bws_bytes and gate is None and acc is None) else None
-    # the token-list backwards overwrite the whole table gradient; the window scatter accumulates into zeros
-    dtable = None
-    if need_table and row_sink is None:
-        dtable = torch.empty_like(table) if (bws_bytes or list_bytes) else torch.zeros_like(table)
-    # the token-product backward zeroes dgate in the launch that zeroes its G rows; the window scatter accumulates into zeros
-    dgate = (torch.empty_like(gate) if bws_bytes else torch.zeros_like(gate)) if need_gate else None
-    wsn = L_.rbr_textcnn_bwd_ws_floats(C.byref(desc))
-    wsb = torch.empty(max(wsn, 1), dtype=F32, device=dev)
-    st = current_stream()
-    common = (C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"), dev_ptr(gate, F32, "gate"),
-              dev_ptr(table, F32, "table"))
-    # many short documents (NARRE's reviews): dW = G^T @ table[distinct tokens] on the MFMA pipe, from the G the
-    # table-gradient call builds anyway (0 floats of workspace = not this shape: the window-row kernels below)
-    dwg_floats = L_.rbr_textcnn_bwd_dw_from_g_ws_floats(C.byref(desc)) if (need_table and bws_bytes) else 0
-    join = None
-    fork = None
-    side = None
-    if not dwg_floats:
-        # the weight-gradient kernels and the table-gradient kernels below both start from d_feat and share nothing
-        # else: the former go to a second stream (fork here, join before returning), so the two chains overlap --
-        # also inside a captured graph, where the fork becomes two parallel branches
-        side = _side_stream(dev) if (need_table or need_gate or use_taps) else None
-        if side is not None:
-            fork = torch.cuda.Event()
-            fork.record()
+    row_sink = _row_grad_sink_for(table) if (need_table and S.gate is None and acc is None) else None
+    flags, out, sq = 0, None, None
+    if row_sink is not None:
+        cap, rot = C.c_int32(0), C.c_void_p()
+        _call(None, L_.rbr_textcnn_token_list, C.byref(desc), S.prod_ws.data_ptr(), C.byref(rot), None, None, C.byref(cap))
+        out = torch.empty(cap.value, table.shape[1], dtype=F32, device=dev)
+        sq = torch.empty(L_.rbr_textcnn_row_grad_partials(C.byref(desc)), dtype=F32, device=dev)   # one per workgroup
+        flags = _lib.G_ROWS
+    elif acc is not None and not dwg_floats:          # shared gradient buffer of the step (table_fanout): rows added, buffer handed back
+        out, flags = acc, _lib.G_ACCUMULATE
+    elif need_table:
+        out = torch.empty_like(table)          # the token-list backwards overwrite the whole table gradient
+    # the token-product backward zeroes dgate in the launch that zeroes its G rows
+    dgate = torch.empty_like(S.gate) if need_gate else None
+    bws = torch.empty(bws_bytes, dtype=torch.uint8, device=dev)
 
-    def run_dw():
-        """The weight-gradient chain, enqueued AFTER the table-gradient chain: in a replayed graph the branch captured first
-        keeps the queue of the nodes before and after the fork, and the join of the other branch into that queue costs
-        ~10 us -- so the longer (table) branch goes first and the step's next kernel follows it without a gap."""
-        if dwg_floats:
-            return join
-        j = None
-        if side is not None:
-            side.wait_event(fork)
-        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-            ev_dw = TIMER.record("textcnn_bwd_dw")
-            check(L_.rbr_textcnn_bwd_dw(*common, dev_ptr(feat, F32, "feat"), dev_ptr(argmax, I32, "argmax"),
-                                        dev_ptr(d_feat, F32, "d_feat"), ptr_array(dWs, F32, "dW"),
-                                        ptr_array(dbs, F32, "dbias"), dev_ptr(wsb, F32, "ws"), current_stream()),
-                  "rbr_textcnn_bwd_dw")
-            if ev_dw is not None:
-                ev_dw.record()
-            if side is not None:
-                j = torch.cuda.Event()
-                j.record()
-        return j
+    def g(key, phases):
+        _g_chain(key, phases, st, desc, (S.ids, S.mask8, S.gate, S.feat, S.argmax, d_feat), S.prod_ws, bws, out, dgate, sq)
 
+    fork = None if dwg_floats else _Fork(dev)          # the weight chain of _bwd_dw, forked ahead of the table chain
     ev = TIMER.record("textcnn_bwd_dtable")
-    if fixed_dtable is not None:          # table gradient done above (order-free fixed-point sums); the weight gradient remains
-        if ev is not None:
-            ev.record()
-        _join(run_dw())
-        return fixed_dtable, dgate, dWs, dbs
-    if use_taps:
-        tok, val = sink.local_buffers(L_.rbr_textcnn_taps_count(C.byref(desc)), dev)
-        check(L_.rbr_textcnn_bwd_taps(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                      dev_ptr(feat, F32, "feat"), dev_ptr(argmax, I32, "argmax"),
-                                      dev_ptr(d_feat, F32, "d_feat"), dev_ptr(tok, I32, "tap tokens"),
-                                      dev_ptr(val, F32, "tap values"), st), "rbr_textcnn_bwd_taps")
-        sink.record(desc, list(ws))
-        if ev is not None:
-            ev.record()
-        _join(run_dw())
-        return None, dgate, dWs, dbs
-    if (need_table or need_gate) and bws_bytes:
-        # token-product backward: dtable = G @ Wprod^T over the forward's distinct-token list (no atomics on the
-        # table); d(gate) of gated convs (D-ATT) is read off the forward's product table
-        zeroed = S.bws is not None                    # the forward's gather launch cleared G's rows
-        bws = S.bws if zeroed else torch.empty(bws_bytes, dtype=torch.uint8, device=dev)
-        flags = _lib.G_ZEROED if zeroed else 0
-        rows = sq = None
-        if row_sink is not None:
-            cap = C.c_int32(0)
-            rot = C.c_void_p()
-            check(L_.rbr_textcnn_token_list(C.byref(desc), S.prod_ws.data_ptr(), C.byref(rot), None, None, C.byref(cap)),
-                  "rbr_textcnn_token_list")
-            rows = torch.empty(cap.value, table.shape[1], dtype=F32, device=dev)
-            sq = torch.empty(L_.rbr_textcnn_row_grad_partials(C.byref(desc)), dtype=F32, device=dev)   # one per workgroup
-            flags |= _lib.G_ROWS
-        out = rows if rows is not None else dtable
+    if dwg_floats or (ev is not None and out is not None):
+        g(None, _lib.G_BUILD)
         if dwg_floats:
             # G first; then its two consumers side by side: dtable = G @ Wprod^T on this stream, dW = G^T @ table rows on the
             # second one (fork after the build, join before returning; two parallel branches in a captured graph)
-            check(L_.rbr_textcnn_bwd_dtable_prod_ex(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                                    dev_ptr(gate, F32, "gate"), dev_ptr(feat, F32, "feat"),
-                                                    dev_ptr(argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"),
-                                                    S.prod_ws.data_ptr(), bws.data_ptr(), None, dev_ptr(dgate, F32, "dgate"), None,
-                                                    _lib.G_BUILD | (flags & _lib.G_ZEROED), st), "rbr_textcnn_bwd_g_build")
             dwg_ws = torch.empty(dwg_floats, dtype=F32, device=dev)
-            side = _side_stream(dev)
-            if side is not None:
-                fork = torch.cuda.Event()
-                fork.record()
-                side.wait_event(fork)
-            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                ev2 = TIMER.record("textcnn_bwd_dw")
-                check(L_.rbr_textcnn_bwd_dw_from_g(C.byref(desc), dev_ptr(table, F32, "table"), dev_ptr(feat, F32, "feat"),
-                                                   dev_ptr(d_feat, F32, "d_feat"), S.prod_ws.data_ptr(), bws.data_ptr(),
-                                                   ptr_array(dWs, F32, "dW"), ptr_array(dbs, F32, "dbias"),
-                                                   dev_ptr(dwg_ws, F32, "ws"), current_stream()), "rbr_textcnn_bwd_dw_from_g")
-                if ev2 is not None:
-                    ev2.record()
-                if side is not None:
-                    join = torch.cuda.Event()
-                    join.record()
-            if need_table:
-                ev3 = TIMER.record("textcnn_bwd_g_product")
-                check(L_.rbr_textcnn_bwd_dtable_prod_ex(C.byref(desc), None, None, None, None, None, None, S.prod_ws.data_ptr(),
-                                                        bws.data_ptr(), dev_ptr(out, F32, "dtable"), None, dev_ptr(sq, F32, "sq_part"),
-                                                        _lib.G_PRODUCT | (flags & _lib.G_ROWS), st), "rbr_textcnn_bwd_g_product")
-                if ev3 is not None:
-                    ev3.record()
-            if ev is not None:
-                ev.record()
-            _join(join)
+            fork = _Fork(dev)
+            with fork:
+                _call("textcnn_bwd_dw", L_.rbr_textcnn_bwd_dw_from_g, C.byref(desc), dev_ptr(table, F32, "table"),
+                      dev_ptr(S.feat, F32, "feat"), dev_ptr(d_feat, F32, "d_feat"), S.prod_ws.data_ptr(), bws.data_ptr(),
+                      ptr_array(dWs, F32, "dW"), ptr_array(dbs, F32, "dbias"), dev_ptr(dwg_ws, F32, "ws"), current_stream())
         else:
-            if acc is not None:          # shared gradient buffer of the step (table_fanout): rows added, buffer handed back
-                dtable = out = acc
-                flags |= _lib.G_ACCUMULATE
-            if ev is not None and out is not None:
-                # timing pass (bench.py): the call's two phases as two calls, so that the sparse product (ONE launch,
-                # g_times_w) gets HIP events of its own -- same kernels, same order, same arguments
-                check(L_.rbr_textcnn_bwd_dtable_prod_ex(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                                        dev_ptr(gate, F32, "gate"), dev_ptr(feat, F32, "feat"),
-                                                        dev_ptr(argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"),
-                                                        S.prod_ws.data_ptr(), bws.data_ptr(), None, dev_ptr(dgate, F32, "dgate"),
-                                                        None, _lib.G_BUILD | (flags & _lib.G_ZEROED), st), "rbr_textcnn_bwd_g_build")
-                ev.record()
-                ev = TIMER.record("textcnn_bwd_g_product")
-                check(L_.rbr_textcnn_bwd_dtable_prod_ex(C.byref(desc), None, None, None, None, None, None, S.prod_ws.data_ptr(),
-                                                        bws.data_ptr(), dev_ptr(out, F32, "dtable"), None, dev_ptr(sq, F32, "sq_part"),
-                                                        _lib.G_PRODUCT | (flags & (_lib.G_ROWS | _lib.G_ACCUMULATE)), st),
-                      "rbr_textcnn_bwd_g_product")
-                ev.record()
-                ev = None
-            else:
-                check(L_.rbr_textcnn_bwd_dtable_prod_ex(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                                        dev_ptr(gate, F32, "gate"), dev_ptr(feat, F32, "feat"),
-                                                        dev_ptr(argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"),
-                                                        S.prod_ws.data_ptr(), bws.data_ptr(), dev_ptr(out, F32, "dtable"),
-                                                        dev_ptr(dgate, F32, "dgate"), dev_ptr(sq, F32, "sq_part"),
-                                                        _lib.G_BUILD | _lib.G_PRODUCT | flags, st), "rbr_textcnn_bwd_dtable_prod")
-            if ev is not None:
-                ev.record()
-            _join(run_dw())
-        if rows is not None:
-            row_sink.put_row_grad(table, RowGradient(table, rows, sq, rot.value, S.prod_ws))
-            return None, dgate, dWs, dbs
-        return dtable, dgate, dWs, dbs
-    if list_bytes:
-        lws = torch.empty(list_bytes, dtype=torch.uint8, device=dev)
-        check(L_.rbr_textcnn_bwd_dtable_list(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                             ptr_array(ws, F32, "conv weight"), dev_ptr(feat, F32, "feat"),
-                                             dev_ptr(argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"), lws.data_ptr(),
-                                             dev_ptr(dtable, F32, "dtable"), st), "rbr_textcnn_bwd_dtable_list")
-        if ev is not None:
+            # timing pass (bench.py): the call's two phases as two calls, so that the sparse product (ONE launch,
+            # g_times_w) gets HIP events of its own -- same kernels, same order, same arguments
             ev.record()
-        _join(run_dw())
-        return dtable, dgate, dWs, dbs
-    if packed is None:
-        packed = _TextCNN._pack(L_, desc, ws, L_.rbr_textcnn_packed_floats(C.byref(desc)), dev, st)
-    check(L_.rbr_textcnn_bwd_dtable(*common, dev_ptr(packed, F32, "packed"), dev_ptr(feat, F32, "feat"),
-                                    dev_ptr(argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"),
-                                    dev_ptr(dtable, F32, "dtable"), dev_ptr(dgate, F32, "dgate"), st),
-          "rbr_textcnn_bwd_dtable")
+            ev = None
+        g("textcnn_bwd_g_product", _lib.G_PRODUCT | flags)
+    else:
+        g(None, _lib.G_BUILD | _lib.G_PRODUCT | flags)
     if ev is not None:
         ev.record()
-    _join(run_dw())
-    return dtable, dgate, dWs, dbs
+    if dwg_floats:
+        fork.join()
+    else:
+        _bwd_dw(S, d_feat, dWs, dbs, fork)
+    if row_sink is not None:
+        row_sink.put_row_grad(table, RowGradient(table, out, sq, rot.value, S.prod_ws))
+        return None, dgate
+    return out, dgate
+
+
+def _bwd_token_list(S, d_feat, list_bytes, dWs, dbs):
+    """Dense forward (no token list of its own), un-gated: the table gradient still goes through a distinct-token list built
+    here (16 us) instead of the window scatter's row of f32 atomics per (document, channel, tap)."""
+    dev = S.table.device
+    dtable = torch.empty_like(S.table)          # the token-list backwards overwrite the whole table gradient
+    lws = torch.empty(list_bytes, dtype=torch.uint8, device=dev)
+    fork = _Fork(dev)
+    _call("textcnn_bwd_dtable", _lib.lib().rbr_textcnn_bwd_dtable_list, C.byref(S.desc), dev_ptr(S.ids, I64, "ids"),
+          dev_ptr(S.mask8, U8, "mask"), ptr_array(S.ws, F32, "conv weight"), dev_ptr(S.feat, F32, "feat"),
+          dev_ptr(S.argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"), lws.data_ptr(), dev_ptr(dtable, F32, "dtable"),
+          current_stream())
+    _bwd_dw(S, d_feat, dWs, dbs, fork)
+    return dtable, None
+
+
+def _bwd_window_scatter(S, d_feat, need_table, need_gate, dWs, dbs):
+    """Window scatter (rbr_textcnn_bwd_dtable): a row of f32 atomics per (document, channel, tap) into zeros, dgate likewise.
+    Also where a backward that owes neither gradient ends up: the call then returns at once.  Returns (dtable, dgate)."""
+    L_ = _lib.lib()
+    dev = S.table.device
+    dtable = torch.zeros_like(S.table) if need_table else None
+    dgate = torch.zeros_like(S.gate) if need_gate else None
+    fork = _Fork(dev, on=need_table or need_gate)
+    st = current_stream()
+    with _timed("textcnn_bwd_dtable"):
+        packed = S.packed
+        if packed is None:
+            packed = _TextCNN._pack(L_, S.desc, S.ws, L_.rbr_textcnn_packed_floats(C.byref(S.desc)), dev, st)
+        _call(None, L_.rbr_textcnn_bwd_dtable, C.byref(S.desc), dev_ptr(S.ids, I64, "ids"), dev_ptr(S.mask8, U8, "mask"),
+              dev_ptr(S.gate, F32, "gate"), dev_ptr(S.table, F32, "table"), dev_ptr(packed, F32, "packed"),
+              dev_ptr(S.feat, F32, "feat"), dev_ptr(S.argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"),
+              dev_ptr(dtable, F32, "dtable"), dev_ptr(dgate, F32, "dgate"), st)
+    _bwd_dw(S, d_feat, dWs, dbs, fork)
+    return dtable, dgate
 
 
 # ---- compact row gradient of an embedding table (consumer: train_step.HipClipAdam) ------------------------------------------
@@ -628,8 +676,8 @@ class RowGradient:
 
     def to_dense(self) -> torch.Tensor:
         dense = torch.empty(self.V, self.D, dtype=F32, device=self.rows.device)
-        check(_lib.lib().rbr_row_grad_to_dense(self.V, self.D, self.row_of_token_ptr, dev_ptr(self.rows, F32, "rows"),
-                                               dev_ptr(dense, F32, "dense"), current_stream()), "rbr_row_grad_to_dense")
+        _call(None, _lib.lib().rbr_row_grad_to_dense, self.V, self.D, self.row_of_token_ptr, dev_ptr(self.rows, F32, "rows"),
+              dev_ptr(dense, F32, "dense"), current_stream())
         return dense
 
 
@@ -652,6 +700,13 @@ def _join(event) -> None:
         torch.cuda.current_stream().wait_event(event)
 
 
+def _pad_runs_flag(pad_runs: bool, mask, padding_idx) -> int:
+    """CONV_PAD_RUNS when the caller vouches for the runs of padding (see textcnn), the conv is un-masked and has a padding
+    token, and RBR_PAD_RUNS=0 does not switch the encoding off."""
+    on = pad_runs and mask is None and padding_idx is not None and os.environ.get("RBR_PAD_RUNS", "1") != "0"
+    return _lib.CONV_PAD_RUNS if on else 0
+
+
 def textcnn(table: torch.Tensor, ids: torch.Tensor, mask: Optional[torch.Tensor], weights: Sequence[torch.Tensor],
             biases: Sequence[torch.Tensor], *, gate=None, pad_mode: int = PAD_SAME,
             act: int = ACT_RELU, padding_idx: Optional[int] = 0, return_argmax: bool = False, pad_runs: bool = False,
@@ -663,8 +718,7 @@ def textcnn(table: torch.Tensor, ids: torch.Tensor, mask: Optional[torch.Tensor]
     pad_runs (un-masked convs only): the caller vouches that `gate` is the same at every position whose tokens are all
     padding_idx within 8 positions either side (RBR_CONV_PAD_RUNS): runs of padding are then encoded once, exactly."""
     kernel_sizes = tuple(int(w.shape[2]) for w in weights)
-    flags = _lib.CONV_PAD_RUNS if (pad_runs and mask is None and padding_idx is not None
-                                   and os.environ.get("RBR_PAD_RUNS", "1") != "0") else 0
+    flags = _pad_runs_flag(pad_runs, mask, padding_idx)
     if gate_split:
         # two gates (RBR_CONV_GATE_SPLIT): banks [0, gate_split) under gate[0], the rest under gate[1]; token-product path only
         if not (isinstance(gate, (tuple, list)) and len(gate) == 2 and 0 < gate_split < len(weights)):
@@ -679,9 +733,7 @@ def textcnn_product_applies(table: torch.Tensor, ids: torch.Tensor, weights: Seq
                             padding_idx: Optional[int]) -> bool:
     """True when textcnn() over these shapes runs the token-product formulation, forward AND table-gradient backward (the only
     one that takes a split gate)."""
-    V, D = table.shape
-    desc = _lib.make_desc(ids.shape[0], ids.shape[1], D, V, [int(w.shape[2]) for w in weights], [int(w.shape[0]) for w in weights],
-                          pad_mode, act, padding_idx, 0)
+    desc = _conv_desc(table, ids.shape[0], ids.shape[1], weights, pad_mode, act, padding_idx)
     L_ = _lib.lib()
     return bool(table.is_cuda and L_.rbr_textcnn_fwd_ws_bytes(C.byref(desc)) > 0 and L_.rbr_textcnn_bwd_prod_ws_bytes(C.byref(desc)) > 0)
 
@@ -726,19 +778,17 @@ class _PairHead(torch.autograd.Function):
             flat = torch.empty(acc_n, dtype=F32, device=dev) if acc_n else None
             seed, state = _drop_rng(dev)
             drop = torch.empty(B, K, dtype=F32, device=dev) if p_drop > 0.0 else None
-            check(L_.rbr_pair_head_fwd_train(B, H, K, dev_ptr(u_feat, F32, "u_feat"), dev_ptr(i_feat, F32, "i_feat"),
-                                             dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp), float(p_drop),
-                                             seed, state.data_ptr(), dev_ptr(drop, F32, "drop"), dev_ptr(flat, F32, "zero_buf"),
-                                             acc_n, dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(pred, F32, "pred"),
-                                             current_stream()), "rbr_pair_head_fwd_train")
+            _call(None, L_.rbr_pair_head_fwd_train, B, H, K, dev_ptr(u_feat, F32, "u_feat"), dev_ptr(i_feat, F32, "i_feat"),
+                  dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp), float(p_drop), seed, state.data_ptr(),
+                  dev_ptr(drop, F32, "drop"), dev_ptr(flat, F32, "zero_buf"), acc_n, dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"),
+                  dev_ptr(pred, F32, "pred"), current_stream())
             ctx.flat = flat
         else:
             if drop is not None:
                 drop = drop.contiguous()
-            check(L_.rbr_pair_head_fwd(B, H, K, dev_ptr(u_feat, F32, "u_feat"), dev_ptr(i_feat, F32, "i_feat"),
-                                       dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp),
-                                       dev_ptr(drop, F32, "drop"), dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"),
-                                       dev_ptr(pred, F32, "pred"), current_stream()), "rbr_pair_head_fwd")
+            _call(None, L_.rbr_pair_head_fwd, B, H, K, dev_ptr(u_feat, F32, "u_feat"), dev_ptr(i_feat, F32, "i_feat"),
+                  dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp), dev_ptr(drop, F32, "drop"),
+                  dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(pred, F32, "pred"), current_stream())
         ctx.dims = (B, H, K, int(pad_u), int(pad_i))
         ctx.has_drop = drop is not None
         ctx.save_for_backward(u_feat, i_feat, u_id, i_id, ul, il, *params, *([drop] if drop is not None else []))
@@ -769,12 +819,10 @@ class _PairHead(torch.autograd.Function):
         wsn = L_.rbr_pair_head_bwd_ws_floats(B, K)
         ws = torch.empty(wsn, dtype=F32, device=dev) if wsn else None
         d_pred = d_pred.contiguous()
-        check(L_.rbr_pair_head_bwd(B, H, K, dev_ptr(u_feat, F32, "u_feat"), dev_ptr(i_feat, F32, "i_feat"),
-                                   dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp),
-                                   dev_ptr(drop, F32, "drop"), dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"),
-                                   dev_ptr(d_pred, F32, "d_pred"), pad_u, pad_i, C.byref(hg),
-                                   dev_ptr(d_uf, F32, "d_ufeat"), dev_ptr(d_if, F32, "d_ifeat"), dev_ptr(ws, F32, "ws"),
-                                   current_stream()), "rbr_pair_head_bwd")
+        _call(None, L_.rbr_pair_head_bwd, B, H, K, dev_ptr(u_feat, F32, "u_feat"), dev_ptr(i_feat, F32, "i_feat"),
+              dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp), dev_ptr(drop, F32, "drop"),
+              dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(d_pred, F32, "d_pred"), pad_u, pad_i, C.byref(hg),
+              dev_ptr(d_uf, F32, "d_ufeat"), dev_ptr(d_if, F32, "d_ifeat"), dev_ptr(ws, F32, "ws"), current_stream())
         if ctx.stacked:
             return (d_pair, None, None, None, None, None, None, *grads)
         return (d_uf, d_if, None, None, None, None, None, *grads)
@@ -861,18 +909,13 @@ class _EncodeHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, table, id_sets, ids, mask, u_id, i_id, drop, target, padding_idx, pad_u, pad_i, n_widths, first, *params):
-        ws_, bs_ = [w.contiguous() for w in params[:n_widths]], [b.contiguous() for b in params[n_widths:2 * n_widths]]
+        bs_ = [b.contiguous() for b in params[n_widths:2 * n_widths]]
         head = [t.contiguous() for t in params[2 * n_widths:]]
         L_ = _lib.lib()
         dev = table.device
-        table_c = table.contiguous()
-        dev_ptr(table_c, F32, "word table")
-        V, D = table.shape
-        kernel_sizes = [int(w.shape[2]) for w in ws_]
-        channels = [int(w.shape[0]) for w in ws_]
-        Ctot = sum(channels)
         st = current_stream()
         # ---- clean id tensors: token ids of both towers first (the conv's [2B, L] batch), then the rest
+        sets = None
         if id_sets is not None:
             tens = [t.contiguous() for t, _, _ in id_sets]
             flat = torch.empty(sum(t.numel() for t in tens), dtype=I64, device=dev)
@@ -887,45 +930,17 @@ class _EncodeHead(torch.autograd.Function):
             n_tok = tens[0].numel() + tens[1].numel()
             ids = flat[:n_tok].view(2 * tens[0].shape[0], tens[0].shape[1])
             u_id, i_id = outs[2], outs[3]
+            sets = (len(tens), arr, _id_err(dev).data_ptr())
         else:
-            ids, u_id, i_id = ids.contiguous(), u_id.contiguous(), i_id.contiguous()
-        n_docs, L = ids.shape
-        B = n_docs // 2
-        mask8 = _mask_u8(mask)
-        if mask8 is not None and mask8.shape != ids.shape:
-            raise AssertionError("inputs.shape[:-1] == masks.shape")   # deepconn/utils.py:58
-        desc = _lib.make_desc(n_docs, L, D, V, kernel_sizes, channels, PAD_SAME, ACT_RELU, padding_idx)
-        n_part = L_.rbr_textcnn_partial_elems(C.byref(desc))
-        ws_bytes = L_.rbr_textcnn_fwd_ws_bytes(C.byref(desc))
-        if not n_part or not ws_bytes:
+            u_id, i_id = u_id.contiguous(), i_id.contiguous()
+        table_c, ids, mask8, ws_, desc = _conv_operands(table, ids, mask, params[:n_widths], PAD_SAME, ACT_RELU, padding_idx)
+        B = ids.shape[0] // 2
+        conv = _conv_fwd_buffers(_ConvSaved(), desc, dev)
+        if conv.prod_ws is None:
             check(-1, "encode_head plan (encode_head_applicable() was not consulted)")
-        pval = torch.empty(n_part, dtype=F32, device=dev)
-        pidx = torch.empty(n_part, dtype=I32, device=dev)
-        feat = torch.empty(n_docs, Ctot, dtype=F32, device=dev)
-        argmax = torch.empty(n_docs, Ctot, dtype=I32, device=dev)
-        prod_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        wsp = prod_ws.data_ptr()
+        pval, pidx, feat, argmax = conv.pval, conv.pidx, conv.feat, conv.argmax
         training = any(ctx.needs_input_grad)          # (grad mode itself is off inside forward)
-        ev = TIMER.record("textcnn_prod_prepare")
-        if id_sets is not None:
-            check(L_.rbr_textcnn_prod_prepare_ids(C.byref(desc), len(tens), arr, _id_err(dev).data_ptr(), dev_ptr(ids, I64, "ids"),
-                                                  dev_ptr(mask8, U8, "mask"), ptr_array(ws_, F32, "conv weight"),
-                                                  dev_ptr(pidx, I32, "pidx"), wsp, st), "rbr_textcnn_prod_prepare_ids")
-        else:
-            check(L_.rbr_textcnn_prod_prepare(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                              ptr_array(ws_, F32, "conv weight"), dev_ptr(pidx, I32, "pidx"), wsp, st),
-                  "rbr_textcnn_prod_prepare")
-        if ev is not None:
-            ev.record()
-        ev = TIMER.record("textcnn_prod_table")
-        check(L_.rbr_textcnn_prod_table(C.byref(desc), dev_ptr(table_c, F32, "word table"), wsp, st), "rbr_textcnn_prod_table")
-        if ev is not None:
-            ev.record()
-        ev = TIMER.record("textcnn_prod_pool")
-        check(L_.rbr_textcnn_prod_pool(C.byref(desc), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"), None,
-                                       dev_ptr(pval, F32, "pval"), dev_ptr(pidx, I32, "pidx"), wsp, st), "rbr_textcnn_prod_pool")
-        if ev is not None:
-            ev.record()
+        _prod_forward(desc, conv, table_c, ids, mask8, None, ws_, st, id_sets=sets)
         # ---- pool epilogue + rating head (+ loss)
         K = head[0].shape[1]
         hp = _lib.HeadParams(*[dev_ptr(t, F32, n) for t, n in zip(head, _HEAD_NAMES)])
@@ -950,23 +965,20 @@ class _EncodeHead(torch.autograd.Function):
             target = target.contiguous()
             loss = torch.empty((), dtype=F32, device=dev)
             d_unit = torch.empty(B, dtype=F32, device=dev)
-        ev = TIMER.record("pair_head_fwd_pool")
-        check(L_.rbr_pair_head_fwd_pool(C.byref(desc), dev_ptr(pval, F32, "pval"), dev_ptr(pidx, I32, "pidx"),
-                                        ptr_array(bs_, F32, "conv bias"), dev_ptr(feat, F32, "feat"), dev_ptr(argmax, I32, "argmax"),
-                                        dev_ptr(first, I64, "first"), K, dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp),
-                                        dev_ptr(drop_t, F32, "drop") if p_drop == 0.0 else None, float(p_drop), seed,
-                                        state.data_ptr() if state is not None else None,
-                                        dev_ptr(drop_t, F32, "drop") if p_drop > 0.0 else None, dev_ptr(flat_zero, F32, "zero_buf"),
-                                        acc_n, dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(pred, F32, "pred"),
-                                        dev_ptr(target, F32, "target"), dev_ptr(loss, F32, "loss"), dev_ptr(d_unit, F32, "d_unit"),
-                                        _ticket(dev).data_ptr() if target is not None else None, st), "rbr_pair_head_fwd_pool")
-        if ev is not None:
-            ev.record()
+        _call("pair_head_fwd_pool", L_.rbr_pair_head_fwd_pool, C.byref(desc), dev_ptr(pval, F32, "pval"), dev_ptr(pidx, I32, "pidx"),
+              ptr_array(bs_, F32, "conv bias"), dev_ptr(feat, F32, "feat"), dev_ptr(argmax, I32, "argmax"),
+              dev_ptr(first, I64, "first"), K, dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp),
+              dev_ptr(drop_t, F32, "drop") if p_drop == 0.0 else None, float(p_drop), seed,
+              state.data_ptr() if state is not None else None,
+              dev_ptr(drop_t, F32, "drop") if p_drop > 0.0 else None, dev_ptr(flat_zero, F32, "zero_buf"),
+              acc_n, dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(pred, F32, "pred"),
+              dev_ptr(target, F32, "target"), dev_ptr(loss, F32, "loss"), dev_ptr(d_unit, F32, "d_unit"),
+              _ticket(dev).data_ptr() if target is not None else None, st)
         ctx.conv = _ConvSaved(table=table_c, ids=ids, packed=None, feat=feat, argmax=argmax, mask8=mask8, gate=None, ws=ws_,
-                              desc=desc, prod_ws=prod_ws, fanout_acc=None, bws=None)
+                              desc=desc, prod_ws=conv.prod_ws, fanout_acc=None)
         ctx.head = (u_id, i_id, ul, il, head, drop_t, flat_zero, d_unit)
         ctx.first = first
-        ctx.dims = (B, Ctot, K, int(pad_u), int(pad_i), n_widths)
+        ctx.dims = (B, feat.shape[1], K, int(pad_u), int(pad_i), n_widths)
         ctx.set_materialize_grads(False)
         if loss is None:
             loss = torch.empty((), dtype=F32, device=dev)      # no target: an unwritten placeholder nobody reads
@@ -998,15 +1010,13 @@ class _EncodeHead(torch.autograd.Function):
         d_pair = torch.empty(2 * B, H, dtype=F32, device=dev)
         feat = S.feat
         need_conv = any(ctx.needs_input_grad[13:13 + 2 * n_widths]) or ctx.needs_input_grad[0]
-        check(L_.rbr_pair_head_bwd(B, H, K, dev_ptr(feat[:B], F32, "u_feat"), dev_ptr(feat[B:], F32, "i_feat"),
-                                   dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp),
-                                   dev_ptr(drop_t, F32, "drop"), dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"),
-                                   dev_ptr(d_pred, F32, "d_pred"), pad_u, pad_i, C.byref(hg),
-                                   dev_ptr(d_pair[:B], F32, "d_ufeat"), dev_ptr(d_pair[B:], F32, "d_ifeat"), None,
-                                   current_stream()), "rbr_pair_head_bwd")
+        _call(None, L_.rbr_pair_head_bwd, B, H, K, dev_ptr(feat[:B], F32, "u_feat"), dev_ptr(feat[B:], F32, "i_feat"),
+              dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp), dev_ptr(drop_t, F32, "drop"),
+              dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(d_pred, F32, "d_pred"), pad_u, pad_i, C.byref(hg),
+              dev_ptr(d_pair[:B], F32, "d_ufeat"), dev_ptr(d_pair[B:], F32, "d_ifeat"), None, current_stream())
         if need_conv and ctx.first is not None:      # in-batch dedup: the repeated documents' gradient rows onto their first occurrence
-            check(L_.rbr_dedup_fold_rows(2 * B, H, dev_ptr(ctx.first, I64, "first"), dev_ptr(d_pair, F32, "d_feat"), current_stream()),
-                  "rbr_dedup_fold_rows")
+            _call(None, L_.rbr_dedup_fold_rows, 2 * B, H, dev_ptr(ctx.first, I64, "first"), dev_ptr(d_pair, F32, "d_feat"),
+                  current_stream())
         if need_conv:
             dtable, _, dWs, dbs = _textcnn_backward(S, d_pair, ctx.needs_input_grad[0], False)
         else:
@@ -1079,8 +1089,8 @@ def dropout_multiplier(shape, p: float, training: bool, device, lane: int = 0) -
     dev = torch.device(device)
     seed, state = _drop_rng(dev, lane)
     out = torch.empty(shape, dtype=F32, device=dev)
-    check(_lib.lib().rbr_dropout_multiplier(out.numel(), float(p), seed, state.data_ptr(), dev_ptr(out, F32, "out"),
-                                            current_stream()), "rbr_dropout_multiplier")
+    _call(None, _lib.lib().rbr_dropout_multiplier, out.numel(), float(p), seed, state.data_ptr(), dev_ptr(out, F32, "out"),
+          current_stream())
     return out
 
 
@@ -1115,9 +1125,8 @@ class _MseLoss(torch.autograd.Function):
             raise RuntimeError(f"mse_loss: pred {tuple(pred.shape)} vs target {tuple(target.shape)}")
         loss = torch.empty((), dtype=F32, device=pred.device)
         d_unit = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
-        check(_lib.lib().rbr_mse_loss_fwd(pred.numel(), dev_ptr(pred, F32, "pred"), dev_ptr(target, F32, "target"),
-                                          dev_ptr(loss, F32, "loss"), dev_ptr(d_unit, F32, "d_pred_unit"), current_stream()),
-              "rbr_mse_loss_fwd")
+        _call(None, _lib.lib().rbr_mse_loss_fwd, pred.numel(), dev_ptr(pred, F32, "pred"), dev_ptr(target, F32, "target"),
+              dev_ptr(loss, F32, "loss"), dev_ptr(d_unit, F32, "d_pred_unit"), current_stream())
         ctx.save_for_backward(pred, target, *([d_unit] if d_unit is not None else []))
         return loss
 
@@ -1129,9 +1138,8 @@ class _MseLoss(torch.autograd.Function):
             return ctx.saved_tensors[2], None
         d_pred = torch.empty_like(pred)
         d_loss = d_loss.contiguous()
-        check(_lib.lib().rbr_mse_loss_bwd(pred.numel(), dev_ptr(pred, F32, "pred"), dev_ptr(target, F32, "target"),
-                                          dev_ptr(d_loss, F32, "d_loss"), dev_ptr(d_pred, F32, "d_pred"), current_stream()),
-              "rbr_mse_loss_bwd")
+        _call(None, _lib.lib().rbr_mse_loss_bwd, pred.numel(), dev_ptr(pred, F32, "pred"), dev_ptr(target, F32, "target"),
+              dev_ptr(d_loss, F32, "d_loss"), dev_ptr(d_pred, F32, "d_pred"), current_stream())
         return d_pred, None
 
 
@@ -1174,9 +1182,9 @@ class _ReviewAttn(torch.autograd.Function):
         drop = drop.contiguous() if drop is not None else None
         if drop is not None and tuple(drop.shape) != (B, H):
             raise RuntimeError(f"review_attention: dropout multiplier {tuple(drop.shape)} is not [B, H] = {(B, H)}")
-        check(L_.rbr_review_attn_fwd(B, R, H, A, dev_ptr(feat, F32, "feat"), dev_ptr(other_id, I64, "other_id"), C.byref(ap),
-                                     dev_ptr(drop, F32, "drop"), dev_ptr(out, F32, "out"), dev_ptr(att, F32, "att"),
-                                     dev_ptr(hid, F32, "hid"), current_stream()), "rbr_review_attn_fwd")
+        _call(None, L_.rbr_review_attn_fwd, B, R, H, A, dev_ptr(feat, F32, "feat"), dev_ptr(other_id, I64, "other_id"), C.byref(ap),
+              dev_ptr(drop, F32, "drop"), dev_ptr(out, F32, "out"), dev_ptr(att, F32, "att"), dev_ptr(hid, F32, "hid"),
+              current_stream())
         ctx.dims = (B, R, H, A, int(pad_idx))
         ctx.has_drop = drop is not None
         ctx.set_materialize_grads(False)     # an unused `att` output arrives as None in backward, not as a freshly filled zero tensor
@@ -1199,11 +1207,10 @@ class _ReviewAttn(torch.autograd.Function):
         ws = torch.empty(L_.rbr_review_attn_bwd_ws_floats(B, R, H, A), dtype=F32, device=dev)
         d_out = d_out.contiguous() if d_out is not None else torch.zeros(B, H, dtype=F32, device=dev)
         d_att = d_att.contiguous() if d_att is not None else None
-        check(L_.rbr_review_attn_bwd(B, R, H, A, dev_ptr(feat, F32, "feat"), dev_ptr(other_id, I64, "other_id"), C.byref(ap),
-                                     dev_ptr(drop, F32, "drop"), dev_ptr(att, F32, "att"), dev_ptr(hid, F32, "hid"),
-                                     dev_ptr(d_out, F32, "d_out"), dev_ptr(d_att, F32, "d_att"), pad_idx, C.byref(ag),
-                                     dev_ptr(d_feat, F32, "d_feat"), dev_ptr(ws, F32, "ws"), current_stream()),
-              "rbr_review_attn_bwd")
+        _call(None, L_.rbr_review_attn_bwd, B, R, H, A, dev_ptr(feat, F32, "feat"), dev_ptr(other_id, I64, "other_id"), C.byref(ap),
+              dev_ptr(drop, F32, "drop"), dev_ptr(att, F32, "att"), dev_ptr(hid, F32, "hid"), dev_ptr(d_out, F32, "d_out"),
+              dev_ptr(d_att, F32, "d_att"), pad_idx, C.byref(ag), dev_ptr(d_feat, F32, "d_feat"), dev_ptr(ws, F32, "ws"),
+              current_stream())
         return (d_feat, None, None, *grads, None)
 
 
@@ -1229,9 +1236,9 @@ class _ReviewAttn2(torch.autograd.Function):
         out = torch.empty(2, B, H, dtype=F32, device=dev)
         att = torch.empty(2, B, R, 1, dtype=F32, device=dev)
         hid = torch.empty(2, B, R, A, dtype=F32, device=dev)
-        check(L_.rbr_review_attn2_fwd(B, R, H, A, dev_ptr(feat, F32, "feat"), dev_ptr(other_id, I64, "other_id"), C.byref(aps[0]),
-                                      C.byref(aps[1]), dev_ptr(drop, F32, "drop"), dev_ptr(out, F32, "out"), dev_ptr(att, F32, "att"),
-                                      dev_ptr(hid, F32, "hid"), current_stream()), "rbr_review_attn2_fwd")
+        _call(None, L_.rbr_review_attn2_fwd, B, R, H, A, dev_ptr(feat, F32, "feat"), dev_ptr(other_id, I64, "other_id"),
+              C.byref(aps[0]), C.byref(aps[1]), dev_ptr(drop, F32, "drop"), dev_ptr(out, F32, "out"), dev_ptr(att, F32, "att"),
+              dev_ptr(hid, F32, "hid"), current_stream())
         ctx.dims = (B, R, H, A, int(pad0), int(pad1))
         ctx.has_drop = drop is not None
         ctx.set_materialize_grads(False)
@@ -1254,11 +1261,10 @@ class _ReviewAttn2(torch.autograd.Function):
         ws = torch.empty(2 * L_.rbr_review_attn_bwd_ws_floats(B, R, H, A), dtype=F32, device=dev)
         d_out = d_out.contiguous() if d_out is not None else torch.zeros(2, B, H, dtype=F32, device=dev)
         d_att = d_att.contiguous() if d_att is not None else None
-        check(L_.rbr_review_attn2_bwd(B, R, H, A, dev_ptr(feat, F32, "feat"), dev_ptr(other_id, I64, "other_id"), C.byref(aps[0]),
-                                      C.byref(aps[1]), dev_ptr(drop, F32, "drop"), dev_ptr(att, F32, "att"), dev_ptr(hid, F32, "hid"),
-                                      dev_ptr(d_out, F32, "d_out"), dev_ptr(d_att, F32, "d_att"), pad0, pad1, C.byref(ags[0]),
-                                      C.byref(ags[1]), params[5].shape[0], params[11].shape[0], dev_ptr(d_feat, F32, "d_feat"),
-                                      dev_ptr(ws, F32, "ws"), current_stream()), "rbr_review_attn2_bwd")
+        _call(None, L_.rbr_review_attn2_bwd, B, R, H, A, dev_ptr(feat, F32, "feat"), dev_ptr(other_id, I64, "other_id"),
+              C.byref(aps[0]), C.byref(aps[1]), dev_ptr(drop, F32, "drop"), dev_ptr(att, F32, "att"), dev_ptr(hid, F32, "hid"),
+              dev_ptr(d_out, F32, "d_out"), dev_ptr(d_att, F32, "d_att"), pad0, pad1, C.byref(ags[0]), C.byref(ags[1]),
+              params[5].shape[0], params[11].shape[0], dev_ptr(d_feat, F32, "d_feat"), dev_ptr(ws, F32, "ws"), current_stream())
         return (d_feat, None, None, None, None, *grads)
 
 
@@ -1282,8 +1288,8 @@ class _BlockCat(torch.autograd.Function):
         if c.shape != a.shape or d.shape != b.shape or b.shape[0] != B:
             raise RuntimeError("block_cat: expected a, c [B, C1] and b, d [B, C2]")
         out = torch.empty(2 * B, C1 + C2, dtype=F32, device=a.device)
-        check(_lib.lib().rbr_block_cat(B, C1, C2, dev_ptr(a, F32, "a"), dev_ptr(b, F32, "b"), dev_ptr(c, F32, "c"),
-                                       dev_ptr(d, F32, "d"), dev_ptr(out, F32, "out"), current_stream()), "rbr_block_cat")
+        _call(None, _lib.lib().rbr_block_cat, B, C1, C2, dev_ptr(a, F32, "a"), dev_ptr(b, F32, "b"), dev_ptr(c, F32, "c"),
+              dev_ptr(d, F32, "d"), dev_ptr(out, F32, "out"), current_stream())
         ctx.dims = (B, C1, C2)
         return out
 
@@ -1293,8 +1299,8 @@ class _BlockCat(torch.autograd.Function):
         g = g.contiguous()
         a, c = (torch.empty(B, C1, dtype=F32, device=g.device) for _ in range(2))
         b, d = (torch.empty(B, C2, dtype=F32, device=g.device) for _ in range(2))
-        check(_lib.lib().rbr_block_split(B, C1, C2, dev_ptr(g, F32, "g"), dev_ptr(a, F32, "a"), dev_ptr(b, F32, "b"),
-                                         dev_ptr(c, F32, "c"), dev_ptr(d, F32, "d"), current_stream()), "rbr_block_split")
+        _call(None, _lib.lib().rbr_block_split, B, C1, C2, dev_ptr(g, F32, "g"), dev_ptr(a, F32, "a"), dev_ptr(b, F32, "b"),
+              dev_ptr(c, F32, "c"), dev_ptr(d, F32, "d"), current_stream())
         return a, b, c, d
 
 
@@ -1310,7 +1316,7 @@ class _PairDot(torch.autograd.Function):
         x = x.contiguous()
         B, K = x.shape[0] // 2, x.shape[1]
         out = torch.empty(B, dtype=F32, device=x.device)
-        check(_lib.lib().rbr_pair_dot_fwd(B, K, dev_ptr(x, F32, "x"), dev_ptr(out, F32, "out"), current_stream()), "rbr_pair_dot_fwd")
+        _call(None, _lib.lib().rbr_pair_dot_fwd, B, K, dev_ptr(x, F32, "x"), dev_ptr(out, F32, "out"), current_stream())
         ctx.save_for_backward(x)
         return out
 
@@ -1320,8 +1326,8 @@ class _PairDot(torch.autograd.Function):
         B, K = x.shape[0] // 2, x.shape[1]
         d_x = torch.empty_like(x)
         d_out = d_out.contiguous()
-        check(_lib.lib().rbr_pair_dot_bwd(B, K, dev_ptr(x, F32, "x"), dev_ptr(d_out, F32, "d_out"), dev_ptr(d_x, F32, "d_x"),
-                                          current_stream()), "rbr_pair_dot_bwd")
+        _call(None, _lib.lib().rbr_pair_dot_bwd, B, K, dev_ptr(x, F32, "x"), dev_ptr(d_out, F32, "d_out"), dev_ptr(d_x, F32, "d_x"),
+              current_stream())
         return d_x
 
 
@@ -1346,9 +1352,8 @@ class _Linear(torch.autograd.Function):
         y = torch.empty(N, OUT, dtype=F32, device=x.device)
         wsn = L_.rbr_linear_fwd_ws_floats(N, IN, OUT)          # > 0: the product is split along K (few output tiles)
         ws = torch.empty(wsn, dtype=F32, device=x.device) if wsn else None
-        check(L_.rbr_linear_fwd_ex(N, IN, OUT, dev_ptr(x, F32, "x"), dev_ptr(W, F32, "W"), dev_ptr(b, F32, "b"), int(relu),
-                                   dev_ptr(drop, F32, "drop"), dev_ptr(y, F32, "y"), dev_ptr(ws, F32, "ws"),
-                                   current_stream()), "rbr_linear_fwd_ex")
+        _call(None, L_.rbr_linear_fwd_ex, N, IN, OUT, dev_ptr(x, F32, "x"), dev_ptr(W, F32, "W"), dev_ptr(b, F32, "b"), int(relu),
+              dev_ptr(drop, F32, "drop"), dev_ptr(y, F32, "y"), dev_ptr(ws, F32, "ws"), current_stream())
         ctx.relu = int(relu)
         ctx.has_b = b is not None
         ctx.has_drop = drop is not None
@@ -1368,10 +1373,9 @@ class _Linear(torch.autograd.Function):
         dW = torch.empty_like(W)
         db = torch.empty(OUT, dtype=F32, device=dev) if ctx.has_b else None
         ws = torch.empty(L_.rbr_linear_bwd_ex_ws_floats(N, IN, OUT), dtype=F32, device=dev)
-        check(L_.rbr_linear_bwd_ex(N, IN, OUT, dev_ptr(x, F32, "x"), dev_ptr(W, F32, "W"), dev_ptr(y, F32, "y"),
-                                   dev_ptr(d_y, F32, "d_y"), ctx.relu, dev_ptr(drop, F32, "drop"), dev_ptr(d_x, F32, "d_x"),
-                                   dev_ptr(dW, F32, "dW"), dev_ptr(db, F32, "db"), dev_ptr(ws, F32, "ws"),
-                                   current_stream()), "rbr_linear_bwd_ex")
+        _call(None, L_.rbr_linear_bwd_ex, N, IN, OUT, dev_ptr(x, F32, "x"), dev_ptr(W, F32, "W"), dev_ptr(y, F32, "y"),
+              dev_ptr(d_y, F32, "d_y"), ctx.relu, dev_ptr(drop, F32, "drop"), dev_ptr(d_x, F32, "d_x"), dev_ptr(dW, F32, "dW"),
+              dev_ptr(db, F32, "db"), dev_ptr(ws, F32, "ws"), current_stream())
         return d_x, dW, db, None, None
 
 
@@ -1391,8 +1395,8 @@ class _ConvShiftAdd(torch.autograd.Function):
         kz = (C.c_int32 * n)(*[int(k) for k in kernel_sizes])
         ch = (C.c_int32 * n)(*[int(c) for c in channels])
         out = torch.empty(bz, sum(channels), L, dtype=F32, device=t.device)
-        check(_lib.lib().rbr_conv_shift_add_fwd(bz, L, n, kz, ch, dev_ptr(t, F32, "T"), ptr_array(bs, F32, "bias"), dev_ptr(out, F32, "out"),
-                                                current_stream()), "rbr_conv_shift_add_fwd")
+        _call(None, _lib.lib().rbr_conv_shift_add_fwd, bz, L, n, kz, ch, dev_ptr(t, F32, "T"), ptr_array(bs, F32, "bias"),
+              dev_ptr(out, F32, "out"), current_stream())
         ctx.job = (bz, L, tuple(kernel_sizes), tuple(channels), tuple(t.shape))
         return out
 
@@ -1405,8 +1409,8 @@ class _ConvShiftAdd(torch.autograd.Function):
         d_out = d_out.contiguous()
         dT = torch.empty(tshape, dtype=F32, device=d_out.device)
         dbs = [torch.empty(c, dtype=F32, device=d_out.device) for c in channels]
-        check(_lib.lib().rbr_conv_shift_add_bwd(bz, L, n, kz, ch, dev_ptr(d_out, F32, "d_out"), dev_ptr(dT, F32, "dT"),
-                                                ptr_array(dbs, F32, "dbias"), current_stream()), "rbr_conv_shift_add_bwd")
+        _call(None, _lib.lib().rbr_conv_shift_add_bwd, bz, L, n, kz, ch, dev_ptr(d_out, F32, "d_out"), dev_ptr(dT, F32, "dT"),
+              ptr_array(dbs, F32, "dbias"), current_stream())
         return (dT, None, None, None, None, *dbs)
 
 
@@ -1435,9 +1439,9 @@ class _ReviewBag(torch.autograd.Function):
         drop = drop.contiguous() if drop is not None else None
         out = torch.empty(n_rev, D, dtype=F32, device=table.device)
         inv_len = torch.empty(n_rev, dtype=F32, device=table.device)
-        check(L_.rbr_review_bag_fwd(n_rev, T, D, dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                    dev_ptr(table_c, F32, "word table"), dev_ptr(drop, F32, "drop"), dev_ptr(out, F32, "out"),
-                                    dev_ptr(inv_len, F32, "inv_len"), current_stream()), "rbr_review_bag_fwd")
+        _call(None, L_.rbr_review_bag_fwd, n_rev, T, D, dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
+              dev_ptr(table_c, F32, "word table"), dev_ptr(drop, F32, "drop"), dev_ptr(out, F32, "out"),
+              dev_ptr(inv_len, F32, "inv_len"), current_stream())
         ctx.dims = (n_rev, T, D, -1 if padding_idx is None else int(padding_idx), tuple(table.shape))
         ctx.has_mask, ctx.has_drop = mask8 is not None, drop is not None
         ctx.save_for_backward(ids, inv_len, *([mask8] if mask8 is not None else []), *([drop] if drop is not None else []))
@@ -1460,10 +1464,9 @@ class _ReviewBag(torch.autograd.Function):
         d_out = d_out.contiguous()
         L_ = _lib.lib()
         ws = torch.empty(L_.rbr_review_bag_bwd_ws_bytes(n_rev, T), dtype=torch.uint8, device=d_out.device)
-        check(L_.rbr_review_bag_bwd(n_rev, T, D, shape[0], dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                    dev_ptr(drop, F32, "drop"), dev_ptr(inv_len, F32, "inv_len"),
-                                    dev_ptr(d_out, F32, "d_out"), pad, dev_ptr(dtable, F32, "dtable"), ws.data_ptr(),
-                                    current_stream()), "rbr_review_bag_bwd")
+        _call(None, L_.rbr_review_bag_bwd, n_rev, T, D, shape[0], dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
+              dev_ptr(drop, F32, "drop"), dev_ptr(inv_len, F32, "inv_len"), dev_ptr(d_out, F32, "d_out"), pad,
+              dev_ptr(dtable, F32, "dtable"), ws.data_ptr(), current_stream())
         return dtable, None, None, None, None
 
 
@@ -1491,11 +1494,10 @@ class _AdditiveAttn(torch.autograd.Function):
         out = torch.empty(B, H, dtype=F32, device=dev)
         scores = torch.empty(B, R, dtype=F32, device=dev)
         t = torch.empty(B, R, K, dtype=F32, device=dev)
-        check(L_.rbr_additive_attn_fwd(B, R, H, K, dev_ptr(rev, F32, "inputs"), dev_ptr(mask8, U8, "mask"),
-                                       dev_ptr(node_drop, F32, "node_drop"), dev_ptr(Wp, F32, "proj weight"),
-                                       dev_ptr(bp, F32, "proj bias"), dev_ptr(wi, F32, "inner_product weight"),
-                                       dev_ptr(out, F32, "out"), dev_ptr(scores, F32, "scores"), dev_ptr(t, F32, "t"),
-                                       current_stream()), "rbr_additive_attn_fwd")
+        _call(None, L_.rbr_additive_attn_fwd, B, R, H, K, dev_ptr(rev, F32, "inputs"), dev_ptr(mask8, U8, "mask"),
+              dev_ptr(node_drop, F32, "node_drop"), dev_ptr(Wp, F32, "proj weight"), dev_ptr(bp, F32, "proj bias"),
+              dev_ptr(wi, F32, "inner_product weight"), dev_ptr(out, F32, "out"), dev_ptr(scores, F32, "scores"),
+              dev_ptr(t, F32, "t"), current_stream())
         ctx.dims = (B, R, H, K)
         ctx.has_mask, ctx.has_nd = mask8 is not None, node_drop is not None
         ctx.wi_shape = None
@@ -1523,12 +1525,11 @@ class _AdditiveAttn(torch.autograd.Function):
         d_bp = torch.empty(K, dtype=F32, device=dev)
         d_wi = torch.empty(K, dtype=F32, device=dev)
         ws = torch.empty(L_.rbr_additive_attn_bwd_ws_floats(B, R, H, K), dtype=F32, device=dev)
-        check(L_.rbr_additive_attn_bwd(B, R, H, K, dev_ptr(rev, F32, "inputs"), dev_ptr(mask8, U8, "mask"),
-                                       dev_ptr(node_drop, F32, "node_drop"), dev_ptr(Wp, F32, "proj weight"),
-                                       dev_ptr(wi, F32, "inner_product weight"), dev_ptr(scores, F32, "scores"),
-                                       dev_ptr(t, F32, "t"), dev_ptr(d_out, F32, "d_out"), dev_ptr(d_rev, F32, "d_inputs"),
-                                       dev_ptr(d_Wp, F32, "d_Wp"), dev_ptr(d_bp, F32, "d_bp"), dev_ptr(d_wi, F32, "d_wi"),
-                                       dev_ptr(ws, F32, "ws"), current_stream()), "rbr_additive_attn_bwd")
+        _call(None, L_.rbr_additive_attn_bwd, B, R, H, K, dev_ptr(rev, F32, "inputs"), dev_ptr(mask8, U8, "mask"),
+              dev_ptr(node_drop, F32, "node_drop"), dev_ptr(Wp, F32, "proj weight"), dev_ptr(wi, F32, "inner_product weight"),
+              dev_ptr(scores, F32, "scores"), dev_ptr(t, F32, "t"), dev_ptr(d_out, F32, "d_out"), dev_ptr(d_rev, F32, "d_inputs"),
+              dev_ptr(d_Wp, F32, "d_Wp"), dev_ptr(d_bp, F32, "d_bp"), dev_ptr(d_wi, F32, "d_wi"), dev_ptr(ws, F32, "ws"),
+              current_stream())
         return d_rev, None, None, d_Wp, d_bp, d_wi.view(1, K)
 
 
@@ -1548,8 +1549,8 @@ class _Embedding(torch.autograd.Function):
         D = table.shape[1]
         out = torch.empty(flat.numel(), D, dtype=F32, device=table.device)
         if flat.numel():
-            check(L_.rbr_embedding_fwd(flat.numel(), D, dev_ptr(flat, I64, "ids"), dev_ptr(table, F32, "table"),
-                                       dev_ptr(out, F32, "out"), current_stream()), "rbr_embedding_fwd")
+            _call(None, L_.rbr_embedding_fwd, flat.numel(), D, dev_ptr(flat, I64, "ids"), dev_ptr(table, F32, "table"),
+                  dev_ptr(out, F32, "out"), current_stream())
         ctx.pad = -1 if padding_idx is None else int(padding_idx)
         ctx.shape = table.shape
         ctx.save_for_backward(flat)
@@ -1563,8 +1564,8 @@ class _Embedding(torch.autograd.Function):
         dtable = torch.zeros(ctx.shape, dtype=F32, device=d_out.device)
         d_out = d_out.contiguous().view(-1, D)
         if flat.numel():
-            check(L_.rbr_embedding_bwd(flat.numel(), D, dev_ptr(flat, I64, "ids"), dev_ptr(d_out, F32, "d_out"), ctx.pad,
-                                       dev_ptr(dtable, F32, "dtable"), current_stream()), "rbr_embedding_bwd")
+            _call(None, L_.rbr_embedding_bwd, flat.numel(), D, dev_ptr(flat, I64, "ids"), dev_ptr(d_out, F32, "d_out"), ctx.pad,
+                  dev_ptr(dtable, F32, "dtable"), current_stream())
         return dtable, None, None
 
 
@@ -1585,9 +1586,9 @@ class _HierPool(torch.autograd.Function):
         mask8 = _mask_u8(mask)
         pooled = torch.empty(n_docs, D, dtype=F32, device=table.device)
         argmax = torch.empty(n_docs, D, dtype=I32, device=table.device)
-        check(L_.rbr_hier_pool_fwd(n_docs, L, D, int(k), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                   dev_ptr(table, F32, "table"), int(relu), dev_ptr(pooled, F32, "pooled"),
-                                   dev_ptr(argmax, I32, "argmax"), current_stream()), "rbr_hier_pool_fwd")
+        _call(None, L_.rbr_hier_pool_fwd, n_docs, L, D, int(k), dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
+              dev_ptr(table, F32, "table"), int(relu), dev_ptr(pooled, F32, "pooled"), dev_ptr(argmax, I32, "argmax"),
+              current_stream())
         ctx.args = (n_docs, L, D, int(k), int(relu), -1 if padding_idx is None else int(padding_idx), tuple(table.shape))
         ctx.has_mask = mask8 is not None
         ctx.save_for_backward(ids, argmax, pooled, *([mask8] if mask8 is not None else []))
@@ -1601,10 +1602,9 @@ class _HierPool(torch.autograd.Function):
         L_ = _lib.lib()
         dtable = torch.zeros(shape, dtype=F32, device=d_pooled.device)
         d_pooled = d_pooled.contiguous()
-        check(L_.rbr_hier_pool_bwd(n_docs, L, D, k, dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
-                                   dev_ptr(argmax, I32, "argmax"), dev_ptr(pooled, F32, "pooled"),
-                                   dev_ptr(d_pooled, F32, "d_pooled"), relu, pad, dev_ptr(dtable, F32, "dtable"),
-                                   current_stream()), "rbr_hier_pool_bwd")
+        _call(None, L_.rbr_hier_pool_bwd, n_docs, L, D, k, dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"),
+              dev_ptr(argmax, I32, "argmax"), dev_ptr(pooled, F32, "pooled"), dev_ptr(d_pooled, F32, "d_pooled"), relu, pad,
+              dev_ptr(dtable, F32, "dtable"), current_stream())
         return dtable, None, None, None, None, None
 
 
@@ -1634,22 +1634,19 @@ class _DattGate(torch.autograd.Function):
         if is_global:
             if win != L:
                 raise RuntimeError(f"GlobalAttention weight spans {win} positions but documents have {L}")
-            check(L_.rbr_datt_global_gate_fwd(B, L, E, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
-                                              dev_ptr(w, F32, "w"), dev_ptr(b0, F32, "b0"), dev_ptr(gate, F32, "gate"),
-                                              current_stream()), "rbr_datt_global_gate_fwd")
+            _call(None, L_.rbr_datt_global_gate_fwd, B, L, E, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
+                  dev_ptr(w, F32, "w"), dev_ptr(b0, F32, "b0"), dev_ptr(gate, F32, "gate"), current_stream())
         else:
             V = table.shape[0]
             ws_bytes = L_.rbr_datt_local_gate_prod_ws_bytes(B, L, E, win, V)     # > 0: token-product form of the gate
             if ws_bytes:
                 ctx.gate_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=table.device)
-                check(L_.rbr_datt_local_gate_fwd_prod(B, L, E, win, V, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
-                                                      dev_ptr(w, F32, "w"), dev_ptr(b0, F32, "b0"), dev_ptr(gate, F32, "gate"),
-                                                      ctx.gate_ws.data_ptr(), None if rows is None else rows.data_ptr(),
-                                                      current_stream()), "rbr_datt_local_gate_fwd_prod")
+                _call(None, L_.rbr_datt_local_gate_fwd_prod, B, L, E, win, V, dev_ptr(ids, I64, "ids"),
+                      dev_ptr(table, F32, "table"), dev_ptr(w, F32, "w"), dev_ptr(b0, F32, "b0"), dev_ptr(gate, F32, "gate"),
+                      ctx.gate_ws.data_ptr(), None if rows is None else rows.data_ptr(), current_stream())
             else:
-                check(L_.rbr_datt_local_gate_fwd(B, L, E, win, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
-                                                 dev_ptr(w, F32, "w"), dev_ptr(b0, F32, "b0"), dev_ptr(gate, F32, "gate"),
-                                                 current_stream()), "rbr_datt_local_gate_fwd")
+                _call(None, L_.rbr_datt_local_gate_fwd, B, L, E, win, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
+                      dev_ptr(w, F32, "w"), dev_ptr(b0, F32, "b0"), dev_ptr(gate, F32, "gate"), current_stream())
         ctx.args = (B, L, E, win, bool(is_global), -1 if padding_idx is None else int(padding_idx))
         ctx.save_for_backward(table, w, ids, gate)
         return gate
@@ -1666,38 +1663,31 @@ class _DattGate(torch.autograd.Function):
         acc = _table_acc(ctx.fanout_acc, dev) if ctx.needs_input_grad[0] else None      # the step's shared gradient buffer
         if ctx.gate_ws is not None:      # token-product local gate: the whole table gradient is overwritten (or its rows added)
             dtable = (acc if acc is not None else torch.empty_like(table)) if ctx.needs_input_grad[0] else None
-            check(L_.rbr_datt_local_gate_bwd_prod(B, L, E, win, table.shape[0], dev_ptr(ids, I64, "ids"),
-                                                  dev_ptr(table, F32, "table"), dev_ptr(w, F32, "w"), dev_ptr(gate, F32, "gate"),
-                                                  dev_ptr(dgate, F32, "dgate"), pad, dev_ptr(dw, F32, "dw"),
-                                                  dev_ptr(db0, F32, "db0"), dev_ptr(dtable, F32, "dtable"),
-                                                  ctx.gate_ws.data_ptr(), None if ctx.rows is None else ctx.rows.data_ptr(),
-                                                  int(acc is not None), current_stream()), "rbr_datt_local_gate_bwd_prod")
+            _call(None, L_.rbr_datt_local_gate_bwd_prod, B, L, E, win, table.shape[0], dev_ptr(ids, I64, "ids"),
+                  dev_ptr(table, F32, "table"), dev_ptr(w, F32, "w"), dev_ptr(gate, F32, "gate"), dev_ptr(dgate, F32, "dgate"), pad,
+                  dev_ptr(dw, F32, "dw"), dev_ptr(db0, F32, "db0"), dev_ptr(dtable, F32, "dtable"), ctx.gate_ws.data_ptr(),
+                  None if ctx.rows is None else ctx.rows.data_ptr(), int(acc is not None), current_stream())
             return dtable, dw, db0, None, None, None, None
         V = table.shape[0]
         rows_floats = L_.rbr_datt_global_gate_bwd_rows_ws_floats(B, L, E, V) if (ctx.rows is not None and is_global) else 0
         if rows_floats:                  # global gate over the tower's token rows: occurrence matrix, dtable overwritten
             dtable = (acc if acc is not None else torch.empty_like(table)) if ctx.needs_input_grad[0] else None
             ws = torch.empty(rows_floats, dtype=F32, device=dev)
-            check(L_.rbr_datt_global_gate_bwd_rows(B, L, E, V, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
-                                                   dev_ptr(w, F32, "w"), dev_ptr(gate, F32, "gate"), dev_ptr(dgate, F32, "dgate"),
-                                                   pad, dev_ptr(dw, F32, "dw"), dev_ptr(db0, F32, "db0"),
-                                                   dev_ptr(dtable, F32, "dtable"), dev_ptr(ws, F32, "ws"), ctx.rows.data_ptr(),
-                                                   int(acc is not None), current_stream()), "rbr_datt_global_gate_bwd_rows")
+            _call(None, L_.rbr_datt_global_gate_bwd_rows, B, L, E, V, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
+                  dev_ptr(w, F32, "w"), dev_ptr(gate, F32, "gate"), dev_ptr(dgate, F32, "dgate"), pad, dev_ptr(dw, F32, "dw"),
+                  dev_ptr(db0, F32, "db0"), dev_ptr(dtable, F32, "dtable"), dev_ptr(ws, F32, "ws"), ctx.rows.data_ptr(),
+                  int(acc is not None), current_stream())
             return dtable, dw, db0, None, None, None, None
         dtable = torch.zeros_like(table) if ctx.needs_input_grad[0] else None
         ws = torch.empty(max(1, L_.rbr_datt_gate_bwd_ws_floats(B, L, E, win, int(is_global))), dtype=F32, device=dev)
         if is_global:
-            check(L_.rbr_datt_global_gate_bwd(B, L, E, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
-                                              dev_ptr(w, F32, "w"), dev_ptr(gate, F32, "gate"), dev_ptr(dgate, F32, "dgate"),
-                                              pad, dev_ptr(dw, F32, "dw"), dev_ptr(db0, F32, "db0"),
-                                              dev_ptr(dtable, F32, "dtable"), dev_ptr(ws, F32, "ws"), current_stream()),
-                  "rbr_datt_global_gate_bwd")
+            _call(None, L_.rbr_datt_global_gate_bwd, B, L, E, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
+                  dev_ptr(w, F32, "w"), dev_ptr(gate, F32, "gate"), dev_ptr(dgate, F32, "dgate"), pad, dev_ptr(dw, F32, "dw"),
+                  dev_ptr(db0, F32, "db0"), dev_ptr(dtable, F32, "dtable"), dev_ptr(ws, F32, "ws"), current_stream())
         else:
-            check(L_.rbr_datt_local_gate_bwd(B, L, E, win, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
-                                             dev_ptr(w, F32, "w"), dev_ptr(gate, F32, "gate"), dev_ptr(dgate, F32, "dgate"),
-                                             pad, dev_ptr(dw, F32, "dw"), dev_ptr(db0, F32, "db0"),
-                                             dev_ptr(dtable, F32, "dtable"), dev_ptr(ws, F32, "ws"), current_stream()),
-                  "rbr_datt_local_gate_bwd")
+            _call(None, L_.rbr_datt_local_gate_bwd, B, L, E, win, dev_ptr(ids, I64, "ids"), dev_ptr(table, F32, "table"),
+                  dev_ptr(w, F32, "w"), dev_ptr(gate, F32, "gate"), dev_ptr(dgate, F32, "dgate"), pad, dev_ptr(dw, F32, "dw"),
+                  dev_ptr(db0, F32, "db0"), dev_ptr(dtable, F32, "dtable"), dev_ptr(ws, F32, "ws"), current_stream())
         return dtable, dw, db0, None, None, None, None
 
 
@@ -1715,14 +1705,14 @@ def _pair_region():
     and leave at the end as shared launches (rbr_pair_begin / _next / _end of rbr_hip.h).  Nothing but library calls and
     allocations may happen inside (a torch op would run ahead of the recorded launches)."""
     L_ = _lib.lib()
-    check(L_.rbr_pair_begin(), "rbr_pair_begin")
+    _call(None, L_.rbr_pair_begin)
 
     class _Region:
         paired = singles = 0
 
         @staticmethod
         def next():
-            check(L_.rbr_pair_next(), "rbr_pair_next")
+            _call(None, L_.rbr_pair_next)
 
     region = _Region()
     try:
@@ -1731,7 +1721,7 @@ def _pair_region():
         L_.rbr_pair_abort()
         raise
     n_p, n_s = C.c_int32(0), C.c_int32(0)
-    check(L_.rbr_pair_end(C.byref(n_p), C.byref(n_s)), "rbr_pair_end")
+    _call(None, L_.rbr_pair_end, C.byref(n_p), C.byref(n_s))
     region.paired, region.singles = n_p.value, n_s.value
 
 
@@ -1759,12 +1749,10 @@ def _region_or_timed():
     return _NoRegion() if TIMER.enabled else _pair_region()
 
 
-def _timed_call(name, rc_fn):
-    """check(rc_fn()) bracketed by TIMER events when the timing pass is on."""
-    ev = TIMER.record(name)
-    check(rc_fn(), name)
-    if ev is not None:
-        ev.record()
+def _token_rows_pay(V: int, B: int, L: int) -> bool:
+    """The distinct-token rows of a tower's [B, L] documents pay: enough positions per vocabulary entry (the same rule as the
+    token-product conv), and RBR_DATT_ROWS=0 does not switch them off."""
+    return not (V * 5 > B * L * 2 or B * L < 4096 or os.environ.get("RBR_DATT_ROWS", "1") == "0")
 
 
 def datt_pair_applies(table, docs2, local_w, conv_ws) -> bool:
@@ -1779,12 +1767,11 @@ def datt_pair_applies(table, docs2, local_w, conv_ws) -> bool:
     V, E = table.shape
     win = int(local_w.shape[2])
     L_ = _lib.lib()
-    if V * 5 > B * L * 2 or B * L < 4096 or os.environ.get("RBR_DATT_ROWS", "1") == "0":
+    if not _token_rows_pay(V, B, L):
         return False
     if not L_.rbr_datt_local_gate_prod_ws_bytes(B, L, E, win, V) or not L_.rbr_datt_global_gate_bwd_rows_ws_floats(B, L, E, V):
         return False
-    desc = _lib.make_desc(B, L, E, V, [int(w.shape[2]) for w in conv_ws], [int(w.shape[0]) for w in conv_ws], PAD_VALID, ACT_TANH, 0,
-                          _lib.conv_gate_split(1))
+    desc = _conv_desc(table, B, L, conv_ws, PAD_VALID, ACT_TANH, 0, _lib.conv_gate_split(1))
     return bool(L_.rbr_textcnn_fwd_ws_bytes(C.byref(desc)) > 0 and L_.rbr_textcnn_bwd_prod_ws_bytes(C.byref(desc)) > 0
                 and conv_ws[0].shape[2] == 1)
 
@@ -1822,61 +1809,44 @@ class _DattTowers(torch.autograd.Function):
                 raise RuntimeError(f"GlobalAttention weight spans {tw.gw.shape[2]} positions but documents have {L}")
             towers.append(tw)
         win = int(towers[0].lw.shape[2])
-        kz = [int(w.shape[2]) for w in towers[0].ws]
-        ch = [int(w.shape[0]) for w in towers[0].ws]
-        for tw in towers:
-            if [int(w.shape[2]) for w in tw.ws] != kz or [int(w.shape[0]) for w in tw.ws] != ch or int(tw.lw.shape[2]) != win:
-                raise RuntimeError("datt_towers: the towers' layers must have equal shapes")
-        flags = _lib.conv_gate_split(1) | (_lib.CONV_PAD_RUNS if (pad_runs and padding_idx is not None
-                                                                   and os.environ.get("RBR_PAD_RUNS", "1") != "0") else 0)
-        desc = _lib.make_desc(B, L, E, V, kz, ch, PAD_VALID, ACT_TANH, padding_idx, flags)
-        Ctot = sum(ch)
-        n_part = L_.rbr_textcnn_partial_elems(C.byref(desc))
-        ws_bytes = L_.rbr_textcnn_fwd_ws_bytes(C.byref(desc))
+
+        def layer_dims(tw):
+            return [int(w.shape[2]) for w in tw.ws], [int(w.shape[0]) for w in tw.ws], int(tw.lw.shape[2])
+
+        if layer_dims(towers[0]) != layer_dims(towers[1]):
+            raise RuntimeError("datt_towers: the towers' layers must have equal shapes")
+        desc = _conv_desc(table, B, L, towers[0].ws, PAD_VALID, ACT_TANH, padding_idx,
+                          _lib.conv_gate_split(1) | _pad_runs_flag(pad_runs, None, padding_idx))
+        Ctot = sum(desc.ch[:desc.n_widths])
         rows_bytes = L_.rbr_datt_token_rows_ws_bytes(B, L, V)
         gws_bytes = L_.rbr_datt_local_gate_prod_ws_bytes(B, L, E, win, V)
-        if not (n_part and ws_bytes and rows_bytes and gws_bytes):
-            check(-1, "datt_towers plan (datt_pair_applies() was not consulted)")
         feats = torch.empty(2 * B, Ctot, dtype=F32, device=dev)
         argmax = torch.empty(2 * B, Ctot, dtype=I32, device=dev)
         for t, tw in enumerate(towers):          # allocations only: nothing here launches
             tw.rows = torch.empty(rows_bytes, dtype=torch.uint8, device=dev)
             tw.gate2 = torch.empty(2, B, L, dtype=F32, device=dev)          # plane 0: local gate, plane 1: global gate
             tw.gate_ws = torch.empty(gws_bytes, dtype=torch.uint8, device=dev)
-            tw.pval = torch.empty(n_part, dtype=F32, device=dev)
-            tw.pidx = torch.empty(n_part, dtype=I32, device=dev)
-            tw.prod_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            tw.feat, tw.argmax = feats[t * B:(t + 1) * B], argmax[t * B:(t + 1) * B]
-        ev = TIMER.record("datt_towers_fwd")
+            _conv_fwd_buffers(tw, desc, dev, feats[t * B:(t + 1) * B], argmax[t * B:(t + 1) * B])
+        if not (rows_bytes and gws_bytes and towers[0].prod_ws is not None):
+            check(-1, "datt_towers plan (datt_pair_applies() was not consulted)")
+        tab = dev_ptr(table_c, F32, "table")
         # (Measured and dropped, round 4: tower 1's product-table GEMM on a second stream beside tower 0's gather -- MFMA / LDS work
         # beside L2-request work.  The GEMM's 137 MB of product-table writes push the table the gather is reading out of the L2s and
         # the Infinity Cache: the gather 125 -> 205 us, the GEMM 48 -> 150 us, the step +80 us.  Also dropped: both gates on the second
         # stream beside tower 0's GEMM, which needs the token list only -- the GEMM 49 -> 81 us, the gates' three kernels 102 -> 134,
         # the gather starts 4 us earlier: everything here queues at the same L2s.)
-        with _region_or_timed() as region:
+        with _timed("datt_towers_fwd"), _region_or_timed() as region:
             for t, tw in enumerate(towers):
                 if t == 1:
                     region.next()
                 ids_p = dev_ptr(tw.ids, I64, "ids")
-                check(L_.rbr_datt_token_rows(B, L, V, ids_p, tw.rows.data_ptr(), st), "rbr_datt_token_rows")
-                check(L_.rbr_datt_local_gate_fwd_prod(B, L, E, win, V, ids_p, dev_ptr(table_c, F32, "table"), dev_ptr(tw.lw, F32, "w"),
-                                                      dev_ptr(tw.lb, F32, "b0"), dev_ptr(tw.gate2[0], F32, "gate"), tw.gate_ws.data_ptr(),
-                                                      tw.rows.data_ptr(), st), "rbr_datt_local_gate_fwd_prod")
-                check(L_.rbr_datt_global_gate_fwd(B, L, E, ids_p, dev_ptr(table_c, F32, "table"), dev_ptr(tw.gw, F32, "w"),
-                                                  dev_ptr(tw.gb, F32, "b0"), dev_ptr(tw.gate2[1], F32, "gate"), st),
-                      "rbr_datt_global_gate_fwd")
-                wsp = tw.prod_ws.data_ptr()
-                check(L_.rbr_textcnn_prod_prepare(C.byref(desc), ids_p, None, ptr_array(tw.ws, F32, "conv weight"),
-                                                  dev_ptr(tw.pidx, I32, "pidx"), wsp, st), "rbr_textcnn_prod_prepare")
-                _timed_call("textcnn_prod_table", lambda: L_.rbr_textcnn_prod_table(C.byref(desc), dev_ptr(table_c, F32, "word table"), wsp, st))
-                _timed_call("textcnn_prod_pool", lambda: L_.rbr_textcnn_prod_pool(
-                    C.byref(desc), ids_p, None, dev_ptr(tw.gate2, F32, "gate"), dev_ptr(tw.pval, F32, "pval"),
-                    dev_ptr(tw.pidx, I32, "pidx"), wsp, st))
-                check(L_.rbr_textcnn_pool_finalize(C.byref(desc), dev_ptr(tw.pval, F32, "pval"), dev_ptr(tw.pidx, I32, "pidx"),
-                                                   ptr_array(tw.bs, F32, "conv bias"), dev_ptr(tw.feat, F32, "feat"),
-                                                   dev_ptr(tw.argmax, I32, "argmax"), st), "rbr_textcnn_pool_finalize")
-        if ev is not None:
-            ev.record()
+                _call(None, L_.rbr_datt_token_rows, B, L, V, ids_p, tw.rows.data_ptr(), st)
+                _call(None, L_.rbr_datt_local_gate_fwd_prod, B, L, E, win, V, ids_p, tab, dev_ptr(tw.lw, F32, "w"),
+                      dev_ptr(tw.lb, F32, "b0"), dev_ptr(tw.gate2[0], F32, "gate"), tw.gate_ws.data_ptr(), tw.rows.data_ptr(), st)
+                _call(None, L_.rbr_datt_global_gate_fwd, B, L, E, ids_p, tab, dev_ptr(tw.gw, F32, "w"), dev_ptr(tw.gb, F32, "b0"),
+                      dev_ptr(tw.gate2[1], F32, "gate"), st)
+                _prod_forward(desc, tw, table_c, tw.ids, None, tw.gate2, tw.ws, st, prepare_key=None)
+                _pool_finalize(desc, tw, tw.bs, st)
         PAIR_STATS["paired"], PAIR_STATS["singles"] = region.paired, region.singles
         for tw in towers:
             tw.pval = tw.pidx = None           # only the backward's inputs stay
@@ -1922,78 +1892,64 @@ class _DattTowers(torch.autograd.Function):
         # gradient -- it needs G.  (One stream for everything but the weight gradient, as in round 3: the second stream idle for
         # 600 us of the backward's 750.)
         side = _side_stream(dev)
-        fork = join = None
         if side is not None:
             fork = torch.cuda.Event()
             fork.record()
             side.wait_event(fork)
         st2 = side.cuda_stream if side is not None else st
         st_prod = st if TIMER.enabled else st2      # (the timing pass brackets calls with events on THIS stream)
-        ev = TIMER.record("datt_towers_bwd")
         tab = dev_ptr(table, F32, "table")
         paired = singles = 0
-        with _region_or_timed() as region:
-            for t, tw in enumerate(towers):
-                if t == 1:
-                    region.next()
-                ids_p = dev_ptr(tw.ids, I64, "ids")
-                d_feat = d_feats[t * B:(t + 1) * B]
-                check(L_.rbr_textcnn_bwd_dw(C.byref(desc), ids_p, None, dev_ptr(tw.gate2, F32, "gate"), tab,
-                                            dev_ptr(tw.feat, F32, "feat"), dev_ptr(tw.argmax, I32, "argmax"),
-                                            dev_ptr(d_feat, F32, "d_feat"), ptr_array(tw.grads[4:8], F32, "dW"),
-                                            ptr_array(tw.grads[8:12], F32, "dbias"), dev_ptr(tw.wsb, F32, "ws"), st2), "rbr_textcnn_bwd_dw")
-                check(L_.rbr_textcnn_bwd_dtable_prod_ex(C.byref(desc), ids_p, None, dev_ptr(tw.gate2, F32, "gate"),
-                                                        dev_ptr(tw.feat, F32, "feat"), dev_ptr(tw.argmax, I32, "argmax"),
-                                                        dev_ptr(d_feat, F32, "d_feat"), tw.prod_ws.data_ptr(), tw.bws.data_ptr(), None,
-                                                        dev_ptr(tw.dgate2, F32, "dgate"), None, _lib.G_BUILD, st), "rbr_textcnn_bwd_g_build")
-        paired, singles = paired + region.paired, singles + region.singles
-        if side is not None:          # G is complete on this stream (the region's launches have left): the product may follow it
-            g_done = torch.cuda.Event()
-            g_done.record()
-            side.wait_event(g_done)
-        with _region_or_timed() as region:
-            for t, tw in enumerate(towers):
-                if t == 1:
-                    region.next()
-                ids_p = dev_ptr(tw.ids, I64, "ids")
-                dt = dev_ptr(dtab[t], F32, "dtable") if need_table else None
-                if need_table:
-                    dc = dev_ptr(dtab[2 + t], F32, "dtable")
-                    _timed_call("textcnn_bwd_g_product", lambda: L_.rbr_textcnn_bwd_dtable_prod_ex(
-                        C.byref(desc), None, None, None, None, None, None, tw.prod_ws.data_ptr(), tw.bws.data_ptr(), dc, None, None,
-                        _lib.G_PRODUCT, st_prod))
-                check(L_.rbr_datt_local_gate_bwd_prod(B, L, E, win, V, ids_p, tab, dev_ptr(tw.lw, F32, "w"),
-                                                      dev_ptr(tw.gate2[0], F32, "gate"), dev_ptr(tw.dgate2[0], F32, "dgate"), pad,
-                                                      dev_ptr(tw.grads[0], F32, "dw"), dev_ptr(tw.grads[1], F32, "db0"), dt,
-                                                      tw.gate_ws.data_ptr(), tw.rows.data_ptr(), 1, st), "rbr_datt_local_gate_bwd_prod")
-                # the global gate's weight phase (dpre, dw: both towers per launch); its table rows follow outside the region
-                check(L_.rbr_datt_global_gate_bwd_rows(B, L, E, V, ids_p, tab, dev_ptr(tw.gw, F32, "w"),
-                                                       dev_ptr(tw.gate2[1], F32, "gate"), dev_ptr(tw.dgate2[1], F32, "dgate"), pad,
-                                                       dev_ptr(tw.grads[2], F32, "dw"), dev_ptr(tw.grads[3], F32, "db0"), None,
-                                                       dev_ptr(tw.gg_ws, F32, "ws"), tw.rows.data_ptr(), 1, st),
-                      "rbr_datt_global_gate_bwd_rows")
-        paired, singles = paired + region.paired, singles + region.singles
-        if need_table:
-            # ... a chain of four launches over the tower's 120 MB occurrence matrix, one tower at a time either way: tower 0's on
-            # this stream into its gate buffer, tower 1's on the second stream behind the sparse products, into the buffer its
-            # conv rows were written to there (same stream: no fifth buffer) -- both streams then end about together
-            if side is not None and not TIMER.enabled:
-                dpre_done = torch.cuda.Event()
-                dpre_done.record()
-                side.wait_event(dpre_done)
-            for t, tw in enumerate(towers):
-                on_side = t == 1 and side is not None and not TIMER.enabled
-                check(L_.rbr_datt_global_gate_bwd_rows(B, L, E, V, dev_ptr(tw.ids, I64, "ids"), None, dev_ptr(tw.gw, F32, "w"), None, None,
-                                                       pad, None, None, dev_ptr(dtab[3] if on_side else dtab[t], F32, "dtable"),
-                                                       dev_ptr(tw.gg_ws, F32, "ws"), tw.rows.data_ptr(), 1 | 2, st2 if on_side else st),
-                      "rbr_datt_global_gate_bwd_rows")
-        if side is not None:
-            with torch.cuda.stream(side):
-                join = torch.cuda.Event()
-                join.record()
-            _join(join)
-        if ev is not None:
-            ev.record()
+        with _timed("datt_towers_bwd"):
+            with _region_or_timed() as region:
+                for t, tw in enumerate(towers):
+                    if t == 1:
+                        region.next()
+                    d_feat = d_feats[t * B:(t + 1) * B]
+                    _call(None, L_.rbr_textcnn_bwd_dw, C.byref(desc), dev_ptr(tw.ids, I64, "ids"), None, dev_ptr(tw.gate2, F32, "gate"),
+                          tab, dev_ptr(tw.feat, F32, "feat"), dev_ptr(tw.argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"),
+                          ptr_array(tw.grads[4:8], F32, "dW"), ptr_array(tw.grads[8:12], F32, "dbias"), dev_ptr(tw.wsb, F32, "ws"), st2)
+                    _g_chain(None, _lib.G_BUILD, st, desc, (tw.ids, None, tw.gate2, tw.feat, tw.argmax, d_feat), tw.prod_ws, tw.bws,
+                             None, tw.dgate2, None)
+            paired, singles = paired + region.paired, singles + region.singles
+            if side is not None:          # G is complete on this stream (the region's launches have left): the product may follow it
+                g_done = torch.cuda.Event()
+                g_done.record()
+                side.wait_event(g_done)
+            with _region_or_timed() as region:
+                for t, tw in enumerate(towers):
+                    if t == 1:
+                        region.next()
+                    ids_p = dev_ptr(tw.ids, I64, "ids")
+                    dt = dev_ptr(dtab[t], F32, "dtable") if need_table else None
+                    if need_table:
+                        _g_chain("textcnn_bwd_g_product", _lib.G_PRODUCT, st_prod, desc, None, tw.prod_ws, tw.bws, dtab[2 + t], None, None)
+                    _call(None, L_.rbr_datt_local_gate_bwd_prod, B, L, E, win, V, ids_p, tab, dev_ptr(tw.lw, F32, "w"),
+                          dev_ptr(tw.gate2[0], F32, "gate"), dev_ptr(tw.dgate2[0], F32, "dgate"), pad, dev_ptr(tw.grads[0], F32, "dw"),
+                          dev_ptr(tw.grads[1], F32, "db0"), dt, tw.gate_ws.data_ptr(), tw.rows.data_ptr(), 1, st)
+                    # the global gate's weight phase (dpre, dw: both towers per launch); its table rows follow outside the region
+                    _call(None, L_.rbr_datt_global_gate_bwd_rows, B, L, E, V, ids_p, tab, dev_ptr(tw.gw, F32, "w"),
+                          dev_ptr(tw.gate2[1], F32, "gate"), dev_ptr(tw.dgate2[1], F32, "dgate"), pad, dev_ptr(tw.grads[2], F32, "dw"),
+                          dev_ptr(tw.grads[3], F32, "db0"), None, dev_ptr(tw.gg_ws, F32, "ws"), tw.rows.data_ptr(), 1, st)
+            paired, singles = paired + region.paired, singles + region.singles
+            if need_table:
+                # ... a chain of four launches over the tower's 120 MB occurrence matrix, one tower at a time either way: tower 0's
+                # on this stream into its gate buffer, tower 1's on the second stream behind the sparse products, into the buffer
+                # its conv rows were written to there (same stream: no fifth buffer) -- both streams then end about together
+                if side is not None and not TIMER.enabled:
+                    dpre_done = torch.cuda.Event()
+                    dpre_done.record()
+                    side.wait_event(dpre_done)
+                for t, tw in enumerate(towers):
+                    on_side = t == 1 and side is not None and not TIMER.enabled
+                    _call(None, L_.rbr_datt_global_gate_bwd_rows, B, L, E, V, dev_ptr(tw.ids, I64, "ids"), None, dev_ptr(tw.gw, F32, "w"),
+                          None, None, pad, None, None, dev_ptr(dtab[3] if on_side else dtab[t], F32, "dtable"),
+                          dev_ptr(tw.gg_ws, F32, "ws"), tw.rows.data_ptr(), 1 | 2, st2 if on_side else st)
+            if side is not None:
+                with torch.cuda.stream(side):
+                    join = torch.cuda.Event()
+                    join.record()
+                _join(join)
         PAIR_STATS["paired"] += paired
         PAIR_STATS["singles"] += singles
         dtable = dtab.sum(0) if need_table else None
@@ -2018,11 +1974,10 @@ def datt_token_rows(ids, vocab_size):
     """Distinct-token row maps of one tower's documents (rbr_datt_token_rows), or None where they do not pay (few positions
     per vocabulary entry: the same rule as the token-product conv)."""
     B, L = ids.shape
-    if vocab_size * 5 > B * L * 2 or B * L < 4096 or os.environ.get("RBR_DATT_ROWS", "1") == "0":
+    if not _token_rows_pay(vocab_size, B, L):
         return None
     L_ = _lib.lib()
     rows = torch.empty(L_.rbr_datt_token_rows_ws_bytes(B, L, vocab_size), dtype=torch.uint8, device=ids.device)
     ids = ids.contiguous()
-    check(L_.rbr_datt_token_rows(B, L, vocab_size, dev_ptr(ids, I64, "ids"), rows.data_ptr(), current_stream()),
-          "rbr_datt_token_rows")
+    _call(None, L_.rbr_datt_token_rows, B, L, vocab_size, dev_ptr(ids, I64, "ids"), rows.data_ptr(), current_stream())
     return rows
