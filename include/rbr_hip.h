@@ -547,6 +547,39 @@ int rbr_doc_gather(int32_t B, int32_t L, const int64_t* u_ids, const int64_t* i_
                    const int32_t* item_docs, int32_t I, int64_t pad_token, int64_t replace_id, int64_t* docs_out,
                    uint8_t* masks_out, int64_t* ids_out, int64_t* err, void* stream);
 
+/* ---- scoring and top-K recommendation from cached tower latents.  Every tower depends on its own side only, so a catalogue is
+ *      encoded once into latent tables ul [U, K] / il [I, K] and a (user, item) score is the pair-dependent tail:
+ *        RBR_SCORE_FM : relu(ul[u,:] * il[i,:]) . h + ub[u] + ib[i] + g    FM.forward in eval mode, no dropout
+ *                       (deepconn/layers.py:189-209); h [K], g [1], ub [U] / ib [I] or NULL (FMWithoutUIBias)
+ *        RBR_SCORE_DOT: sum_k ul[u,k] * il[i,k]                            torch.sum(torch.mul(u_feat, i_feat), 1)
+ *                       (dual_att/dual_att.py:58); h, g, ub, ib are ignored
+ *      The three entries use one arithmetic (fmaf / separately rounded product, k ascending): the same pair has the same bits
+ *      in all of them.
+ *      pair_score_ids : out[b] = score(u_id[b], i_id[b]) for B pairs.  An id outside [0, U) / [0, I) is never read: row 0 stands
+ *        in and err (the int64[4] record of rbr_sanitize_ids, set 0 = u_id, 1 = i_id; may be NULL) is updated.
+ *      pair_score_dense: out [Nu, Ni] for the Nu user rows ul [Nu, K] (ub [Nu]) against the item table (tests, small catalogues).
+ *      pair_score_topk : for each of the Nu user rows the k best items of [item_lo, Ni): out_item int64 [Nu, k], out_score
+ *        [Nu, k], score descending, ties by the lower item id; the same bytes on every run.  excl_off int64 [Nu + 1] /
+ *        excl_item int32 [excl_nnz] (CSR, sorted within a row; both NULL and excl_nnz 0 for none) lists items that never appear;
+ *        offsets outside [0, excl_nnz] are clamped.  excl_row int64 [Nu] (or NULL): user row r takes row excl_row[r] of a CSR of
+ *        excl_rows rows instead of row r (a CSR over all user ids serving a block of users; a row outside it excludes nothing).
+ *        A row with fewer than k candidates ends in item -1, score -inf.  NaN scores
+ *        are never returned.  1 <= k <= 128 and K <= 4096, else RBR_ERR_UNSUPPORTED.  [Nu, Ni] is never materialised:
+ *        ws is rbr_pair_score_topk_ws_bytes(Nu, Ni, K, k) bytes = Nu * k * 8 * item slices (<= 64 slices).  Two launches on
+ *        `stream`, no host synchronisation, no allocation: graph-capturable.                                         ---- */
+#define RBR_SCORE_FM 0
+#define RBR_SCORE_DOT 1
+int rbr_pair_score_ids(int32_t mode, int32_t B, int32_t K, const float* ul, int32_t U, const float* il, int32_t I,
+                       const int64_t* u_id, const int64_t* i_id, const float* h, const float* g, const float* ub,
+                       const float* ib, float* out, int64_t* err, void* stream);
+int rbr_pair_score_dense(int32_t mode, int32_t Nu, int32_t Ni, int32_t K, const float* ul, const float* il, const float* h,
+                         const float* g, const float* ub, const float* ib, float* out, void* stream);
+size_t rbr_pair_score_topk_ws_bytes(int32_t Nu, int32_t Ni, int32_t K, int32_t k);
+int rbr_pair_score_topk(int32_t mode, int32_t Nu, int32_t Ni, int32_t K, int32_t k, int32_t item_lo, const float* ul,
+                        const float* il, const float* h, const float* g, const float* ub, const float* ib,
+                        const int64_t* excl_off, const int32_t* excl_item, int64_t excl_nnz, const int64_t* excl_row,
+                        int32_t excl_rows, int64_t* out_item, float* out_score, void* ws, void* stream);
+
 /* ---- NgramFeat arch="HierPooling" (deepconn/layers.py:62-98,110-114): pooled[doc,d] =
  *      max_l mean_{j<k} x[doc,l+j,d] over l in [0, L-k], x = mask * table[ids]; relu != 0 applies the
  *      trailing ReLU when there is no projection layer.  argmax[doc,d] = first maximising window start.

@@ -20,6 +20,7 @@ RBR_MAX_WIDTHS = 8
 PAD_SAME, PAD_VALID = 0, 1
 ACT_RELU, ACT_TANH = 0, 1
 PROD_F32, PROD_BF16X3, PROD_BF16X2, PROD_BF16 = 0, 1, 2, 3     # rbr_set_prod_precision (RBR_PROD_* of rbr_hip.h)
+SCORE_FM, SCORE_DOT = 0, 1                                       # RBR_SCORE_* of rbr_hip.h (pair_score_*)
 PROD_PRECISIONS = {"f32": PROD_F32, "bf16x3": PROD_BF16X3, "bf16x2": PROD_BF16X2, "bf16": PROD_BF16}
 
 c_f32p = C.c_void_p
@@ -202,6 +203,12 @@ SIGNATURES = {
     "rbr_dedup_rows": (C.c_int, [i32, i32, c_i64p, c_i64p, i32, i32, c_u8p, C.c_void_p, c_i64p, c_u8p, c_stream]),
     "rbr_doc_gather": (C.c_int, [i32, i32, c_i64p, c_i64p, c_i32p, i32, c_i32p, i32, C.c_int64, C.c_int64, c_i64p, c_u8p, c_i64p,
                                  c_i64p, c_stream]),
+    "rbr_pair_score_ids": (C.c_int, [i32, i32, i32, c_f32p, i32, c_f32p, i32, c_i64p, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                     c_i64p, c_stream]),
+    "rbr_pair_score_dense": (C.c_int, [i32, i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "rbr_pair_score_topk_ws_bytes": (C.c_size_t, [i32, i32, i32, i32]),
+    "rbr_pair_score_topk": (C.c_int, [i32, i32, i32, i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p, c_i32p,
+                                      C.c_int64, c_i64p, i32, c_i64p, c_f32p, C.c_void_p, c_stream]),
     "rbr_embedding_fwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, c_f32p, c_stream]),
     "rbr_embedding_bwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, i32, c_f32p, c_stream]),
     "rbr_hier_pool_fwd": (C.c_int, [i32, i32, i32, i32, c_i64p, c_u8p, c_f32p, i32, c_f32p, c_i32p, c_stream]),

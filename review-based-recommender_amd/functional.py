@@ -1981,3 +1981,108 @@ def datt_token_rows(ids, vocab_size):
     ids = ids.contiguous()
     _call(None, L_.rbr_datt_token_rows, B, L, vocab_size, dev_ptr(ids, I64, "ids"), rows.data_ptr(), current_stream())
     return rows
+
+
+# --------------------------------------------------------------------------- scores and top-K from cached tower latents
+@contextlib.contextmanager
+def eval_mode(module):
+    """no_grad + module.eval() for the block (the towers' encode_users / encode_items, Recommender.refresh): no dropout is drawn
+    and nothing is recorded for a backward; the module's previous train / eval mode is restored afterwards."""
+    was = module.training
+    module.eval()
+    try:
+        with torch.no_grad():
+            yield
+    finally:
+        module.train(was)
+
+
+SCORE_MODES = {"fm": _lib.SCORE_FM, "dot": _lib.SCORE_DOT}
+
+
+def _score_operands(mode, ul, il, h, g, ub, ib):
+    """The operands every pair_score_* entry shares: mode code, detached contiguous tables, the FM parameters as flat vectors
+    (h [K, 1] -> [K], ub / ib [n, 1] -> [n]).  The dot mode ignores h, g, ub, ib."""
+    if mode not in SCORE_MODES:
+        raise ValueError(f"unknown score mode {mode!r}; one of {sorted(SCORE_MODES)}")
+    ul, il = ul.detach().contiguous(), il.detach().contiguous()
+    if ul.dim() != 2 or il.dim() != 2 or ul.shape[1] != il.shape[1]:
+        raise RuntimeError(f"latent tables must be [U, K] / [I, K], got {tuple(ul.shape)} / {tuple(il.shape)}")
+    dev_ptr(ul, F32, "user latents")        # device gate first: a CPU tensor is refused before anything else is looked at
+    dev_ptr(il, F32, "item latents")
+    K = ul.shape[1]
+    if mode == "dot":
+        return SCORE_MODES[mode], ul, il, None, None, None, None
+    if h is None or g is None:
+        raise RuntimeError("the fm score needs h [K] and g [1]")
+    flat = [None if t is None else t.detach().contiguous().view(-1) for t in (h, g, ub, ib)]
+    for t, n, name in zip(flat, (K, 1, ul.shape[0], il.shape[0]), ("h", "g", "ub", "ib")):
+        if t is not None and t.numel() != n:
+            raise RuntimeError(f"{name} must hold {n} values, got {t.numel()}")
+    return (SCORE_MODES[mode], ul, il, *flat)
+
+
+def pair_score(mode, ul, il, u_ids, i_ids, h=None, g=None, ub=None, ib=None):
+    """scores [B] of the pairs (u_ids[b], i_ids[b]) from the latent tables ul [U, K] / il [I, K] (rbr_pair_score_ids): mode "fm" =
+    relu(ul[u] * il[i]) . h + ub[u] + ib[i] + g (FM.forward in eval mode; ub / ib None = FMWithoutUIBias), mode "dot" =
+    sum(ul[u] * il[i]) (D-ATT).  No autograd.  An id outside its table scores as row 0 and is recorded like sanitize_ids()
+    records it: check_id_errors() raises the IndexError at the caller's next synchronisation point."""
+    code, ul, il, h, g, ub, ib = _score_operands(mode, ul, il, h, g, ub, ib)
+    u_ids, i_ids = u_ids.contiguous(), i_ids.contiguous()
+    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
+        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+    B = u_ids.shape[0]
+    out = torch.empty(B, dtype=F32, device=ul.device)
+    if B:
+        _call("pair_score_ids", _lib.lib().rbr_pair_score_ids, code, B, ul.shape[1], dev_ptr(ul, F32, "ul"), ul.shape[0],
+              dev_ptr(il, F32, "il"), il.shape[0], dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"), dev_ptr(h, F32, "h"),
+              dev_ptr(g, F32, "g"), dev_ptr(ub, F32, "ub"), dev_ptr(ib, F32, "ib"), dev_ptr(out, F32, "out"),
+              _id_err(ul.device).data_ptr(), current_stream())
+    return out
+
+
+def pair_score_dense(mode, ul, il, h=None, g=None, ub=None, ib=None):
+    """scores [Nu, Ni] of every user row of ul [Nu, K] (ub [Nu]) against every item row of il [Ni, K] (rbr_pair_score_dense): the
+    same arithmetic, bit for bit, as pair_score and pair_score_topk.  For tests and small catalogues -- it IS the U x I matrix."""
+    code, ul, il, h, g, ub, ib = _score_operands(mode, ul, il, h, g, ub, ib)
+    out = torch.empty(ul.shape[0], il.shape[0], dtype=F32, device=ul.device)
+    if out.numel():
+        _call("pair_score_dense", _lib.lib().rbr_pair_score_dense, code, ul.shape[0], il.shape[0], ul.shape[1], dev_ptr(ul, F32, "ul"),
+              dev_ptr(il, F32, "il"), dev_ptr(h, F32, "h"), dev_ptr(g, F32, "g"), dev_ptr(ub, F32, "ub"), dev_ptr(ib, F32, "ib"),
+              dev_ptr(out, F32, "out"), current_stream())
+    return out
+
+
+def pair_score_topk(mode, ul, il, k, h=None, g=None, ub=None, ib=None, *, item_lo=0, exclude=None):
+    """(items int64 [Nu, k], scores f32 [Nu, k]): for every user row of ul [Nu, K] the k best items of [item_lo, Ni), score
+    descending, ties by the lower item id, the same bytes on every run (rbr_pair_score_topk; 1 <= k <= 128).  `exclude` lists
+    the items a row must never get, CSR and sorted within a row: (excl_off int64 [Nu + 1], excl_item int32), or
+    (excl_off [R + 1], excl_item, rows int64 [Nu]) where user row r takes row rows[r] of a CSR of R rows.  A row with fewer than
+    k candidates ends in item -1, score -inf.  The [Nu, Ni] matrix is never built; no autograd, no host synchronisation, one
+    workspace from the torch allocator: recordable into a graph on one stream."""
+    code, ul, il, h, g, ub, ib = _score_operands(mode, ul, il, h, g, ub, ib)
+    Nu, Ni, K, k = ul.shape[0], il.shape[0], ul.shape[1], int(k)
+    dev = ul.device
+    off = items = rows = None
+    nnz = n_rows = 0
+    if exclude is not None:
+        off, items = exclude[0].contiguous(), exclude[1].contiguous()
+        rows = exclude[2].contiguous() if len(exclude) > 2 else None
+        n_rows = off.shape[0] - 1
+        if off.dim() != 1 or (rows is None and n_rows != Nu) or (rows is not None and (rows.shape != (Nu,) or n_rows < 1)):
+            raise RuntimeError(f"exclude offsets must be [{Nu + 1}] (or [R + 1] with rows [{Nu}]), got {tuple(off.shape)}")
+        nnz = items.numel()
+        if nnz == 0:         # a zero-sized tensor has no pointer to hand over: one unused entry keeps the CSR form
+            items = torch.zeros(1, dtype=I32, device=dev)
+    L_ = _lib.lib()
+    if Nu == 0:
+        return torch.empty(0, k, dtype=I64, device=dev), torch.empty(0, k, dtype=F32, device=dev)
+    # a shape the entry refuses has a workspace of 0 bytes: the call below then returns its error code and text before any launch
+    ws = torch.empty(max(L_.rbr_pair_score_topk_ws_bytes(Nu, Ni, K, k), 8), dtype=torch.uint8, device=dev)
+    out_item = torch.empty(Nu, max(k, 0), dtype=I64, device=dev)
+    out_score = torch.empty(Nu, max(k, 0), dtype=F32, device=dev)
+    _call("pair_score_topk", L_.rbr_pair_score_topk, code, Nu, Ni, K, k, int(item_lo), dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"),
+          dev_ptr(h, F32, "h"), dev_ptr(g, F32, "g"), dev_ptr(ub, F32, "ub"), dev_ptr(ib, F32, "ib"), dev_ptr(off, I64, "exclude offsets"),
+          dev_ptr(items, I32, "exclude items"), nnz, dev_ptr(rows, I64, "exclude rows"), n_rows if rows is not None else 0,
+          dev_ptr(out_item, I64, "out_item"), dev_ptr(out_score, F32, "out_score"), ws.data_ptr(), current_stream())
+    return out_item, out_score

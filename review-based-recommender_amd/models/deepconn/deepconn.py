@@ -94,3 +94,26 @@ class DeepCoNNpp(nn.Module):
             u_rev_feats, i_rev_feats = feats, None          # [2*bz, H], user rows first: the head takes it whole
         preds = rating_head(self.user_feat, self.item_feat, self.fm, u_rev_feats, i_rev_feats, u_ids, i_ids)
         return preds.view(bz)
+
+    # ---- one tower at a time (recommend.Recommender): a tower depends on its own side only, so a catalogue is encoded once
+    def _encode_side(self, docs, masks, ids, last):
+        with RF.eval_mode(self):
+            pad = self.word_embeddings.padding_idx
+            if self.validate_ids:
+                (docs,) = RF.sanitize_ids([(docs, self.vocab_size, pad)])
+            feats = self.ngram.encode(self.word_embeddings.weight, docs.contiguous(), masks.contiguous(), padding_idx=pad)
+            return last(feats, ids)        # LastFeat checks its ids itself
+
+    def encode_users(self, u_revs, u_rev_masks, u_ids):
+        """u_revs / masks [n, doc_len], u_ids [n] -> the users' latent rows [n, latent_dim] = LastFeat(ngram(doc), id) in eval
+        semantics (deepconn.py:46,48), no autograd.  Any n: the item side is not needed."""
+        return self._encode_side(u_revs, u_rev_masks, u_ids, self.user_feat)
+
+    def encode_items(self, i_revs, i_rev_masks, i_ids):
+        """The item tower's counterpart of encode_users (deepconn.py:47,49)."""
+        return self._encode_side(i_revs, i_rev_masks, i_ids, self.item_feat)
+
+    def score_mode_and_params(self):
+        """(mode, h, g, ub, ib) of functional.pair_score*: the FM head over the two latent rows (layers.py:189-209)."""
+        fm = self.fm
+        return "fm", fm.h, fm.g_bias, fm.user_bias.weight, fm.item_bias.weight

@@ -97,3 +97,25 @@ class DualAtt(nn.Module):
                 i_loc, i_glo = i_loc[:, :self.i_local_atten.out_size], i_loc[:, self.i_local_atten.out_size:]
             feats = self._fc(RF.block_cat(u_loc, u_glo, i_loc, i_glo))      # [2*bz, hidden_2], user rows first
         return RF.pair_dot(feats).view(-1)                                  # sum(u_feat * i_feat, 1)  (dual_att.py:58)
+
+    # ---- one tower at a time (recommend.Recommender): a tower reads its own documents only, the shared fc included
+    def _encode_side(self, docs, local, glob):
+        with RF.eval_mode(self):
+            pad = self.word_embeddings.padding_idx
+            if self.validate_ids:
+                (docs,) = RF.sanitize_ids([(docs, self.vocab_size, pad)])
+            loc, glo = self._encode(docs.contiguous(), local, glob, RF.table_fanout(self.word_embeddings.weight, 4))
+            return self._fc(loc if glo is None else torch.cat((loc, glo), 1))       # cat((local, global), 1): dual_att.py:50,56
+
+    def encode_users(self, u_docs):
+        """u_docs [n, doc_len] int64 -> the users' latent rows [n, hidden_size_2] = fc(cat(local, global)) in eval semantics
+        (dual_att.py:45-51), no autograd.  Any n: the item side is not needed."""
+        return self._encode_side(u_docs, self.u_local_atten, self.u_global_atten)
+
+    def encode_items(self, i_docs):
+        """The item tower's counterpart of encode_users (dual_att.py:52-57)."""
+        return self._encode_side(i_docs, self.i_local_atten, self.i_global_atten)
+
+    def score_mode_and_params(self):
+        """(mode, h, g, ub, ib) of functional.pair_score*: the plain inner product of the two latent rows (dual_att.py:58)."""
+        return "dot", None, None, None, None

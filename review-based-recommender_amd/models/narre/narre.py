@@ -89,3 +89,30 @@ class NARRE(nn.Module):
 
         pred = rating_head(self.user_feat, self.item_feat, self.fm, out.view(2 * bz, self.hiddem_dim), None, u_id, i_id)
         return pred.view(-1), u_att_scores, i_att_scores
+
+    # ---- one tower at a time (recommend.Recommender).  The attention pool of a side is keyed by its reviews' own counterpart
+    # ids (reuid / reiid, narre.py:177-178), not by the target pair, so a side's latent row is a function of that side alone.
+    def _encode_side(self, text, masks, my_id, other_id, my_rows, other_rows, att, last):
+        with RF.eval_mode(self):
+            n, T = text.shape[0], self.doc_len
+            wp = self.word_embeddings.padding_idx
+            text, masks = text.reshape(-1, T), masks.reshape(-1, T)
+            if self.validate_ids:
+                text, other_id = RF.sanitize_ids([(text, self.vocab_size, wp), (other_id, other_rows, att.padding_idx)])
+            feats = self.ngram.encode(self.word_embeddings.weight, text.contiguous(), masks.contiguous(), padding_idx=wp)
+            pooled, _ = att(feats.view(n, self.doc_num, self.hiddem_dim), other_id)
+            return last(pooled, my_id)         # LastFeat checks its ids itself
+
+    def encode_users(self, u_text, u_text_masks, u_id, reuid):
+        """u_text / masks [n, doc_num, doc_len], u_id [n], reuid [n, doc_num] (item ids of the user's reviews) -> the users' latent
+        rows [n, latent_dim] in eval semantics, no autograd.  Any n: the item side is not needed."""
+        return self._encode_side(u_text, u_text_masks, u_id, reuid, self.user_size, self.item_size, self.user_att, self.user_feat)
+
+    def encode_items(self, i_text, i_text_masks, i_id, reiid):
+        """The item tower's counterpart of encode_users (reiid: user ids of the item's reviews)."""
+        return self._encode_side(i_text, i_text_masks, i_id, reiid, self.item_size, self.user_size, self.item_att, self.item_feat)
+
+    def score_mode_and_params(self):
+        """(mode, h, g, ub, ib) of functional.pair_score*: the FM head over the two latent rows (narre.py:112-137)."""
+        fm = self.fm
+        return "fm", fm.h, fm.g_bias, fm.user_bias.weight, fm.item_bias.weight

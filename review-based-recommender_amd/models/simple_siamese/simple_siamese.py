@@ -75,3 +75,26 @@ class SimpleSiamese(nn.Module):
         out_logits = rating_head(self.user_last_feat_layer, self.item_last_feat_layer, self.fm, u_rev_feat, i_rev_feat,
                                  u_ids, i_ids)
         return out_logits.view(bz), None, None
+
+    # ---- one tower at a time (recommend.Recommender): the towers share their layers but each reads its own side only
+    def _encode_side(self, revs, word_masks, rev_masks, ids, last):
+        with RF.eval_mode(self):
+            if self.validate_ids:
+                (revs,) = RF.sanitize_ids([(revs, self.vocab_size, 0)])
+            return last(self._tower(revs.contiguous(), word_masks.contiguous(), rev_masks.contiguous()), ids)   # LastFeat checks its ids
+
+    def encode_users(self, u_revs, u_rev_word_masks, u_rev_masks, u_ids):
+        """u_revs / word masks [n, rv_num, rv_len], review masks [n, rv_num], u_ids [n] -> the users' latent rows
+        [n, latent_dim] = LastFeat(tower(reviews), id) in eval semantics (simple_siamese.py:58-77), no autograd.  Any n."""
+        return self._encode_side(u_revs, u_rev_word_masks, u_rev_masks, u_ids, self.user_last_feat_layer)
+
+    def encode_items(self, i_revs, i_rev_word_masks, i_rev_masks, i_ids):
+        """The item tower's counterpart of encode_users."""
+        return self._encode_side(i_revs, i_rev_word_masks, i_rev_masks, i_ids, self.item_last_feat_layer)
+
+    def score_mode_and_params(self):
+        """(mode, h, g, ub, ib) of functional.pair_score*: FM, or FMWithoutUIBias (ub = ib = None) without use_ui_bias."""
+        fm = self.fm
+        if fm.WITH_ID_BIASES:
+            return "fm", fm.h, fm.g_bias, fm.user_bias.weight, fm.item_bias.weight
+        return "fm", fm.h, fm.g_bias, None, None

@@ -1,0 +1,214 @@
+"""Catalogue scoring and top-K recommendation from cached tower latents.
+
+    python -m review_based_recommender_amd.recommend --model deepconn --config cfg.json --checkpoint best_model.pt \\
+        --k 10 [--exclude-train] --out recs.jsonl
+
+Every tower of the four models depends on its own side only (DeepCoNN++ / SimpleSiamese: LastFeat(encoder(doc), id); NARRE: the
+same over an attention pool keyed by the reviews' own counterpart ids; D-ATT: the shared fc over cat(local, global)), and the
+pair-dependent rest is the FM head or an inner product.  `Recommender.refresh()` therefore encodes every user and every item
+ONCE into latent tables [U, K] / [I, K]; `score`, `score_all` and `topk` then run on the tables alone (csrc/pair_score.hip) --
+`topk` without ever building the U x I score matrix.  The reference can only score a pair by encoding both of its documents
+(models/deepconn/deepconn.py:43-53) and has no ranking entry at all.
+
+The output file holds one JSON line per user id 1 .. U-1 (id 0 is the padding id of both sides: never a user, never recommended):
+    {"user": u, "items": [...], "scores": [...]}
+"""
+from __future__ import annotations
+
+import argparse
+import json
+from types import SimpleNamespace
+from typing import NamedTuple, Optional
+
+import torch
+
+from . import functional as RF
+
+KINDS = {"DeepCoNNpp": "deepconn", "NARRE": "narre", "DualAtt": "dual_att", "SimpleSiamese": "simple_siamese"}
+PAD = 0                 # padding token and padding user / item id of the reference's data (utils.py:30-42, meta.pkl row 0)
+
+
+class SeenItems(NamedTuple):
+    """Items every USER ID has already rated, CSR over all user ids: off int64 [U + 1], items int32 sorted within a user."""
+    off: torch.Tensor
+    items: torch.Tensor
+
+
+class Recommender:
+    """Latent tables of a trained model over a whole catalogue, and the queries on them.
+
+    `cache`: a data.DeviceDocCache (doc split for DeepCoNN++ / D-ATT, review split for NARRE / SimpleSiamese); or pass the
+    per-id document tensors yourself: `user` / `item` = [U, L] (doc split) or [U, R, T] (review split) integer tensors on the
+    model's device, plus `user_rids` / `item_rids` [U, R] int64 for NARRE.  Row 0 of each side is the padding id.
+
+    The tables are a snapshot: call refresh() again after the parameters change.  `stale` compares the parameters' torch
+    version counters with those seen by the last refresh -- it catches torch-side in-place updates (optimizer.step(),
+    load_state_dict), NOT the updates train_step.HipClipAdam or a replayed hipGraph write through raw pointers."""
+
+    def __init__(self, model, cache=None, *, user=None, item=None, user_rids=None, item_rids=None):
+        kind = KINDS.get(type(model).__name__)
+        if kind is None:
+            raise ValueError(f"{type(model).__name__} is not one of {sorted(KINDS)}")
+        if cache is None:
+            if user is None or item is None:
+                raise ValueError("Recommender needs a DeviceDocCache or the per-id `user` / `item` document tensors")
+            cache = SimpleNamespace(user=user, item=item, user_rids=user_rids, item_rids=item_rids)
+        want_dim = 3 if kind in ("narre", "simple_siamese") else 2
+        if cache.user.dim() != want_dim or cache.item.dim() != want_dim:
+            raise ValueError(f"{kind} reads {'[U, R, T] reviews' if want_dim == 3 else '[U, L] documents'} per id, got "
+                             f"{tuple(cache.user.shape)} / {tuple(cache.item.shape)}")
+        if kind == "narre" and (cache.user_rids is None or cache.item_rids is None):
+            raise ValueError("NARRE's attention pools need the reviews' counterpart ids (user_rids / item_rids)")
+        self.model, self.kind, self.cache = model, kind, cache
+        self.n_users, self.n_items = cache.user.shape[0], cache.item.shape[0]
+        self.item_lo = 1                     # the padding id 0 is never recommended
+        self.user_latents: Optional[torch.Tensor] = None
+        self.item_latents: Optional[torch.Tensor] = None
+        self._versions = None
+
+    # ------------------------------------------------------------------ the tables
+    def _encode(self, side: str, a: int, b: int) -> torch.Tensor:
+        c, m = self.cache, self.model
+        docs = (c.user if side == "user" else c.item)[a:b].to(torch.int64)
+        ids = torch.arange(a, b, dtype=torch.int64, device=docs.device)
+        enc = m.encode_users if side == "user" else m.encode_items
+        if self.kind == "deepconn":
+            return enc(docs, docs != PAD, ids)
+        if self.kind == "dual_att":
+            return enc(docs)
+        if self.kind == "narre":
+            return enc(docs, docs != PAD, ids, (c.user_rids if side == "user" else c.item_rids)[a:b])
+        word_masks = docs != PAD
+        return enc(docs, word_masks, word_masks.any(-1), ids)      # review masks: the reviews that hold any token
+
+    def refresh(self, chunk: int = 256) -> "Recommender":
+        """Encodes all users and all items, `chunk` ids at a time, into the latent tables (eval semantics, no autograd; the
+        model's train / eval mode is restored afterwards).  Call it again after the parameters change."""
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        with RF.eval_mode(self.model):
+            tables = []
+            for side, n in (("user", self.n_users), ("item", self.n_items)):
+                table = None
+                for a in range(0, n, chunk):
+                    rows = self._encode(side, a, min(a + chunk, n))
+                    if table is None:
+                        table = torch.empty(n, rows.shape[1], dtype=torch.float32, device=rows.device)
+                    table[a:a + rows.shape[0]] = rows
+                tables.append(table)
+            self.user_latents, self.item_latents = tables
+        self._versions = [p._version for p in self.model.parameters()]
+        return self
+
+    @property
+    def stale(self) -> bool:
+        """True before the first refresh() and when a parameter's torch version counter moved since the last one (see the class
+        docstring for what that does not see)."""
+        return self._versions is None or self._versions != [p._version for p in self.model.parameters()]
+
+    def _tables(self):
+        if self.user_latents is None:
+            raise RuntimeError("Recommender.refresh() has not been called: there are no latent tables yet")
+        return self.user_latents, self.item_latents
+
+    def _user_rows(self, u_ids):
+        """The latent rows and bias rows of u_ids (HIP row gathers), the checked ids, and the rest of the head's parameters."""
+        ul, il = self._tables()
+        mode, h, g, ub, ib = self.model.score_mode_and_params()
+        (u_ids,) = RF.sanitize_ids([(u_ids, self.n_users, PAD)])
+        with torch.no_grad():
+            rows = RF.embedding(ul, u_ids, None)
+            ub_rows = RF.embedding(ub.detach(), u_ids, None) if ub is not None else None
+        return mode, rows, il, h, g, ub_rows, ib, u_ids
+
+    # ------------------------------------------------------------------ the queries
+    def score(self, u_ids: torch.Tensor, i_ids: torch.Tensor) -> torch.Tensor:
+        """Predicted ratings [B] of the pairs (u_ids[b], i_ids[b]): two row gathers and the head's arithmetic per pair."""
+        ul, il = self._tables()
+        mode, h, g, ub, ib = self.model.score_mode_and_params()
+        return RF.pair_score(mode, ul, il, u_ids, i_ids, h, g, ub, ib)
+
+    def score_all(self, u_ids: torch.Tensor) -> torch.Tensor:
+        """Predicted ratings [len(u_ids), I] of the given users against every item id (column 0 is the padding id)."""
+        mode, rows, il, h, g, ub_rows, ib, _ = self._user_rows(u_ids)
+        return RF.pair_score_dense(mode, rows, il, h, g, ub_rows, ib)
+
+    def topk(self, u_ids: torch.Tensor, k: int, exclude=None):
+        """(items int64 [len(u_ids), k], scores [len(u_ids), k]): each user's k best items, score descending, ties by the lower
+        item id; item 0 never appears.  `exclude`: a SeenItems (Recommender.seen_from: CSR over all user ids), or a CSR pair
+        (off int64 [len(u_ids) + 1], items int32 sorted within a row) aligned with u_ids.  Rows with fewer than k candidates
+        end in item -1, score -inf."""
+        mode, rows, il, h, g, ub_rows, ib, u_ids = self._user_rows(u_ids)
+        if isinstance(exclude, SeenItems):
+            exclude = (exclude.off, exclude.items, u_ids)
+        return RF.pair_score_topk(mode, rows, il, k, h, g, ub_rows, ib, item_lo=self.item_lo, exclude=exclude)
+
+    @staticmethod
+    def seen_from(examples, n_users: int, device=None) -> SeenItems:
+        """The items each user id has rated in `examples` (a dataset's examples: sequences starting (u_id, i_id, ...)) as a
+        SeenItems over user ids 0 .. n_users-1: duplicates dropped, items ascending within a user."""
+        pairs = sorted({(int(e[0]), int(e[1])) for e in examples})
+        if pairs and not (0 <= pairs[0][0] and pairs[-1][0] < n_users):
+            raise IndexError(f"user ids span [{pairs[0][0]}, {pairs[-1][0]}] but there are {n_users} users")
+        counts = torch.zeros(n_users + 1, dtype=torch.int64)
+        if pairs:
+            counts[1:] = torch.bincount(torch.tensor([u for u, _ in pairs], dtype=torch.int64), minlength=n_users)
+        off = torch.cumsum(counts, 0)
+        items = torch.tensor([i for _, i in pairs], dtype=torch.int32)
+        return SeenItems(off.to(device), items.to(device)) if device is not None else SeenItems(off, items)
+
+
+# ---------------------------------------------------------------------------------------------------------------- CLI
+def parse_cli(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m review_based_recommender_amd.recommend",
+                                 description="top-K recommendations of a trained model for every user of its dataset")
+    ap.add_argument("--model", required=True, choices=sorted(KINDS.values()))
+    ap.add_argument("--config", required=True, help="the flat JSON config the model was trained with (trainer.py)")
+    ap.add_argument("--checkpoint", required=True, help="best_model.pt written by the trainer")
+    ap.add_argument("--k", type=int, default=10, help="items per user (1..128)")
+    ap.add_argument("--exclude-train", action="store_true", help="never recommend an item the user rated in the training split")
+    ap.add_argument("--out", required=True, help="output file, one JSON line per user")
+    ap.add_argument("--chunk", type=int, default=256, help="ids encoded / users ranked per launch")
+    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--reference-quirks", action="store_true", help="as for the trainer: kernel_sizes=[3] (NARRE hidden_dim=150)")
+    a = ap.parse_args(argv)
+    if not 1 <= a.k <= 128:
+        ap.error("--k must be in 1..128")
+    if a.chunk < 1:
+        ap.error("--chunk must be at least 1")
+    return a
+
+
+def main(argv=None) -> int:
+    a = parse_cli(argv)
+    from . import data as D
+    from .trainer import DEFAULTS, make_model, parse_args
+    if not torch.cuda.is_available():
+        raise RuntimeError("the HIP path needs an MI355X: there is no CPU fallback")
+    cfg = parse_args(a.config)
+    for key, v in DEFAULTS.items():
+        if not hasattr(cfg, key):
+            setattr(cfg, key, v)
+    dev = torch.device(a.device)
+    review_split = a.model in ("narre", "simple_siamese")
+    ds = D.ReviewDataset(cfg.data_dir, "train") if review_split else D.DocDataset(cfg.data_dir, "train", with_ids=a.model == "deepconn")
+    model = make_model(a.model, cfg, ds, a.reference_quirks)
+    ck = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
+    model.load_state_dict(ck["model"] if "model" in ck else ck)
+    model.to(dev).eval()
+    rec = Recommender(model, D.DeviceDocCache(ds, dev)).refresh(chunk=a.chunk)
+    seen = Recommender.seen_from(ds.examples, rec.n_users, dev) if a.exclude_train else None
+    with open(a.out, "w") as f:
+        for lo in range(1, rec.n_users, a.chunk):
+            u_ids = torch.arange(lo, min(lo + a.chunk, rec.n_users), dtype=torch.int64, device=dev)
+            items, scores = rec.topk(u_ids, a.k, exclude=seen)
+            items, scores = items.cpu(), scores.cpu()
+            for r, u in enumerate(u_ids.tolist()):
+                keep = items[r] >= 0
+                f.write(json.dumps({"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}) + "\n")
+    RF.check_id_errors(dev)
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

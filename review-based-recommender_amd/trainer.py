@@ -21,7 +21,9 @@ once in the all-reduced RMSE; running loss / gnorm are accumulated on
 the device and read back only at log lines (the reference calls loss.item() twice per step); the config key
 `fast_step: true` switches to HipClipAdam and hipGraph replay of the step (train_step.py); `device_cache: true` (DeepCoNN++ and
 D-ATT) keeps meta.pkl's documents on the GPU and feeds the step (u_id, i_id, rating) batches whose documents are gathered
-there (data.DeviceDocCache; the loaders check once that every example's documents are meta's for its ids).
+there (data.DeviceDocCache; the loaders check once that every example's documents are meta's for its ids); `eval_from_towers:
+true` (with device_cache) validates from latent tables: every user / item document is encoded once per validation pass and a
+pair is scored from two table rows (recommend.Recommender), instead of both documents being encoded for every pair.
 """
 from __future__ import annotations
 
@@ -58,7 +60,7 @@ class EarlyStop(Exception):
 
 DEFAULTS = dict(log_dir="logs", dataset="dataset", log=True, log_idx=500, verbose=False, parallel=False, epochs=64,
                 batch_size=50, lr=0.002, max_grad_norm=5.0, patience=5, dropout=0.5, arch="CNN", use_pretrain=False,
-                num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False)
+                num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False, eval_from_towers=False)
 
 
 class _ShardSampler(torch.utils.data.Sampler):
@@ -99,6 +101,43 @@ def make_loaders(train_set, valid_set, args, rank: int, world: int):
     return train_loader, valid_loader, train_sampler, valid_sampler, rank_batch
 
 
+def make_model(kind: str, a: Args, ds, quirks: bool = False):
+    """The model of `kind` for the config `a` and the dataset `ds` (train_*.py build_model), on the CPU; also what
+    recommend.py rebuilds before it loads a checkpoint."""
+    import contextlib
+    import io
+    with contextlib.redirect_stdout(io.StringIO()):
+        if kind == "deepconn":
+            from .models.deepconn.deepconn import DeepCoNNpp
+            ks = [3] if quirks else a.kernel_sizes
+            return DeepCoNNpp(user_size=ds.user_num, item_size=ds.item_num, vocab_size=ds.vocab_size, kernel_sizes=ks,
+                              hidden_dim=a.hidden_dim, embedding_dim=a.embedding_dim, dropout=a.dropout,
+                              latent_dim=a.latent_dim, doc_len=ds.doc_len, pretrained_embeddings=None, arch=a.arch)
+        if kind == "narre":
+            from .models.narre.narre import NARRE
+            ks = [3] if quirks else a.kernel_sizes
+            hd = 150 if quirks else a.hidden_dim
+            return NARRE(user_size=ds.user_num, item_size=ds.item_num, vocab_size=ds.vocab_size, kernel_sizes=ks,
+                         hidden_dim=hd, embedding_dim=a.embedding_dim, att_dim=a.att_dim, latent_dim=a.latent_dim,
+                         max_doc_num=ds.rv_num, max_doc_len=ds.rv_len, dropout=a.dropout, word_padding_idx=0,
+                         user_padding_idx=0, item_padding_idx=0, pretrained_embeddings=None, arch=a.arch)
+        if kind == "simple_siamese":
+            # trainer/train_simple_siamese.py:161-167 (keys of models/simple_siamese/defalut_simple_train.json)
+            from .models.simple_siamese.simple_siamese import SimpleSiamese
+            return SimpleSiamese(embedding_dim=a.embedding_dim, latent_dim=a.latent_dim, vocab_size=ds.vocab_size,
+                                 user_size=ds.user_num, item_size=ds.item_num, pretrained_embeddings=None,
+                                 freeze_embeddings=getattr(a, "freeze_embeddings", False), dropout=a.dropout,
+                                 word_dropout=getattr(a, "word_dropout", 0.2),
+                                 review_dropout=getattr(a, "review_dropout", 0.0),
+                                 use_ui_bias=getattr(a, "use_ui_bias", True),
+                                 latent_transform=getattr(a, "latent_transform", False))
+        from .models.dual_att.dual_att import DualAtt
+        return DualAtt(vocab_size=ds.vocab_size, doc_len=ds.doc_len, l_window_size=a.l_window_size,
+                       l_out_size=a.l_out_size, g_out_size=a.g_out_size, emb_size=a.emb_size,
+                       hidden_size_1=a.hidden_size_1, hidden_size_2=a.hidden_size_2, dropout=a.dropout,
+                       pretrained_embeddings=None)
+
+
 class ReviewExperiment:
     KINDS = ("deepconn", "narre", "dual_att", "simple_siamese")
 
@@ -116,6 +155,9 @@ class ReviewExperiment:
             # the user's and the item's lists before truncating (preprocess/divide_and_create_example_word.py:263-285)
             raise ValueError(f"device_cache is valid for --model deepconn and dual_att, not {kind}: the review split's examples "
                              "are not per-id documents")
+        if bool(args.eval_from_towers) and not (bool(args.device_cache) and kind in ("deepconn", "dual_att")):
+            raise ValueError("eval_from_towers needs device_cache and --model deepconn or dual_att: validation then scores each "
+                             "pair from latent tables encoded once per epoch from the per-id documents")
         self.kind, self.args, self.quirks = kind, args, reference_quirks
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -204,40 +246,7 @@ class ReviewExperiment:
 
     # ------------------------------------------------------------------ model (train_*.py build_model)
     def build_model(self):
-        a, ds = self.args, self.train_set
-        import contextlib
-        import io
-        with contextlib.redirect_stdout(io.StringIO()):
-            if self.kind == "deepconn":
-                from .models.deepconn.deepconn import DeepCoNNpp
-                ks = [3] if self.quirks else a.kernel_sizes
-                self.model = DeepCoNNpp(user_size=ds.user_num, item_size=ds.item_num, vocab_size=ds.vocab_size, kernel_sizes=ks,
-                                        hidden_dim=a.hidden_dim, embedding_dim=a.embedding_dim, dropout=a.dropout,
-                                        latent_dim=a.latent_dim, doc_len=ds.doc_len, pretrained_embeddings=None, arch=a.arch)
-            elif self.kind == "narre":
-                from .models.narre.narre import NARRE
-                ks = [3] if self.quirks else a.kernel_sizes
-                hd = 150 if self.quirks else a.hidden_dim
-                self.model = NARRE(user_size=ds.user_num, item_size=ds.item_num, vocab_size=ds.vocab_size, kernel_sizes=ks,
-                                   hidden_dim=hd, embedding_dim=a.embedding_dim, att_dim=a.att_dim, latent_dim=a.latent_dim,
-                                   max_doc_num=ds.rv_num, max_doc_len=ds.rv_len, dropout=a.dropout, word_padding_idx=0,
-                                   user_padding_idx=0, item_padding_idx=0, pretrained_embeddings=None, arch=a.arch)
-            elif self.kind == "simple_siamese":
-                # trainer/train_simple_siamese.py:161-167 (keys of models/simple_siamese/defalut_simple_train.json)
-                from .models.simple_siamese.simple_siamese import SimpleSiamese
-                self.model = SimpleSiamese(embedding_dim=a.embedding_dim, latent_dim=a.latent_dim, vocab_size=ds.vocab_size,
-                                           user_size=ds.user_num, item_size=ds.item_num, pretrained_embeddings=None,
-                                           freeze_embeddings=getattr(a, "freeze_embeddings", False), dropout=a.dropout,
-                                           word_dropout=getattr(a, "word_dropout", 0.2),
-                                           review_dropout=getattr(a, "review_dropout", 0.0),
-                                           use_ui_bias=getattr(a, "use_ui_bias", True),
-                                           latent_transform=getattr(a, "latent_transform", False))
-            else:
-                from .models.dual_att.dual_att import DualAtt
-                self.model = DualAtt(vocab_size=ds.vocab_size, doc_len=ds.doc_len, l_window_size=a.l_window_size,
-                                     l_out_size=a.l_out_size, g_out_size=a.g_out_size, emb_size=a.emb_size,
-                                     hidden_size_1=a.hidden_size_1, hidden_size_2=a.hidden_size_2, dropout=a.dropout,
-                                     pretrained_embeddings=None)
+        self.model = make_model(self.kind, self.args, self.train_set, self.quirks)
         self.model.to(self.device)
 
     # ------------------------------------------------------------------ data
@@ -381,9 +390,21 @@ class ReviewExperiment:
         count = torch.zeros((), device=self.device, dtype=torch.float64)
         steps = 0
         self.model.eval()
+        towers = None
+        if self.args.eval_from_towers:
+            # every user / item document encoded ONCE into latent tables (the parameters changed since the last epoch), then a
+            # pair is two row gathers and the head's arithmetic instead of two document encodes (recommend.Recommender)
+            if getattr(self, "_towers", None) is None:
+                from .recommend import Recommender
+                self._towers = Recommender(self.model, self.cache)
+            towers = self._towers
+            towers.refresh()
         with torch.no_grad():
             for batch in loader:
-                if self.cache is not None:
+                if towers is not None:
+                    u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
+                    pred = towers.score(u_ids, i_ids)
+                elif self.cache is not None:
                     u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
                     pred = self._eval_forward_ids(u_ids, i_ids)
                 else:
