@@ -547,6 +547,25 @@ int rbr_doc_gather(int32_t B, int32_t L, const int64_t* u_ids, const int64_t* i_
                    const int32_t* item_docs, int32_t I, int64_t pad_token, int64_t replace_id, int64_t* docs_out,
                    uint8_t* masks_out, int64_t* ids_out, int64_t* err, void* stream);
 
+/* ---- id-fed review-split batch (NARRE, SimpleSiamese).  Replaces the reference's host collate of the review split
+ *      (trainer/train_narre.py:316-330: LongTensor(u_revs / i_revs) + get_mask + the rid blocks) with ONE launch over
+ *      device-resident int32 tables of R + 1 slots per id: user_revs [U, R+1, T] / user_rids [U, R+1] (the counterpart item ids),
+ *      item_revs [I, R+1, T] / item_rids [I, R+1]; unused slots hold pad_token / 0.  For output row r (user rows [0, B) by u_ids,
+ *      item rows [B, 2B) by i_ids) with own id a and counterpart c (the other side's id of the same pair):
+ *        leave_one_out = 1 (a TRAIN example, preprocess/divide_and_create_example_word.py:263-285): d = the first j in [0, R) with
+ *          rids[a][j] == c, where a c <= 0 or outside the other side's table never matches; no match, or leave_one_out = 0 (a valid /
+ *          test example, :306-323): nothing is dropped (d = R);
+ *        output slot q copies table slot q + (q >= d), reviews and rids alike.
+ *      revs_out [2B, R, T] int64; word_masks_out [2B, R, T] = (revs_out != pad_token); rev_masks_out [2B, R] (or NULL) = any token
+ *      of the review is not pad_token; rids_out [2B, R] int64 (or NULL); ids_out [2B] = the checked ids (or NULL).
+ *      An own id outside its table is never read: row `replace_id` (0 <= replace_id < min(U, I)) stands in, ids_out gets
+ *      replace_id and err (the int64[4] record of rbr_sanitize_ids; set 0 = u_ids, 1 = i_ids) is updated, as in rbr_doc_gather.
+ *      No sync, no allocation, static shapes: graph-capturable.                                                        ---- */
+int rbr_review_gather(int32_t B, int32_t R, int32_t T, const int64_t* u_ids, const int64_t* i_ids, const int32_t* user_revs,
+                      const int32_t* user_rids, int32_t U, const int32_t* item_revs, const int32_t* item_rids, int32_t I,
+                      int32_t leave_one_out, int64_t pad_token, int64_t replace_id, int64_t* revs_out, uint8_t* word_masks_out,
+                      uint8_t* rev_masks_out, int64_t* rids_out, int64_t* ids_out, int64_t* err, void* stream);
+
 /* ---- scoring and top-K recommendation from cached tower latents.  Every tower depends on its own side only, so a catalogue is
  *      encoded once into latent tables ul [U, K] / il [I, K] and a (user, item) score is the pair-dependent tail:
  *        RBR_SCORE_FM : relu(ul[u,:] * il[i,:]) . h + ub[u] + ib[i] + g    FM.forward in eval mode, no dropout

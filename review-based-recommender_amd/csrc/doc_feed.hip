@@ -7,36 +7,20 @@
 //   masks_out      = docs_out != pad_token                                                 (utils.py:30-42, get_mask)
 //   ids_out[r]     = id_r
 // An id outside its table is never dereferenced: row `replace_id` stands in for it, ids_out gets `replace_id`, and err is
-// updated as rbr::sanitize_id does (err[0] count, err[1] one offending value, err[2] its set: 0 = u_ids, 1 = i_ids).
+// updated as rbr::sanitize_id does (feed_ids.h: the convention review_feed.hip shares).
 #include "rbr_common.h"
+#include "feed_ids.h"
 
 namespace rbr {
 
 struct DocGather {
-    const long long* ids[2];
+    FeedIds F;
     const int* table[2];
-    long long rows[2];
     long long* docs;
     unsigned char* masks;
-    long long* ids_out;
-    long long pad, replace;
+    long long pad;
     int B, L;
 };
-
-// row r of the stacked output -> its side, its checked id; the lane that owns the row's first token records a bad id
-__device__ __forceinline__ long long gather_row_id(const DocGather& G, int r, int& side, bool first_lane, long long* __restrict__ err) {
-    side = r >= G.B ? 1 : 0;
-    long long v = G.ids[side][r - side * G.B];
-    if ((unsigned long long)v >= (unsigned long long)G.rows[side]) {
-        if (first_lane) {
-            err[1] = v; err[2] = side;                // any one offender (benign race)
-            atomicAdd(reinterpret_cast<unsigned long long*>(err), 1ull);
-        }
-        v = G.replace;
-    }
-    if (first_lane && G.ids_out) G.ids_out[r] = v;
-    return v;
-}
 
 // L % 4 == 0: one 4-token chunk per lane -- a 16-byte load of int32 tokens, two 16-byte int64 stores, one 4-byte mask store
 __global__ __launch_bounds__(256) void doc_gather_vec_kernel(const DocGather G, long long* __restrict__ err) {
@@ -45,7 +29,7 @@ __global__ __launch_bounds__(256) void doc_gather_vec_kernel(const DocGather G, 
     for (long long c = (long long)blockIdx.x * 256 + threadIdx.x; c < n; c += (long long)gridDim.x * 256) {
         const int r = (int)(c / cpr), q = (int)(c - (long long)r * cpr);
         int side;
-        const long long id = gather_row_id(G, r, side, q == 0, err);
+        const long long id = feed_row_id(G.F, r, side, q == 0, err);
         const int4 t = *reinterpret_cast<const int4*>(G.table[side] + id * G.L + 4 * q);
         longlong2* d = reinterpret_cast<longlong2*>(G.docs + c * 4);
         d[0] = make_longlong2(t.x, t.y);
@@ -64,7 +48,7 @@ __global__ __launch_bounds__(256) void doc_gather_scalar_kernel(const DocGather 
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
         const int r = (int)(e / G.L), j = (int)(e - (long long)r * G.L);
         int side;
-        const long long id = gather_row_id(G, r, side, j == 0, err);
+        const long long id = feed_row_id(G.F, r, side, j == 0, err);
         const long long t = G.table[side][id * G.L + j];
         G.docs[e] = t;
         if (G.masks) G.masks[e] = t != G.pad;
@@ -84,13 +68,15 @@ extern "C" int rbr_doc_gather(int32_t B, int32_t L, const int64_t* u_ids, const 
         return RBR_ERR_BAD_ARG;
     }
     DocGather G;
-    G.ids[0] = reinterpret_cast<const long long*>(u_ids); G.ids[1] = reinterpret_cast<const long long*>(i_ids);
+    G.F.ids[0] = reinterpret_cast<const long long*>(u_ids); G.F.ids[1] = reinterpret_cast<const long long*>(i_ids);
+    G.F.rows[0] = U; G.F.rows[1] = I;
+    G.F.ids_out = reinterpret_cast<long long*>(ids_out);
+    G.F.replace = replace_id;
+    G.F.B = B;
     G.table[0] = user_docs; G.table[1] = item_docs;
-    G.rows[0] = U; G.rows[1] = I;
     G.docs = reinterpret_cast<long long*>(docs_out);
     G.masks = masks_out;
-    G.ids_out = reinterpret_cast<long long*>(ids_out);
-    G.pad = pad_token; G.replace = replace_id;
+    G.pad = pad_token;
     G.B = B; G.L = L;
     hipStream_t st = (hipStream_t)stream;
     const auto aligned = [](const void* p, uintptr_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) % a) == 0; };

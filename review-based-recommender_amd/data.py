@@ -179,10 +179,47 @@ class DocDataset(torch.utils.data.Dataset):
         return torch.LongTensor(u_ids), torch.LongTensor(i_ids), torch.FloatTensor(ratings)
 
 
-class ReviewDataset(torch.utils.data.Dataset):
-    """review split (NARRE): examples are (u_id, i_id, rating, u_revs, i_revs, u_rids, i_rids[, extra])."""
+def _first_slots(lists, idx: int, n: int, pad):
+    """The first n entries of id idx's list in meta (absent id: none), padded with `pad`: truncate_pad_tokens of the reference's
+    preprocess, which is all an example ever reads of a per-id list."""
+    row = list((lists.get(idx, ()) if isinstance(lists, dict) else lists[idx])[:n])
+    return row + [pad] * (n - len(row))
 
-    def __init__(self, data_dir: str, set_name: str):
+
+def review_example_from_meta(ds, u_id: int, i_id: int, leave_one_out: bool):
+    """Fields 3..6 (u_revs, i_revs, u_rids, i_rids) of the review-split example of the pair, from meta's per-id lists alone.
+    leave_one_out (the train split, preprocess/divide_and_create_example_word.py:263-285): the id's review of the pair's
+    counterpart -- the first one in its rid list -- is removed before the list is truncated / padded to rv_num; removing one
+    slot and keeping rv_num reads the first rv_num + 1 entries only, and a match at or beyond slot rv_num changes nothing.
+    Without leave_one_out (valid / test, :306-323), or without such a review, the first rv_num slots as they are."""
+    R, T = ds.rv_num, ds.rv_len
+    zero = [0] * T
+    out = []
+    for revs, rids, own, other in ((ds.user_reviews, ds.user_rids, u_id, i_id), (ds.item_reviews, ds.item_rids, i_id, u_id)):
+        rv = [list(r[:T]) + [0] * (T - len(r)) for r in _first_slots(revs, own, R + 1, zero)]
+        rd = [int(x) for x in _first_slots(rids, own, R + 1, 0)]
+        d = R
+        if leave_one_out and other > 0 and other in rd[:R]:
+            d = rd.index(other)
+        out.append(([rv[q + (q >= d)] for q in range(R)], [rd[q + (q >= d)] for q in range(R)]))
+    (u_revs, u_rids), (i_revs, i_rids) = out
+    return u_revs, i_revs, u_rids, i_rids
+
+
+class ReviewDataset(torch.utils.data.Dataset):
+    """review split (NARRE, SimpleSiamese): examples are (u_id, i_id, rating, u_revs, i_revs, u_rids, i_rids[, extra]).
+
+    feed="examples" (the reference's): a batch carries its reviews (collate_fn, train_narre.py:316-330).
+    feed="ids": a batch is (u_ids int64, i_ids int64, ratings f32) and the reviews are rebuilt on the device from meta.pkl's
+    per-id lists (DeviceReviewCache).  That is only the same batch when every example IS what review_example_from_meta gives
+    for its ids (the reference's preprocess builds them so); the id feed checks it once, at load time, and refuses a split
+    that differs (ValueError naming the first such example and field)."""
+
+    FEEDS = ("examples", "ids")
+
+    def __init__(self, data_dir: str, set_name: str, feed: str = "examples"):
+        if feed not in self.FEEDS:
+            raise ValueError(f"feed must be one of {self.FEEDS}, got {feed!r}")
         meta = load_pickle(os.path.join(data_dir, "meta.pkl"))
         self.user_num, self.item_num = meta["user_num"], meta["item_num"]
         self.rv_num, self.rv_len = meta["rv_num"], meta["rv_len"]
@@ -190,7 +227,11 @@ class ReviewDataset(torch.utils.data.Dataset):
         self.user_reviews, self.item_reviews = meta["user_reviews"], meta["item_reviews"]
         self.user_rids, self.item_rids = meta["user_rids"], meta["item_rids"]
         self.examples = load_pickle(os.path.join(data_dir, f"{set_name}_exmaples.pkl"))
+        self.set_name = set_name
+        self.feed = feed
         self.validate_ranges()
+        if feed == "ids":
+            self.check_examples_match_meta()
 
     def validate_ranges(self) -> None:
         _check_range([e[0] for e in self.examples], self.user_num, "user ids")
@@ -200,18 +241,60 @@ class ReviewDataset(torch.utils.data.Dataset):
         _check_range([e[5] for e in self.examples], self.item_num, "user-side counterpart (item) ids")
         _check_range([e[6] for e in self.examples], self.user_num, "item-side counterpart (user) ids")
 
+    def check_examples_match_meta(self) -> None:
+        """The id feed's precondition: fields 3..6 of example k are review_example_from_meta of its ids -- leave-one-out for the
+        train split, plain otherwise."""
+        loo = self.set_name == "train"
+        names = ("u_revs", "i_revs", "u_rids", "i_rids")
+        for k, e in enumerate(self.examples):
+            want = review_example_from_meta(self, int(e[0]), int(e[1]), loo)
+            for name, got, ref in zip(names, e[3:7], want):
+                got = [list(r) for r in got] if name.endswith("revs") else [int(x) for x in got]
+                if got != ref:
+                    rule = "with the pair's own review left out" if loo else "truncated / padded to rv_num"
+                    raise ValueError(f"{self.set_name} example {k}: its {name} is not meta.pkl's list of id "
+                                     f"{int(e[0]) if name[0] == 'u' else int(e[1])} {rule}, so the id feed would train on other "
+                                     "reviews than the example's (use feed='examples')")
+
     def __len__(self):
         return len(self.examples)
 
     def __getitem__(self, i):
+        if self.feed == "ids":
+            return self.examples[i][:3]
         return self.examples[i][:7]     # train examples carry an 8th field that the trainer drops
 
     def collate_fn(self, batch):
-        """train_narre.py:316-330."""
-        u_ids, i_ids, ratings, u_revs, i_revs, u_rids, i_rids = zip(*batch)
+        """train_narre.py:316-330; the id feed's batch is DocDataset.id_collate_fn's."""
+        if self.feed == "ids":
+            return DocDataset.id_collate_fn(batch)
+        u_ids, i_ids, ratings, u_revs, i_revs, u_rids, i_rids = zip(*[e[:7] for e in batch])
         u_revs, i_revs = torch.LongTensor(u_revs), torch.LongTensor(i_revs)
         return (u_revs, i_revs, get_mask(u_revs), get_mask(i_revs), torch.LongTensor(u_ids), torch.LongTensor(i_ids),
                 torch.LongTensor(u_rids), torch.LongTensor(i_rids), torch.FloatTensor(ratings))
+
+
+def _review_tables(reviews, rids, n: int, slots: int, T: int):
+    """meta's per-id review lists -- ragged: an id has as many reviews as it wrote, and absent ids have none -- as rectangular
+    tables of `slots` reviews per id: (int64 [n, slots, T], int64 [n, slots]) on the host, zero-padded (pad token / rid 0)."""
+    import numpy as np
+    tab = np.zeros((n, slots, T), dtype=np.int64)
+    rid = np.zeros((n, slots), dtype=np.int64)
+    for i in range(n):
+        rv = _first_slots(reviews, i, slots, None)
+        rd = _first_slots(rids, i, slots, None)
+        k = sum(r is not None for r in rv)
+        if k != sum(r is not None for r in rd):
+            raise ValueError(f"id {i} has {k} reviews but {sum(r is not None for r in rd)} counterpart ids in meta.pkl")
+        if k:
+            rid[i, :k] = rd[:k]
+            if all(len(r) == T for r in rv[:k]):
+                tab[i, :k] = rv[:k]
+            else:                                    # reviews of another length: truncated / zero-padded one by one
+                for j in range(k):
+                    r = list(rv[j])[:T]
+                    tab[i, j, :len(r)] = r
+    return torch.from_numpy(tab), torch.from_numpy(rid)
 
 
 class DeviceDocCache:
@@ -222,19 +305,20 @@ class DeviceDocCache:
     vocabulary once, here, so a gathered batch needs no per-step token check); review split: reviews [U, R, T] plus
     counterpart ids [U, R], int64.
     The reference trains on the examples' own copies (train_deepconn_pp.py:276); for the doc split those are
-    the same per-id documents (DocDataset.check_documents_match_meta), so gathering by id is equivalent.  (For NARRE's train
-    split the reference blanks the target review inside each example, divide_and_create_example_word.py:262-288 -- use the
-    examples there.)"""
+    the same per-id documents (DocDataset.check_documents_match_meta), so gathering by id is equivalent.  (For the review split's train
+    examples the reference removes the target pair's own review, divide_and_create_example_word.py:262-288: DeviceReviewCache
+    rebuilds those from ids; this cache holds the first rv_num reviews per id, the valid / test rule.)"""
 
     PAD = 0          # get_mask's padding id (utils.py:30-42)
 
     def __init__(self, ds, device):
         self.device = torch.device(device)
         if isinstance(ds, ReviewDataset):
-            self.user = torch.tensor(_rows(ds.user_reviews, ds.user_num, "user_reviews"), dtype=torch.int64, device=self.device)
-            self.item = torch.tensor(_rows(ds.item_reviews, ds.item_num, "item_reviews"), dtype=torch.int64, device=self.device)
-            self.user_rids = torch.tensor(_rows(ds.user_rids, ds.user_num, "user_rids"), dtype=torch.int64, device=self.device)
-            self.item_rids = torch.tensor(_rows(ds.item_rids, ds.item_num, "item_rids"), dtype=torch.int64, device=self.device)
+            # meta's lists are ragged on a real split (an id has as many reviews as it wrote): the first rv_num, zero-padded
+            user, urid = _review_tables(ds.user_reviews, ds.user_rids, ds.user_num, ds.rv_num, ds.rv_len)
+            item, irid = _review_tables(ds.item_reviews, ds.item_rids, ds.item_num, ds.rv_num, ds.rv_len)
+            self.user, self.item = user.to(self.device), item.to(self.device)
+            self.user_rids, self.item_rids = urid.to(self.device), irid.to(self.device)
         else:
             user = torch.tensor(_rows(ds.user_docs, ds.user_num, "user_docs"), dtype=torch.int64)
             item = torch.tensor(_rows(ds.item_docs, ds.item_num, "item_docs"), dtype=torch.int64)
@@ -253,7 +337,7 @@ class DeviceDocCache:
         all-pad row 0 and an IndexError at functional.check_id_errors()."""
         from . import functional as RF
         if self.user_rids is not None:
-            raise RuntimeError("gather is the doc split's id feed (the review split's examples are not per-id data)")
+            raise RuntimeError("gather is the doc split's id feed (the review split's is DeviceReviewCache.feed)")
         u_ids = u_ids.to(self.device, non_blocking=True)
         i_ids = i_ids.to(self.device, non_blocking=True)
         if out is None:
@@ -294,6 +378,122 @@ class DeviceDocCache:
         u, i = self.user.index_select(0, u_ids), self.item.index_select(0, i_ids)
         return (u, i, get_mask(u), get_mask(i), u_ids, i_ids, self.user_rids.index_select(0, u_ids),
                 self.item_rids.index_select(0, i_ids))
+
+
+class DeviceReviewCache:
+    """meta.pkl's reviews resident on the device, R + 1 = rv_num + 1 slots per id, so that a review-split batch -- train
+    (leave-one-out) or valid -- is rebuilt from (u_ids, i_ids) by one launch (functional.review_gather; see
+    review_example_from_meta for the rule and why R + 1 slots are enough).
+
+    Tables: int32 reviews [N, R+1, T] and counterpart ids [N, R+1] per side, from meta's possibly ragged per-id lists; ids absent
+    from meta, and id 0, are all-pad rows.  Tokens were range-checked against the vocabulary and rids against the other side's
+    id count once, here, so a gathered batch needs no per-step check.  `.user` / `.item` / `.user_rids` / `.item_rids` are the
+    first R slots -- the valid rule, what recommend.Recommender encodes.  With device "cpu" the same methods run a plain torch
+    restatement of the kernel (host tests, cross-checks)."""
+
+    PAD = 0
+    ORDER = {"narre": ("revs", "word_masks", "ids", "rids"), "simple_siamese": ("revs", "word_masks", "rev_masks", "ids")}
+
+    def __init__(self, ds, device):
+        self.device = torch.device(device)
+        self.rv_num, self.rv_len = int(ds.rv_num), int(ds.rv_len)
+        R = self.rv_num
+        tabs = {}
+        for side, revs, rids, n, n_other in (("user", ds.user_reviews, ds.user_rids, ds.user_num, ds.item_num),
+                                             ("item", ds.item_reviews, ds.item_rids, ds.item_num, ds.user_num)):
+            tab, rid = _review_tables(revs, rids, n, R + 1, self.rv_len)
+            _check_range(tab, ds.vocab_size, f"meta.pkl {side}_reviews tokens")
+            _check_range(rid, n_other, f"meta.pkl {side}_rids")
+            tab[0] = self.PAD                   # id 0 is the padding id: the row a bad id is replaced by
+            rid[0] = 0
+            tabs[side] = (tab.to(torch.int32).to(self.device), rid.to(torch.int32).to(self.device))
+        (self.user_table, self.user_rid_table), (self.item_table, self.item_rid_table) = tabs["user"], tabs["item"]
+        self.user, self.item = self.user_table[:, :R], self.item_table[:, :R]
+        self.user_rids = self.user_rid_table[:, :R].to(torch.int64)
+        self.item_rids = self.item_rid_table[:, :R].to(torch.int64)
+
+    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, leave_one_out: bool, revs=None, word_masks=None, rev_masks=True,
+               rids=True, ids=True):
+        """functional.review_gather over the tables (stacked outputs, user rows first); on the cpu, its torch restatement,
+        which raises the IndexError of an id outside its table at once."""
+        u_ids, i_ids = u_ids.to(self.device, non_blocking=True), i_ids.to(self.device, non_blocking=True)
+        if self.device.type == "cuda":
+            from . import functional as RF
+            return RF.review_gather(u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table, self.item_rid_table,
+                                    leave_one_out, self.PAD, 0, revs=revs, word_masks=word_masks, rev_masks=rev_masks, rids=rids,
+                                    ids=ids)
+        got = self._gather_torch(u_ids, i_ids, leave_one_out)
+        outs = []
+        for n, (val, dst) in enumerate(zip(got, (revs, word_masks, rev_masks, rids, ids))):
+            if torch.is_tensor(dst):
+                outs.append(dst.copy_(val))
+            else:                               # revs / word_masks: None allocates; the others: True allocates, None / False omits
+                outs.append(val if dst is True or (dst is None and n < 2) else None)
+        return tuple(outs)
+
+    def _gather_torch(self, u_ids, i_ids, leave_one_out: bool):
+        R, T = self.rv_num, self.rv_len
+        q = torch.arange(R)
+        revs, rids = [], []
+        for own, other, tab, rid, n_other in ((u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table.shape[0]),
+                                              (i_ids, u_ids, self.item_table, self.item_rid_table, self.user_table.shape[0])):
+            _check_range(own, tab.shape[0], "ids of a gathered batch")
+            rr = rid.index_select(0, own).to(torch.int64)                                   # [B, R + 1]
+            hit = (rr[:, :R] == other[:, None]) & ((other > 0) & (other < n_other))[:, None] & bool(leave_one_out)
+            d = torch.where(hit.any(1), hit.to(torch.int64).argmax(1), torch.full_like(own, R))      # the FIRST match, else R
+            src = q[None, :] + (q[None, :] >= d[:, None]).to(torch.int64)
+            revs.append(tab.index_select(0, own).to(torch.int64).gather(1, src[:, :, None].expand(-1, -1, T)))
+            rids.append(rr.gather(1, src))
+        revs2, rids2 = torch.cat(revs), torch.cat(rids)
+        wm = revs2 != self.PAD
+        return revs2, wm, wm.any(-1), rids2, torch.cat([u_ids, i_ids])
+
+    def feed(self, kind: str, leave_one_out: bool) -> "ReviewFeed":
+        """The id feed of model `kind` ("narre" / "simple_siamese"): what GraphedTrainStep.from_ids / GraphedForward.from_ids and
+        the trainer take for `cache`.  leave_one_out=True rebuilds train examples, False valid / test examples."""
+        return ReviewFeed(self, kind, leave_one_out)
+
+
+class ReviewFeed:
+    """One model's view of a DeviceReviewCache under one rule: empty_inputs / gather / inputs with DeviceDocCache's meaning, in
+    the model's own argument order --
+      narre          (u_revs, i_revs, u_word_masks, i_word_masks, u_ids, i_ids, u_rids, i_rids)
+      simple_siamese (u_revs, i_revs, u_word_masks, i_word_masks, u_rev_masks, i_rev_masks, u_ids, i_ids)"""
+
+    def __init__(self, cache: DeviceReviewCache, kind: str, leave_one_out: bool):
+        if kind not in cache.ORDER:
+            raise ValueError(f"the review feed serves {sorted(cache.ORDER)}, not {kind}")
+        self.cache, self.kind, self.leave_one_out = cache, kind, bool(leave_one_out)
+        self.order = cache.ORDER[kind]
+        self.device = cache.device
+
+    def empty_inputs(self, B: int, with_ids: bool = True):
+        """Zeroed tensors of inputs()' shapes and dtypes for B pairs (what a recorded step lays its input block out by).
+        `with_ids` is DeviceDocCache's parameter: both review models take their ids, so it changes nothing here."""
+        R, T, dev = self.cache.rv_num, self.cache.rv_len, self.device
+        like = {"revs": ((B, R, T), torch.int64), "word_masks": ((B, R, T), torch.bool), "rev_masks": ((B, R), torch.bool),
+                "rids": ((B, R), torch.int64), "ids": ((B,), torch.int64)}
+        return tuple(torch.zeros(like[k][0], dtype=like[k][1], device=dev) for k in self.order for _ in range(2))
+
+    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None):
+        """The pairs' batch, stacked ({name: [2B, ...]} in the model's order).  `out`: the model's eight arguments to write into
+        instead, each (user, item) pair adjacent in one allocation -- the input views of a recorded step."""
+        if out is None:
+            kw = {k: True for k in self.order if k not in ("revs", "word_masks")}
+        else:
+            if len(out) != 2 * len(self.order):
+                raise RuntimeError(f"out must be the {2 * len(self.order)} arguments of {self.kind}")
+            kw = {k: _adjacent(out[2 * n], out[2 * n + 1]) for n, k in enumerate(self.order)}
+        for k in ("rev_masks", "rids", "ids"):
+            kw.setdefault(k, None)
+        got = self.cache.gather(u_ids, i_ids, self.leave_one_out, **kw)
+        return dict(zip(("revs", "word_masks", "rev_masks", "rids", "ids"), got))
+
+    def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
+        """The model's arguments for the pairs -- views of one gather."""
+        B = u_ids.shape[0]
+        got = self.gather(u_ids, i_ids)
+        return tuple(half for k in self.order for half in (got[k][:B], got[k][B:]))
 
 
 def _adjacent(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:

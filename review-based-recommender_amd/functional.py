@@ -209,6 +209,52 @@ def doc_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_docs: torch.Tensor
     return docs, masks, ids
 
 
+def review_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_revs: torch.Tensor, user_rids: torch.Tensor,
+                  item_revs: torch.Tensor, item_rids: torch.Tensor, leave_one_out: bool, pad_token: int = 0, replace_id: int = 0,
+                  revs: Optional[torch.Tensor] = None, word_masks: Optional[torch.Tensor] = None, rev_masks=True, rids=True, ids=True):
+    """The id-fed review-split batch (rbr_review_gather, one launch): returns (revs2 [2B, R, T] int64, word_masks2 [2B, R, T]
+    bool, rev_masks2 [2B, R] bool or None, rids2 [2B, R] int64 or None, ids2 [2B] int64 or None), user rows first -- the halves
+    are what ReviewDataset.collate_fn builds from the examples of the same pairs.  Tables: user_revs [U, R+1, T] / user_rids
+    [U, R+1], item_revs [I, R+1, T] / item_rids [I, R+1], int32 (data.DeviceReviewCache).
+
+    leave_one_out (a train example): the first of an id's R leading reviews that was written for the pair's counterpart is
+    dropped and the following slots move up; without it, or without such a review, the first R slots are taken as they are.
+    word_masks2 = revs2 != pad_token, rev_masks2 = word_masks2.any(-1).  An own id outside its table reads row `replace_id`
+    and is recorded as doc_gather records it (check_id_errors()).
+
+    `revs` / `word_masks`: stacked tensors to write into, or None to allocate; `rev_masks` / `rids` / `ids`: a stacked tensor,
+    True to allocate, None / False to leave out.  No autograd, no sync: graph-capturable."""
+    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
+        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+    if user_revs.dim() != 3 or item_revs.dim() != 3 or user_revs.shape[1:] != item_revs.shape[1:] or user_revs.shape[1] < 2:
+        raise RuntimeError(f"review tables must be [U, R+1, T] / [I, R+1, T], got {tuple(user_revs.shape)} / {tuple(item_revs.shape)}")
+    B, R, T = u_ids.shape[0], user_revs.shape[1] - 1, user_revs.shape[2]
+    if user_rids.shape != (user_revs.shape[0], R + 1) or item_rids.shape != (item_revs.shape[0], R + 1):
+        raise RuntimeError(f"rid tables must be [U, {R + 1}] / [I, {R + 1}], got {tuple(user_rids.shape)} / {tuple(item_rids.shape)}")
+    dev = u_ids.device
+    if revs is None:
+        revs = torch.empty(2 * B, R, T, dtype=I64, device=dev)
+    if word_masks is None:
+        word_masks = torch.empty(2 * B, R, T, dtype=torch.bool, device=dev)
+    rev_masks = torch.empty(2 * B, R, dtype=torch.bool, device=dev) if rev_masks is True else (None if rev_masks is False else rev_masks)
+    rids = torch.empty(2 * B, R, dtype=I64, device=dev) if rids is True else (None if rids is False else rids)
+    ids = torch.empty(2 * B, dtype=I64, device=dev) if ids is True else (None if ids is False else ids)
+    for name, t, shape, dtype in (("revs", revs, (2 * B, R, T), I64), ("word_masks", word_masks, (2 * B, R, T), torch.bool),
+                                  ("rev_masks", rev_masks, (2 * B, R), torch.bool), ("rids", rids, (2 * B, R), I64),
+                                  ("ids", ids, (2 * B,), I64)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}, got {t.dtype} {list(t.shape)}")
+    if B == 0:
+        return revs, word_masks, rev_masks, rids, ids
+    _call(None, _lib.lib().rbr_review_gather, B, R, T, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),
+          dev_ptr(user_revs, I32, "user_revs"), dev_ptr(user_rids, I32, "user_rids"), user_revs.shape[0],
+          dev_ptr(item_revs, I32, "item_revs"), dev_ptr(item_rids, I32, "item_rids"), item_revs.shape[0],
+          int(bool(leave_one_out)), int(pad_token), int(replace_id), dev_ptr(revs, I64, "revs"),
+          dev_ptr(word_masks.view(U8), U8, "word_masks"), dev_ptr(None if rev_masks is None else rev_masks.view(U8), U8, "rev_masks"),
+          dev_ptr(rids, I64, "rids"), dev_ptr(ids, I64, "ids"), _id_err(dev).data_ptr(), current_stream())
+    return revs, word_masks, rev_masks, rids, ids
+
+
 def set_tap_sink(sink, table: Optional[torch.Tensor] = None) -> None:
     """Installs `sink` for the word table it exchanges (sink.table); set_tap_sink(None, table) removes that table's sink,
     set_tap_sink(None) removes all of them."""

@@ -37,7 +37,8 @@ class SeenItems(NamedTuple):
 class Recommender:
     """Latent tables of a trained model over a whole catalogue, and the queries on them.
 
-    `cache`: a data.DeviceDocCache (doc split for DeepCoNN++ / D-ATT, review split for NARRE / SimpleSiamese); or pass the
+    `cache`: a data.DeviceDocCache (doc split for DeepCoNN++ / D-ATT) or data.DeviceReviewCache (review split for NARRE /
+    SimpleSiamese; a DeviceDocCache of the review split serves too); or pass the
     per-id document tensors yourself: `user` / `item` = [U, L] (doc split) or [U, R, T] (review split) integer tensors on the
     model's device, plus `user_rids` / `item_rids` [U, R] int64 for NARRE.  Row 0 of each side is the padding id.
 
@@ -69,7 +70,7 @@ class Recommender:
     # ------------------------------------------------------------------ the tables
     def _encode(self, side: str, a: int, b: int) -> torch.Tensor:
         c, m = self.cache, self.model
-        docs = (c.user if side == "user" else c.item)[a:b].to(torch.int64)
+        docs = (c.user if side == "user" else c.item)[a:b].to(torch.int64).contiguous()
         ids = torch.arange(a, b, dtype=torch.int64, device=docs.device)
         enc = m.encode_users if side == "user" else m.encode_items
         if self.kind == "deepconn":
@@ -192,11 +193,14 @@ def main(argv=None) -> int:
     dev = torch.device(a.device)
     review_split = a.model in ("narre", "simple_siamese")
     ds = D.ReviewDataset(cfg.data_dir, "train") if review_split else D.DocDataset(cfg.data_dir, "train", with_ids=a.model == "deepconn")
+    # the review split's meta holds as many reviews per id as the id wrote: DeviceReviewCache's first rv_num slots are what a
+    # valid / test example reads
+    cache = D.DeviceReviewCache(ds, dev) if review_split else D.DeviceDocCache(ds, dev)
     model = make_model(a.model, cfg, ds, a.reference_quirks)
     ck = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     model.load_state_dict(ck["model"] if "model" in ck else ck)
     model.to(dev).eval()
-    rec = Recommender(model, D.DeviceDocCache(ds, dev)).refresh(chunk=a.chunk)
+    rec = Recommender(model, cache).refresh(chunk=a.chunk)
     seen = Recommender.seen_from(ds.examples, rec.n_users, dev) if a.exclude_train else None
     with open(a.out, "w") as f:
         for lo in range(1, rec.n_users, a.chunk):

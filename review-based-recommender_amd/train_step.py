@@ -335,8 +335,9 @@ class GraphedForward:
     the model in eval() first.  __call__ copies a batch of the same shapes into the static input block (one copy when it was
     pack()ed) and replays; the returned prediction tensor is static: overwritten by the next replay.
 
-    `feed` (a data.DeviceDocCache; from_ids()): the batch is (u_ids, i_ids) and the graph starts with the gather of their
-    documents into the model's input block (with_ids=False: documents only, D-ATT's forward)."""
+    `feed` (a data.DeviceDocCache, or a data.ReviewFeed for the review split; from_ids()): the batch is (u_ids, i_ids) and the
+    graph starts with the gather of their documents into the model's input block (with_ids=False: documents only, D-ATT's
+    forward)."""
 
     def __init__(self, model: nn.Module, batch, warmup: int = 2, capture_error_mode: str = "global", feed=None,
                  with_ids: bool = True):
@@ -457,7 +458,7 @@ class GraphedTrainStep:
 
     The optimizer must have been built with make_optimizer(..., capturable=True).
 
-    `feed` (a data.DeviceDocCache; from_ids()): the id-fed step.  `batch` is then (u_ids, i_ids); a slot stages only
+    `feed` (a data.DeviceDocCache, or a data.ReviewFeed for the review split; from_ids()): the id-fed step.  `batch` is then (u_ids, i_ids); a slot stages only
     (u_ids, i_ids, ratings) -- one small block, `stage` / `slot_inputs` -- and its graph starts with the gather of the
     documents into the slot's document block (cache.gather: documents, masks and checked ids for DeepCoNN++; documents
     only with with_ids=False, D-ATT), followed by the unchanged step."""

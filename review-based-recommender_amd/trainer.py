@@ -23,7 +23,11 @@ the device and read back only at log lines (the reference calls loss.item() twic
 D-ATT) keeps meta.pkl's documents on the GPU and feeds the step (u_id, i_id, rating) batches whose documents are gathered
 there (data.DeviceDocCache; the loaders check once that every example's documents are meta's for its ids); `eval_from_towers:
 true` (with device_cache) validates from latent tables: every user / item document is encoded once per validation pass and a
-pair is scored from two table rows (recommend.Recommender), instead of both documents being encoded for every pair.
+pair is scored from two table rows (recommend.Recommender), instead of both documents being encoded for every pair;
+`device_reviews: true` (NARRE and SimpleSiamese) is the review split's counterpart of device_cache: meta.pkl's reviews stay on the
+GPU (data.DeviceReviewCache), the loaders ship (u_id, i_id, rating) and one launch rebuilds the batch -- training examples with
+the pair's own review left out, validation examples plain (the loaders check once that every example is what that rule gives
+for its ids); eval_from_towers works on top of it.
 """
 from __future__ import annotations
 
@@ -60,7 +64,8 @@ class EarlyStop(Exception):
 
 DEFAULTS = dict(log_dir="logs", dataset="dataset", log=True, log_idx=500, verbose=False, parallel=False, epochs=64,
                 batch_size=50, lr=0.002, max_grad_norm=5.0, patience=5, dropout=0.5, arch="CNN", use_pretrain=False,
-                num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False, eval_from_towers=False)
+                num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False, eval_from_towers=False,
+                device_reviews=False)
 
 
 class _ShardSampler(torch.utils.data.Sampler):
@@ -154,10 +159,14 @@ class ReviewExperiment:
             # the review split's training examples are not per-id data: the reference drops the target pair's own review from
             # the user's and the item's lists before truncating (preprocess/divide_and_create_example_word.py:263-285)
             raise ValueError(f"device_cache is valid for --model deepconn and dual_att, not {kind}: the review split's examples "
-                             "are not per-id documents")
-        if bool(args.eval_from_towers) and not (bool(args.device_cache) and kind in ("deepconn", "dual_att")):
-            raise ValueError("eval_from_towers needs device_cache and --model deepconn or dual_att: validation then scores each "
-                             "pair from latent tables encoded once per epoch from the per-id documents")
+                             "are not per-id documents (its id feed is device_reviews)")
+        if bool(args.device_reviews) and kind not in ("narre", "simple_siamese"):
+            raise ValueError(f"device_reviews is valid for --model narre and simple_siamese, not {kind}: the doc split's id feed "
+                             "is device_cache")
+        if bool(args.eval_from_towers) and not (bool(args.device_cache) or bool(args.device_reviews)):
+            raise ValueError("eval_from_towers needs device_cache (--model deepconn or dual_att) or device_reviews (narre or "
+                             "simple_siamese): validation then scores each pair from latent tables encoded once per epoch from "
+                             "the per-id documents")
         self.kind, self.args, self.quirks = kind, args, reference_quirks
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -175,12 +184,17 @@ class ReviewExperiment:
         review_split = kind in ("narre", "simple_siamese")
         cls = D.ReviewDataset if review_split else D.DocDataset
         kw = {} if review_split else {"with_ids": kind == "deepconn"}
-        if args.device_cache:
+        if args.device_cache or args.device_reviews:
             kw["feed"] = "ids"
         self.train_set = cls(args.data_dir, "train", **kw)
         self.valid_set = cls(args.data_dir, "valid", **kw)
         # device_cache: meta.pkl's documents resident on this GPU (train and valid share meta.pkl, so one cache serves both)
         self.cache = D.DeviceDocCache(self.train_set, self.device) if args.device_cache else None
+        self.train_feed = self.eval_feed = self.cache     # what rebuilds a batch from its ids
+        if args.device_reviews:
+            # meta.pkl's reviews resident on this GPU; a train batch leaves each pair's own review out, a valid batch does not
+            self.cache = D.DeviceReviewCache(self.train_set, self.device)
+            self.train_feed, self.eval_feed = self.cache.feed(kind, True), self.cache.feed(kind, False)
         self._make_dir()
         self.build_model()
         # both splits were range-checked against their tables when they were loaded (data.validate_ranges): the per-forward
@@ -305,7 +319,7 @@ class ReviewExperiment:
         the step's input block (GraphedTrainStep.stage) and the step is replayed -- no intermediate device tensors, no
         device-to-device copies.  None: not applicable (first batch, ragged batch, a model whose inputs are derived on the
         device), the caller takes the _to_device + _step route."""
-        if not self.args.fast_step or self._graphed is None or self.kind == "simple_siamese":
+        if not self.args.fast_step or self._graphed is None or (self.kind == "simple_siamese" and self.cache is None):
             return None
         key = tuple((t.shape, t.dtype) for t in batch)
         if key != self._graphed_key:
@@ -330,40 +344,40 @@ class ReviewExperiment:
         return loss, gnorm
 
     def _id_step(self, batch):
-        """device_cache: one step on a (u_ids, i_ids, ratings) batch.  With `fast_step` the id-fed step recorded for this batch
-        shape (gather + step) is replayed; otherwise, and for a ragged last batch, the documents are gathered eagerly and
-        train_step runs on them."""
+        """device_cache / device_reviews: one step on a (u_ids, i_ids, ratings) batch.  With `fast_step` the id-fed step recorded
+        for this batch shape (gather + step) is replayed; otherwise, and for a ragged last batch, the documents are gathered
+        eagerly and train_step runs on them."""
         a = self.args
         u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
-        with_ids = self.kind == "deepconn"
+        with_ids = self.kind != "dual_att"
         if a.fast_step:
             key = tuple((t.shape, t.dtype) for t in batch)
             if self._graphed is None:
-                self._graphed = GraphedTrainStep.from_ids(self.model, self.optimizer, self.cache, u_ids, i_ids, ratings,
+                self._graphed = GraphedTrainStep.from_ids(self.model, self.optimizer, self.train_feed, u_ids, i_ids, ratings,
                                                           a.max_grad_norm, self.grad_sync, with_ids=with_ids)
                 self._graphed_key = key
             if key == self._graphed_key:
                 loss, gnorm, _ = self._graphed((u_ids, i_ids), ratings)
                 return loss.clone(), gnorm.clone(), ratings
-        inputs = self.cache.inputs(u_ids, i_ids, with_ids=with_ids)
+        inputs = self.train_feed.inputs(u_ids, i_ids, with_ids=with_ids)
         loss, gnorm, _ = train_step(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync)
         return loss, gnorm, ratings
 
     def _eval_forward_ids(self, u_ids, i_ids):
-        """device_cache: the eval forward of an id batch -- gather + forward replayed from a hipGraph for the loader's regular
-        batch shape with `fast_step`, eager otherwise."""
-        with_ids = self.kind == "deepconn"
+        """device_cache / device_reviews: the eval forward of an id batch -- gather + forward replayed from a hipGraph for the
+        loader's regular batch shape with `fast_step`, eager otherwise."""
+        with_ids = self.kind != "dual_att"
         if self.args.fast_step:
             g = getattr(self, "_graphed_eval", None)
             if g is None:
                 try:
-                    g = self._graphed_eval = GraphedForward.from_ids(self.model, self.cache, u_ids, i_ids, with_ids=with_ids)
+                    g = self._graphed_eval = GraphedForward.from_ids(self.model, self.eval_feed, u_ids, i_ids, with_ids=with_ids)
                 except Exception as e:          # a capture the runtime refuses costs the speed-up, not the validation
                     self.print_write_to_log(f"eval forward not graphed ({type(e).__name__}: {str(e)[:100]})")
                     g = self._graphed_eval = False
             if g and g.matches((u_ids, i_ids)):
                 return g((u_ids, i_ids))
-        out = self.model(*self.cache.inputs(u_ids, i_ids, with_ids=with_ids))
+        out = self.model(*self.eval_feed.inputs(u_ids, i_ids, with_ids=with_ids))
         return out[0] if isinstance(out, tuple) else out
 
     def _eval_forward(self, inputs):
