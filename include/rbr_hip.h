@@ -349,7 +349,24 @@ int rbr_pair_head_fwd_pool(const rbr_textcnn_desc* d, const float* pval, const i
                            float* drop_out, float* zero_buf, int64_t zero_n, float* ul, float* il, float* pred,
                            const float* target, float* loss, float* d_pred_unit, int32_t* ticket, void* stream);
 
-/* d_ufeat/d_ifeat [B,H] overwritten; dense grads overwritten; embedding grads accumulated
+/* The same launch with one more output.  d_feat_unit [2B, C] (may be NULL; needs target): block b also writes the rows of
+ * documents b and B + b of d loss / d feat for an upstream gradient of 1 -- from its own prediction, d loss / d pred[b] =
+ * (pred[b] - target[b]) * 2/B, with the device function rbr_pair_head_bwd's pair blocks run: the same bits as
+ * rbr_pair_head_bwd(d_pred = d_pred_unit) writes to d_ufeat / d_ifeat.  The conv backward of a training step can then start
+ * without waiting for rbr_pair_head_bwd, which is called with NULL d_ufeat / d_ifeat for the rest (the embedding-row atomics
+ * go into the buffer THIS launch clears, so they cannot move here). */
+/* Dynamic LDS bytes rbr_pair_head_fwd_pool[_ex] needs for this conv and K (with_d_feat: with the d_feat_unit output); 0 when the
+ * launch would refuse -- more than one channel group, or more than 60 KB.  No GPU needed. */
+size_t rbr_pair_head_fwd_pool_lds_bytes(const rbr_textcnn_desc* d, int32_t K, int32_t with_d_feat);
+int rbr_pair_head_fwd_pool_ex(const rbr_textcnn_desc* d, const float* pval, const int32_t* pidx, const float* const* bias,
+                              float* feat, int32_t* argmax, const int64_t* first, int32_t K, const int64_t* u_id, const int64_t* i_id,
+                              const rbr_head_params* p, const float* drop, float p_drop, uint64_t seed, uint64_t* rng_state,
+                              float* drop_out, float* zero_buf, int64_t zero_n, float* ul, float* il, float* pred,
+                              const float* target, float* loss, float* d_pred_unit, int32_t* ticket, float* d_feat_unit,
+                              void* stream);
+
+/* d_ufeat/d_ifeat [B,H] overwritten -- or both NULL: d_feat is not computed (rbr_pair_head_fwd_pool_ex's d_feat_unit holds it)
+ * and the pair blocks only accumulate the embedding grads; dense grads overwritten; embedding grads accumulated
  * (rows u_id==pad_u / i_id==pad_i get none: nn.Embedding padding_idx).
  * ws: rbr_pair_head_bwd_ws_floats(B, K) floats (may be 0 / NULL: the current kernel needs no scratch). */
 size_t rbr_pair_head_bwd_ws_floats(int32_t B, int32_t K);
@@ -650,7 +667,10 @@ int rbr_clip_adam_step(int32_t n_tensors, float* const* params, float* const* gr
  * every other row -- the update formula is unchanged (so parameters and Adam state come out as with the dense gradient
  * nn.Embedding's backward builds, deepconn/layers.py:22-24 + trainer/train_deepconn_pp.py:166-167, bit for bit), but the
  * zero rows are neither read for the norm, nor read for the update, nor written back when the clip scales the gradient.
- * grads[rg->tensor] is ignored (may be NULL); `rows` is left clipped.  D % 4 == 0, V * D < 2^32, 16-byte aligned pointers. */
+ * grads[rg->tensor] is ignored (may be NULL).  `rows` is read only: it is NOT left clipped -- the clip coefficient (1 when
+ * nothing was clipped) goes to *coef_out, and the clipped gradient clip_grad_norm_ would leave is rows * coef (one rounding
+ * per element).  The dense gradients of the other tensors are clipped in place as before.
+ * D % 4 == 0, V * D < 2^32, 16-byte aligned pointers. */
 typedef struct rbr_row_grad {
     int32_t tensor;                 /* index of the table among the n_tensors */
     int32_t V, D;
@@ -658,6 +678,7 @@ typedef struct rbr_row_grad {
     float* rows;                    /* [list rows, D] */
     const float* sq_part;           /* [n_sq] partial sums of squares of `rows` */
     int32_t n_sq;
+    float* coef_out;                /* [1] device float receiving the clip coefficient (may be NULL) */
 } rbr_row_grad;
 int rbr_clip_adam_step_rows(int32_t n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
                             float* const* exp_avg_sq, const int64_t* numel, float max_norm, float lr, float beta1, float beta2,

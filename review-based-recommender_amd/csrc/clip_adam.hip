@@ -7,7 +7,8 @@
 //   grad_sqnorm : sum of squares of every gradient, fixed-order partials (no atomics: bitwise reproducible)
 //   clip_adam   : every workgroup reduces the partials to the total norm, derives the clip coefficient, and applies
 //                 g*coef -> exp_avg, exp_avg_sq, param in ONE pass (the clipped gradient is written back, as
-//                 clip_grad_norm_ leaves it, unless the coefficient is exactly 1): 60 + 420..480 MB.
+//                 clip_grad_norm_ leaves it, unless the coefficient is exactly 1 -- except a compact row gradient, whose
+//                 rows stay as they are beside the coefficient, rbr_row_grad.coef_out): 60 + 420..480 MB.
 // Math as torch.optim.Adam (amsgrad=False, weight_decay=0, maximize=False):
 //   m = m + (1-b1)(g - m);  v = b2 v + (1-b2) g^2;  p -= (lr / (1-b1^t)) * m / (sqrt(v)/sqrt(1-b2^t) + eps)
 // The step count t lives in device memory (a float, as torch's capturable Adam keeps it) and is advanced by the
@@ -36,8 +37,10 @@ struct OptTable {
     // sq_part[n_sq]: the producer's partial sums of squares of grows (the table's share of the norm).
     int rows_k, rows_D, n_sq;
     const int* row_of_token;
-    float* grows;
+    const float* grows;
     const float* sq_part;
+    float* coef_out;                           // the clip coefficient, for whoever reads the rows after the step (may be NULL)
+    long skip_at, skip_n;                      // the table's chunks [skip_at, skip_at + skip_n): not walked by grad_sqnorm (0 chunks: no table)
 };
 
 // One element's update, every operation individually rounded (no contraction): the dense path and the row-gradient path (g = 0
@@ -86,15 +89,16 @@ __device__ __forceinline__ float block_sum(float x, float* s_red) {
     return s_red[0] + s_red[1] + s_red[2] + s_red[3];        // fixed order
 }
 
-__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const OptTable T, long nchunks, float* __restrict__ partials,
+// nread: the chunks of the tensors whose gradient is READ here -- all but the compact-gradient table's, whose sum of squares
+// comes as partials (below).  The grid is sized to them (round 7: it was sized to all chunks, 1024 workgroups for the 92 chunks
+// the benched step reads, and every clip_adam workgroup then summed 1024 partials).
+__global__ __launch_bounds__(256) void grad_sqnorm_kernel(const OptTable T, long nread, float* __restrict__ partials,
                                                           float* __restrict__ step) {
     __shared__ float s_red[4];
     float acc = 0.f;
-    for (long c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    for (long cr = blockIdx.x; cr < nread; cr += gridDim.x) {
+        const long c = cr < T.skip_at ? cr : cr + T.skip_n;       // global chunk: past the table's
         const int k = tensor_of_chunk(T, c);
-        if (k == T.rows_k) {                 // compact-gradient table: its sum of squares comes as partials (below)
-            continue;
-        }
         const long e0 = (c - T.chunk0[k]) * kOptChunk;
         const long n = min((long)kOptChunk, T.n[k] - e0);
         const float* g = T.g[k] + e0;
@@ -144,6 +148,10 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const OptTable T, long n
     // clip_grad_norm_: coef = clamp(max_norm / (total + 1e-6), max = 1)
     const float coef = (max_norm > 0.f) ? fminf(max_norm / (total + 1e-6f), 1.f) : 1.f;
     const bool clipped = coef != 1.f;          // workgroup-uniform
+    // The compact rows are NOT re-written clipped (round 7): nobody reads them as rows, and the store was 4 of this kernel's ~32
+    // vector-memory instructions per thread and chunk.  Whoever makes them dense later multiplies by the coefficient left here
+    // (functional.RowGradient): g * coef rounded once, the bits the store used to leave.
+    if (MODE == 1 && blockIdx.x == 0 && threadIdx.x == 0 && T.coef_out != nullptr) *T.coef_out = coef;
     const AdamK K = adam_constants(coef, lr, beta1, beta2, eps, (double)*step);
 #define RBR_ADAM1(G, M, V, P, c) adam1(K, G.c, M.c, V.c, P.c);
     for (long c = blockIdx.x; c < nchunks; c += gridDim.x) {
@@ -200,7 +208,6 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const OptTable T, long n
                 const int i = threadIdx.x + 256 * u;
                 RBR_ADAM1(G[u], M[u], V[u], P[u], x) RBR_ADAM1(G[u], M[u], V[u], P[u], y)
                 RBR_ADAM1(G[u], M[u], V[u], P[u], z) RBR_ADAM1(G[u], M[u], V[u], P[u], w)
-                if (clipped && rl[u] >= 0) *reinterpret_cast<float4*>(T.grows + (long)rl[u] * D + ofs[u]) = G[u];
                 nt_store4(m, i, M[u]);
                 nt_store4(v, i, V[u]);
                 reinterpret_cast<float4*>(p)[i] = P[u];
@@ -219,7 +226,6 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const OptTable T, long n
                 if (r < 0) G = float4{0.f, 0.f, 0.f, 0.f};
                 float4 M = reinterpret_cast<float4*>(m)[i], V = reinterpret_cast<float4*>(v)[i], P = reinterpret_cast<float4*>(p)[i];
                 RBR_ADAM1(G, M, V, P, x) RBR_ADAM1(G, M, V, P, y) RBR_ADAM1(G, M, V, P, z) RBR_ADAM1(G, M, V, P, w)
-                if (clipped && r >= 0) *reinterpret_cast<float4*>(T.grows + go) = G;
                 reinterpret_cast<float4*>(m)[i] = M;
                 reinterpret_cast<float4*>(v)[i] = V;
                 reinterpret_cast<float4*>(p)[i] = P;
@@ -291,6 +297,7 @@ static int clip_adam_step(int32_t n_tensors, float* const* params, float* const*
             return RBR_ERR_BAD_ARG;
         }
         T.rows_k = k; T.rows_D = rg->D; T.n_sq = rg->n_sq; T.row_of_token = rg->row_of_token; T.grows = rg->rows; T.sq_part = rg->sq_part;
+        T.coef_out = rg->coef_out;
     }
     long chunks = 0;
     for (int k = 0; k < n_tensors; ++k) {
@@ -300,9 +307,17 @@ static int clip_adam_step(int32_t n_tensors, float* const* params, float* const*
         chunks += (numel[k] + kOptChunk - 1) / kOptChunk;
     }
     T.chunk0[n_tensors] = chunks;
+    long nread = chunks;
+    if (T.rows_k >= 0) {
+        T.skip_at = T.chunk0[T.rows_k];
+        T.skip_n = T.chunk0[T.rows_k + 1] - T.skip_at;
+        nread -= T.skip_n;
+    }
     hipStream_t st = (hipStream_t)stream;
-    const int nb1 = (int)std::min<long>(chunks, kOptMaxPartials);
-    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(nb1), dim3(256), 0, st, T, chunks, ws, step);
+    // one workgroup per chunk that is read, and enough of them for one element of sq_part per thread; at least one
+    const long sq_blocks = T.rows_k >= 0 ? ((long)T.n_sq + 255) / 256 : 0;
+    const int nb1 = (int)std::min<long>(std::max<long>(std::max(nread, sq_blocks), 1), kOptMaxPartials);
+    hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(nb1), dim3(256), 0, st, T, nread, ws, step);
     RBR_CHECK_LAUNCH("grad_sqnorm launch");
     const int nb2 = (int)std::min<long>(chunks, 4096);
     if (T.rows_k < 0)

@@ -17,6 +17,51 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// d_l of one (pair, k) from the saved latents; the batch-reduction blocks of the backward recompute it with the same function
+__device__ __forceinline__ void head_dl(float su, float si, float dr, float dp, float hk, float& dul, float& dil, float& zdp) {
+    const float prod = su * si;
+    const float dz = (prod > 0.f) ? dp * hk * dr : 0.f;
+    dul = dz * si;
+    dil = dz * su;
+    zdp = fmaxf(prod, 0.f) * dr * dp;
+}
+
+// The pair role of the backward, one workgroup per pair: d_l of the pair into s_dul / s_dil [K] (16-byte aligned), then -- unless
+// d_uf is NULL -- d_feat with all 256 threads over the 2*H outputs (rows of Wu / Wi read as float4 when K allows).  ulb / ilb / drb
+// (NULL: no dropout): the pair's rows of ul / il / drop, in global memory (head_bwd_kernel) or in LDS (head_fwd_pool_kernel, where
+// they may BE s_dul / s_dil: thread k reads element k before it writes it).  Both kernels call this one function with the same
+// values, so the d_feat of the forward launch and of the backward launch are the same bits.
+__device__ __forceinline__ void head_pair_dfeat(int H, int K, const float* ulb, const float* ilb, const float* drb, float dp,
+                                                const rbr_head_params& p, float* s_dul, float* s_dil, float* d_uf, float* d_if) {
+    const int t = threadIdx.x;
+    for (int k = t; k < K; k += 256) {
+        const float dr = (drb != nullptr) ? drb[k] : 1.f;
+        float dul, dil, zdp;
+        head_dl(ulb[k], ilb[k], dr, dp, p.h[k], dul, dil, zdp);
+        s_dul[k] = dul;
+        s_dil[k] = dil;
+    }
+    __syncthreads();
+    if (d_uf == nullptr) return;
+    const bool vec = (K & 3) == 0 && ((((uintptr_t)p.Wu) | ((uintptr_t)p.Wi)) & 15) == 0;
+    for (int e = t; e < 2 * H; e += 256) {
+        const int side = e >= H, hh = side ? e - H : e;
+        const float* wrow = (side ? p.Wi : p.Wu) + (long)hh * K;
+        const float* sd = side ? s_dil : s_dul;
+        float a = 0.f;
+        if (vec) {
+            for (int k = 0; k < K; k += 4) {
+                const float4 wv = *reinterpret_cast<const float4*>(wrow + k);
+                const float4 dv = *reinterpret_cast<const float4*>(sd + k);
+                a = fmaf(dv.x, wv.x, a); a = fmaf(dv.y, wv.y, a); a = fmaf(dv.z, wv.z, a); a = fmaf(dv.w, wv.w, a);
+            }
+        } else {
+            for (int k = 0; k < K; ++k) a = fmaf(sd[k], wrow[k], a);
+        }
+        (side ? d_if : d_uf)[hh] = a;
+    }
+}
+
 struct HeadTrain {               // rbr_pair_head_fwd_train extras; all zero for the plain forward
     float p_drop;
     unsigned long long seed;
@@ -50,12 +95,15 @@ struct HeadMse {
 // one workgroup per pair: threads [0,128) run the user tower, [128,256) the item tower; inside a tower 4 thread groups
 // split the H-long dots by h mod 4 and 32 lanes cover k (looped for K > 32).  A thread's loads are issued 8 at a time.
 // ft0 / ft1: this pair's user / item feature vectors (global memory, or the LDS copy the fused pool epilogue leaves).
-__device__ __forceinline__ void head_pair(int b, int B, int H, int K, const float* ft0, const float* ft1,
+// s_bwd (NULL, or LDS [3][(K + 3) & ~3]): the pair's ul, il and dropout multiplier are left there as well, for a caller that goes
+// on to the pair's backward.  Returns pred[b] (thread 0 only).
+__device__ __forceinline__ float head_pair(int b, int B, int H, int K, const float* ft0, const float* ft1,
                                           const long long* __restrict__ uid, const long long* __restrict__ iid,
                                           const rbr_head_params& p, const float* __restrict__ drop, float* __restrict__ ul,
                                           float* __restrict__ il, float* __restrict__ pred, const HeadTrain& tr,
-                                          float (*s_part)[4][32], float (*s_l)[32]) {
+                                          float (*s_part)[4][32], float (*s_l)[32], float* s_bwd = nullptr) {
     const int t = threadIdx.x;
+    const int K4 = (K + 3) & ~3;
     const unsigned long long call = (tr.p_drop > 0.f) ? tr.rng_state[0] : 0;
     const int side = t >> 7, hp = (t >> 5) & 3, kk = t & 31;
     const long id = side ? iid[b] : uid[b];
@@ -84,31 +132,39 @@ __device__ __forceinline__ void head_pair(int b, int B, int H, int K, const floa
         __syncthreads();
         if (hp == 0) {
             const float tot = (s_part[side][0][kk] + s_part[side][1][kk]) + (s_part[side][2][kk] + s_part[side][3][kk]);
-            if (k < K) outl[k] = tot;
+            if (k < K) {
+                outl[k] = tot;
+                if (s_bwd != nullptr) s_bwd[side * K4 + k] = tot;
+            }
             s_l[side][kk] = tot;
         }
         __syncthreads();
         if (t < 32 && k < K) {
             float z = fmaxf(s_l[0][kk] * s_l[1][kk], 0.f);
+            float m = 1.f;
             if (tr.p_drop > 0.f) {       // the draw rbr_dropout_multiplier would make for element (b, k) of this call
                 const unsigned long long e = (unsigned long long)b * K + k;
                 unsigned w[4];
                 philox4x32_10(e >> 2, call, tr.seed, w[0], w[1], w[2], w[3]);
-                const float m = dropout_keep(w[e & 3], tr.p_drop) ? 1.f / (1.f - tr.p_drop) : 0.f;
+                m = dropout_keep(w[e & 3], tr.p_drop) ? 1.f / (1.f - tr.p_drop) : 0.f;
                 tr.drop_out[e] = m;
                 z *= m;
             } else if (drop != nullptr) {
-                z *= drop[(long)b * K + k];
+                m = drop[(long)b * K + k];
+                z *= m;
             }
+            if (s_bwd != nullptr) s_bwd[2 * K4 + k] = m;
             part = fmaf(z, p.h[k], part);
         }
     }
+    float pr = 0.f;
     if (t < 64) {
         part = wave_sum(part);
-        if (t == 0) pred[b] = part + p.ub[uid[b]] + p.ib[iid[b]] + p.g[0];
+        if (t == 0) pred[b] = pr = part + p.ub[uid[b]] + p.ib[iid[b]] + p.g[0];
     }
     if (t == 0 && tr.rng_state != nullptr) head_rng_ticket(tr, call);
     (void)B;
+    return pr;
 }
 
 __global__ __launch_bounds__(256) void head_fwd_kernel(int B, int H, int K, const float* __restrict__ uf,
@@ -146,10 +202,11 @@ __global__ __launch_bounds__(256) void head_fwd_pool_kernel(const ConvPlan P, co
                                                             const long long* __restrict__ uid, const long long* __restrict__ iid,
                                                             const rbr_head_params p, const float* __restrict__ drop,
                                                             float* __restrict__ ul, float* __restrict__ il, float* __restrict__ pred,
-                                                            const HeadTrain tr, const HeadMse mse) {
+                                                            const HeadTrain tr, const HeadMse mse, float* __restrict__ d_feat_unit) {
     __shared__ float s_part[2][4][32];
     __shared__ float s_l[2][32];
     __shared__ int s_last;
+    __shared__ float s_dp;
     extern __shared__ __attribute__((aligned(16))) float s_feat[];      // [2][C]
     const int b = blockIdx.x, t = threadIdx.x;
     if (b >= B) {
@@ -224,8 +281,21 @@ __global__ __launch_bounds__(256) void head_fwd_pool_kernel(const ConvPlan P, co
         s_feat[side * P.C + chan] = f;
     }
     __syncthreads();
-    head_pair(b, B, P.C, K, s_feat, s_feat + P.C, uid, iid, p, drop, ul, il, pred, tr, s_part, s_l);
+    // d_feat_unit: the pair's ul / il / multiplier stay in LDS behind the slab partials (offset rounded to 16 bytes)
+    float* s_bwd = d_feat_unit != nullptr ? s_feat + ((2 * P.C + 2 * wpd * nslots + 2 * wpd + 3) & ~3) : nullptr;
+    const float pr = head_pair(b, B, P.C, K, s_feat, s_feat + P.C, uid, iid, p, drop, ul, il, pred, tr, s_part, s_l, s_bwd);
     if (mse.target == nullptr) return;
+    if (d_feat_unit != nullptr) {
+        // The pair role of the backward for an upstream gradient of 1, from this pair's own prediction: d loss / d pred[b] with the
+        // operations of the loss tail below (the same bits as d_unit[b]).  In front of the ticket, so that the conv backward's
+        // operand does not wait for the loss.  (The embedding-row atomics stay in rbr_pair_head_bwd: their buffer is cleared by
+        // THIS launch's spare workgroups.)
+        const int K4 = (K + 3) & ~3;
+        if (t == 0) s_dp = (pr - mse.target[b]) * (2.f / (float)B);
+        __syncthreads();
+        head_pair_dfeat(P.C, K, s_bwd, s_bwd + K4, s_bwd + 2 * K4, s_dp, p, s_bwd, s_bwd + K4, d_feat_unit + (long)b * P.C,
+                        d_feat_unit + (long)(B + b) * P.C);
+    }
     if (t == 0) {
         __threadfence();                                        // pred[b] is visible before the ticket is taken
         s_last = atomicAdd(mse.ticket, 1) == B - 1;
@@ -250,19 +320,11 @@ __global__ __launch_bounds__(256) void head_fwd_pool_kernel(const ConvPlan P, co
     }
 }
 
-// The backward in ONE launch.  Blocks [0, B): one workgroup per pair -- embedding-row grads (atomics), then d_feat with all
-// 256 threads over the 2*H outputs (rows of Wu / Wi read as float4 when K allows).  Blocks [B, B + 2(H+1)): the batch
+// The backward in ONE launch.  Blocks [0, B): one workgroup per pair -- d_feat (head_pair_dfeat; skipped when the forward launch
+// wrote it), then the embedding-row grads (atomics).  Blocks [B, B + 2(H+1)): the batch
 // reductions dW = feat^T @ d_l, db, dh, dg, one workgroup per output row (side, r), 8 thread groups striding the batch in a
 // fixed partition and order (bitwise reproducible); they recompute d_l from ul / il / drop / d_pred (a few flops) instead
 // of waiting for the pair blocks to publish it, so both halves run side by side.
-__device__ __forceinline__ void head_dl(float su, float si, float dr, float dp, float hk, float& dul, float& dil, float& zdp) {
-    const float prod = su * si;
-    const float dz = (prod > 0.f) ? dp * hk * dr : 0.f;
-    dul = dz * si;
-    dil = dz * su;
-    zdp = fmaxf(prod, 0.f) * dr * dp;
-}
-
 __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int H, int K, const float* __restrict__ uf,
                                                        const float* __restrict__ itf, const long long* __restrict__ uid,
                                                        const long long* __restrict__ iid, const rbr_head_params p,
@@ -285,36 +347,16 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int H, int K, cons
         float* s_dil = sm + K4;
         const long u = uid[b], it = iid[b];
         const float dp = d_pred[b];
+        // d_uf NULL: the forward launch already wrote d_feat (rbr_pair_head_fwd_pool_ex's d_feat_unit); the atomics remain
+        head_pair_dfeat(H, K, ul + (long)b * K, il + (long)b * K, drop != nullptr ? drop + (long)b * K : nullptr, dp, p, s_dul, s_dil,
+                        d_uf != nullptr ? d_uf + (long)b * H : nullptr, d_uf != nullptr ? d_if + (long)b * H : nullptr);
         for (int k = t; k < K; k += 256) {
-            const float dr = (drop != nullptr) ? drop[(long)b * K + k] : 1.f;
-            float dul, dil, zdp;
-            head_dl(ul[(long)b * K + k], il[(long)b * K + k], dr, dp, p.h[k], dul, dil, zdp);
-            s_dul[k] = dul;
-            s_dil[k] = dil;
-            if (u != pad_u) atomicAdd(g.dEu + u * K + k, dul);
-            if (it != pad_i) atomicAdd(g.dEi + it * K + k, dil);
+            if (u != pad_u) atomicAdd(g.dEu + u * K + k, s_dul[k]);
+            if (it != pad_i) atomicAdd(g.dEi + it * K + k, s_dil[k]);
         }
         if (t == 0) {
             if (u != pad_u) atomicAdd(g.dub + u, dp);
             if (it != pad_i) atomicAdd(g.dib + it, dp);
-        }
-        __syncthreads();
-        const bool vec = (K & 3) == 0 && ((((uintptr_t)p.Wu) | ((uintptr_t)p.Wi)) & 15) == 0;
-        for (int e = t; e < 2 * H; e += 256) {
-            const int side = e >= H, hh = side ? e - H : e;
-            const float* wrow = (side ? p.Wi : p.Wu) + (long)hh * K;
-            const float* sd = side ? s_dil : s_dul;
-            float a = 0.f;
-            if (vec) {
-                for (int k = 0; k < K; k += 4) {
-                    const float4 wv = *reinterpret_cast<const float4*>(wrow + k);
-                    const float4 dv = *reinterpret_cast<const float4*>(sd + k);
-                    a = fmaf(dv.x, wv.x, a); a = fmaf(dv.y, wv.y, a); a = fmaf(dv.z, wv.z, a); a = fmaf(dv.w, wv.w, a);
-                }
-            } else {
-                for (int k = 0; k < K; ++k) a = fmaf(sd[k], wrow[k], a);
-            }
-            (side ? d_if : d_uf)[(long)b * H + hh] = a;
         }
         return;
     }
@@ -467,11 +509,29 @@ extern "C" int rbr_pair_head_fwd_train(int32_t B, int32_t H, int32_t K, const fl
 
 // Head forward with the encoder's pool epilogue (rbr_textcnn_pool_finalize) in front and, optionally, the trainers' MSELoss
 // behind: one launch.  The encoder batch holds the B user documents, then the B item documents.
-extern "C" int rbr_pair_head_fwd_pool(const rbr_textcnn_desc* d, const float* pval, const int32_t* pidx, const float* const* bias,
-                                      float* feat, int32_t* argmax, const int64_t* first, int32_t K, const int64_t* u_id,
-                                      const int64_t* i_id, const rbr_head_params* p, const float* drop, float p_drop, uint64_t seed,
-                                      uint64_t* rng_state, float* drop_out, float* zero_buf, int64_t zero_n, float* ul, float* il,
-                                      float* pred, const float* target, float* loss, float* d_pred_unit, int32_t* ticket, void* stream) {
+// Dynamic LDS of head_fwd_pool_kernel: feat [2][C], the slab partials [2][wpd][slots], their flags [2][wpd] and -- with
+// d_feat_unit -- the pair's ul / il / multiplier [3][K4] behind them on a 16-byte boundary.
+static size_t head_fwd_pool_lds(const ConvPlan& P, int K, bool with_d_feat) {
+    size_t lds = ((size_t)2 * P.C + (size_t)2 * P.wpd * P.ntiles * kTile + (size_t)2 * P.wpd) * sizeof(float);
+    if (with_d_feat) lds = ((lds + 15) & ~(size_t)15) + (size_t)3 * ((K + 3) & ~3) * sizeof(float);
+    return lds;
+}
+
+extern "C" size_t rbr_pair_head_fwd_pool_lds_bytes(const rbr_textcnn_desc* d, int32_t K, int32_t with_d_feat) {
+    ConvPlan plans[kMaxGroups];
+    if (K <= 0 || build_plans(d, plans, kMaxTiles) != 1) return 0;
+    const size_t lds = head_fwd_pool_lds(plans[0], K, with_d_feat != 0);
+    return lds > 60 * 1024 ? 0 : lds;
+}
+
+// d_feat_unit [2B, C] (optional; needs target): block b also writes the d_feat rows of documents b and B + b for an upstream
+// gradient of 1 -- the pair role of rbr_pair_head_bwd, which is then called with NULL d_ufeat / d_ifeat.
+extern "C" int rbr_pair_head_fwd_pool_ex(const rbr_textcnn_desc* d, const float* pval, const int32_t* pidx, const float* const* bias,
+                                         float* feat, int32_t* argmax, const int64_t* first, int32_t K, const int64_t* u_id,
+                                         const int64_t* i_id, const rbr_head_params* p, const float* drop, float p_drop, uint64_t seed,
+                                         uint64_t* rng_state, float* drop_out, float* zero_buf, int64_t zero_n, float* ul, float* il,
+                                         float* pred, const float* target, float* loss, float* d_pred_unit, int32_t* ticket,
+                                         float* d_feat_unit, void* stream) {
     ConvPlan plans[kMaxGroups];
     const int ng = build_plans(d, plans, kMaxTiles);
     if (!ng) return RBR_ERR_BAD_ARG;
@@ -484,6 +544,7 @@ extern "C" int rbr_pair_head_fwd_pool(const rbr_textcnn_desc* d, const float* pv
     if (p_drop > 0.f && (!rng_state || !drop_out)) { set_error("pair_head_fwd_pool: dropout needs rng_state and drop_out"); return RBR_ERR_BAD_ARG; }
     if (zero_n < 0 || (zero_n > 0 && !zero_buf)) { set_error("pair_head_fwd_pool: bad zero buffer"); return RBR_ERR_BAD_ARG; }
     if (target != nullptr && (!loss || !ticket)) { set_error("pair_head_fwd_pool: the loss needs loss and ticket"); return RBR_ERR_BAD_ARG; }
+    if (d_feat_unit != nullptr && !target) { set_error("pair_head_fwd_pool: d_feat_unit needs the loss target"); return RBR_ERR_BAD_ARG; }
     HeadTrain tr{};
     tr.p_drop = p_drop; tr.seed = seed;
     tr.rng_state = (p_drop > 0.f) ? reinterpret_cast<unsigned long long*>(rng_state) : nullptr;
@@ -493,13 +554,22 @@ extern "C" int rbr_pair_head_fwd_pool(const rbr_textcnn_desc* d, const float* pv
     for (int w = 0; w < d->n_widths; ++w) hp.bias.p[w] = bias[w];
     HeadMse mse{target, loss, d_pred_unit, ticket};
     const int zblocks = zero_n > 0 ? (int)std::min<long>((zero_n + 1023) / 1024, 256) : 0;
-    const size_t lds = ((size_t)2 * C + (size_t)2 * plans[0].wpd * plans[0].ntiles * kTile + (size_t)2 * plans[0].wpd) * sizeof(float);
+    const size_t lds = head_fwd_pool_lds(plans[0], K, d_feat_unit != nullptr);
     if (lds > 60 * 1024) { set_error("pair_head_fwd_pool: %zu bytes of LDS for the slab partials (documents too long)", lds); return RBR_ERR_UNSUPPORTED; }
     hipLaunchKernelGGL(head_fwd_pool_kernel, dim3(B + zblocks), dim3(256), lds, (hipStream_t)stream,
                        plans[0], hp, B, K, reinterpret_cast<const long long*>(u_id), reinterpret_cast<const long long*>(i_id), *p,
-                       (p_drop > 0.f) ? nullptr : drop, ul, il, pred, tr, mse);
+                       (p_drop > 0.f) ? nullptr : drop, ul, il, pred, tr, mse, d_feat_unit);
     RBR_CHECK_LAUNCH("pair_head_fwd_pool launch");
     return 0;
+}
+
+extern "C" int rbr_pair_head_fwd_pool(const rbr_textcnn_desc* d, const float* pval, const int32_t* pidx, const float* const* bias,
+                                      float* feat, int32_t* argmax, const int64_t* first, int32_t K, const int64_t* u_id,
+                                      const int64_t* i_id, const rbr_head_params* p, const float* drop, float p_drop, uint64_t seed,
+                                      uint64_t* rng_state, float* drop_out, float* zero_buf, int64_t zero_n, float* ul, float* il,
+                                      float* pred, const float* target, float* loss, float* d_pred_unit, int32_t* ticket, void* stream) {
+    return rbr_pair_head_fwd_pool_ex(d, pval, pidx, bias, feat, argmax, first, K, u_id, i_id, p, drop, p_drop, seed, rng_state, drop_out,
+                                     zero_buf, zero_n, ul, il, pred, target, loss, d_pred_unit, ticket, nullptr, stream);
 }
 
 extern "C" size_t rbr_pair_head_bwd_ws_floats(int32_t B, int32_t K) { (void)B; (void)K; return 0; }
@@ -509,7 +579,7 @@ extern "C" int rbr_pair_head_bwd(int32_t B, int32_t H, int32_t K, const float* u
                                  const float* ul, const float* il, const float* d_pred, int32_t pad_u, int32_t pad_i,
                                  const rbr_head_grads* g, float* d_ufeat, float* d_ifeat, float* ws, void* stream) {
     if (!head_args_ok(B, H, K)) return RBR_ERR_BAD_ARG;
-    if (!u_feat || !i_feat || !u_id || !i_id || !p || !ul || !il || !d_pred || !g || !d_ufeat || !d_ifeat) {
+    if (!u_feat || !i_feat || !u_id || !i_id || !p || !ul || !il || !d_pred || !g || (!d_ufeat != !d_ifeat)) {
         set_error("null pointer");
         return RBR_ERR_BAD_ARG;
     }

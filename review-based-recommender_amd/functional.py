@@ -497,11 +497,13 @@ def _g_chain(key, flags, st, desc, operands, fwd_ws, bws, dtable, dgate, sq):
           dev_ptr(dgate if build else None, F32, "dgate"), dev_ptr(sq if product else None, F32, "sq_part"), flags, st)
 
 
-def _textcnn_backward(S, d_feat, need_table: bool, need_gate: bool):
+def _textcnn_backward(S, d_feat, need_table: bool, need_gate: bool, side_job=None):
     """Backward of the fused encoder from d_feat [n_docs, C]: returns (dtable, dgate, dWs, dbs).  dtable is None when the table
     gradient left through a side channel instead: the data-parallel tap sink, or -- compact row form -- the optimizer that
     registered for it (set_row_grad_sink).  Picks the table-gradient strategy; each one also runs the weight-gradient chain.
-    Precedence: tap sink (one that accepts the call wins over fixed mode), fixed point, token product, token list, window scatter."""
+    Precedence: tap sink (one that accepts the call wins over fixed mode), fixed point, token product, token list, window scatter.
+    side_job: a callable that enqueues work independent of this backward on the current stream; it runs on the weight-gradient
+    branch, behind the weight-gradient kernels, inside the same fork and join (_EncodeHead: what is left of the head's backward)."""
     L_ = _lib.lib()
     table, gate, desc = S.table, S.gate, S.desc
     dev = table.device
@@ -511,19 +513,19 @@ def _textcnn_backward(S, d_feat, need_table: bool, need_gate: bool):
     plain = need_table and gate is None          # the tap and token-list forms of the table gradient serve un-gated convs only
     sink = _TAP_SINKS.get(table.data_ptr())          # only the sink installed for THIS table ever sees the call
     if plain and sink is not None and sink.accepts(table, desc, L_):
-        dtable, dgate = _bwd_tap_sink(S, d_feat, sink, dWs, dbs)
+        dtable, dgate = _bwd_tap_sink(S, d_feat, sink, dWs, dbs, side_job)
     elif plain and _dtable_fixed() and (fixed_bytes := L_.rbr_textcnn_dtable_from_taps_ws_bytes(C.byref(desc), 1)):
-        dtable, dgate = _bwd_fixed(S, d_feat, fixed_bytes, dWs, dbs)
+        dtable, dgate = _bwd_fixed(S, d_feat, fixed_bytes, dWs, dbs, side_job)
     elif (need_table or need_gate) and S.prod_ws is not None and (bws_bytes := L_.rbr_textcnn_bwd_prod_ws_bytes(C.byref(desc))):
-        dtable, dgate = _bwd_token_product(S, d_feat, need_table, need_gate, bws_bytes, dWs, dbs)
+        dtable, dgate = _bwd_token_product(S, d_feat, need_table, need_gate, bws_bytes, dWs, dbs, side_job)
     elif plain and (list_bytes := L_.rbr_textcnn_bwd_dtable_list_ws_bytes(C.byref(desc))):
-        dtable, dgate = _bwd_token_list(S, d_feat, list_bytes, dWs, dbs)
+        dtable, dgate = _bwd_token_list(S, d_feat, list_bytes, dWs, dbs, side_job)
     else:
-        dtable, dgate = _bwd_window_scatter(S, d_feat, need_table, need_gate, dWs, dbs)
+        dtable, dgate = _bwd_window_scatter(S, d_feat, need_table, need_gate, dWs, dbs, side_job)
     return dtable, dgate, dWs, dbs
 
 
-def _bwd_dw(S, d_feat, dWs, dbs, fork) -> None:
+def _bwd_dw(S, d_feat, dWs, dbs, fork, side_job=None) -> None:
     """The weight-gradient chain (rbr_textcnn_bwd_dw) on `fork`'s stream, joined before returning.  The weight-gradient kernels
     and the table-gradient kernels both start from d_feat and share nothing else: the former go to a second stream, so the two
     chains overlap -- also inside a captured graph, where the fork becomes two parallel branches.  A strategy forks BEFORE its
@@ -537,6 +539,11 @@ def _bwd_dw(S, d_feat, dWs, dbs, fork) -> None:
               dev_ptr(S.gate, F32, "gate"), dev_ptr(S.table, F32, "table"), dev_ptr(S.feat, F32, "feat"),
               dev_ptr(S.argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"), ptr_array(dWs, F32, "dW"),
               ptr_array(dbs, F32, "dbias"), dev_ptr(wsb, F32, "ws"), current_stream())
+        # side_job BEHIND the weight-gradient kernels.  (Measured and dropped, round 7: in front of them -- head_bwd then takes
+        # 29 us beside the zero fill and the G build, dw_partial4 starts 35 us later and the join waits for this branch: the step
+        # 0.377-0.379 ms against 0.348-0.351.)
+        if side_job is not None:
+            side_job()
     fork.join()
 
 
@@ -547,18 +554,18 @@ def _bwd_taps(key, S, d_feat, tok, val) -> None:
           dev_ptr(tok, I32, "tap tokens"), dev_ptr(val, F32, "tap values"), current_stream())
 
 
-def _bwd_tap_sink(S, d_feat, sink, dWs, dbs):
+def _bwd_tap_sink(S, d_feat, sink, dWs, dbs, side_job=None):
     """Data-parallel tap sink: the taps go to the exchange, which produces table.grad after the all-gather -- no dtable here."""
     dev = S.table.device
     fork = _Fork(dev)
     tok, val = sink.local_buffers(_lib.lib().rbr_textcnn_taps_count(C.byref(S.desc)), dev)
     _bwd_taps("textcnn_bwd_dtable", S, d_feat, tok, val)
     sink.record(S.desc, list(S.ws))
-    _bwd_dw(S, d_feat, dWs, dbs, fork)
+    _bwd_dw(S, d_feat, dWs, dbs, fork, side_job)
     return None, None
 
 
-def _bwd_fixed(S, d_feat, fixed_bytes, dWs, dbs):
+def _bwd_fixed(S, d_feat, fixed_bytes, dWs, dbs, side_job=None):
     """set_dtable_mode("fixed"): order-free fixed-point sums, the data-parallel tap rebuild run on this rank's taps alone.  The
     weight gradient follows on the same stream."""
     if torch.cuda.is_current_stream_capturing():
@@ -573,11 +580,11 @@ def _bwd_fixed(S, d_feat, fixed_bytes, dWs, dbs):
     _bwd_taps(None, S, d_feat, tok, val)
     _call(None, L_.rbr_textcnn_dtable_from_taps, C.byref(S.desc), 1, dev_ptr(tok, I32, "tap tokens"), dev_ptr(val, F32, "tap values"),
           ptr_array(S.ws, F32, "conv weight"), tws.data_ptr(), dev_ptr(dtable, F32, "dtable"), current_stream())
-    _bwd_dw(S, d_feat, dWs, dbs, _Fork(dev, on=False))
+    _bwd_dw(S, d_feat, dWs, dbs, _Fork(dev, on=False), side_job)
     return dtable, None
 
 
-def _bwd_token_product(S, d_feat, need_table, need_gate, bws_bytes, dWs, dbs):
+def _bwd_token_product(S, d_feat, need_table, need_gate, bws_bytes, dWs, dbs, side_job=None):
     """Token-product backward: dtable = G @ Wprod^T over the forward's distinct-token list (no atomics on the table); d(gate) of
     gated convs (D-ATT) is read off the forward's product table.  Returns (dtable, dgate); dtable is None when the rows went to
     the optimizer's row sink."""
@@ -623,6 +630,8 @@ def _bwd_token_product(S, d_feat, need_table, need_gate, bws_bytes, dWs, dbs):
                 _call("textcnn_bwd_dw", L_.rbr_textcnn_bwd_dw_from_g, C.byref(desc), dev_ptr(table, F32, "table"),
                       dev_ptr(S.feat, F32, "feat"), dev_ptr(d_feat, F32, "d_feat"), S.prod_ws.data_ptr(), bws.data_ptr(),
                       ptr_array(dWs, F32, "dW"), ptr_array(dbs, F32, "dbias"), dev_ptr(dwg_ws, F32, "ws"), current_stream())
+                if side_job is not None:
+                    side_job()
         else:
             # timing pass (bench.py): the call's two phases as two calls, so that the sparse product (ONE launch,
             # g_times_w) gets HIP events of its own -- same kernels, same order, same arguments
@@ -636,14 +645,14 @@ def _bwd_token_product(S, d_feat, need_table, need_gate, bws_bytes, dWs, dbs):
     if dwg_floats:
         fork.join()
     else:
-        _bwd_dw(S, d_feat, dWs, dbs, fork)
+        _bwd_dw(S, d_feat, dWs, dbs, fork, side_job)
     if row_sink is not None:
         row_sink.put_row_grad(table, RowGradient(table, out, sq, rot.value, S.prod_ws))
         return None, dgate
     return out, dgate
 
 
-def _bwd_token_list(S, d_feat, list_bytes, dWs, dbs):
+def _bwd_token_list(S, d_feat, list_bytes, dWs, dbs, side_job=None):
     """Dense forward (no token list of its own), un-gated: the table gradient still goes through a distinct-token list built
     here (16 us) instead of the window scatter's row of f32 atomics per (document, channel, tap)."""
     dev = S.table.device
@@ -654,11 +663,11 @@ def _bwd_token_list(S, d_feat, list_bytes, dWs, dbs):
           dev_ptr(S.mask8, U8, "mask"), ptr_array(S.ws, F32, "conv weight"), dev_ptr(S.feat, F32, "feat"),
           dev_ptr(S.argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"), lws.data_ptr(), dev_ptr(dtable, F32, "dtable"),
           current_stream())
-    _bwd_dw(S, d_feat, dWs, dbs, fork)
+    _bwd_dw(S, d_feat, dWs, dbs, fork, side_job)
     return dtable, None
 
 
-def _bwd_window_scatter(S, d_feat, need_table, need_gate, dWs, dbs):
+def _bwd_window_scatter(S, d_feat, need_table, need_gate, dWs, dbs, side_job=None):
     """Window scatter (rbr_textcnn_bwd_dtable): a row of f32 atomics per (document, channel, tap) into zeros, dgate likewise.
     Also where a backward that owes neither gradient ends up: the call then returns at once.  Returns (dtable, dgate)."""
     L_ = _lib.lib()
@@ -675,7 +684,7 @@ def _bwd_window_scatter(S, d_feat, need_table, need_gate, dWs, dbs):
               dev_ptr(S.gate, F32, "gate"), dev_ptr(S.table, F32, "table"), dev_ptr(packed, F32, "packed"),
               dev_ptr(S.feat, F32, "feat"), dev_ptr(S.argmax, I32, "argmax"), dev_ptr(d_feat, F32, "d_feat"),
               dev_ptr(dtable, F32, "dtable"), dev_ptr(dgate, F32, "dgate"), st)
-    _bwd_dw(S, d_feat, dWs, dbs, fork)
+    _bwd_dw(S, d_feat, dWs, dbs, fork, side_job)
     return dtable, dgate
 
 
@@ -714,15 +723,19 @@ class RowGradient:
     """Gradient of an embedding table as the rows of the tokens one batch holds (rbr_textcnn_bwd_dtable_prod_ex, RBR_G_ROWS):
     rows [cap, D] (row r = token tok_of_row[r] of the forward's list), sq [partials] = sums of squares of the rows, and the
     list's inverse map row_of_token [V] inside the forward's workspace (kept alive here).  Every other row of the dense
-    gradient nn.Embedding's backward would build is exactly zero."""
+    gradient nn.Embedding's backward would build is exactly zero.
+    coef: None, or the device scalar a clipping optimizer step left (rbr_clip_adam_step_rows does not re-write `rows`): the
+    gradient is then rows * coef, which to_dense() applies -- one f32 multiply per element, on the device (capturable)."""
 
     def __init__(self, table, rows, sq, row_of_token_ptr, keep_alive):
         self.V, self.D = int(table.shape[0]), int(table.shape[1])
         self.rows, self.sq, self.row_of_token_ptr, self._keep = rows, sq, int(row_of_token_ptr), keep_alive
+        self.coef = None
 
     def to_dense(self) -> torch.Tensor:
+        rows = self.rows if self.coef is None else self.rows * self.coef
         dense = torch.empty(self.V, self.D, dtype=F32, device=self.rows.device)
-        _call(None, _lib.lib().rbr_row_grad_to_dense, self.V, self.D, self.row_of_token_ptr, dev_ptr(self.rows, F32, "rows"),
+        _call(None, _lib.lib().rbr_row_grad_to_dense, self.V, self.D, self.row_of_token_ptr, dev_ptr(rows, F32, "rows"),
               dev_ptr(dense, F32, "dense"), current_stream())
         return dense
 
@@ -951,7 +964,10 @@ class _EncodeHead(torch.autograd.Function):
     """pred[B] (and the MSE loss against `target`) = rating head(TextCNN(user docs), TextCNN(item docs), ids): the training /
     eval forward of DeepCoNN++ (deepconn.py:43-53) as 6 launches -- id check + list state | token marks + slab scan | token list
     + weight images | distinct-token GEMM | gather + max-pool (+ clearing the backward's G) | pool epilogue + LastFeat x2 + FM
-    (+ MSELoss) -- and its backward as head_bwd, then [zero G, G build, G @ Wprod^T] beside [dW] (see _textcnn_backward)."""
+    (+ MSELoss) -- and its backward as head_bwd, then [zero G, G build, G @ Wprod^T] beside [dW] (see _textcnn_backward).
+    With the fused loss the head launch also writes d loss / d feat for a unit root gradient (rbr_pair_head_fwd_pool_ex); a
+    backward that is handed exactly that gradient starts the conv backward at once and runs what is left of head_bwd (id-row
+    atomics, batch reductions) behind dW on the weight-gradient branch.  RBR_HEAD_BWD_IN_FWD=0 restores the old order."""
 
     @staticmethod
     def forward(ctx, table, id_sets, ids, mask, u_id, i_id, drop, target, padding_idx, pad_u, pad_i, n_widths, first, *params):
@@ -1006,12 +1022,15 @@ class _EncodeHead(torch.autograd.Function):
                 drop_t = torch.empty(B, K, dtype=F32, device=dev)
         elif drop is not None:
             drop_t = drop.contiguous()
-        loss = d_unit = None
+        loss = d_unit = d_feat_unit = None
         if target is not None:
             target = target.contiguous()
             loss = torch.empty((), dtype=F32, device=dev)
             d_unit = torch.empty(B, dtype=F32, device=dev)
-        _call("pair_head_fwd_pool", L_.rbr_pair_head_fwd_pool, C.byref(desc), dev_ptr(pval, F32, "pval"), dev_ptr(pidx, I32, "pidx"),
+            if training and first is None and os.environ.get("RBR_HEAD_BWD_IN_FWD", "1") != "0" \
+                    and L_.rbr_pair_head_fwd_pool_lds_bytes(C.byref(desc), K, 1):
+                d_feat_unit = torch.empty(2 * B, feat.shape[1], dtype=F32, device=dev)
+        _call("pair_head_fwd_pool", L_.rbr_pair_head_fwd_pool_ex, C.byref(desc), dev_ptr(pval, F32, "pval"), dev_ptr(pidx, I32, "pidx"),
               ptr_array(bs_, F32, "conv bias"), dev_ptr(feat, F32, "feat"), dev_ptr(argmax, I32, "argmax"),
               dev_ptr(first, I64, "first"), K, dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp),
               dev_ptr(drop_t, F32, "drop") if p_drop == 0.0 else None, float(p_drop), seed,
@@ -1019,7 +1038,8 @@ class _EncodeHead(torch.autograd.Function):
               dev_ptr(drop_t, F32, "drop") if p_drop > 0.0 else None, dev_ptr(flat_zero, F32, "zero_buf"),
               acc_n, dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(pred, F32, "pred"),
               dev_ptr(target, F32, "target"), dev_ptr(loss, F32, "loss"), dev_ptr(d_unit, F32, "d_unit"),
-              _ticket(dev).data_ptr() if target is not None else None, st)
+              _ticket(dev).data_ptr() if target is not None else None, dev_ptr(d_feat_unit, F32, "d_feat_unit"), st)
+        ctx.d_feat_unit = d_feat_unit
         ctx.conv = _ConvSaved(table=table_c, ids=ids, packed=None, feat=feat, argmax=argmax, mask8=mask8, gate=None, ws=ws_,
                               desc=desc, prod_ws=conv.prod_ws, fanout_acc=None)
         ctx.head = (u_id, i_id, ul, il, head, drop_t, flat_zero, d_unit)
@@ -1038,8 +1058,12 @@ class _EncodeHead(torch.autograd.Function):
         S = ctx.conv
         dev = S.table.device
         L_ = _lib.lib()
+        need_conv = any(ctx.needs_input_grad[13:13 + 2 * n_widths]) or ctx.needs_input_grad[0]
+        unit = _UNIT.get(dev)
+        # the forward launch wrote d_feat for exactly this upstream gradient: the conv backward does not wait for head_bwd
+        early = (ctx.d_feat_unit is not None and need_conv and d_pred is None and ctx.first is None and d_loss is not None
+                 and unit is not None and d_loss.data_ptr() == unit.data_ptr())
         if d_loss is not None:                  # the fused loss: d loss / d pred was written by the forward launch
-            unit = _UNIT.get(dev)
             g = d_unit if (unit is not None and d_loss.data_ptr() == unit.data_ptr()) else d_unit * d_loss
             d_pred = g if d_pred is None else d_pred + g
         if d_pred is None:
@@ -1053,13 +1077,20 @@ class _EncodeHead(torch.autograd.Function):
         zeroed = iter(v.view_as(t) for v, t in zip(flat.split([t.numel() for t in accs]), accs))
         grads = [next(zeroed) if n in _HEAD_ACC else torch.empty_like(t) for t, n in zip(head, _HEAD_NAMES)]
         hg = _lib.HeadGrads(*[dev_ptr(t, F32, "d" + n) for t, n in zip(grads, _HEAD_NAMES)])
-        d_pair = torch.empty(2 * B, H, dtype=F32, device=dev)
+        d_pair = ctx.d_feat_unit if early else torch.empty(2 * B, H, dtype=F32, device=dev)
         feat = S.feat
-        need_conv = any(ctx.needs_input_grad[13:13 + 2 * n_widths]) or ctx.needs_input_grad[0]
-        _call(None, L_.rbr_pair_head_bwd, B, H, K, dev_ptr(feat[:B], F32, "u_feat"), dev_ptr(feat[B:], F32, "i_feat"),
-              dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp), dev_ptr(drop_t, F32, "drop"),
-              dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(d_pred, F32, "d_pred"), pad_u, pad_i, C.byref(hg),
-              dev_ptr(d_pair[:B], F32, "d_ufeat"), dev_ptr(d_pair[B:], F32, "d_ifeat"), None, current_stream())
+
+        def head_bwd():          # early: the pair blocks only accumulate the id-row gradients
+            _call(None, L_.rbr_pair_head_bwd, B, H, K, dev_ptr(feat[:B], F32, "u_feat"), dev_ptr(feat[B:], F32, "i_feat"),
+                  dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp), dev_ptr(drop_t, F32, "drop"),
+                  dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(d_pred, F32, "d_pred"), pad_u, pad_i, C.byref(hg),
+                  None if early else dev_ptr(d_pair[:B], F32, "d_ufeat"), None if early else dev_ptr(d_pair[B:], F32, "d_ifeat"),
+                  None, current_stream())
+
+        if early:
+            dtable, _, dWs, dbs = _textcnn_backward(S, d_pair, ctx.needs_input_grad[0], False, side_job=head_bwd)
+            return (dtable, None, None, None, None, None, None, None, None, None, None, None, None, *dWs, *dbs, *grads)
+        head_bwd()
         if need_conv and ctx.first is not None:      # in-batch dedup: the repeated documents' gradient rows onto their first occurrence
             _call(None, L_.rbr_dedup_fold_rows, 2 * B, H, dev_ptr(ctx.first, I64, "first"), dev_ptr(d_pair, F32, "d_feat"),
                   current_stream())

@@ -205,7 +205,11 @@ class HipClipAdam(torch.optim.Optimizer):
             rowp = [k for k, p in enumerate(ps) if p in self._row_grads]
             if rowp:
                 rg = self._row_grads[ps[rowp[0]]]
-                crg = _lib.RowGrad(rowp[0], rg.V, rg.D, rg.row_of_token_ptr, rg.rows.data_ptr(), rg.sq.data_ptr(), rg.sq.numel())
+                # the kernel leaves the rows as they are and the clip coefficient beside them: to_dense() applies it
+                if rg.coef is None:
+                    rg.coef = torch.empty((), dtype=torch.float32, device=dev)
+                crg = _lib.RowGrad(rowp[0], rg.V, rg.D, rg.row_of_token_ptr, rg.rows.data_ptr(), rg.sq.data_ptr(), rg.sq.numel(),
+                                   rg.coef.data_ptr())
                 _lib.check(L_.rbr_clip_adam_step_rows(*args, C.byref(crg), st), "rbr_clip_adam_step_rows")
             else:
                 _lib.check(L_.rbr_clip_adam_step(*args, st), "rbr_clip_adam_step")
