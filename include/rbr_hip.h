@@ -602,7 +602,22 @@ int rbr_review_gather(int32_t B, int32_t R, int32_t T, const int64_t* u_ids, con
  *        A row with fewer than k candidates ends in item -1, score -inf.  NaN scores
  *        are never returned.  1 <= k <= 128 and K <= 4096, else RBR_ERR_UNSUPPORTED.  [Nu, Ni] is never materialised:
  *        ws is rbr_pair_score_topk_ws_bytes(Nu, Ni, K, k) bytes = Nu * k * 8 * item slices (<= 64 slices).  Two launches on
- *        `stream`, no host synchronisation, no allocation: graph-capturable.                                         ---- */
+ *        `stream`, no host synchronisation, no allocation: graph-capturable.
+ *      pair_score_rank : where a held-out item lands.  For B pairs of a user row (ul [B, K], ub [B] or NULL: gathered per pair,
+ *        as pair_score_topk takes them) and a target item tgt[b], with key(j) = (score(b, j) descending, then j ascending), the
+ *        order of pair_score_topk, and the candidates
+ *          C_b = { j in [item_lo, Ni) : (j not in b's exclusion list or j == tgt[b]) and score(b, j) is not NaN }
+ *        (the target is never excluded, even when the list names it):
+ *          n_cand[b] = |C_b|,   rank[b] = #{ j in C_b : key(j) > key(tgt[b]) }          both int32 [B]
+ *        so that rank[b] < k exactly when pair_score_topk with the same arguments (and a list that does not name tgt[b]) has
+ *        tgt[b] at position rank[b] of row b.
+ *        rank[b] = -1 (unranked: in no such list) when tgt[b] is outside [item_lo, Ni) or its score is NaN; a target outside
+ *        [0, Ni) is never read -- row 0 stands in -- and err (the int64[4] record of rbr_sanitize_ids, set 1; may be NULL) is
+ *        updated.  The exclusion arguments are pair_score_topk's, one CSR row per pair (a list may hold an item twice in a
+ *        row of entries; the second is ignored).  K <= 4096, else RBR_ERR_UNSUPPORTED.  [B, Ni] is never materialised: ws is
+ *        rbr_pair_score_rank_ws_bytes(B, Ni, K) bytes = B * 8 * item slices (<= 64 slices; 0 and an error text for a shape
+ *        the entry refuses).  All counts are integers: the same bytes on every run.  Two launches on `stream`, no host
+ *        synchronisation, no allocation: graph-capturable.                                                           ---- */
 #define RBR_SCORE_FM 0
 #define RBR_SCORE_DOT 1
 int rbr_pair_score_ids(int32_t mode, int32_t B, int32_t K, const float* ul, int32_t U, const float* il, int32_t I,
@@ -615,6 +630,11 @@ int rbr_pair_score_topk(int32_t mode, int32_t Nu, int32_t Ni, int32_t K, int32_t
                         const float* il, const float* h, const float* g, const float* ub, const float* ib,
                         const int64_t* excl_off, const int32_t* excl_item, int64_t excl_nnz, const int64_t* excl_row,
                         int32_t excl_rows, int64_t* out_item, float* out_score, void* ws, void* stream);
+size_t rbr_pair_score_rank_ws_bytes(int32_t B, int32_t Ni, int32_t K);
+int rbr_pair_score_rank(int32_t mode, int32_t B, int32_t Ni, int32_t K, int32_t item_lo, const float* ul, const float* il,
+                        const float* h, const float* g, const float* ub, const float* ib, const int64_t* tgt,
+                        const int64_t* excl_off, const int32_t* excl_item, int64_t excl_nnz, const int64_t* excl_row,
+                        int32_t excl_rows, int32_t* rank, int32_t* n_cand, int64_t* err, void* ws, void* stream);
 
 /* ---- NgramFeat arch="HierPooling" (deepconn/layers.py:62-98,110-114): pooled[doc,d] =
  *      max_l mean_{j<k} x[doc,l+j,d] over l in [0, L-k], x = mask * table[ids]; relu != 0 applies the

@@ -215,6 +215,9 @@ SIGNATURES = {
     "rbr_pair_score_topk_ws_bytes": (C.c_size_t, [i32, i32, i32, i32]),
     "rbr_pair_score_topk": (C.c_int, [i32, i32, i32, i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p, c_i32p,
                                       C.c_int64, c_i64p, i32, c_i64p, c_f32p, C.c_void_p, c_stream]),
+    "rbr_pair_score_rank_ws_bytes": (C.c_size_t, [i32, i32, i32]),
+    "rbr_pair_score_rank": (C.c_int, [i32, i32, i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p, c_i64p, c_i32p,
+                                      C.c_int64, c_i64p, i32, c_i32p, c_i32p, c_i64p, C.c_void_p, c_stream]),
     "rbr_embedding_fwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, c_f32p, c_stream]),
     "rbr_embedding_bwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, i32, c_f32p, c_stream]),
     "rbr_hier_pool_fwd": (C.c_int, [i32, i32, i32, i32, c_i64p, c_u8p, c_f32p, i32, c_f32p, c_i32p, c_stream]),

@@ -3,7 +3,7 @@
 //   RBR_SCORE_FM : relu(ul[u,:] * il[i,:]) . h + ub[u] + ib[i] + g     FM.forward in eval mode (deepconn/layers.py:189-209;
 //                                                                      ub / ib NULL = FMWithoutUIBias)
 //   RBR_SCORE_DOT: sum_k ul[u,k] * il[i,k]                             D-ATT (dual_att/dual_att.py:58)
-// The FM score is not a GEMM (the ReLU sits between the product and the sum over k).  Three entries share ONE arithmetic,
+// The FM score is not a GEMM (the ReLU sits between the product and the sum over k).  Four entries share ONE arithmetic,
 // score_step / score_finish below -- explicit fmaf / __fmul_rn, k ascending -- so they agree bit for bit on the same pair:
 //   rbr_pair_score_ids  : B pairs gathered by id (validation from the tables instead of two document encodes per pair)
 //   rbr_pair_score_dense: the [Nu, Ni] matrix (tests, small catalogues)
@@ -18,6 +18,15 @@
 //   A key is (order-preserving bits of the score) << 32 | (2^32 - 1 - item): keys are distinct, "larger" is "score descending,
 //   then item ascending", so the k largest keys are one well-defined set whatever order candidates arrive in -- no float
 //   atomics, no order-dependent merge, the same bytes on every run.  NaN scores are never candidates.
+//   rbr_pair_score_rank : where a held-out item lands -- for B (user row, target item) pairs the number of candidates whose key
+//   beats the target's, the position the target has in that user's topk list of any k, without the [B, Ni] matrix, two launches:
+//     1. rank_slice_kernel, the topk tile (score_chunk) with kTU integer counters per lane in place of the sorted lists: every
+//        non-NaN item of the slice whose key beats the tile's wave-uniform target keys is counted, excluded or not, and so is
+//        every NaN item; a wave reduction writes (beats, NaNs) per (pair, slice).
+//     2. rank_finish_kernel, one wave per pair: the slices summed, then the pair's exclusion list walked (some 20 entries
+//        against the Ni items of the sweep) and every entry that was counted taken off again -- exclusion is a subtraction
+//        after the sweep, not a binary search per (pair, item) inside it.
+//   All counts are integers: the same bytes on every run.
 #include "rbr_common.h"
 
 #include <cmath>
@@ -146,12 +155,21 @@ struct TopKArgs {
     int Nu, Ni, k, item_lo, S, vec;
 };
 
-__device__ __forceinline__ bool excluded(const TopKArgs& A, int urow, int item) {
-    const long long row = A.excl_row ? A.excl_row[urow] : (long long)urow;
-    if ((unsigned long long)row >= (unsigned long long)A.excl_rows) return false;      // no list for this row
-    long long a = A.excl_off[row], e = A.excl_off[row + 1];
+// [a, e) of excl_item that serves user row urow, false when the row has no list; a malformed CSR cannot send a reader outside
+// excl_item
+__device__ __forceinline__ bool excl_bounds(const long long* __restrict__ excl_off, const long long* __restrict__ excl_row, int excl_rows,
+                                            long long excl_nnz, int urow, long long& a, long long& e) {
+    const long long row = excl_row ? excl_row[urow] : (long long)urow;
+    if ((unsigned long long)row >= (unsigned long long)excl_rows) return false;
+    a = excl_off[row]; e = excl_off[row + 1];
     a = a < 0 ? 0 : a;
-    e = e > A.excl_nnz ? A.excl_nnz : e;        // a malformed CSR cannot send the search outside excl_item
+    e = e > excl_nnz ? excl_nnz : e;
+    return true;
+}
+
+__device__ __forceinline__ bool excluded(const TopKArgs& A, int urow, int item) {
+    long long a, e;
+    if (!excl_bounds(A.excl_off, A.excl_row, A.excl_rows, A.excl_nnz, urow, a, e)) return false;      // no list for this row
     long long b = e;
     while (a < b) {
         const long long mid = a + ((b - a) >> 1);
@@ -274,6 +292,127 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const unsigned long long
     }
 }
 
+// ----------------------------------------------------------------------------------------------------------------- rank
+struct RankArgs {
+    ScoreParams P;                 // P.ul [B, K] / P.ub [B]: the user rows gathered per pair
+    const long long* tgt;          // [B] target item ids
+    const long long* excl_off; const int* excl_item; const long long* excl_row;      // as in TopKArgs
+    long long excl_nnz;
+    int excl_rows;
+    int2* ws;                      // [B, S] (items of the slice that beat the target, NaN items of the slice)
+    int* rank; int* n_cand;        // [B]
+    long long* err;                // the int64[4] record of rbr_sanitize_ids, or null
+    long long per;                 // items per slice (a multiple of 64)
+    int B, Ni, item_lo, S, vec;
+};
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// Key of pair b's target from score_pair (the bits every other entry gives that pair).  A target outside [0, Ni) is never
+// dereferenced: row 0 stands in (the pair is unranked whatever its key).  false: the target's score is NaN.
+template <int MODE>
+__device__ __forceinline__ bool target_key(const RankArgs& A, int b, unsigned long long& key) {
+    long long t = A.tgt[b];
+    if ((unsigned long long)t >= (unsigned long long)A.Ni) t = 0;
+    const int K = A.P.K;
+    const float ub = (MODE == RBR_SCORE_FM && A.P.ub) ? A.P.ub[b] : 0.f, ib = (MODE == RBR_SCORE_FM && A.P.ib) ? A.P.ib[t] : 0.f;
+    const float s = score_pair<MODE>(A.P.ul + (size_t)b * K, A.P.il + (size_t)t * K, A.P.h, K, ub, ib, MODE == RBR_SCORE_FM ? A.P.g[0] : 0.f);
+    key = make_key(s, (int)t);
+    return s == s;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64) void rank_slice_kernel(const RankArgs A) {
+    const int lane = threadIdx.x, u0 = blockIdx.x * kTU, s = blockIdx.y;
+    const int K = A.P.K, B = A.B;
+    const float* __restrict__ ul = A.P.ul;
+    const float* __restrict__ il = A.P.il;
+    const float* __restrict__ h = A.P.h;
+    unsigned long long tk[kTU];       // wave-uniform
+    int beats[kTU], nans[kTU];
+#pragma unroll
+    for (int u = 0; u < kTU; ++u) {
+        target_key<MODE>(A, min(u0 + u, B - 1), tk[u]);
+        beats[u] = nans[u] = 0;
+    }
+    const long long lo = (long long)A.item_lo + (long long)s * A.per;
+    const long long hi = min(lo + A.per, (long long)A.Ni);
+    const float g = MODE == RBR_SCORE_FM ? A.P.g[0] : 0.f;
+    for (long long base = lo; base < hi; base += 64) {
+        const bool valid = base + lane < hi;
+        const int item = (int)(valid ? base + lane : hi - 1);
+        const float* __restrict__ ip = il + (size_t)item * K;
+        float acc[kTU];
+#pragma unroll
+        for (int u = 0; u < kTU; ++u) acc[u] = 0.f;
+        int k0 = 0;
+        for (; k0 + 32 <= K; k0 += 32) score_chunk<MODE, 32>(acc, ip, A.vec != 0, ul, h, u0, B, K, k0);
+        for (; k0 + 8 <= K; k0 += 8) score_chunk<MODE, 8>(acc, ip, A.vec != 0, ul, h, u0, B, K, k0);
+        for (; k0 < K; ++k0) {
+            const float v = ip[k0], hk = MODE == RBR_SCORE_FM ? h[k0] : 0.f;
+#pragma unroll
+            for (int u = 0; u < kTU; ++u) acc[u] = score_step<MODE>(acc[u], ul[(size_t)min(u0 + u, B - 1) * K + k0], v, hk);
+        }
+        const float ib = (MODE == RBR_SCORE_FM && A.P.ib) ? A.P.ib[item] : 0.f;
+#pragma unroll
+        for (int u = 0; u < kTU; ++u) {
+            const float ub = (MODE == RBR_SCORE_FM && A.P.ub) ? A.P.ub[min(u0 + u, B - 1)] : 0.f;
+            const float sc = score_finish<MODE>(acc[u], ub, ib, g);
+            const bool nan = sc != sc;
+            nans[u] += (valid && nan) ? 1 : 0;
+            beats[u] += (valid && !nan && make_key(sc, item) > tk[u]) ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < kTU; ++u) {
+        const int nb = wave_sum(beats[u]), nn = wave_sum(nans[u]);
+        if (lane == 0 && u0 + u < B) A.ws[(size_t)(u0 + u) * A.S + s] = make_int2(nb, nn);
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64) void rank_finish_kernel(const RankArgs A) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int K = A.P.K;
+    const long long t = A.tgt[b];
+    const bool in_table = (unsigned long long)t < (unsigned long long)A.Ni;
+    if (!in_table && lane == 0 && A.err) {            // recorded once per pair, as checked_id records an item id
+        A.err[1] = t; A.err[2] = 1;
+        atomicAdd(reinterpret_cast<unsigned long long*>(A.err), 1ull);
+    }
+    unsigned long long tk;
+    const bool ranked = target_key<MODE>(A, b, tk) && in_table && t >= A.item_lo;
+    int beats = 0, gone = 0;                          // `gone`: items of [item_lo, Ni) that are no candidates
+    for (int s = lane; s < A.S; s += 64) {
+        const int2 p = A.ws[(size_t)b * A.S + s];
+        beats += p.x; gone += p.y;
+    }
+    long long a, e;
+    if (A.excl_off && excl_bounds(A.excl_off, A.excl_row, A.excl_rows, A.excl_nnz, b, a, e)) {
+        const float ub = (MODE == RBR_SCORE_FM && A.P.ub) ? A.P.ub[b] : 0.f, g = MODE == RBR_SCORE_FM ? A.P.g[0] : 0.f;
+        for (long long q = a + lane; q < e; q += 64) {
+            const int j = A.excl_item[q];
+            // outside the sweep, the target itself (never excluded), or the entry before it again
+            if (j < A.item_lo || j >= A.Ni || (in_table && j == t) || (q > a && A.excl_item[q - 1] == j)) continue;
+            const float ib = (MODE == RBR_SCORE_FM && A.P.ib) ? A.P.ib[j] : 0.f;
+            const float sc = score_pair<MODE>(A.P.ul + (size_t)b * K, A.P.il + (size_t)j * K, A.P.h, K, ub, ib, g);
+            if (sc != sc) continue;                   // the sweep has it among the NaNs already
+            gone += 1;
+            beats -= make_key(sc, j) > tk ? 1 : 0;
+        }
+    }
+    beats = wave_sum(beats);
+    gone = wave_sum(gone);
+    if (lane == 0) {
+        A.rank[b] = ranked ? beats : -1;
+        A.n_cand[b] = A.Ni - A.item_lo - gone;
+    }
+}
+
 // item slices of a call: a function of (Nu, Ni) only, so the workspace query and the call agree
 static int topk_splits(int Nu, int Ni) {
     const long long tiles = ((long long)Nu + kTU - 1) / kTU;
@@ -295,6 +434,12 @@ static int topk_shape_ok(const char* what, int Nu, int Ni, int K, int k) {
     if (Nu <= 0 || Ni <= 0 || K <= 0) { set_error("%s: bad shape Nu=%d Ni=%d K=%d", what, Nu, Ni, K); return RBR_ERR_BAD_ARG; }
     if (k < 1) { set_error("%s: k=%d must be at least 1", what, k); return RBR_ERR_BAD_ARG; }
     if (k > kTopKMax) { set_error("%s: k=%d above the supported %d", what, k, kTopKMax); return RBR_ERR_UNSUPPORTED; }
+    if (K > kScoreDimMax) { set_error("%s: K=%d above the supported %d", what, K, kScoreDimMax); return RBR_ERR_UNSUPPORTED; }
+    return 0;
+}
+
+static int rank_shape_ok(const char* what, int B, int Ni, int K) {
+    if (B <= 0 || Ni <= 0 || K <= 0) { set_error("%s: bad shape B=%d Ni=%d K=%d", what, B, Ni, K); return RBR_ERR_BAD_ARG; }
     if (K > kScoreDimMax) { set_error("%s: K=%d above the supported %d", what, K, kScoreDimMax); return RBR_ERR_UNSUPPORTED; }
     return 0;
 }
@@ -386,5 +531,56 @@ extern "C" int rbr_pair_score_topk(int32_t mode, int32_t Nu, int32_t Ni, int32_t
     hipLaunchKernelGGL(topk_merge_kernel, dim3(Nu), dim3(64), (size_t)k * sizeof(unsigned long long), st, A.ws, A.S, k,
                        reinterpret_cast<long long*>(out_item), out_score);
     RBR_CHECK_LAUNCH("pair_score_topk merge launch");
+    return 0;
+}
+
+extern "C" size_t rbr_pair_score_rank_ws_bytes(int32_t B, int32_t Ni, int32_t K) {
+    using namespace rbr;
+    if (rank_shape_ok("rbr_pair_score_rank_ws_bytes", B, Ni, K)) return 0;
+    return (size_t)B * (size_t)topk_splits(B, Ni) * sizeof(int2);
+}
+
+extern "C" int rbr_pair_score_rank(int32_t mode, int32_t B, int32_t Ni, int32_t K, int32_t item_lo, const float* ul, const float* il,
+                                   const float* h, const float* g, const float* ub, const float* ib, const int64_t* tgt,
+                                   const int64_t* excl_off, const int32_t* excl_item, int64_t excl_nnz, const int64_t* excl_row,
+                                   int32_t excl_rows, int32_t* rank, int32_t* n_cand, int64_t* err, void* ws, void* stream) {
+    using namespace rbr;
+    if (int e = rank_shape_ok("rbr_pair_score_rank", B, Ni, K)) return e;
+    if (int e = score_args_ok("rbr_pair_score_rank", mode, K, ul, il, h, g)) return e;
+    if (item_lo < 0 || item_lo >= Ni) { set_error("rbr_pair_score_rank: item_lo=%d outside [0, %d)", item_lo, Ni); return RBR_ERR_BAD_ARG; }
+    if (!tgt || !rank || !n_cand || !ws) { set_error("rbr_pair_score_rank: null targets, output or workspace"); return RBR_ERR_BAD_ARG; }
+    if ((excl_off != nullptr) != (excl_item != nullptr) || excl_nnz < 0 || (!excl_off && (excl_nnz != 0 || excl_row))) {
+        set_error("rbr_pair_score_rank: the exclusion list is excl_off [rows + 1] AND excl_item [excl_nnz], or neither");
+        return RBR_ERR_BAD_ARG;
+    }
+    if (excl_row && excl_rows <= 0) { set_error("rbr_pair_score_rank: excl_row with excl_rows=%d", excl_rows); return RBR_ERR_BAD_ARG; }
+    RankArgs A;
+    A.P = ScoreParams{ul, il, h, g, ub, ib, K};
+    A.tgt = reinterpret_cast<const long long*>(tgt);
+    A.excl_off = reinterpret_cast<const long long*>(excl_off);
+    A.excl_item = excl_item;
+    A.excl_row = reinterpret_cast<const long long*>(excl_row);
+    A.excl_nnz = excl_nnz;
+    A.excl_rows = excl_row ? excl_rows : B;
+    A.ws = static_cast<int2*>(ws);
+    A.rank = rank; A.n_cand = n_cand;
+    A.err = reinterpret_cast<long long*>(err);
+    A.B = B; A.Ni = Ni; A.item_lo = item_lo;
+    A.S = topk_splits(B, Ni);
+    const long long n = (long long)Ni - item_lo;
+    A.per = (((n + A.S - 1) / A.S) + 63) / 64 * 64;
+    A.vec = (K % 4 == 0 && (reinterpret_cast<uintptr_t>(il) % 16) == 0) ? 1 : 0;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((B + kTU - 1) / kTU, A.S);
+    if (mode == RBR_SCORE_FM)
+        hipLaunchKernelGGL(rank_slice_kernel<RBR_SCORE_FM>, grid, dim3(64), 0, st, A);
+    else
+        hipLaunchKernelGGL(rank_slice_kernel<RBR_SCORE_DOT>, grid, dim3(64), 0, st, A);
+    RBR_CHECK_LAUNCH("pair_score_rank slice launch");
+    if (mode == RBR_SCORE_FM)
+        hipLaunchKernelGGL(rank_finish_kernel<RBR_SCORE_FM>, dim3(B), dim3(64), 0, st, A);
+    else
+        hipLaunchKernelGGL(rank_finish_kernel<RBR_SCORE_DOT>, dim3(B), dim3(64), 0, st, A);
+    RBR_CHECK_LAUNCH("pair_score_rank finish launch");
     return 0;
 }

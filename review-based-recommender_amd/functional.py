@@ -2130,6 +2130,22 @@ def pair_score_dense(mode, ul, il, h=None, g=None, ub=None, ib=None):
     return out
 
 
+def _exclusion_csr(exclude, Nu, dev):
+    """(off, items, rows, nnz, n_rows) of the `exclude` argument of pair_score_topk / pair_score_rank for Nu user rows; all None /
+    0 for no list."""
+    if exclude is None:
+        return None, None, None, 0, 0
+    off, items = exclude[0].contiguous(), exclude[1].contiguous()
+    rows = exclude[2].contiguous() if len(exclude) > 2 else None
+    n_rows = off.shape[0] - 1
+    if off.dim() != 1 or (rows is None and n_rows != Nu) or (rows is not None and (rows.shape != (Nu,) or n_rows < 1)):
+        raise RuntimeError(f"exclude offsets must be [{Nu + 1}] (or [R + 1] with rows [{Nu}]), got {tuple(off.shape)}")
+    nnz = items.numel()
+    if nnz == 0:         # a zero-sized tensor has no pointer to hand over: one unused entry keeps the CSR form
+        items = torch.zeros(1, dtype=I32, device=dev)
+    return off, items, rows, nnz, n_rows if rows is not None else 0
+
+
 def pair_score_topk(mode, ul, il, k, h=None, g=None, ub=None, ib=None, *, item_lo=0, exclude=None):
     """(items int64 [Nu, k], scores f32 [Nu, k]): for every user row of ul [Nu, K] the k best items of [item_lo, Ni), score
     descending, ties by the lower item id, the same bytes on every run (rbr_pair_score_topk; 1 <= k <= 128).  `exclude` lists
@@ -2140,17 +2156,7 @@ def pair_score_topk(mode, ul, il, k, h=None, g=None, ub=None, ib=None, *, item_l
     code, ul, il, h, g, ub, ib = _score_operands(mode, ul, il, h, g, ub, ib)
     Nu, Ni, K, k = ul.shape[0], il.shape[0], ul.shape[1], int(k)
     dev = ul.device
-    off = items = rows = None
-    nnz = n_rows = 0
-    if exclude is not None:
-        off, items = exclude[0].contiguous(), exclude[1].contiguous()
-        rows = exclude[2].contiguous() if len(exclude) > 2 else None
-        n_rows = off.shape[0] - 1
-        if off.dim() != 1 or (rows is None and n_rows != Nu) or (rows is not None and (rows.shape != (Nu,) or n_rows < 1)):
-            raise RuntimeError(f"exclude offsets must be [{Nu + 1}] (or [R + 1] with rows [{Nu}]), got {tuple(off.shape)}")
-        nnz = items.numel()
-        if nnz == 0:         # a zero-sized tensor has no pointer to hand over: one unused entry keeps the CSR form
-            items = torch.zeros(1, dtype=I32, device=dev)
+    off, items, rows, nnz, n_rows = _exclusion_csr(exclude, Nu, dev)
     L_ = _lib.lib()
     if Nu == 0:
         return torch.empty(0, k, dtype=I64, device=dev), torch.empty(0, k, dtype=F32, device=dev)
@@ -2160,6 +2166,36 @@ def pair_score_topk(mode, ul, il, k, h=None, g=None, ub=None, ib=None, *, item_l
     out_score = torch.empty(Nu, max(k, 0), dtype=F32, device=dev)
     _call("pair_score_topk", L_.rbr_pair_score_topk, code, Nu, Ni, K, k, int(item_lo), dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"),
           dev_ptr(h, F32, "h"), dev_ptr(g, F32, "g"), dev_ptr(ub, F32, "ub"), dev_ptr(ib, F32, "ib"), dev_ptr(off, I64, "exclude offsets"),
-          dev_ptr(items, I32, "exclude items"), nnz, dev_ptr(rows, I64, "exclude rows"), n_rows if rows is not None else 0,
+          dev_ptr(items, I32, "exclude items"), nnz, dev_ptr(rows, I64, "exclude rows"), n_rows,
           dev_ptr(out_item, I64, "out_item"), dev_ptr(out_score, F32, "out_score"), ws.data_ptr(), current_stream())
     return out_item, out_score
+
+
+def pair_score_rank(mode, ul, il, targets, h=None, g=None, ub=None, ib=None, *, item_lo=0, exclude=None):
+    """(rank int32 [B], n_cand int32 [B]) of the held-out items `targets` int64 [B] for the user rows ul [B, K] (ub [B]), one row
+    per pair (rbr_pair_score_rank): rank[b] is the number of candidates that come before targets[b] in the order of
+    pair_score_topk (score descending, ties by the lower item id) -- its position in that row's top-k list of any k -- and
+    n_cand[b] the number of candidates.  Candidates are the items of [item_lo, Ni) with a non-NaN score that `exclude` (the forms
+    of pair_score_topk, a row per pair) does not list; the target is a candidate even when its row lists it.  rank -1: the target
+    is outside [item_lo, Ni) or scores NaN (it is in no top-k list); one outside [0, Ni) is also recorded for check_id_errors().
+    Exact integers from the arithmetic of every other pair_score entry; the [B, Ni] matrix is never built; no autograd, no host
+    synchronisation, one workspace from the torch allocator: recordable into a graph on one stream."""
+    code, ul, il, h, g, ub, ib = _score_operands(mode, ul, il, h, g, ub, ib)
+    B, Ni, K = ul.shape[0], il.shape[0], ul.shape[1]
+    dev = ul.device
+    targets = targets.contiguous()
+    if targets.shape != (B,):
+        raise RuntimeError(f"targets must be [{B}], one per user row, got {tuple(targets.shape)}")
+    off, items, rows, nnz, n_rows = _exclusion_csr(exclude, B, dev)
+    rank = torch.empty(B, dtype=I32, device=dev)
+    n_cand = torch.empty(B, dtype=I32, device=dev)
+    if B == 0:
+        return rank, n_cand
+    L_ = _lib.lib()
+    # a shape the entry refuses has a workspace of 0 bytes: the call below then returns its error code and text before any launch
+    ws = torch.empty(max(L_.rbr_pair_score_rank_ws_bytes(B, Ni, K), 8), dtype=torch.uint8, device=dev)
+    _call("pair_score_rank", L_.rbr_pair_score_rank, code, B, Ni, K, int(item_lo), dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"),
+          dev_ptr(h, F32, "h"), dev_ptr(g, F32, "g"), dev_ptr(ub, F32, "ub"), dev_ptr(ib, F32, "ib"), dev_ptr(targets, I64, "targets"),
+          dev_ptr(off, I64, "exclude offsets"), dev_ptr(items, I32, "exclude items"), nnz, dev_ptr(rows, I64, "exclude rows"), n_rows,
+          dev_ptr(rank, I32, "rank"), dev_ptr(n_cand, I32, "n_cand"), _id_err(dev).data_ptr(), ws.data_ptr(), current_stream())
+    return rank, n_cand

@@ -2,21 +2,27 @@
 
     python -m review_based_recommender_amd.recommend --model deepconn --config cfg.json --checkpoint best_model.pt \\
         --k 10 [--exclude-train] --out recs.jsonl
+    python -m review_based_recommender_amd.recommend --model deepconn --config cfg.json --checkpoint best_model.pt \\
+        --eval-split test [--ks 5,10,20] [--exclude-train] [--metrics-out metrics.json]
 
 Every tower of the four models depends on its own side only (DeepCoNN++ / SimpleSiamese: LastFeat(encoder(doc), id); NARRE: the
 same over an attention pool keyed by the reviews' own counterpart ids; D-ATT: the shared fc over cat(local, global)), and the
 pair-dependent rest is the FM head or an inner product.  `Recommender.refresh()` therefore encodes every user and every item
 ONCE into latent tables [U, K] / [I, K]; `score`, `score_all` and `topk` then run on the tables alone (csrc/pair_score.hip) --
-`topk` without ever building the U x I score matrix.  The reference can only score a pair by encoding both of its documents
-(models/deepconn/deepconn.py:43-53) and has no ranking entry at all.
+`topk` without ever building the U x I score matrix, and `rank` / `evaluate` say where the held-out item of a (user, item) pair
+lands in that user's ranking (HR@K, NDCG@K, MRR, AUC), without it too.  The reference can only score a pair by encoding both of
+its documents (models/deepconn/deepconn.py:43-53) and has no ranking entry at all.
 
 The output file holds one JSON line per user id 1 .. U-1 (id 0 is the padding id of both sides: never a user, never recommended):
     {"user": u, "items": [...], "scores": [...]}
+With --eval-split the (user, item) pairs of that split are ranked instead (as well, when --out is given too) and one JSON line of
+rank_metrics goes to --metrics-out, or to stdout.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import os
 from types import SimpleNamespace
 from typing import NamedTuple, Optional
 
@@ -32,6 +38,41 @@ class SeenItems(NamedTuple):
     """Items every USER ID has already rated, CSR over all user ids: off int64 [U + 1], items int32 sorted within a user."""
     off: torch.Tensor
     items: torch.Tensor
+
+
+def rank_metrics(rank: torch.Tensor, n_cand: torch.Tensor, ks) -> dict:
+    """Ranking metrics of held-out pairs from their exact ranks (Recommender.rank; any integer tensors, CPU or GPU), summed in
+    float64.  rank < 0 is an unranked pair: a miss in the first three.
+        hr@K      mean(0 <= rank < K)
+        ndcg@K    mean(1 / log2(rank + 2) where 0 <= rank < K, else 0)         one relevant item per pair: the ideal DCG is 1
+        mrr       mean(1 / (rank + 1), 0 where unranked)
+        auc       mean(1 - rank / (n_cand - 1)) over the ranked pairs with n_cand > 1: the share of the other candidates below
+        mean_rank mean(rank) over the ranked pairs
+        n, unranked   pairs, and pairs with rank < 0
+    A mean over no pair at all is None."""
+    ks = [int(k) for k in ks]
+    if any(k < 1 for k in ks):
+        raise ValueError(f"every K of rank_metrics must be at least 1, got {ks}")
+    r, c = rank.reshape(-1).to(torch.int64), n_cand.reshape(-1).to(torch.int64)
+    if r.shape != c.shape:
+        raise ValueError(f"rank and n_cand must hold one value per pair each, got {tuple(rank.shape)} / {tuple(n_cand.shape)}")
+    ranked = r >= 0
+    rd = r.clamp_min(0).double()
+    in_auc = ranked & (c > 1)
+    sums = [ranked.sum().double(), in_auc.sum().double(), (ranked.double() / (rd + 1)).sum(),
+            (in_auc.double() * (1 - rd / (c - 1).clamp_min(1).double())).sum(), (ranked.double() * rd).sum()]
+    for k in ks:
+        hit = (ranked & (r < k)).double()
+        sums += [hit.sum(), (hit / torch.log2(rd + 2)).sum()]
+    n = r.numel()
+    n_ranked, n_auc, mrr, auc, rank_sum, *per_k = torch.stack(sums).tolist()       # one read-back
+    mean = lambda total, count: total / count if count else None                   # noqa: E731
+    out = {}
+    for j, k in enumerate(ks):
+        out[f"hr@{k}"], out[f"ndcg@{k}"] = mean(per_k[2 * j], n), mean(per_k[2 * j + 1], n)
+    out.update({"mrr": mean(mrr, n), "auc": mean(auc, n_auc), "mean_rank": mean(rank_sum, n_ranked), "n": n,
+                "unranked": n - int(n_ranked)})
+    return out
 
 
 class Recommender:
@@ -144,6 +185,34 @@ class Recommender:
             exclude = (exclude.off, exclude.items, u_ids)
         return RF.pair_score_topk(mode, rows, il, k, h, g, ub_rows, ib, item_lo=self.item_lo, exclude=exclude)
 
+    def rank(self, u_ids: torch.Tensor, i_ids: torch.Tensor, exclude=None):
+        """(rank int32 [B], n_cand int32 [B]) of the held-out pairs (u_ids[b], i_ids[b]): rank[b] is the position of item
+        i_ids[b] in the list topk(u_ids[b], k, exclude) of any k -- the number of candidates that come before it -- and n_cand[b]
+        the number of candidates it competes in; exact, without the score matrix, for ranks beyond every k.  `exclude` as in
+        topk, a row per pair; the held-out item itself is never excluded.  rank -1: the padding item 0, an id outside the
+        table, or a NaN score."""
+        mode, rows, il, h, g, ub_rows, ib, u_ids = self._user_rows(u_ids)
+        if isinstance(exclude, SeenItems):
+            exclude = (exclude.off, exclude.items, u_ids)
+        return RF.pair_score_rank(mode, rows, il, i_ids, h, g, ub_rows, ib, item_lo=self.item_lo, exclude=exclude)
+
+    def evaluate(self, pairs, ks=(5, 10, 20), exclude=None, chunk: int = 4096) -> dict:
+        """rank_metrics of held-out pairs: `pairs` is a dataset's examples (sequences starting (u_id, i_id, ...)) or the id
+        tensors (u_ids, i_ids) themselves.  Ranked `chunk` pairs at a time, one rank_metrics call over all of them; `exclude`: a
+        SeenItems (the CLI's --exclude-train: the training split's seen_from) or None."""
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        dev = self._tables()[0].device
+        if len(pairs) == 2 and all(torch.is_tensor(t) for t in pairs):
+            u_ids, i_ids = (t.to(dev, torch.int64) for t in pairs)
+        else:
+            u_ids = torch.tensor([int(e[0]) for e in pairs], dtype=torch.int64, device=dev)
+            i_ids = torch.tensor([int(e[1]) for e in pairs], dtype=torch.int64, device=dev)
+        parts = [self.rank(u_ids[a:a + chunk], i_ids[a:a + chunk], exclude) for a in range(0, u_ids.shape[0], chunk)]
+        rank = torch.cat([p[0] for p in parts]) if parts else torch.empty(0, dtype=torch.int32, device=dev)
+        n_cand = torch.cat([p[1] for p in parts]) if parts else torch.empty(0, dtype=torch.int32, device=dev)
+        return rank_metrics(rank, n_cand, ks)
+
     @staticmethod
     def seen_from(examples, n_users: int, device=None) -> SeenItems:
         """The items each user id has rated in `examples` (a dataset's examples: sequences starting (u_id, i_id, ...)) as a
@@ -168,7 +237,10 @@ def parse_cli(argv=None):
     ap.add_argument("--checkpoint", required=True, help="best_model.pt written by the trainer")
     ap.add_argument("--k", type=int, default=10, help="items per user (1..128)")
     ap.add_argument("--exclude-train", action="store_true", help="never recommend an item the user rated in the training split")
-    ap.add_argument("--out", required=True, help="output file, one JSON line per user")
+    ap.add_argument("--out", help="output file, one JSON line per user (required unless --eval-split is given)")
+    ap.add_argument("--eval-split", choices=["valid", "test"], help="rank this split's held-out (user, item) pairs: HR / NDCG / MRR / AUC")
+    ap.add_argument("--ks", help="cut-offs K of hr@K / ndcg@K with --eval-split, comma-separated (default 5,10,20)")
+    ap.add_argument("--metrics-out", help="file for the one JSON line of metrics of --eval-split (default: stdout)")
     ap.add_argument("--chunk", type=int, default=256, help="ids encoded / users ranked per launch")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--reference-quirks", action="store_true", help="as for the trainer: kernel_sizes=[3] (NARRE hidden_dim=150)")
@@ -177,6 +249,17 @@ def parse_cli(argv=None):
         ap.error("--k must be in 1..128")
     if a.chunk < 1:
         ap.error("--chunk must be at least 1")
+    if a.eval_split is None:
+        if a.out is None:
+            ap.error("--out is required unless --eval-split is given")
+        if a.ks is not None or a.metrics_out is not None:
+            ap.error("--ks and --metrics-out belong to --eval-split")
+    try:
+        a.ks = tuple(int(k) for k in ("5,10,20" if a.ks is None else a.ks).split(","))
+    except ValueError:
+        ap.error(f"--ks must be comma-separated integers, got {a.ks!r}")
+    if any(not 1 <= k < 2 ** 31 for k in a.ks):
+        ap.error("every K of --ks must be in 1..2^31-1")
     return a
 
 
@@ -202,14 +285,23 @@ def main(argv=None) -> int:
     model.to(dev).eval()
     rec = Recommender(model, cache).refresh(chunk=a.chunk)
     seen = Recommender.seen_from(ds.examples, rec.n_users, dev) if a.exclude_train else None
-    with open(a.out, "w") as f:
-        for lo in range(1, rec.n_users, a.chunk):
-            u_ids = torch.arange(lo, min(lo + a.chunk, rec.n_users), dtype=torch.int64, device=dev)
-            items, scores = rec.topk(u_ids, a.k, exclude=seen)
-            items, scores = items.cpu(), scores.cpu()
-            for r, u in enumerate(u_ids.tolist()):
-                keep = items[r] >= 0
-                f.write(json.dumps({"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}) + "\n")
+    if a.out is not None:
+        with open(a.out, "w") as f:
+            for lo in range(1, rec.n_users, a.chunk):
+                u_ids = torch.arange(lo, min(lo + a.chunk, rec.n_users), dtype=torch.int64, device=dev)
+                items, scores = rec.topk(u_ids, a.k, exclude=seen)
+                items, scores = items.cpu(), scores.cpu()
+                for r, u in enumerate(u_ids.tolist()):
+                    keep = items[r] >= 0
+                    f.write(json.dumps({"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}) + "\n")
+    if a.eval_split is not None:
+        held_out = D.load_pickle(os.path.join(cfg.data_dir, f"{a.eval_split}_exmaples.pkl"))
+        line = json.dumps(dict(rec.evaluate(held_out, a.ks, exclude=seen), split=a.eval_split, exclude_train=bool(a.exclude_train)))
+        if a.metrics_out is not None:
+            with open(a.metrics_out, "w") as f:
+                f.write(line + "\n")
+        else:
+            print(line, flush=True)
     RF.check_id_errors(dev)
     return 0
 

@@ -24,6 +24,9 @@ D-ATT) keeps meta.pkl's documents on the GPU and feeds the step (u_id, i_id, rat
 there (data.DeviceDocCache; the loaders check once that every example's documents are meta's for its ids); `eval_from_towers:
 true` (with device_cache) validates from latent tables: every user / item document is encoded once per validation pass and a
 pair is scored from two table rows (recommend.Recommender), instead of both documents being encoded for every pair;
+`rank_metrics: [10]` (with eval_from_towers, one process) also ranks every validation pair's item among all items the user has
+not rated in the training split and logs `valid hr@10: ..., ndcg@10: ..., mrr: ...` after the RMSE line, which, like best-model
+selection and early stopping, is unchanged;
 `device_reviews: true` (NARRE and SimpleSiamese) is the review split's counterpart of device_cache: meta.pkl's reviews stay on the
 GPU (data.DeviceReviewCache), the loaders ship (u_id, i_id, rating) and one launch rebuilds the batch -- training examples with
 the pair's own review left out, validation examples plain (the loaders check once that every example is what that rule gives
@@ -65,7 +68,7 @@ class EarlyStop(Exception):
 DEFAULTS = dict(log_dir="logs", dataset="dataset", log=True, log_idx=500, verbose=False, parallel=False, epochs=64,
                 batch_size=50, lr=0.002, max_grad_norm=5.0, patience=5, dropout=0.5, arch="CNN", use_pretrain=False,
                 num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False, eval_from_towers=False,
-                device_reviews=False)
+                device_reviews=False, rank_metrics=[])
 
 
 class _ShardSampler(torch.utils.data.Sampler):
@@ -167,6 +170,15 @@ class ReviewExperiment:
             raise ValueError("eval_from_towers needs device_cache (--model deepconn or dual_att) or device_reviews (narre or "
                              "simple_siamese): validation then scores each pair from latent tables encoded once per epoch from "
                              "the per-id documents")
+        if args.rank_metrics:
+            ks = args.rank_metrics
+            if not isinstance(ks, (list, tuple)) or any(isinstance(k, bool) or not isinstance(k, int) or k < 1 for k in ks):
+                raise ValueError(f"rank_metrics must be a list of cut-offs K >= 1, got {ks!r}")
+            if not bool(args.eval_from_towers):
+                raise ValueError("rank_metrics needs eval_from_towers: the validation pairs are ranked from the latent tables")
+            if bool(args.parallel):
+                raise ValueError("rank_metrics is not available with parallel: the ranks of the shards are not reduced over the "
+                                 "processes")
         self.kind, self.args, self.quirks = kind, args, reference_quirks
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -413,11 +425,17 @@ class ReviewExperiment:
                 self._towers = Recommender(self.model, self.cache)
             towers = self._towers
             towers.refresh()
+        ranks = []
+        if self.args.rank_metrics and getattr(self, "_seen", None) is None:
+            # what a validation item competes against: every item its user has not rated in the training split
+            self._seen = towers.seen_from(self.train_set.examples, towers.n_users, self.device)
         with torch.no_grad():
             for batch in loader:
                 if towers is not None:
                     u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
                     pred = towers.score(u_ids, i_ids)
+                    if self.args.rank_metrics:
+                        ranks.append(towers.rank(u_ids, i_ids, exclude=self._seen))
                 elif self.cache is not None:
                     u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
                     pred = self._eval_forward_ids(u_ids, i_ids)
@@ -445,6 +463,12 @@ class ReviewExperiment:
             self.patience += 1
         self.print_write_to_log("valid loss: {:.3f}, valid rmse: {:.3f}, best rmse: {:.3f}".format(
             float(loss_sum) / max(steps, 1), rmse, self.best_rmse))
+        if ranks:
+            from .recommend import rank_metrics
+            m = self.last_rank_metrics = rank_metrics(torch.cat([r for r, _ in ranks]), torch.cat([c for _, c in ranks]),
+                                                      self.args.rank_metrics)
+            keys = [f"{name}@{k}" for k in self.args.rank_metrics for name in ("hr", "ndcg")] + ["mrr"]
+            self.print_write_to_log("valid " + ", ".join("{}: {:.3f}".format(k, m[k]) for k in keys))
         if self.patience >= self.args.patience:
             raise EarlyStop("early stop")
 
