@@ -399,6 +399,21 @@ int rbr_block_split(int32_t B, int32_t C1, int32_t C2, const float* g, float* a,
 int rbr_mse_loss_bwd(int64_t n, const float* pred, const float* target, const float* d_loss, float* d_pred,
                      void* stream);
 
+/* ---- BPR (pairwise ranking) loss over sampled negatives; the reference trains for rating regression only.
+ *   pred f32 [(1 + n_neg) * B] in rbr_sample_negatives' slab-major layout: pred[b] scores the observed pair b, pred[(j+1)*B + b]
+ *   its j-th negative.  With x[j,b] = pred[(j+1)*B + b] - pred[b] and valid f32 [n_neg * B] (row j*B + b; NULL = all ones):
+ *     n       = max(sum valid, 1)
+ *     loss[0] = sum valid[j,b] * softplus(x[j,b]) / n            softplus(x) = max(x, 0) + log1p(exp(-|x|))
+ *     d_pred[(j+1)*B + b] = valid[j,b] * sigmoid(x[j,b]) / n * d_loss[0];   d_pred[b] = -sum_j d_pred[(j+1)*B + b]
+ *   One workgroup, no atomics, fixed summation order: the same bits on every run; an all-zero valid gives loss 0 and zero
+ *   gradients.  d_pred_unit (optional, [(1 + n_neg) * B]): the gradient for an upstream gradient of exactly 1, written by the
+ *   forward launch (as rbr_mse_loss_fwd's); rbr_bpr_loss_bwd is the launch for any other d_loss (a device scalar).
+ *   B >= 1, n_neg >= 1, (1 + n_neg) * B <= 2^30. */
+int rbr_bpr_loss_fwd(int32_t B, int32_t n_neg, const float* pred, const float* valid, float* loss, float* d_pred_unit,
+                     void* stream);
+int rbr_bpr_loss_bwd(int32_t B, int32_t n_neg, const float* pred, const float* valid, const float* d_loss, float* d_pred,
+                     void* stream);
+
 /* ---- NARRE review-level attention pool (narre.py:40-64)
  *   e = ebd[other_id];  logit = relu(feat@W_rv + e@W_id + b1) @ h + b2
  *   att = exp(logit) / (sum_R exp(logit) + 1e-8)   (unmasked, no max subtraction)
@@ -582,6 +597,31 @@ int rbr_review_gather(int32_t B, int32_t R, int32_t T, const int64_t* u_ids, con
                       const int32_t* user_rids, int32_t U, const int32_t* item_revs, const int32_t* item_rids, int32_t I,
                       int32_t leave_one_out, int64_t pad_token, int64_t replace_id, int64_t* revs_out, uint8_t* word_masks_out,
                       uint8_t* rev_masks_out, int64_t* rids_out, int64_t* ids_out, int64_t* err, void* stream);
+
+/* ---- negatives for a pairwise objective, in front of either id feed: for each of the B observed pairs (u_ids[b], i_ids[b]),
+ *      n_neg >= 1 items of [item_lo, I) that are neither i_ids[b] nor in the user's seen row, with replacement across j.
+ *      seen_off int64 [U + 1] / seen_item int32 [seen_nnz]: the CSR rbr_pair_score_topk takes for its exclusion (sorted within a
+ *      row; both NULL and seen_nnz 0 for none; offsets outside [0, seen_nnz] are clamped).  A u_id outside [0, U) has an empty
+ *      seen row (the feed's own id check reports it).
+ *      Outputs, slab-major, row r = j * B + b: u_out / i_out int64 [(1 + n_neg) * B] -- slab 0 holds the observed pairs
+ *      (i_out[b] = i_ids[b]), slab 1 + j the j-th negatives, u_out[j*B + b] = u_ids[b] in every slab; valid f32 [n_neg * B],
+ *      valid[j*B + b] = 1 when pair b's j-th negative (row (j+1)*B + b) was drawn, 0 when no item is acceptable.
+ *      THE DRAW (integers only; a host restatement gives the same outputs).  Negative j of pair b has draw index
+ *      d = b * n_neg + j.  Attempt t = 0, 1, ..: word = word (t & 3) of Philox4x32-10 with counter (d * 16 + (t >> 2), state[0])
+ *      and key seed -- the generator of rbr_dropout_multiplier: counter words (lo, hi of the first; lo, hi of the second), key
+ *      (lo, hi of seed), 10 rounds, multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85 -- and
+ *        candidate = item_lo + (((uint64)word * (uint64)(I - item_lo)) >> 32).
+ *      The first acceptable candidate is taken.  After max_tries (1..64) rejected attempts: c = the last candidate, then
+ *      c -> item_lo + (c - item_lo + 1) % (I - item_lo) repeatedly, the first acceptable c is taken; after I - item_lo such
+ *      steps without one (no item is acceptable) i_out = replace_id (0 <= replace_id < I) and valid = 0.
+ *      state: 2 x uint64 in device memory, zero-initialised (or set to [call, 0]) by the caller; every lane reads the call number
+ *      state[0] first, and the last workgroup to finish (ticket in state[1]) resets the ticket and stores state[0] + 1 -- the
+ *      convention of rbr_dropout_multiplier: a launch recorded into a graph draws a new set on every replay.
+ *      One launch, one lane per draw, plain stores, nothing read back on the host: graph-capturable.  B * n_neg <= 2^30.  ---- */
+int rbr_sample_negatives(int32_t B, int32_t n_neg, int32_t I, int32_t item_lo, const int64_t* u_ids, const int64_t* i_ids,
+                         const int64_t* seen_off, const int32_t* seen_item, int64_t seen_nnz, int32_t U, uint64_t seed,
+                         uint64_t* state, int32_t max_tries, int64_t replace_id, int64_t* u_out, int64_t* i_out, float* valid,
+                         void* stream);
 
 /* ---- scoring and top-K recommendation from cached tower latents.  Every tower depends on its own side only, so a catalogue is
  *      encoded once into latent tables ul [U, K] / il [I, K] and a (user, item) score is the pair-dependent tail:

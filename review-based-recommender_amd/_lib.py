@@ -169,6 +169,10 @@ SIGNATURES = {
     "rbr_block_cat": (C.c_int, [i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "rbr_block_split": (C.c_int, [i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "rbr_mse_loss_bwd": (C.c_int, [C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "rbr_bpr_loss_fwd": (C.c_int, [i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "rbr_bpr_loss_bwd": (C.c_int, [i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "rbr_sample_negatives": (C.c_int, [i32, i32, i32, i32, c_i64p, c_i64p, c_i64p, c_i32p, C.c_int64, i32, C.c_uint64, C.c_void_p,
+                                       i32, C.c_int64, c_i64p, c_i64p, c_f32p, c_stream]),
     "rbr_review_attn_fwd": (C.c_int, [i32, i32, i32, i32, c_f32p, c_i64p, C.POINTER(AttnParams), c_f32p, c_f32p, c_f32p,
                                       c_f32p, c_stream]),
     "rbr_review_attn_bwd_ws_floats": (C.c_size_t, [i32, i32, i32, i32]),

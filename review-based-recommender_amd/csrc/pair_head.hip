@@ -456,6 +456,57 @@ __global__ __launch_bounds__(256) void mse_bwd_kernel(long n, const float* __res
     if (i < n) d_pred[i] = (pred[i] - target[i]) * (2.f / (float)n) * d_loss[0];
 }
 
+// ---- BPR (pairwise ranking) loss over sampled negatives, pred in rbr_sample_negatives' slab-major layout: slab 0 = the B observed
+// pairs, slab 1 + j = their j-th negatives.  x[j,b] = pred[(j+1)B + b] - pred[b];
+//   loss = sum valid * softplus(x) / max(sum valid, 1);  d pred[(j+1)B + b] = valid * sigmoid(x) / max(sum valid, 1) * d_loss,
+//   d pred[b] = -(the sum of its own negatives' gradients).
+// One workgroup, no atomics, fixed summation order (lane-strided partial sums, xor-shuffle tree, four wave sums in order): the
+// same bits on every run.  Pass 1 sums the loss and the count, pass 2 writes the gradient once the count is known.
+__device__ __forceinline__ float bpr_softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float bpr_sigmoid(float x) {
+    const float e = expf(-fabsf(x));          // in (0, 1]: never overflows
+    return x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+}
+
+__global__ __launch_bounds__(256) void bpr_loss_kernel(int B, int n_neg, const float* __restrict__ pred, const float* __restrict__ valid,
+                                                       const float* __restrict__ d_loss, float* __restrict__ loss,
+                                                       float* __restrict__ d_pred) {
+    __shared__ float s_red[2][4];
+    float acc = 0.f, cnt = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const float p = pred[b];
+        for (int j = 0; j < n_neg; ++j) {
+            const long e = (long)j * B + b;
+            const float v = valid ? valid[e] : 1.f;
+            if (v != 0.f) {
+                acc += v * bpr_softplus(pred[e + B] - p);
+                cnt += v;
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { acc += __shfl_xor(acc, o); cnt += __shfl_xor(cnt, o); }
+    if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = acc; s_red[1][threadIdx.x >> 6] = cnt; }
+    __syncthreads();
+    const float total = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
+    const float denom = fmaxf(s_red[1][0] + s_red[1][1] + s_red[1][2] + s_red[1][3], 1.f);
+    if (loss != nullptr && threadIdx.x == 0) *loss = total / denom;
+    if (d_pred == nullptr) return;
+    const float scale = (d_loss ? d_loss[0] : 1.f) / denom;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const float p = pred[b];
+        float own = 0.f;
+        for (int j = 0; j < n_neg; ++j) {
+            const long e = (long)j * B + b;
+            const float v = valid ? valid[e] : 1.f;
+            const float g = v != 0.f ? v * bpr_sigmoid(pred[e + B] - p) * scale : 0.f;
+            d_pred[e + B] = g;
+            own += g;
+        }
+        d_pred[b] = 0.f - own;
+    }
+}
+
 }  // namespace rbr
 
 extern "C" int rbr_mse_loss_fwd(int64_t n, const float* pred, const float* target, float* loss, float* d_pred_unit, void* stream) {
@@ -471,6 +522,32 @@ extern "C" int rbr_mse_loss_bwd(int64_t n, const float* pred, const float* targe
     hipLaunchKernelGGL(rbr::mse_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (long)n, pred,
                        target, d_loss, d_pred);
     RBR_CHECK_LAUNCH("mse_bwd launch");
+    return 0;
+}
+
+static bool bpr_args_ok(const char* who, int B, int n_neg, const void* pred) {
+    if (B <= 0 || n_neg < 1 || (long long)B * (1LL + n_neg) > (1LL << 30)) { set_error("%s: bad shape B=%d n_neg=%d", who, B, n_neg); return false; }
+    if (!pred) { set_error("%s: null pointer", who); return false; }
+    return true;
+}
+
+extern "C" int rbr_bpr_loss_fwd(int32_t B, int32_t n_neg, const float* pred, const float* valid, float* loss, float* d_pred_unit,
+                                void* stream) {
+    if (!bpr_args_ok("bpr_loss_fwd", B, n_neg, pred)) return RBR_ERR_BAD_ARG;
+    if (!loss) { set_error("bpr_loss_fwd: null pointer"); return RBR_ERR_BAD_ARG; }
+    hipLaunchKernelGGL(rbr::bpr_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, B, n_neg, pred, valid,
+                       (const float*)nullptr, loss, d_pred_unit);
+    RBR_CHECK_LAUNCH("bpr_loss_fwd launch");
+    return 0;
+}
+
+extern "C" int rbr_bpr_loss_bwd(int32_t B, int32_t n_neg, const float* pred, const float* valid, const float* d_loss, float* d_pred,
+                                void* stream) {
+    if (!bpr_args_ok("bpr_loss_bwd", B, n_neg, pred)) return RBR_ERR_BAD_ARG;
+    if (!d_loss || !d_pred) { set_error("bpr_loss_bwd: null pointer"); return RBR_ERR_BAD_ARG; }
+    hipLaunchKernelGGL(rbr::bpr_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, B, n_neg, pred, valid, d_loss,
+                       (float*)nullptr, d_pred);
+    RBR_CHECK_LAUNCH("bpr_loss_bwd launch");
     return 0;
 }
 

@@ -496,6 +496,79 @@ class ReviewFeed:
         return tuple(half for k in self.order for half in (got[k][:B], got[k][B:]))
 
 
+class NegativeFeed:
+    """An id feed (DeviceDocCache, ReviewFeed) behind a negative sampler, for a pairwise objective (train_step.BprObjective): a
+    batch of B observed pairs becomes (1 + n_neg) * B pairs -- rows [0, B) the pairs themselves, rows [(j+1)B, (j+2)B) each
+    pair's j-th negative, an item of [item_lo, n_items) its user has not rated (functional.sample_negatives; `seen`: the training
+    split's recommend.Recommender.seen_from, or None) -- and the inner feed gathers those.  It speaks the inner feed's protocol
+    (empty_inputs / gather / inputs), so GraphedTrainStep.from_ids records sampler + gather + step, and every replay draws new
+    negatives.  A review feed applies its leave-one-out rule to every expanded pair as to any pair (a negative's pair has no
+    review of its own to leave out).
+
+    The expanded ids and the `valid` flags (f32 [n_neg * B]: 0 where a user has no unrated item) live in static buffers, one
+    set per batch size B (`buffers(B)`; `u_out` / `i_out` / `valid` are those of the last gather); `state` is the sampler's
+    [call number, ticket] on the device.  reseed(seed, call) restarts the sequence: (seed, call) fixes a draw exactly."""
+
+    def __init__(self, feed, seen, n_items: int, n_neg: int = 1, seed: int = 0, item_lo: int = 1, max_tries: int = 16):
+        if isinstance(n_neg, bool) or not isinstance(n_neg, int) or n_neg < 1:
+            raise ValueError(f"n_neg must be an integer >= 1, got {n_neg!r}")
+        if not 0 <= int(item_lo) < int(n_items):
+            raise ValueError(f"item_lo {item_lo} leaves no item of [0, {n_items})")
+        if not 1 <= int(max_tries) <= 64:
+            raise ValueError(f"max_tries must be in [1, 64], got {max_tries}")
+        self.feed, self.device = feed, torch.device(feed.device)
+        self.seen = None if seen is None else (seen[0].to(self.device), seen[1].to(self.device))
+        self.n_items, self.n_neg, self.item_lo, self.max_tries = int(n_items), n_neg, int(item_lo), int(max_tries)
+        self.seed = int(seed)
+        self.state = torch.zeros(2, dtype=torch.int64, device=self.device)
+        self._buffers = {}
+        self._last = None
+
+    def reseed(self, seed: int, call: int = 0) -> None:
+        """The next draw is call number `call` under `seed` (no host synchronisation: one small copy on the current stream).
+        A recorded step holds the seed it was recorded with: reseed it with that seed, to move the call number only."""
+        self.seed = int(seed)
+        self.state.copy_(torch.tensor([int(call), 0], dtype=torch.int64), non_blocking=True)
+
+    def buffers(self, B: int):
+        """(u_out, i_out, valid) of batch size B: the sampler's static outputs."""
+        buf = self._buffers.get(B)
+        if buf is None:
+            rows = (1 + self.n_neg) * B
+            buf = self._buffers[B] = (torch.zeros(rows, dtype=torch.int64, device=self.device),
+                                      torch.zeros(rows, dtype=torch.int64, device=self.device),
+                                      torch.zeros(self.n_neg * B, dtype=torch.float32, device=self.device))
+        return buf
+
+    u_out = property(lambda self: self._last[0])
+    i_out = property(lambda self: self._last[1])
+    valid = property(lambda self: self._last[2])
+
+    def sample(self, u_ids: torch.Tensor, i_ids: torch.Tensor):
+        """Draws the negatives of the pairs into buffers(B) and returns them."""
+        from . import functional as RF
+        u_ids, i_ids = u_ids.to(self.device, non_blocking=True), i_ids.to(self.device, non_blocking=True)
+        self._last = RF.sample_negatives(u_ids, i_ids, self.n_neg, self.n_items, self.seen, state=self.state, seed=self.seed,
+                                         item_lo=self.item_lo, max_tries=self.max_tries, replace_id=self.item_lo,
+                                         out=self.buffers(u_ids.shape[0]))
+        return self._last
+
+    def empty_inputs(self, B: int, with_ids: bool = True):
+        """The inner feed's empty_inputs for the (1 + n_neg) * B expanded pairs."""
+        self.buffers(B)            # allocated here, outside any capture
+        return self.feed.empty_inputs((1 + self.n_neg) * B, with_ids)
+
+    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None, **kw):
+        """Sampler, then the inner feed's gather of the expanded pairs (`out`: the model's arguments for (1 + n_neg) * B pairs)."""
+        u_out, i_out, _ = self.sample(u_ids, i_ids)
+        return self.feed.gather(u_out, i_out, out=out, **kw)
+
+    def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
+        """The model's arguments for the expanded pairs."""
+        u_out, i_out, _ = self.sample(u_ids, i_ids)
+        return self.feed.inputs(u_out, i_out, with_ids=with_ids)
+
+
 def _adjacent(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """[a; b] as ONE view when b directly follows a in the same allocation (a write through it lands in a and b)."""
     if not (a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype and a.shape == b.shape and a.device == b.device

@@ -1238,6 +1238,54 @@ def mse_loss(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return _MseLoss.apply(pred, target)
 
 
+class _BprLoss(torch.autograd.Function):
+    """The pairwise ranking loss over sampled negatives (rbr_bpr_loss_* in rbr_hip.h).  As _MseLoss: the forward launch also
+    writes d loss / d pred for an upstream gradient of 1, and a backward that is handed unit_scalar() returns it without a launch."""
+
+    @staticmethod
+    def forward(ctx, pred, n_neg, valid):
+        pred = pred.contiguous()
+        n_neg = int(n_neg)
+        if pred.dim() != 1 or n_neg < 1 or pred.shape[0] == 0 or pred.shape[0] % (1 + n_neg):
+            raise RuntimeError(f"bpr_loss: pred must be [(1 + n_neg) * B] with n_neg >= 1, got {tuple(pred.shape)} for n_neg={n_neg}")
+        B = pred.shape[0] // (1 + n_neg)
+        if valid is not None:
+            valid = valid.contiguous()
+            if valid.shape != (n_neg * B,):
+                raise RuntimeError(f"bpr_loss: valid must be [{n_neg * B}], got {tuple(valid.shape)}")
+        loss = torch.empty((), dtype=F32, device=pred.device)
+        d_unit = torch.empty_like(pred) if ctx.needs_input_grad[0] else None
+        _call(None, _lib.lib().rbr_bpr_loss_fwd, B, n_neg, dev_ptr(pred, F32, "pred"), dev_ptr(valid, F32, "valid"),
+              dev_ptr(loss, F32, "loss"), dev_ptr(d_unit, F32, "d_pred_unit"), current_stream())
+        ctx.B, ctx.n_neg, ctx.has_valid = B, n_neg, valid is not None
+        ctx.save_for_backward(pred, *([valid] if valid is not None else []), *([d_unit] if d_unit is not None else []))
+        return loss
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        saved = ctx.saved_tensors
+        pred = saved[0]
+        valid = saved[1] if ctx.has_valid else None
+        d_unit = saved[-1] if len(saved) == 2 + int(ctx.has_valid) else None
+        unit = _UNIT.get(pred.device)
+        if unit is not None and d_unit is not None and d_loss.data_ptr() == unit.data_ptr():
+            return d_unit, None, None
+        d_pred = torch.empty_like(pred)
+        d_loss = d_loss.contiguous()
+        _call(None, _lib.lib().rbr_bpr_loss_bwd, ctx.B, ctx.n_neg, dev_ptr(pred, F32, "pred"), dev_ptr(valid, F32, "valid"),
+              dev_ptr(d_loss, F32, "d_loss"), dev_ptr(d_pred, F32, "d_pred"), current_stream())
+        return d_pred, None, None
+
+
+def bpr_loss(pred: torch.Tensor, n_neg: int, valid: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The BPR loss of pred f32 [(1 + n_neg) * B] in sample_negatives' layout (rows [0, B) score the observed pairs, rows
+    [(j+1)B, (j+2)B) their j-th negatives): mean over the valid negatives of softplus(pred_neg - pred_pos) =
+    -log sigmoid(pred_pos - pred_neg).  valid f32 [n_neg * B] (1 / 0, sample_negatives' third output; None = all ones) takes a
+    negative out of the sum and the mean; no valid negative at all gives loss 0 and zero gradients.  Fixed summation order:
+    the same bits on every run."""
+    return _BprLoss.apply(pred, n_neg, valid)
+
+
 # --------------------------------------------------------------------------- NARRE attention pool
 class _ReviewAttn(torch.autograd.Function):
     """out[B,H], att[B,R,1] = LinearAttention(feat[B,R,H], other_id[B,R])  -- rbr_review_attn_* in rbr_hip.h."""
@@ -2199,3 +2247,40 @@ def pair_score_rank(mode, ul, il, targets, h=None, g=None, ub=None, ib=None, *, 
           dev_ptr(off, I64, "exclude offsets"), dev_ptr(items, I32, "exclude items"), nnz, dev_ptr(rows, I64, "exclude rows"), n_rows,
           dev_ptr(rank, I32, "rank"), dev_ptr(n_cand, I32, "n_cand"), _id_err(dev).data_ptr(), ws.data_ptr(), current_stream())
     return rank, n_cand
+
+
+# --------------------------------------------------------------------------- negatives for a pairwise objective
+def sample_negatives(u_ids, i_ids, n_neg: int, n_items: int, seen=None, *, state, seed: int = 0, item_lo: int = 1,
+                     max_tries: int = 16, replace_id: int = 0, out=None):
+    """(u_out int64 [(1 + n_neg) * B], i_out int64 [(1 + n_neg) * B], valid f32 [n_neg * B]) for the observed pairs (u_ids[b],
+    i_ids[b]) (rbr_sample_negatives, one launch): rows [0, B) are the pairs themselves, rows [(j+1)B, (j+2)B) pair b's j-th
+    negative -- an item of [item_lo, n_items) that is neither i_ids[b] nor in the user's row of `seen`, with replacement across j;
+    valid[j*B + b] = 0 (and item replace_id) where a user has no such item.  `seen`: a recommend.SeenItems / (off int64 [U + 1],
+    items int32 sorted within a row) over all user ids -- the first exclusion form of pair_score_topk -- or None.
+    `state`: int64 [2] on the device, [call number, 0]; the launch advances the call number itself, so two calls (or two replays of
+    a recorded call) draw different sets, and (seed, call number) fixes a set exactly (the draw is stated in include/rbr_hip.h).
+    `out`: the three tensors to write into.  No autograd, no host synchronisation, no allocation with `out`: graph-capturable."""
+    u_ids, i_ids = u_ids.contiguous(), i_ids.contiguous()
+    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
+        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+    B, n_neg, dev = u_ids.shape[0], int(n_neg), u_ids.device
+    if seen is not None and len(seen) != 2:
+        raise RuntimeError("seen must be (off [U + 1], items): one row per user id")
+    U = 0 if seen is None else seen[0].shape[0] - 1
+    off, items, _, nnz, _ = _exclusion_csr(seen, U, dev)
+    if state.shape != (2,) or state.dtype != I64:
+        raise RuntimeError(f"state must be int64 [2], got {state.dtype} {tuple(state.shape)}")
+    rows = (1 + max(n_neg, 0)) * B
+    if out is None:
+        out = (torch.empty(rows, dtype=I64, device=dev), torch.empty(rows, dtype=I64, device=dev),
+               torch.empty(max(n_neg, 0) * B, dtype=F32, device=dev))
+    u_out, i_out, valid = out
+    if u_out.shape != (rows,) or i_out.shape != (rows,) or valid.shape != (rows - B,):
+        raise RuntimeError(f"out must be u_out [{rows}], i_out [{rows}], valid [{rows - B}]")
+    if B == 0 and n_neg >= 1:
+        return u_out, i_out, valid
+    _call("sample_negatives", _lib.lib().rbr_sample_negatives, B, n_neg, int(n_items), int(item_lo), dev_ptr(u_ids, I64, "u_ids"),
+          dev_ptr(i_ids, I64, "i_ids"), dev_ptr(off, I64, "seen offsets"), dev_ptr(items, I32, "seen items"), nnz, U,
+          int(seed) & 0xFFFFFFFFFFFFFFFF, dev_ptr(state, I64, "state"), int(max_tries), int(replace_id), dev_ptr(u_out, I64, "u_out"),
+          dev_ptr(i_out, I64, "i_out"), dev_ptr(valid, F32, "valid"), current_stream())
+    return u_out, i_out, valid

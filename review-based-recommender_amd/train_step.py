@@ -239,12 +239,17 @@ class HipClipAdam(torch.optim.Optimizer):
 
 
 def train_step(model: nn.Module, optimizer: torch.optim.Optimizer, batch, ratings: torch.Tensor,
-               max_grad_norm: float = MAX_GRAD_NORM, grad_sync=None):
+               max_grad_norm: float = MAX_GRAD_NORM, grad_sync=None, objective=None):
     """One step.  `batch` is the tuple passed to model(*batch); models returning a tuple
     (NARRE: pred, u_att, i_att) contribute their first element.  `grad_sync(model)` is the
-    data-parallel gradient all-reduce hook (None on one GPU).  Returns (loss, gnorm, pred) tensors."""
+    data-parallel gradient all-reduce hook (None on one GPU).  Returns (loss, gnorm, pred) tensors.
+    `objective` (None: the trainers' MSELoss against `ratings`): a callable pred -> scalar loss that replaces it, e.g.
+    BprObjective; `ratings` is then not looked at and `pred` has as many rows as the objective's feed made of the batch."""
     optimizer.zero_grad()
-    pred, loss = _forward_loss_backward(model, batch, ratings, optimizer if grad_sync is None else None)
+    if objective is None:
+        pred, loss = _forward_loss_backward(model, batch, ratings, optimizer if grad_sync is None else None)
+    else:
+        pred, loss = _forward_objective_backward(model, batch, objective, optimizer if grad_sync is None else None)
     if grad_sync is not None:
         if isinstance(optimizer, HipClipAdam):
             optimizer.materialize_grads()        # the all-reduce wants every gradient as a dense .grad
@@ -269,6 +274,34 @@ def _forward_loss_backward(model: nn.Module, batch, ratings: torch.Tensor, optim
             loss.backward(RF.unit_scalar(pred.device))
             return pred, loss
         return pred, _loss_and_backward(pred, ratings)
+
+
+def _forward_objective_backward(model: nn.Module, batch, objective, optimizer=None):
+    """y = model(*batch); loss = objective(y); loss.backward() -- no MSE target is announced to the forward (the model's head runs
+    un-fused), and the root gradient is the cached unit scalar, which functional.bpr_loss answers without a launch."""
+    scope = optimizer.row_grad_scope() if isinstance(optimizer, HipClipAdam) else contextlib.nullcontext()
+    with scope:
+        out = model(*batch)
+        pred = out[0] if isinstance(out, tuple) else out
+        loss = objective(pred)
+        loss.backward(RF.unit_scalar(pred.device) if pred.is_cuda else None)
+    return pred, loss
+
+
+class BprObjective:
+    """loss = functional.bpr_loss(pred, feed.n_neg, feed.valid) for a step fed through `feed` (a data.NegativeFeed): pred's rows
+    are the feed's expanded pairs -- the B observed pairs, then n_neg slabs of their sampled negatives -- and the loss is the mean
+    of -log sigmoid(pred_pos - pred_neg) over the negatives the sampler could draw.  Pass it as `objective` to train_step /
+    GraphedTrainStep together with the feed."""
+
+    def __init__(self, feed):
+        self.feed = feed
+
+    def __call__(self, pred: torch.Tensor) -> torch.Tensor:
+        n_neg = self.feed.n_neg
+        if pred.dim() != 1 or pred.shape[0] % (1 + n_neg):
+            raise RuntimeError(f"BprObjective: pred {tuple(pred.shape)} is not (1 + {n_neg}) * B scores")
+        return RF.bpr_loss(pred, n_neg, self.feed.buffers(pred.shape[0] // (1 + n_neg))[2])
 
 
 def _loss_and_backward(pred: torch.Tensor, ratings: torch.Tensor) -> torch.Tensor:
@@ -465,15 +498,22 @@ class GraphedTrainStep:
     `feed` (a data.DeviceDocCache, or a data.ReviewFeed for the review split; from_ids()): the id-fed step.  `batch` is then (u_ids, i_ids); a slot stages only
     (u_ids, i_ids, ratings) -- one small block, `stage` / `slot_inputs` -- and its graph starts with the gather of the
     documents into the slot's document block (cache.gather: documents, masks and checked ids for DeepCoNN++; documents
-    only with with_ids=False, D-ATT), followed by the unchanged step."""
+    only with with_ids=False, D-ATT), followed by the unchanged step.
+
+    `objective` (None: the MSE step): train_step's `objective`, e.g. BprObjective(feed) with `feed` a data.NegativeFeed -- the graph
+    then starts with the negative sampler, the staged ratings are not looked at and `pred` has the feed's expanded rows."""
 
     def __init__(self, model: nn.Module, optimizer: torch.optim.Optimizer, batch, ratings: torch.Tensor,
                  max_grad_norm: float = MAX_GRAD_NORM, grad_sync=None, warmup: int = 3, capture_error_mode: str | None = None,
-                 slots: int = 1, keep_graph: bool = False, feed=None, with_ids: bool = True):
+                 slots: int = 1, keep_graph: bool = False, feed=None, with_ids: bool = True, objective=None):
         if not ratings.is_cuda:
             raise RuntimeError("GraphedTrainStep needs HIP tensors")
         if slots < 1:
             raise ValueError("slots must be >= 1")
+        if objective is not None and grad_sync is not None:
+            raise ValueError("a recorded step with an objective is not available with grad_sync (data-parallel training keeps "
+                             "the MSE step)")
+        self.objective = objective
         self.model, self.optimizer, self.grad_sync, self.max_grad_norm = model, optimizer, grad_sync, max_grad_norm
         self._keep_graph = bool(keep_graph)      # keeps the hipGraph_t behind the executable: kernel_launches() can count its nodes
         self._feed, self._with_ids = feed, with_ids
@@ -517,7 +557,7 @@ class GraphedTrainStep:
         with torch.cuda.stream(side):      # warm-up off the default stream: allocator, lazy optimizer state, occupancy queries
             for _ in range(warmup):
                 self._prologue(first)
-                train_step(model, optimizer, first.batch, first.ratings, max_grad_norm, grad_sync)
+                train_step(model, optimizer, first.batch, first.ratings, max_grad_norm, grad_sync, objective)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         # with a process group alive, RCCL's watchdog thread polls events while we record: only this thread's calls
@@ -531,7 +571,8 @@ class GraphedTrainStep:
             if grad_sync is None:
                 with _lib_mod().capture_guard(cs), torch.cuda.graph(sl.g_fwd_bwd, stream=cs, capture_error_mode=mode):
                     self._prologue(sl)
-                    sl.loss, sl.gnorm, sl.pred = train_step(model, optimizer, sl.batch, sl.ratings, max_grad_norm)
+                    sl.loss, sl.gnorm, sl.pred = train_step(model, optimizer, sl.batch, sl.ratings, max_grad_norm,
+                                                            objective=objective)
                 sl.static_grads = [(p, p.grad) for p in model.parameters()]
             else:
                 with _lib_mod().capture_guard(cs), torch.cuda.graph(sl.g_fwd_bwd, stream=cs, capture_error_mode=mode):

@@ -30,7 +30,13 @@ selection and early stopping, is unchanged;
 `device_reviews: true` (NARRE and SimpleSiamese) is the review split's counterpart of device_cache: meta.pkl's reviews stay on the
 GPU (data.DeviceReviewCache), the loaders ship (u_id, i_id, rating) and one launch rebuilds the batch -- training examples with
 the pair's own review left out, validation examples plain (the loaders check once that every example is what that rule gives
-for its ids); eval_from_towers works on top of it.
+for its ids); eval_from_towers works on top of it;
+`loss: "bpr"` (with device_cache or device_reviews, one process; `n_neg: 1`, `neg_seed` = `seed`) trains for ranking instead of
+rating regression: every batch pair is joined by n_neg items its user has not rated in the training split, drawn on the device
+(data.NegativeFeed), and the step minimises -log sigmoid(score(u, i+) - score(u, i-)) (train_step.BprObjective); the step log line
+keeps its format with the BPR loss under `loss` (its `rmse` field is sqrt of the mean loss then, not an RMSE);
+`select_by: "hr@K" | "ndcg@K" | "mrr"` (default "rmse"; K must be in rank_metrics; required with loss "bpr") makes best_model.pt
+and `patience` follow that validation metric, higher is better, and the rank line ends in `best <metric>: ...`.
 """
 from __future__ import annotations
 
@@ -68,7 +74,21 @@ class EarlyStop(Exception):
 DEFAULTS = dict(log_dir="logs", dataset="dataset", log=True, log_idx=500, verbose=False, parallel=False, epochs=64,
                 batch_size=50, lr=0.002, max_grad_norm=5.0, patience=5, dropout=0.5, arch="CNN", use_pretrain=False,
                 num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False, eval_from_towers=False,
-                device_reviews=False, rank_metrics=[])
+                device_reviews=False, rank_metrics=[], loss="mse", n_neg=1, neg_seed=None, select_by="rmse")
+
+LOSSES = ("mse", "bpr")
+
+
+def _rank_metric_of(select_by):
+    """("hr" | "ndcg", K) or ("mrr", None) for a rank-metric `select_by`, None for "rmse"; anything else is refused."""
+    if select_by == "rmse":
+        return None
+    if select_by == "mrr":
+        return "mrr", None
+    name, _, k = str(select_by).partition("@")
+    if name in ("hr", "ndcg") and k.isdigit() and int(k) >= 1 and str(int(k)) == k:
+        return name, int(k)
+    raise ValueError(f"select_by must be \"rmse\", \"hr@K\", \"ndcg@K\" or \"mrr\", got {select_by!r}")
 
 
 class _ShardSampler(torch.utils.data.Sampler):
@@ -179,6 +199,27 @@ class ReviewExperiment:
             if bool(args.parallel):
                 raise ValueError("rank_metrics is not available with parallel: the ranks of the shards are not reduced over the "
                                  "processes")
+        if args.loss not in LOSSES:
+            raise ValueError(f"loss must be one of {LOSSES}, got {args.loss!r}")
+        metric = _rank_metric_of(args.select_by)
+        if metric is not None and (not args.rank_metrics or (metric[1] is not None and metric[1] not in args.rank_metrics)):
+            raise ValueError(f"select_by {args.select_by!r} needs rank_metrics to contain "
+                             f"{'a cut-off' if metric[1] is None else metric[1]}: the model is selected by a metric the "
+                             "validation pass computes")
+        if args.loss == "bpr":
+            if isinstance(args.n_neg, bool) or not isinstance(args.n_neg, int) or args.n_neg < 1:
+                raise ValueError(f"n_neg must be an integer >= 1, got {args.n_neg!r}")
+            if not (bool(args.device_cache) or bool(args.device_reviews)):
+                raise ValueError("loss \"bpr\" needs device_cache (--model deepconn or dual_att) or device_reviews (narre or "
+                                 "simple_siamese): a negative's documents are gathered on the device by its id")
+            if bool(args.parallel):
+                raise ValueError("loss \"bpr\" is not available with parallel: the negative sampler and the pairwise step "
+                                 "run in one process")
+            if metric is None:
+                raise ValueError("loss \"bpr\" needs a rank metric in select_by (\"hr@K\", \"ndcg@K\" or \"mrr\"): a "
+                                 "pairwise loss does not fit ratings, so the validation RMSE cannot select the model")
+        self.select_metric = None if metric is None else args.select_by
+        self.best_score = -math.inf          # the best select_by metric so far (higher is better); unused with "rmse"
         self.kind, self.args, self.quirks = kind, args, reference_quirks
         self.rank = int(os.environ.get("RANK", "0"))
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -207,6 +248,15 @@ class ReviewExperiment:
             # meta.pkl's reviews resident on this GPU; a train batch leaves each pair's own review out, a valid batch does not
             self.cache = D.DeviceReviewCache(self.train_set, self.device)
             self.train_feed, self.eval_feed = self.cache.feed(kind, True), self.cache.feed(kind, False)
+        self.objective = None
+        if args.loss == "bpr":
+            # negatives are items the user has not rated in the training split: the same CSR the validation ranks against
+            from .recommend import Recommender
+            from .train_step import BprObjective
+            self._seen = Recommender.seen_from(self.train_set.examples, self.train_set.user_num, self.device)
+            seed = args.seed if args.neg_seed is None else args.neg_seed
+            self.train_feed = D.NegativeFeed(self.train_feed, self._seen, self.cache.item.shape[0], n_neg=args.n_neg, seed=int(seed))
+            self.objective = BprObjective(self.train_feed)
         self._make_dir()
         self.build_model()
         # both splits were range-checked against their tables when they were loaded (data.validate_ranges): the per-forward
@@ -365,14 +415,20 @@ class ReviewExperiment:
         if a.fast_step:
             key = tuple((t.shape, t.dtype) for t in batch)
             if self._graphed is None:
+                # recording runs warm-up steps: they must not use up the negative sampler's draws either
+                calls = self.train_feed.state.clone() if self.objective is not None else None
                 self._graphed = GraphedTrainStep.from_ids(self.model, self.optimizer, self.train_feed, u_ids, i_ids, ratings,
-                                                          a.max_grad_norm, self.grad_sync, with_ids=with_ids)
+                                                          a.max_grad_norm, self.grad_sync, with_ids=with_ids,
+                                                          objective=self.objective)
+                if calls is not None:
+                    self.train_feed.state.copy_(calls)
                 self._graphed_key = key
             if key == self._graphed_key:
                 loss, gnorm, _ = self._graphed((u_ids, i_ids), ratings)
                 return loss.clone(), gnorm.clone(), ratings
         inputs = self.train_feed.inputs(u_ids, i_ids, with_ids=with_ids)
-        loss, gnorm, _ = train_step(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync)
+        loss, gnorm, _ = train_step(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync,
+                                    objective=self.objective)
         return loss, gnorm, ratings
 
     def _eval_forward_ids(self, u_ids, i_ids):
@@ -455,7 +511,9 @@ class ReviewExperiment:
         rmse = math.sqrt(float(sq_err) / max(float(count), 1.0))
         self.last_valid_rmse = rmse
         RF.check_id_errors(self.device)
-        if rmse < self.best_rmse:
+        if self.select_metric is not None:
+            self.best_rmse = min(self.best_rmse, rmse)        # reported; the model is selected below, by its rank metric
+        elif rmse < self.best_rmse:
             self.best_rmse = rmse
             self.save("best_model.pt")
             self.patience = 0
@@ -468,7 +526,17 @@ class ReviewExperiment:
             m = self.last_rank_metrics = rank_metrics(torch.cat([r for r, _ in ranks]), torch.cat([c for _, c in ranks]),
                                                       self.args.rank_metrics)
             keys = [f"{name}@{k}" for k in self.args.rank_metrics for name in ("hr", "ndcg")] + ["mrr"]
-            self.print_write_to_log("valid " + ", ".join("{}: {:.3f}".format(k, m[k]) for k in keys))
+            line = "valid " + ", ".join("{}: {:.3f}".format(k, m[k]) for k in keys)
+            if self.select_metric is not None:
+                score = m[self.select_metric]
+                if score is not None and score > self.best_score:
+                    self.best_score = score
+                    self.save("best_model.pt")
+                    self.patience = 0
+                else:
+                    self.patience += 1
+                line += ", best {}: {:.3f}".format(self.select_metric, self.best_score)
+            self.print_write_to_log(line)
         if self.patience >= self.args.patience:
             raise EarlyStop("early stop")
 
