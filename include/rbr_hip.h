@@ -679,6 +679,7 @@ int rbr_pair_score_rank(int32_t mode, int32_t B, int32_t Ni, int32_t K, int32_t 
 /* ---- NgramFeat arch="HierPooling" (deepconn/layers.py:62-98,110-114): pooled[doc,d] =
  *      max_l mean_{j<k} x[doc,l+j,d] over l in [0, L-k], x = mask * table[ids]; relu != 0 applies the
  *      trailing ReLU when there is no projection layer.  argmax[doc,d] = first maximising window start.
+ *      A NaN window mean wins the max (the first one is kept, as ATen's max pooling does) and passes the ReLU.
  *      Backward: dtable ACCUMULATED (each of the k rows of the winning window gets g/k).          ---- */
 int rbr_hier_pool_fwd(int32_t n_docs, int32_t L, int32_t D, int32_t k, const int64_t* ids, const uint8_t* mask,
                       const float* table, int32_t relu, float* pooled, int32_t* argmax, void* stream);

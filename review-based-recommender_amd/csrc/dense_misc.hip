@@ -380,6 +380,8 @@ __global__ __launch_bounds__(256) void emb_bwd_kernel(long n_tok, int D, const l
 // ------------------------------------------------------------------------------------ HierPooling
 // pooled[doc, d] = max_{l in [0, L-k]} (sum_{j<k} x[doc, l+j, d]) / k, x = mask * table[ids]; first argmax kept.
 // The window sum is re-formed in the reference's order (j ascending) at every l, so values match avg_pool1d.
+// NaN propagates as in ATen's max pooling (`val > max || isnan(val)`): the first NaN window is taken and kept, and the trailing
+// ReLU keeps it too (torch.relu(NaN) is NaN), so a diverged table shows in the features instead of being pooled away.
 __global__ __launch_bounds__(256) void hier_fwd_kernel(int n_docs, int L, int D, int k, const long long* __restrict__ ids,
                                                        const unsigned char* __restrict__ mask, const float* __restrict__ table,
                                                        int relu, float* __restrict__ pooled, int* __restrict__ argmax) {
@@ -402,9 +404,9 @@ __global__ __launch_bounds__(256) void hier_fwd_kernel(int n_docs, int L, int D,
                 s += (row >= 0) ? table[row + d] : 0.f;
             }
             const float v = s / (float)k;
-            if (v > best) { best = v; bidx = l; }
+            if (v > best || (v != v && best == best)) { best = v; bidx = l; }      // a NaN window wins once, then nothing beats it
         }
-        pooled[(long)doc * D + d] = relu ? fmaxf(best, 0.f) : best;
+        pooled[(long)doc * D + d] = (relu && best < 0.f) ? 0.f : best;              // not fmaxf: it would turn NaN into 0
         argmax[(long)doc * D + d] = bidx;
     }
 }
