@@ -480,7 +480,8 @@ int rbr_datt_global_gate_bwd(int32_t B, int32_t L, int32_t E, const int64_t* ids
                              const float* w, const float* gate, const float* dgate, int32_t pad_idx, float* dw,
                              float* db0, float* dtable, float* ws, void* stream);
 /* Distinct-token rows of one tower's documents (ids [B,L] over a table of V rows): row_of_token / tok_of_row maps in `rows`
- * (rbr_datt_token_rows_ws_bytes bytes), built once per tower and step and handed to the gate backwards below.
+ * (rbr_datt_token_rows_ws_bytes bytes), built once per tower and step and handed to the gate backwards below.  Rows are
+ * numbered in vocabulary order (shared and private maps of the same ids are identical, run after run).
  * rbr_datt_global_gate_bwd_rows == rbr_datt_global_gate_bwd, except that the table gradient goes through the occurrence
  * matrix A[row, p] = sum of dpre over the documents that carry the row's token at position p (one scalar atomic per position
  * instead of a row of E per distinct token and window), every table row is then written once from its non-zeros, and

@@ -79,7 +79,7 @@ __device__ __forceinline__ void gate_bwd_dx_kernel(int B, int L, int E, int win,
                                                           long c_stride) {
     __shared__ int s_tok[kGWin];
     __shared__ short s_leader[kGWin], s_cnt[kGWin], s_start[kGWin], s_sorted[kGWin];
-    __shared__ int s_fill[kGWin];
+    __shared__ int s_fill[kGWin];                    // positions per leader (counted with LDS atomics: integers, any order)
     __shared__ int s_hkey[kGHash], s_hval[kGHash];
     __shared__ float s_dpre[kGWin + 2 * kMaxKF];     // local: dpre of the window plus a halo of `pad` each side
     __shared__ short s_keys[kGWin];                  // the leaders (first position of each distinct token), dense
@@ -143,7 +143,6 @@ __device__ __forceinline__ void gate_bwd_dx_kernel(int B, int L, int E, int win,
             }
             s_start[r] = (short)(run + inc - c);
             s_cnt[r] = (short)c;
-            s_fill[r] = 0;
             if (c > 0) s_keys[krun + kinc - 1] = (short)r;
             run += __shfl(inc, 63);
             krun += __shfl(kinc, 63);
@@ -151,9 +150,18 @@ __device__ __forceinline__ void gate_bwd_dx_kernel(int B, int L, int E, int win,
         if (lane == 0) s_nkeys = krun;
     }
     __syncthreads();
+    // a token's positions in ascending order (an atomic fill left them in arrival order: the tap sums below rounded differently
+    // from run to run); `lead` is the token's first position, so the walk starts there.  Up to 255 LDS reads for the last
+    // position of a window that holds one token, where the atomic fill took one.  Not measured in isolation; the whole backward
+    // of the token-product gate at the cfg4 tower shape (512 x 1024 Zipf ids, V = 50 k) went from 96 to 101 us with it, the
+    // row maps (rbr_datt_token_rows) from 21.6 to 15.8 us without the contended counter
     for (int r = tid; r < kGWin; r += 256) {
         const int lead = s_leader[r];
-        if (lead >= 0) s_sorted[s_start[lead] + atomicAdd(&s_fill[lead], 1)] = (short)r;
+        if (lead >= 0) {
+            int rank = 0;
+            for (int q = lead; q < r; ++q) rank += (s_leader[q] == lead);
+            s_sorted[s_start[lead] + rank] = (short)r;
+        }
     }
     __syncthreads();
     // The folded rows leave the workgroup thread-parallel: a wave per token walked <= 64 tokens one after the other, each
@@ -464,15 +472,43 @@ __device__ __forceinline__ void gp_mark_kernel(long n, const long long* __restri
     for (long k = (long)blockIdx.x * 256 + threadIdx.x; k < n; k += (long)gridDim.x * 256) used[ids[k]] = 1;
 }
 
-__device__ __forceinline__ void gp_compact_kernel(int V, int cap, const int* __restrict__ used, int* __restrict__ row_of_token,
-                                                         int* __restrict__ tok_of_row, int* __restrict__ counter) {
+// Row numbers in vocabulary order: the number of used tokens below v.  (They came from an atomic counter, one add per wave in
+// arrival order: the same batch got another permutation of rows from run to run, and everything summed in row order -- dw and
+// db0 of the token-product gate -- rounded differently each time, and differently between a tower's shared maps and private ones.)
+// gp_count_kernel leaves the used tokens of every 256 vocabulary entries, gp_compact_kernel's workgroup adds up those before it:
+// nblk^2 / 2 reads of L2-resident ints over the grid (nblk = V / 256: 20 k reads at the 50 k vocabularies of the configs, 8 M at
+// V = 1 M -- a vocabulary of that size wants a scan of the block counts first).  The last workgroup writes the row counter.
+__device__ __forceinline__ void gp_count_kernel(int V, const int* __restrict__ used, int* __restrict__ blk_count) {
+    __shared__ int s_n[4];
     const int v = blockIdx.x * 256 + threadIdx.x;
     const int u = (v < V) ? used[v] : 0;
     const unsigned long long b = __ballot(u);
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (lane == 0 && b) base = atomicAdd(counter, __popcll(b));
-    base = __shfl(base, 0);
+    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = __popcll(b);
+    __syncthreads();
+    if (threadIdx.x == 0) blk_count[blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+}
+
+__device__ __forceinline__ void gp_compact_kernel(int V, int cap, const int* __restrict__ used, const int* __restrict__ blk_count,
+                                                         int* __restrict__ row_of_token, int* __restrict__ tok_of_row,
+                                                         int* __restrict__ counter) {
+    __shared__ int s_red[256];
+    __shared__ int s_n[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int v = blockIdx.x * 256 + tid;
+    const int u = (v < V) ? used[v] : 0;
+    const unsigned long long b = __ballot(u);
+    int part = 0;
+    for (int k = tid; k < (int)blockIdx.x; k += 256) part += blk_count[k];
+    s_red[tid] = part;
+    if (lane == 0) s_n[wave] = __popcll(b);
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) s_red[tid] += s_red[tid + o];
+        __syncthreads();
+    }
+    int base = s_red[0];
+    for (int w2 = 0; w2 < wave; ++w2) base += s_n[w2];
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) *counter = s_red[0] + s_n[0] + s_n[1] + s_n[2] + s_n[3];
     if (v < V) {
         int row = -1;
         if (u) {
@@ -836,7 +872,7 @@ extern "C" int rbr_datt_global_gate_bwd(int32_t B, int32_t L, int32_t E, const i
 
 // ---- token-product local gate (same results as rbr_datt_local_gate_fwd / _bwd; `ws` must survive from forward to backward)
 namespace {
-struct GateProdLayout { size_t used, counter, row_of_token, tok_of_row, S, c, part, total; int cap, n_chunks; };
+struct GateProdLayout { size_t used, counter, row_of_token, tok_of_row, S, c, part, blk, total; int cap, n_chunks; };
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 bool gate_prod_layout(int B, int L, int E, int win, int V, GateProdLayout& G) {
     if (B <= 0 || L <= 0 || E <= 0 || V <= 0 || win <= 0 || win > kGateWP || win % 2 == 0) return false;
@@ -851,14 +887,15 @@ bool gate_prod_layout(int B, int L, int E, int win, int V, GateProdLayout& G) {
     G.S = o;            o += al256((size_t)G.cap * kGateWP * sizeof(float));
     G.c = o;            o += al256((size_t)G.cap * kGateWP * sizeof(float) * kGateCopies);
     G.part = o;         o += al256((size_t)G.n_chunks * ((size_t)win * E + 1) * sizeof(float));
+    G.blk = o;          o += al256((((size_t)V + 255) / 256) * sizeof(int));        // used tokens per 256 vocabulary entries
     G.total = o;
     return true;
 }
 }  // namespace
 
-// ---- distinct-token rows of a document batch, shared by the gates of one tower (layout: counter | used | row_of_token | tok_of_row)
+// ---- distinct-token rows of a document batch, shared by the gates of one tower (layout: counter | used | row_of_token | tok_of_row | block counts)
 namespace {
-struct TokenRowsLayout { size_t counter, used, row_of_token, tok_of_row, total; int cap; };
+struct TokenRowsLayout { size_t counter, used, row_of_token, tok_of_row, blk, total; int cap; };
 bool token_rows_layout(int B, int L, int V, TokenRowsLayout& T) {
     if (B <= 0 || L <= 0 || V <= 0) return false;
     T.cap = (int)std::min<long>(V, (long)B * L);
@@ -867,6 +904,7 @@ bool token_rows_layout(int B, int L, int V, TokenRowsLayout& T) {
     T.used = o;         o += al256((size_t)V * sizeof(int));      // contiguous with the counter: zeroed together
     T.row_of_token = o; o += al256((size_t)V * sizeof(int));
     T.tok_of_row = o;   o += al256((size_t)T.cap * sizeof(int));
+    T.blk = o;          o += al256((((size_t)V + 255) / 256) * sizeof(int));        // used tokens per 256 vocabulary entries
     T.total = o;
     return true;
 }
@@ -921,7 +959,8 @@ extern "C" int rbr_datt_local_gate_fwd_prod(int32_t B, int32_t L, int32_t E, int
     if (rows == nullptr) {               // the tower's shared maps (rbr_datt_token_rows) were not handed in: build private ones
         if (int e = zero_words(used, G.row_of_token - G.used, st)) return e;
         if (int e_ = rbr::launch<gp_mark_kernel, 256>(dim3((unsigned)std::min<long>((n_pos + 255) / 256, 2048)), dim3(256), 0, st, "datt gate mark launch", n_pos, ids64, used)) return e_;
-        if (int e_ = rbr::launch<gp_compact_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "datt gate compact launch", V, G.cap, used, reinterpret_cast<int*>(base + G.row_of_token), reinterpret_cast<int*>(base + G.tok_of_row), reinterpret_cast<int*>(base + G.counter))) return e_;
+        if (int e_ = rbr::launch<gp_count_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "datt gate count launch", V, (const int*)used, reinterpret_cast<int*>(base + G.blk))) return e_;
+        if (int e_ = rbr::launch<gp_compact_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "datt gate compact launch", V, G.cap, (const int*)used, (const int*)reinterpret_cast<int*>(base + G.blk), reinterpret_cast<int*>(base + G.row_of_token), reinterpret_cast<int*>(base + G.tok_of_row), reinterpret_cast<int*>(base + G.counter))) return e_;
     }
     if (int e_ = rbr::launch<gp_taps_kernel, 256>(dim3((unsigned)std::min((G.cap + 15) / 16, 4096)), dim3(256), 0, st, "datt gate taps launch", E, win, G.cap, counter, tok_of_row, table, w, S)) return e_;
     if (int e_ = rbr::launch<gp_gate_kernel, 256>(dim3((unsigned)std::min<long>((n_pos + 255) / 256, 8192)), dim3(256), 0, st, "datt gate gather launch", B, L, win, ids64, row_of_token, S, b0, gate)) return e_;
@@ -977,7 +1016,8 @@ extern "C" int rbr_datt_token_rows(int32_t B, int32_t L, int32_t V, const int64_
     if (int e = zero_words(counter, T.row_of_token - T.counter, st)) return e;
     const long n_pos = (long)B * L;
     if (int e_ = rbr::launch<gp_mark_kernel, 256>(dim3((unsigned)std::min<long>((n_pos + 255) / 256, 2048)), dim3(256), 0, st, "token rows mark launch", n_pos, reinterpret_cast<const long long*>(ids), used)) return e_;
-    if (int e_ = rbr::launch<gp_compact_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "token rows compact launch", V, T.cap, used, reinterpret_cast<int*>(base + T.row_of_token), reinterpret_cast<int*>(base + T.tok_of_row), counter)) return e_;
+    if (int e_ = rbr::launch<gp_count_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "token rows count launch", V, (const int*)used, reinterpret_cast<int*>(base + T.blk))) return e_;
+    if (int e_ = rbr::launch<gp_compact_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "token rows compact launch", V, T.cap, (const int*)used, (const int*)reinterpret_cast<int*>(base + T.blk), reinterpret_cast<int*>(base + T.row_of_token), reinterpret_cast<int*>(base + T.tok_of_row), counter)) return e_;
     return 0;
 }
 
