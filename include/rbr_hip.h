@@ -319,6 +319,8 @@ typedef struct rbr_head_grads {
     float* dub; float* dib;
 } rbr_head_grads;
 
+/* pred = (relu(ul * il) * drop) @ h + ub[u_id] + ib[i_id] + g.  A NaN latent passes the ReLU (torch.relu(NaN) is NaN): the
+ * predictions of the pairs that read it are NaN, as the reference's are, instead of a finite value. */
 int rbr_pair_head_fwd(int32_t B, int32_t H, int32_t K, const float* u_feat, const float* i_feat,
                       const int64_t* u_id, const int64_t* i_id, const rbr_head_params* p, const float* drop,
                       float* ul, float* il, float* pred, void* stream);
@@ -503,7 +505,8 @@ int rbr_datt_global_gate_bwd_rows(int32_t B, int32_t L, int32_t E, int32_t V, co
  *      (`relu`: 0 none, 1 ReLU, 2 Tanh -- SimpleSiamese's latent_transform_layer, simple_siamese.py:24-26)
  *      replaces D-ATT's shared fc (dual_att/dual_att.py:31-35,51,57) and HierPooling's projection
  *      (deepconn/layers.py:76-79,96).  x [N,IN], W [OUT,IN] (torch layout), b [OUT] or NULL,
- *      drop [N,OUT] multiplier or NULL, y [N,OUT].
+ *      drop [N,OUT] multiplier or NULL, y [N,OUT].  A NaN pre-activation passes the ReLU (torch.relu(NaN) is NaN), in the
+ *      one-slice and in the split-K epilogue: a row of x that holds a NaN gives a NaN row of y.
  *      Backward: d_x [N,IN] (NULL to skip), dW [OUT,IN], db [OUT] (NULL to skip) overwritten;
  *      ws: rbr_linear_bwd_ws_floats(N, OUT) floats.                                           ---- */
 int rbr_linear_fwd(int32_t N, int32_t IN, int32_t OUT, const float* x, const float* W, const float* b, int32_t relu,
@@ -716,7 +719,9 @@ int rbr_additive_attn_bwd(int32_t B, int32_t R, int32_t H, int32_t K, const floa
  *      optimizer of :135: lr only, betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad), two launches over all
  *      tensors.  params / grads / exp_avg / exp_avg_sq: HOST arrays of n_tensors device pointers (fp32, contiguous,
  *      numel[k] elements each).  `step`: device float holding the number of steps taken so far; it is advanced by one
- *      and the bias corrections use the new value.  max_norm <= 0 skips the clipping.  The gradients are left clipped
+ *      and the bias corrections use the new value.  max_norm <= 0 skips the clipping.  A NaN norm gives a NaN clip coefficient
+ *      (torch.clamp(nan, max=1) is NaN, as in clip_grad_norm_): every gradient and parameter of the call becomes NaN; an
+ *      infinite norm gives coefficient 0.  The gradients are left clipped
  *      (as clip_grad_norm_ leaves them), *gnorm_out (device, may be NULL) receives the norm before clipping.
  *      ws: rbr_clip_adam_ws_floats() floats.                                                             ---- */
 #define RBR_OPT_MAX_TENSORS 64

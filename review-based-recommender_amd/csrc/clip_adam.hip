@@ -145,8 +145,10 @@ __global__ __launch_bounds__(256) void clip_adam_kernel(const OptTable T, long n
     for (int i = threadIdx.x; i < npartials; i += 256) ps += partials[i];
     const float total = sqrtf(block_sum(ps, s_red));
     if (blockIdx.x == 0 && threadIdx.x == 0 && gnorm_out != nullptr) *gnorm_out = total;
-    // clip_grad_norm_: coef = clamp(max_norm / (total + 1e-6), max = 1)
-    const float coef = (max_norm > 0.f) ? fminf(max_norm / (total + 1e-6f), 1.f) : 1.f;
+    // clip_grad_norm_: coef = clamp(max_norm / (total + 1e-6), max = 1).  Not fminf: it would answer 1 for a NaN norm, where
+    // torch.clamp keeps the NaN (every gradient and parameter then becomes NaN: a diverged step shows instead of passing unclipped)
+    const float ratio = max_norm / (total + 1e-6f);
+    const float coef = (max_norm > 0.f) ? ((ratio > 1.f) ? 1.f : ratio) : 1.f;
     const bool clipped = coef != 1.f;          // workgroup-uniform
     // The compact rows are NOT re-written clipped (round 7): nobody reads them as rows, and the store was 4 of this kernel's ~32
     // vector-memory instructions per thread and chunk.  Whoever makes them dense later multiplies by the coefficient left here

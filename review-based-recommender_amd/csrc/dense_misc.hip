@@ -159,7 +159,7 @@ __device__ __forceinline__ void gemm_body(const GemmJob& J, const int bx, const 
         const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (m < M) {
             float v = acc[r] + bv;
-            if (ep.relu == 1) v = fmaxf(v, 0.f);
+            if (ep.relu == 1) v = (v < 0.f) ? 0.f : v;        // not fmaxf: it would turn NaN into 0 (torch.relu(NaN) is NaN)
             else if (ep.relu == 2) v = tanhf(v);
             if (ep.mul) v *= ep.mul[(long)m * N + n];
             C[(long)m * ldc + n] = v;
@@ -241,7 +241,7 @@ __device__ __forceinline__ void gemm_reduce_body(const ReduceJob& J, const int b
         const int m = m0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         if (m < M) {
             float v = acc[r] + bv;
-            if (ep.relu == 1) v = fmaxf(v, 0.f);
+            if (ep.relu == 1) v = (v < 0.f) ? 0.f : v;        // not fmaxf: it would turn NaN into 0 (torch.relu(NaN) is NaN)
             else if (ep.relu == 2) v = tanhf(v);
             C[(long)m * ldc + n] = v * mulv[r];
         }

@@ -140,7 +140,8 @@ __device__ __forceinline__ float head_pair(int b, int B, int H, int K, const flo
         }
         __syncthreads();
         if (t < 32 && k < K) {
-            float z = fmaxf(s_l[0][kk] * s_l[1][kk], 0.f);
+            const float prod = s_l[0][kk] * s_l[1][kk];
+            float z = (prod < 0.f) ? 0.f : prod;                 // not fmaxf: it would turn NaN into 0 (torch.relu(NaN) is NaN)
             float m = 1.f;
             if (tr.p_drop > 0.f) {       // the draw rbr_dropout_multiplier would make for element (b, k) of this call
                 const unsigned long long e = (unsigned long long)b * K + k;

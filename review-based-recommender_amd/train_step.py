@@ -50,7 +50,17 @@ class HipClipAdam(torch.optim.Optimizer):
 
     Same update rule and state names as torch.optim.Adam (amsgrad / weight_decay / maximize unsupported, as the
     reference trainers never set them); `state_dict()` interchanges with it.  The step counter lives on the device,
-    so `clip_and_step` can be recorded into a hipGraph.  Parameters must be contiguous fp32 HIP tensors."""
+    so `clip_and_step` can be recorded into a hipGraph.  Parameters must be contiguous fp32 HIP tensors.
+
+    Step counts are per parameter, as torch.optim.Adam's: a parameter counts the steps on which it had a gradient.  The
+    tensors of one launch pair share ONE device counter, so only tensors that have stepped together since their state was
+    created (or that a checkpoint loaded with equal counts) go into one pair.  When every parameter has a gradient on every
+    step -- the trainers' case -- that is one pair and one counter, as recorded by GraphedTrainStep.  A parameter whose first
+    gradient arrives later starts a counter of its own at 0 (its first update uses t = 1 whatever the others' count is), and
+    a parameter that sits a step out keeps its count while the others take a copy of the counter and move on; either way
+    the step then takes one launch pair per distinct count, and with more than one pair the norm and the clipping are
+    torch's clip_grad_norm_ (device-side) in front of unclipped pairs.  load_state_dict reads the loaded counts once (a
+    host synchronisation) to put equal counts of a parameter group on one counter."""
 
     MAX_TENSORS = 64      # RBR_OPT_MAX_TENSORS
 
@@ -140,13 +150,30 @@ class HipClipAdam(torch.optim.Optimizer):
         self._row_grads.clear()
         super().zero_grad(set_to_none=set_to_none)
 
-    def _state_of(self, p):
-        st = self.state[p]
-        if not st:
-            st["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
-            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        return st
+    def _counter_of(self, p):
+        st = self.state.get(p)
+        return st["step"] if st else None
+
+    def _shared_counter(self, ps):
+        """The device step counter of one launch pair.  `ps` hold one counter already, or have no state yet: their state is
+        created around a fresh counter at 0 (torch.optim.Adam's lazy state: the count starts with the first gradient).  A counter
+        that tensors outside `ps` hold as well -- they have no gradient on this step, or lie beyond the 64 tensors of a pair --
+        must not advance for them: `ps` move on with a copy."""
+        step = self._counter_of(ps[0])
+        if step is None:
+            step = torch.zeros((), dtype=torch.float32, device=ps[0].device)
+            for p in ps:
+                st = self.state[p]
+                st["step"] = step
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            return step
+        mine = {id(p) for p in ps}
+        if any(st.get("step") is step and id(q) not in mine for q, st in self.state.items()):
+            step = step.clone()
+            for p in ps:
+                self.state[p]["step"] = step
+        return step
 
     @torch.no_grad()
     def clip_and_step(self, max_grad_norm: float | None = None) -> torch.Tensor:
@@ -165,14 +192,20 @@ class HipClipAdam(torch.optim.Optimizer):
             self._ws = torch.empty(L_.rbr_clip_adam_ws_floats(), dtype=torch.float32, device=dev)
             self._gnorm = torch.zeros((), dtype=torch.float32, device=dev)
         st = _lib.current_stream()
-        # one launch pair per parameter group and per 64 tensors; the common case (17 tensors, one group) is one pair.
+        # one launch pair per parameter group, per step counter (the tensors of a pair share one: the class docstring) and per 64
+        # tensors; the common case (17 tensors, one group, always stepping together) is one pair.
         # With several pairs the norm must still be global: a first sweep with lr = 0 would be wasteful, so more than
         # one pair is only allowed without clipping.
         batches = []
         for g in self.param_groups:
-            ps = [p for gg, p in todo if gg is g]
-            for k in range(0, len(ps), self.MAX_TENSORS):
-                batches.append((g, ps[k:k + self.MAX_TENSORS]))
+            by_counter = {}               # id of the counter (None: no state yet) -> its tensors, in parameter order
+            for gg, p in todo:
+                if gg is g:
+                    c = self._counter_of(p)
+                    by_counter.setdefault(None if c is None else id(c), []).append(p)
+            for ps in by_counter.values():
+                for k in range(0, len(ps), self.MAX_TENSORS):
+                    batches.append((g, ps[k:k + self.MAX_TENSORS]))
         if self._row_grads and (len(batches) > 1 or len(self._row_grads) > 1):
             self.materialize_grads()          # one compact table per launch pair: anything else takes the dense path
         if len(batches) > 1 and max_grad_norm is not None:
@@ -182,12 +215,11 @@ class HipClipAdam(torch.optim.Optimizer):
             gn = nn.utils.clip_grad_norm_([p for _, p in todo], max_grad_norm)
             self._gnorm.copy_(gn)
             max_grad_norm = None
+        elif len(batches) > 1:            # no pair sees every gradient: the returned norm is torch's as well
+            self._gnorm.copy_(torch.linalg.vector_norm(torch.stack(torch._foreach_norm([p.grad for _, p in todo]))))
         for g, ps in batches:
-            states = [self._state_of(p) for p in ps]
-            step = states[0]["step"]
-            for s_ in states[1:]:          # the tensors of a batch step together: one shared device counter
-                if s_["step"] is not step:
-                    s_["step"] = step
+            step = self._shared_counter(ps)
+            states = [self.state[p] for p in ps]
             grads = [p.grad for p in ps]          # None for the table whose gradient is in row form
             for p, gr in zip(ps, grads):
                 if not (p.is_contiguous() and (gr is None or gr.is_contiguous())):
@@ -232,10 +264,17 @@ class HipClipAdam(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        for st in self.state.values():      # torch.optim.Adam checkpoints hold a CPU float / int step
-            if "step" in st and (not torch.is_tensor(st["step"]) or not st["step"].is_cuda):
-                dev = st["exp_avg"].device
-                st["step"] = torch.as_tensor(float(st["step"]), dtype=torch.float32, device=dev)
+        # torch.optim.Adam checkpoints hold a step per parameter (a CPU float / int, or a tensor each): equal counts of a group
+        # go onto one device counter, so that the group is one launch pair again; reading them is a host synchronisation
+        for g in self.param_groups:
+            shared = {}
+            for p in g["params"]:
+                st = self.state.get(p)
+                if st and "step" in st:
+                    key = (float(st["step"]), st["exp_avg"].device)
+                    if key not in shared:
+                        shared[key] = torch.as_tensor(key[0], dtype=torch.float32, device=key[1])
+                    st["step"] = shared[key]
 
 
 def train_step(model: nn.Module, optimizer: torch.optim.Optimizer, batch, ratings: torch.Tensor,
