@@ -300,7 +300,26 @@ int rbr_textcnn_bwd(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t
                     const float* d_feat, float* const* dW, float* const* dbias, float* dtable, float* dgate,
                     float* ws, void* stream);
 
-/* ---- Rating head: LastFeat x2 + FM  (deepconn/layers.py:156-165,189-209; narre.py:84-93,118-137)
+/* Explaining a score: per-position contributions (gradient x input) of the encoder, with the max-pool routing held fixed.  For
+ * a gradient d_feat [n_docs, C] on the pooled features (feat / argmax [n_docs, C] as rbr_textcnn_pool_finalize left them):
+ *   sal[doc, t] = sum over banks w, channels c of w and taps j < kz[w] with pos(argmax[doc,c], j) == t of
+ *                 d_feat[doc,c] * act'(feat[doc,c]) * mask[doc,t] * gate[doc,t] * <table[ids[doc,t], :], W[w][c, :, j]>
+ *   pos(p, j) = p + j - (kz[w]-1)/2 (RBR_PAD_SAME), p + j (RBR_PAD_VALID); act' = [feat > 0] (ReLU), 1 - feat^2 (tanh): the gates
+ *   rbr_textcnn_bwd applies.  That is <d score / d x[doc,t,:], x[doc,t,:]> for the embedded, masked, gated rows x, so for ReLU
+ *   sum_t sal[doc,t] = sum over c with feat > 0 of d_feat[doc,c] * (feat[doc,c] - bias[c]).
+ * A tap outside [0, L) is the zero padding, a masked position contributes exactly 0, an argmax outside the pooled range
+ * contributes nothing and is never used as an index; padding_idx plays no part (the sum is over the rows, not the table).
+ * sal [n_docs, L] is OVERWRITTEN: every element is written once with a plain store, 0.0f where no window lands.  One launch, one
+ * workgroup per document, no atomics: a document's row has the same bits on every run and in every batch.  Needs no forward
+ * workspace and does not depend on the conv mode or RBR_PROD_*; W is the HOST array of the torch-layout conv weights.
+ * mask / gate may be NULL; n_docs == 0 returns 0 without a launch; RBR_CONV_GATE_SPLIT: RBR_ERR_UNSUPPORTED.
+ * Reference counterpart: none (the reference computes NARRE's attention scores and drops them, narre.py:177-192; it has no
+ * token-level attribution). */
+int rbr_textcnn_saliency(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* gate,
+                         const float* table, const float* const* W, const float* feat, const int32_t* argmax,
+                         const float* d_feat, float* sal, void* stream);
+
+/* ---- Rating head: LastFeat x2 + FM (deepconn/layers.py:156-165,189-209; narre.py:84-93,118-137)
  *   ul = u_feat @ Wu + bu + Eu[u_id];  il = i_feat @ Wi + bi + Ei[i_id]
  *   pred = (relu(ul*il) * drop) @ h + ub[u_id] + ib[i_id] + g
  * drop [B,K] is the dropout multiplier (0 or 1/(1-p)) drawn by the caller; NULL = no dropout.

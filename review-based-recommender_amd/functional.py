@@ -797,6 +797,37 @@ def textcnn_product_applies(table: torch.Tensor, ids: torch.Tensor, weights: Seq
     return bool(table.is_cuda and L_.rbr_textcnn_fwd_ws_bytes(C.byref(desc)) > 0 and L_.rbr_textcnn_bwd_prod_ws_bytes(C.byref(desc)) > 0)
 
 
+def textcnn_saliency(table: torch.Tensor, ids: torch.Tensor, mask: Optional[torch.Tensor], weights: Sequence[torch.Tensor],
+                     feat: torch.Tensor, argmax: torch.Tensor, d_feat: torch.Tensor, *, gate=None, pad_mode: int = PAD_SAME,
+                     act: int = ACT_RELU, gate_split: int = 0) -> torch.Tensor:
+    """sal [n_docs, L]: what every token position contributes to a score whose gradient on the pooled features of textcnn() is
+    d_feat [n_docs, C] -- gradient x input of the embedded, masked, gated rows with the max-pool routing (feat / argmax
+    [n_docs, C], as textcnn(return_argmax=True) returned them) held fixed; rbr_textcnn_saliency in rbr_hip.h has the formula.
+    One launch, no autograd, no embedded rows are materialised; a document's row is bit-identical in every batch.
+    gate_split: a split gate (see textcnn) is refused by the library."""
+    table_c, ids, mask8, ws, desc = _conv_operands(table, ids, mask, weights, pad_mode, act, None,
+                                                   _lib.conv_gate_split(gate_split) if gate_split else 0)
+    n_docs, L = ids.shape
+    Ctot = sum(int(w.shape[0]) for w in ws)
+    for w in ws:
+        if w.dim() != 3 or w.shape[1] != table_c.shape[1]:
+            raise RuntimeError(f"conv weights must be [C_w, D = {table_c.shape[1]}, kz_w], got {tuple(w.shape)}")
+    feat, argmax, d_feat = feat.detach().contiguous(), argmax.contiguous(), d_feat.detach().contiguous()
+    for t, name in ((feat, "feat"), (argmax, "argmax"), (d_feat, "d_feat")):
+        if tuple(t.shape) != (n_docs, Ctot):
+            raise RuntimeError(f"{name} must be [n_docs, C] = {(n_docs, Ctot)}, got {tuple(t.shape)}")
+    if gate is not None:
+        gate = gate.detach().contiguous()
+        if gate.shape != ids.shape:
+            raise RuntimeError(f"gate must be [n_docs, L] = {tuple(ids.shape)}, got {tuple(gate.shape)}")
+    ptrs = (dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"), dev_ptr(gate, F32, "gate"), dev_ptr(table_c.detach(), F32, "word table"),
+            ptr_array([w.detach() for w in ws], F32, "conv weight"), dev_ptr(feat, F32, "feat"), dev_ptr(argmax, I32, "argmax"),
+            dev_ptr(d_feat, F32, "d_feat"))
+    sal = torch.empty(n_docs, L, dtype=F32, device=table_c.device)
+    _call("textcnn_saliency", _lib.lib().rbr_textcnn_saliency, C.byref(desc), *ptrs, dev_ptr(sal, F32, "sal"), current_stream())
+    return sal
+
+
 _HEAD_NAMES = ("Wu", "bu", "Eu", "Wi", "bi", "Ei", "h", "g", "ub", "ib")
 _HEAD_ACC = ("Eu", "Ei", "ub", "ib")       # gradients accumulated with atomics (rows addressed by id)
 

@@ -113,6 +113,34 @@ class DeepCoNNpp(nn.Module):
         """The item tower's counterpart of encode_users (deepconn.py:47,49)."""
         return self._encode_side(i_revs, i_rev_masks, i_ids, self.item_feat)
 
+    # ---- why a pair scored as it did: per-token contributions of one tower (recommend.Recommender.explain)
+    def _explain_side(self, docs, masks, d_latent, last):
+        if self.ngram.arch != "CNN":
+            raise ValueError("explain_users / explain_items cover DeepCoNN++ and NARRE with arch='CNN' (the TextCNN's max-pool "
+                             f"routing is what they read); arch={self.ngram.arch!r} is not covered")
+        with RF.eval_mode(self):
+            pad = self.word_embeddings.padding_idx
+            if self.validate_ids:
+                (docs,) = RF.sanitize_ids([(docs, self.vocab_size, pad)])
+            conv, table = self.ngram.feature_layer[0], self.word_embeddings.weight
+            docs, masks = docs.contiguous(), masks.contiguous()
+            feat, argmax = RF.textcnn(table, docs, masks, conv.weights(), conv.biases(), padding_idx=pad, return_argmax=True)
+            g = RF.linear(d_latent, last.W)                    # d score / d feat = d_latent @ W^T  [n, H]
+            tokens = RF.textcnn_saliency(table, docs, masks, conv.weights(), feat, argmax, g)
+            return tokens, (g * feat).sum(1)
+
+    def explain_users(self, u_revs, u_rev_masks, u_ids, d_latent):
+        """encode_users' arguments plus d_latent [n, latent_dim] = d score / d (the users' latent rows) -> (tokens [n, doc_len],
+        text [n]) in eval semantics, no autograd.  tokens[n, t] is gradient x input of position t's embedded row with the
+        max-pool routing held fixed (functional.textcnn_saliency); text[n] = <d score / d feat, feat> is what the document as a
+        whole adds to the score through LastFeat's W, so that tokens.sum(1) = text - sum over the channels with feat > 0 of
+        g * conv bias.  The id embedding's share of the latent row is not text and is not attributed.  CNN arch only."""
+        return self._explain_side(u_revs, u_rev_masks, d_latent, self.user_feat)
+
+    def explain_items(self, i_revs, i_rev_masks, i_ids, d_latent):
+        """The item tower's counterpart of explain_users."""
+        return self._explain_side(i_revs, i_rev_masks, d_latent, self.item_feat)
+
     def score_mode_and_params(self):
         """(mode, h, g, ub, ib) of functional.pair_score*: the FM head over the two latent rows (layers.py:189-209)."""
         fm = self.fm

@@ -116,6 +116,12 @@ class DualAtt(nn.Module):
         """The item tower's counterpart of encode_users (dual_att.py:52-57)."""
         return self._encode_side(i_docs, self.i_local_atten, self.i_global_atten)
 
+    def explain_users(self, *args, **kwargs):
+        """Not covered: the token-level explanation reads the un-gated TextCNN's max-pool routing."""
+        raise ValueError("explain_users / explain_items cover DeepCoNN++ and NARRE with arch='CNN'; D-ATT is not covered")
+
+    explain_items = explain_users
+
     def score_mode_and_params(self):
         """(mode, h, g, ub, ib) of functional.pair_score*: the plain inner product of the two latent rows (dual_att.py:58)."""
         return "dot", None, None, None, None

@@ -112,6 +112,42 @@ class NARRE(nn.Module):
         """The item tower's counterpart of encode_users (reiid: user ids of the item's reviews)."""
         return self._encode_side(i_text, i_text_masks, i_id, reiid, self.item_size, self.user_size, self.item_att, self.item_feat)
 
+    # ---- why a pair scored as it did: per-review and per-token contributions of one tower (recommend.Recommender.explain)
+    def _explain_side(self, text, masks, other_id, other_rows, att, last, d_latent):
+        if self.ngram.arch != "CNN":
+            raise ValueError("explain_users / explain_items cover DeepCoNN++ and NARRE with arch='CNN' (the TextCNN's max-pool "
+                             f"routing is what they read); arch={self.ngram.arch!r} is not covered")
+        with RF.eval_mode(self):
+            n, R, T, H = text.shape[0], self.doc_num, self.doc_len, self.hiddem_dim
+            wp = self.word_embeddings.padding_idx
+            text, masks = text.reshape(-1, T), masks.reshape(-1, T)
+            if self.validate_ids:
+                text, other_id = RF.sanitize_ids([(text, self.vocab_size, wp), (other_id, other_rows, att.padding_idx)])
+            conv, table = self.ngram.feature_layer[0], self.word_embeddings.weight
+            text, masks = text.contiguous(), masks.contiguous()
+            feat, argmax = RF.textcnn(table, text, masks, conv.weights(), conv.biases(), padding_idx=wp, return_argmax=True)
+            _, a = att(feat.view(n, R, H), other_id)
+            a = a.view(n, R)
+            g = RF.linear(d_latent, last.W)                                   # d score / d pooled = d_latent @ W^T  [n, H]
+            reviews = a * (g.unsqueeze(1) * feat.view(n, R, H)).sum(-1)
+            d_feat = (a.unsqueeze(-1) * g.unsqueeze(1)).reshape(n * R, H)      # attention weights held constant
+            tokens = RF.textcnn_saliency(table, text, masks, conv.weights(), feat, argmax, d_feat).view(n, R, T)
+            return tokens, reviews.sum(1), a, reviews
+
+    def explain_users(self, u_text, u_text_masks, u_id, reuid, d_latent):
+        """encode_users' arguments plus d_latent [n, latent_dim] = d score / d (the users' latent rows) -> (tokens [n, doc_num,
+        doc_len], text [n], att [n, doc_num], reviews [n, doc_num]) in eval semantics, no autograd.
+        The attention weights att are HELD CONSTANT -- the NARRE paper's reading of att as the usefulness of a review: with
+        g = d score / d (pooled feature), review r contributes reviews[n, r] = att[n, r] * <g, feat[n, r]>, text = reviews.sum(1),
+        and tokens[n, r, t] is gradient x input of the token's embedded row under the gradient att[n, r] * g on the review's
+        pooled features, max-pool routing fixed (functional.textcnn_saliency).  How the score would move through a change of
+        att itself is not attributed.  CNN arch only."""
+        return self._explain_side(u_text, u_text_masks, reuid, self.item_size, self.user_att, self.user_feat, d_latent)
+
+    def explain_items(self, i_text, i_text_masks, i_id, reiid, d_latent):
+        """The item tower's counterpart of explain_users (reiid: user ids of the item's reviews)."""
+        return self._explain_side(i_text, i_text_masks, reiid, self.user_size, self.item_att, self.item_feat, d_latent)
+
     def score_mode_and_params(self):
         """(mode, h, g, ub, ib) of functional.pair_score*: the FM head over the two latent rows (narre.py:112-137)."""
         fm = self.fm

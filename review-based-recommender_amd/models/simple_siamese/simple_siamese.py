@@ -92,6 +92,12 @@ class SimpleSiamese(nn.Module):
         """The item tower's counterpart of encode_users."""
         return self._encode_side(i_revs, i_rev_word_masks, i_rev_masks, i_ids, self.item_last_feat_layer)
 
+    def explain_users(self, *args, **kwargs):
+        """Not covered: the token-level explanation reads a TextCNN's max-pool routing, and this model has no conv."""
+        raise ValueError("explain_users / explain_items cover DeepCoNN++ and NARRE with arch='CNN'; SimpleSiamese is not covered")
+
+    explain_items = explain_users
+
     def score_mode_and_params(self):
         """(mode, h, g, ub, ib) of functional.pair_score*: FM, or FMWithoutUIBias (ub = ib = None) without use_ui_bias."""
         fm = self.fm

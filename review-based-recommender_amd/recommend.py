@@ -15,6 +15,10 @@ its documents (models/deepconn/deepconn.py:43-53) and has no ranking entry at al
 
 The output file holds one JSON line per user id 1 .. U-1 (id 0 is the padding id of both sides: never a user, never recommended):
     {"user": u, "items": [...], "scores": [...]}
+With --explain N every line also carries "why", one entry per recommended item (DeepCoNN++ and NARRE, CNN arch): the N tokens of
+the user's and of the item's text that moved the score most, as [position, token, weight] (words where meta.pkl's vocabulary is
+readable, else token ids; NARRE: position = review slot * rv_len + position in the review), and for NARRE the item's N
+weightiest reviews as [slot, id of the review's author, attention weight, contribution] (Recommender.explain).
 With --eval-split the (user, item) pairs of that split are ranked instead (as well, when --out is given too) and one JSON line of
 rank_metrics goes to --metrics-out, or to stdout.
 """
@@ -38,6 +42,33 @@ class SeenItems(NamedTuple):
     """Items every USER ID has already rated, CSR over all user ids: off int64 [U + 1], items int32 sorted within a user."""
     off: torch.Tensor
     items: torch.Tensor
+
+
+class Explanation(NamedTuple):
+    """Recommender.explain: why the pairs (u_ids[b], i_ids[b]) scored as they did.  tokens: DeepCoNN++ [B, doc_len], NARRE
+    [B, rv_num, rv_len]; the four review fields are None for DeepCoNN++ (its towers read one document each)."""
+    score: torch.Tensor                                   # [B] = Recommender.score
+    user_tokens: torch.Tensor                             # contribution of every token position of the user's text
+    item_tokens: torch.Tensor
+    user_text: torch.Tensor                               # [B] what the user's text as a whole adds to the score
+    item_text: torch.Tensor
+    user_review_weights: Optional[torch.Tensor] = None    # [B, rv_num] NARRE's attention weights
+    user_reviews: Optional[torch.Tensor] = None           # [B, rv_num] contribution of every review; sums to user_text
+    item_review_weights: Optional[torch.Tensor] = None
+    item_reviews: Optional[torch.Tensor] = None
+
+
+def top_tokens(tokens: torch.Tensor, docs: torch.Tensor, n: int):
+    """(position int64 [rows, n'], token id [rows, n'], weight [rows, n']) of the n' = min(n, positions) entries of largest
+    |weight| in every row of tokens [rows, ...] (trailing dimensions are flattened: a NARRE position is slot * rv_len + t),
+    |weight| descending, ties by the lower position; docs holds the token ids, same shape."""
+    if n < 1:
+        raise ValueError("top_tokens needs n >= 1")
+    if tokens.shape != docs.shape:
+        raise ValueError(f"tokens and docs must have one shape, got {tuple(tokens.shape)} / {tuple(docs.shape)}")
+    w, d = tokens.reshape(tokens.shape[0], -1), docs.reshape(docs.shape[0], -1)
+    pos = torch.sort(w.abs(), dim=1, descending=True, stable=True).indices[:, :min(int(n), w.shape[1])]
+    return pos, torch.gather(d, 1, pos), torch.gather(w, 1, pos)
 
 
 def rank_metrics(rank: torch.Tensor, n_cand: torch.Tensor, ks) -> dict:
@@ -196,6 +227,49 @@ class Recommender:
             exclude = (exclude.off, exclude.items, u_ids)
         return RF.pair_score_rank(mode, rows, il, i_ids, h, g, ub_rows, ib, item_lo=self.item_lo, exclude=exclude)
 
+    def _explain_side(self, side: str, ids: torch.Tensor, d_latent: torch.Tensor):
+        """The model's explain_users / explain_items on the cache rows of `ids` (checked ids), read as _encode reads them."""
+        c, m = self.cache, self.model
+        docs = (c.user if side == "user" else c.item).index_select(0, ids).to(torch.int64).contiguous()
+        fn = m.explain_users if side == "user" else m.explain_items
+        if self.kind == "deepconn":
+            return fn(docs, docs != PAD, ids, d_latent)
+        rids = (c.user_rids if side == "user" else c.item_rids).index_select(0, ids)
+        return fn(docs, docs != PAD, ids, rids, d_latent)
+
+    def explain(self, u_ids: torch.Tensor, i_ids: torch.Tensor, chunk: int = 256) -> Explanation:
+        """Why the pairs (u_ids[b], i_ids[b]) scored as they did (DeepCoNN++ and NARRE, CNN arch), `chunk` pairs at a time, from
+        the latent tables and the cache rows; eval semantics, no autograd, the model's mode is restored.
+        With zu, zi the pair's latent rows the FM head is score = relu(zu * zi) . h + biases, so d score / d zu =
+        h * [zu * zi > 0] * zi (and zu for the item side); each tower turns that gradient into gradient x input of its own text
+        (the models' explain_users / explain_items): *_tokens per token position, *_text per side, and for NARRE *_reviews per
+        review under the attention weights *_review_weights, which are held constant.  The id embeddings and the biases are the
+        part of the score no text explains."""
+        if self.kind not in ("deepconn", "narre"):
+            raise ValueError(f"Recommender.explain covers DeepCoNN++ and NARRE with arch='CNN'; {type(self.model).__name__} is not covered")
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
+            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+        ul, il = self._tables()
+        _, h, _, _, _ =self.model.score_mode_and_params()
+        score = self.score(u_ids, i_ids)
+        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
+        with torch.no_grad():
+            zu, zi = RF.embedding(ul, u_ids, None), RF.embedding(il, i_ids, None)
+            live = h.detach().view(1, -1) * (zu * zi > 0)
+            d_u, d_i = live * zi, live * zu
+        parts = []
+        for a in range(0, u_ids.shape[0], chunk):
+            parts.append(self._explain_side("user", u_ids[a:a + chunk], d_u[a:a + chunk]) +
+                         self._explain_side("item", i_ids[a:a + chunk], d_i[a:a + chunk]))
+        cols = [torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts)]
+        if self.kind == "deepconn":
+            ut, ux, it, ix = cols
+            return Explanation(score, ut, it, ux, ix)
+        ut, ux, ua, ur, it, ix, ia, ir = cols
+        return Explanation(score, ut, it, ux, ix, ua, ur, ia, ir)
+
     def evaluate(self, pairs, ks=(5, 10, 20), exclude=None, chunk: int = 4096) -> dict:
         """rank_metrics of held-out pairs: `pairs` is a dataset's examples (sequences starting (u_id, i_id, ...)) or the id
         tensors (u_ids, i_ids) themselves.  Ranked `chunk` pairs at a time, one rank_metrics call over all of them; `exclude`: a
@@ -241,6 +315,8 @@ def parse_cli(argv=None):
     ap.add_argument("--eval-split", choices=["valid", "test"], help="rank this split's held-out (user, item) pairs: HR / NDCG / MRR / AUC")
     ap.add_argument("--ks", help="cut-offs K of hr@K / ndcg@K with --eval-split, comma-separated (default 5,10,20)")
     ap.add_argument("--metrics-out", help="file for the one JSON line of metrics of --eval-split (default: stdout)")
+    ap.add_argument("--explain", type=int, metavar="N", help="with --out: add \"why\" to every line, the N weightiest tokens (and, "
+                    "for NARRE, reviews) behind each recommended item; deepconn and narre only")
     ap.add_argument("--chunk", type=int, default=256, help="ids encoded / users ranked per launch")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--reference-quirks", action="store_true", help="as for the trainer: kernel_sizes=[3] (NARRE hidden_dim=150)")
@@ -249,6 +325,13 @@ def parse_cli(argv=None):
         ap.error("--k must be in 1..128")
     if a.chunk < 1:
         ap.error("--chunk must be at least 1")
+    if a.explain is not None:
+        if a.explain < 1:
+            ap.error("--explain must be at least 1")
+        if a.out is None:
+            ap.error("--explain adds to the lines of --out: give --out")
+        if a.model not in ("deepconn", "narre"):
+            ap.error("--explain covers deepconn and narre")
     if a.eval_split is None:
         if a.out is None:
             ap.error("--out is required unless --eval-split is given")
@@ -261,6 +344,49 @@ def parse_cli(argv=None):
     if any(not 1 <= k < 2 ** 31 for k in a.ks):
         ap.error("every K of --ks must be in 1..2^31-1")
     return a
+
+
+def _vocabulary(data_dir):
+    """token id -> word from meta.pkl's indexlizer (_vocab._token2id), or None where it cannot be read."""
+    from . import data as D
+    try:
+        ix = D.load_pickle(os.path.join(data_dir, "meta.pkl"))["indexlizer"]
+        t2i = getattr(getattr(ix, "_vocab", ix), "_token2id", None)
+        return {int(i): str(t) for t, i in t2i.items()} if isinstance(t2i, dict) else None
+    except Exception:
+        return None
+
+
+def _why(rec, u_ids, items, n, words):
+    """The "why" lists of --explain for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill)."""
+    dev = u_ids.device
+    keep = items >= 0
+    rows, cols = keep.nonzero(as_tuple=True)
+    why = [[None] * int(keep[r].sum()) for r in range(items.shape[0])]
+    if rows.numel() == 0:
+        return why
+    pu, pi = u_ids[rows.to(dev)], items[rows, cols].to(dev)
+    ex = rec.explain(pu, pi)
+    c = rec.cache
+    word = (lambda t: words.get(int(t), int(t))) if words else int
+
+    def tops(tokens, docs):
+        pos, tok, w = (t.cpu() for t in top_tokens(tokens, docs.to(torch.int64), n))
+        return [[[int(p), word(t), float(x)] for p, t, x in zip(pr, tr, wr) if x != 0.0] for pr, tr, wr in zip(pos, tok, w)]
+
+    ut, it = tops(ex.user_tokens, c.user.index_select(0, pu)), tops(ex.item_tokens, c.item.index_select(0, pi))
+    rv = None
+    if ex.item_reviews is not None:
+        slot, rid, contrib = (t.cpu() for t in top_tokens(ex.item_reviews, c.item_rids.index_select(0, pi), n))
+        att = torch.gather(ex.item_review_weights.cpu(), 1, slot)
+        rv = [[[int(s), int(r), float(a), float(x)] for s, r, a, x in zip(*q) if x != 0.0] for q in zip(slot, rid, att, contrib)]
+    slot_of = keep.cumsum(1) - 1
+    for p, (r, k) in enumerate(zip(rows.tolist(), cols.tolist())):
+        entry = {"user_tokens": ut[p], "item_tokens": it[p]}
+        if rv is not None:
+            entry["item_reviews"] = rv[p]
+        why[r][int(slot_of[r, k])] = entry
+    return why
 
 
 def main(argv=None) -> int:
@@ -285,15 +411,20 @@ def main(argv=None) -> int:
     model.to(dev).eval()
     rec = Recommender(model, cache).refresh(chunk=a.chunk)
     seen = Recommender.seen_from(ds.examples, rec.n_users, dev) if a.exclude_train else None
+    words = _vocabulary(cfg.data_dir) if a.explain is not None else None
     if a.out is not None:
         with open(a.out, "w") as f:
             for lo in range(1, rec.n_users, a.chunk):
                 u_ids = torch.arange(lo, min(lo + a.chunk, rec.n_users), dtype=torch.int64, device=dev)
                 items, scores = rec.topk(u_ids, a.k, exclude=seen)
                 items, scores = items.cpu(), scores.cpu()
+                why = _why(rec, u_ids, items, a.explain, words) if a.explain is not None else None
                 for r, u in enumerate(u_ids.tolist()):
                     keep = items[r] >= 0
-                    f.write(json.dumps({"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}) + "\n")
+                    line = {"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}
+                    if why is not None:
+                        line["why"] = why[r]
+                    f.write(json.dumps(line) + "\n")
     if a.eval_split is not None:
         held_out = D.load_pickle(os.path.join(cfg.data_dir, f"{a.eval_split}_exmaples.pkl"))
         line = json.dumps(dict(rec.evaluate(held_out, a.ks, exclude=seen), split=a.eval_split, exclude_train=bool(a.exclude_train)))
