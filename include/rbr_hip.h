@@ -435,6 +435,50 @@ int rbr_bpr_loss_fwd(int32_t B, int32_t n_neg, const float* pred, const float* v
 int rbr_bpr_loss_bwd(int32_t B, int32_t n_neg, const float* pred, const float* valid, const float* d_loss, float* d_pred,
                      void* stream);
 
+/* ---- In-batch softmax ranking loss over all B x B pairs of a batch's latents (pair_softmax.hip); the reference has none.
+ *   Square: B users against the B items of the same batch, the positive of row a is column a.  mode RBR_SCORE_FM / RBR_SCORE_DOT
+ *   (defined below, with the catalogue scores).  f32 unless stated:
+ *     ul, il [B, K] latent rows; h [K] (FM); row_bias [B] or NULL (the caller passes ub[u_id] + g); col_bias [B] or NULL (ib[i_id]);
+ *     dropout (FM only): drop [B, B, K] an explicit multiplier, OR p_drop > 0 with seed and rng_state: element (a, b, k) gets
+ *     exactly what rbr_dropout_multiplier(B*B*K, p_drop, seed, rng_state, ...) writes at (a*B + b)*K + k for the same call number
+ *     (both launches read the call number before the second advances it, once); u_id, i_id int64 [B]; the seen-items CSR of
+ *     rbr_sample_negatives (seen_off int64 [U + 1], seen_item int32 [seen_nnz] sorted within a row; both NULL = none; offsets
+ *     clamped to [0, seen_nnz]; a u_id outside [0, U) has an empty row); item_lo; logq [B] or NULL (log sampling probability of
+ *     column b's item); inv_temp > 0.
+ *       core(a,b)    = FM: sum_k relu(ul[a,k] * il[b,k]) * drop[a,b,k] * h[k]      DOT: sum_k ul[a,k] * il[b,k]
+ *       s[a,b]       = core(a,b) + row_bias[a] + col_bias[b]
+ *       z[a,b]       = inv_temp * s[a,b] - logq[b]
+ *       allowed[a,b] = (b == a) or (i_id[b] >= item_lo and i_id[b] != i_id[a] and i_id[b] not in seen(u_id[a]))
+ *       lse[a]       = log sum over allowed b of exp(z[a,b])           (max-subtracted)
+ *       loss[0]      = (1/B) * sum_a (lse[a] - z[a,a]);   pos[a] = s[a,a]
+ *     A row whose only allowed column is its own contributes exactly 0 to the loss and exactly zero gradients.
+ *   Gradients, with P[a,b] = allowed ? exp(z[a,b] - lse[a]) : 0 and ds[a,b] = inv_temp * (P[a,b] - [a == b]) / B * d_loss:
+ *     d_ul, d_il, d_h by the chain rule through core (ReLU gate ul[a,k] * il[b,k] > 0, as in the head's backward; all
+ *     OVERWRITTEN), d_col_bias[b] = sum_a ds[a,b].  d_row_bias[a] = sum_b ds[a,b] is 0 in exact arithmetic -- a per-user constant
+ *     cancels in a softmax over items -- and is DEFINED as exactly 0.0: d_row_bias (optional, [B]) is written as zeros, never summed.
+ *   rbr_pair_softmax_fwd writes loss and pos and, when d_ul is given (then d_il too, d_h in FM mode, d_col_bias exactly when
+ *   col_bias is), the gradients for an upstream gradient of exactly 1 (the d_pred_unit convention of rbr_mse_loss_fwd); call_out
+ *   (optional, uint64 [1]) receives the call number the draw used.  rbr_pair_softmax_bwd is the entry for any other device-scalar
+ *   d_loss: it recomputes the forward (pos_scratch [B] is overwritten) and draws with the call number saved in `call`.
+ *   Two launches each (row-owned, column-owned), no host synchronisation, no allocation (ws: rbr_pair_softmax_ws_bytes), graph-
+ *   capturable; no float atomics, one owner per output element, fixed summation order: the same bits on every run.
+ *   1 <= B <= 4096 and 1 <= K <= 256, else RBR_ERR_UNSUPPORTED (and 0 bytes): there is no fallback.  RBR_ERR_BAD_ARG before any
+ *   launch: a null required pointer, inv_temp <= 0 or non-finite, drop together with p_drop > 0, dropout in DOT mode, p_drop
+ *   outside [0, 1).  Ids are only compared and searched; u_id indexes seen_off after a range check. */
+size_t rbr_pair_softmax_ws_bytes(int32_t B, int32_t K);
+int rbr_pair_softmax_fwd(int32_t mode, int32_t B, int32_t K, const float* ul, const float* il, const float* h,
+                         const float* row_bias, const float* col_bias, const float* drop, float p_drop, uint64_t seed,
+                         uint64_t* rng_state, const int64_t* u_id, const int64_t* i_id, const int64_t* seen_off,
+                         const int32_t* seen_item, int64_t seen_nnz, int32_t U, int64_t item_lo, const float* logq, float inv_temp,
+                         float* loss, float* pos, float* d_ul, float* d_il, float* d_h, float* d_col_bias, float* d_row_bias,
+                         uint64_t* call_out, void* ws, void* stream);
+int rbr_pair_softmax_bwd(int32_t mode, int32_t B, int32_t K, const float* ul, const float* il, const float* h,
+                         const float* row_bias, const float* col_bias, const float* drop, float p_drop, uint64_t seed,
+                         const uint64_t* call, const int64_t* u_id, const int64_t* i_id, const int64_t* seen_off,
+                         const int32_t* seen_item, int64_t seen_nnz, int32_t U, int64_t item_lo, const float* logq, float inv_temp,
+                         const float* d_loss, float* pos_scratch, float* d_ul, float* d_il, float* d_h, float* d_col_bias,
+                         float* d_row_bias, void* ws, void* stream);
+
 /* ---- NARRE review-level attention pool (narre.py:40-64)
  *   e = ebd[other_id];  logit = relu(feat@W_rv + e@W_id + b1) @ h + b2
  *   att = exp(logit) / (sum_R exp(logit) + 1e-8)   (unmasked, no max subtraction)

@@ -172,6 +172,13 @@ SIGNATURES = {
     "rbr_mse_loss_bwd": (C.c_int, [C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "rbr_bpr_loss_fwd": (C.c_int, [i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "rbr_bpr_loss_bwd": (C.c_int, [i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "rbr_pair_softmax_ws_bytes": (C.c_size_t, [i32, i32]),
+    "rbr_pair_softmax_fwd": (C.c_int, [i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, C.c_uint64,
+                                       C.c_void_p, c_i64p, c_i64p, c_i64p, c_i32p, C.c_int64, i32, C.c_int64, c_f32p, C.c_float,
+                                       c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_stream]),
+    "rbr_pair_softmax_bwd": (C.c_int, [i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_float, C.c_uint64,
+                                       C.c_void_p, c_i64p, c_i64p, c_i64p, c_i32p, C.c_int64, i32, C.c_int64, c_f32p, C.c_float,
+                                       c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, c_stream]),
     "rbr_sample_negatives": (C.c_int, [i32, i32, i32, i32, c_i64p, c_i64p, c_i64p, c_i32p, C.c_int64, i32, C.c_uint64, C.c_void_p,
                                        i32, C.c_int64, c_i64p, c_i64p, c_f32p, c_stream]),
     "rbr_review_attn_fwd": (C.c_int, [i32, i32, i32, i32, c_f32p, c_i64p, C.POINTER(AttnParams), c_f32p, c_f32p, c_f32p,

@@ -569,6 +569,56 @@ class NegativeFeed:
         return self.feed.inputs(u_out, i_out, with_ids=with_ids)
 
 
+class InBatchFeed:
+    """An id feed (DeviceDocCache, ReviewFeed) for the in-batch softmax objective (train_step.InBatchSoftmaxObjective): the batch
+    stays the B observed pairs -- every user's negatives are the other B - 1 items of the same batch, at no encoder cost -- so
+    the inner feed gathers exactly what it would for the MSE step.  What this class adds is what the all-pairs loss needs beside
+    the latents: the (u_ids, i_ids) of the last gather (`u_ids` / `i_ids`: references, not copies, as NegativeFeed's buffers --
+    a recorded slot's objective therefore reads that slot's own static id tensors), the seen-items CSR on the device (`seen`:
+    the training split's recommend.Recommender.seen_from, or None: an item its user has rated is no negative) and item_lo (ids
+    below it, the pad id, are nobody's negative).  It speaks the inner feed's protocol (empty_inputs / gather / inputs)."""
+
+    def __init__(self, feed, seen, item_lo: int = 1):
+        for name in ("empty_inputs", "gather", "inputs", "device"):
+            if not hasattr(feed, name):
+                raise ValueError(f"InBatchFeed wraps an id feed (empty_inputs / gather / inputs / device); {type(feed).__name__} has no {name}")
+        if isinstance(item_lo, bool) or not isinstance(item_lo, int) or item_lo < 0:
+            raise ValueError(f"item_lo must be an integer >= 0, got {item_lo!r}")
+        if seen is not None:
+            if len(seen) != 2:
+                raise ValueError("seen must be (off [U + 1], items): one row per user id (recommend.Recommender.seen_from)")
+            off, items = seen
+            if off.dtype != torch.int64 or items.dtype != torch.int32 or off.dim() != 1 or items.dim() != 1 or off.shape[0] < 2:
+                raise ValueError(f"seen must be (int64 [U + 1], int32 [nnz]), got {off.dtype} {tuple(off.shape)}, "
+                                 f"{items.dtype} {tuple(items.shape)}")
+        self.feed, self.device = feed, torch.device(feed.device)
+        self.seen = None if seen is None else (seen[0].to(self.device), seen[1].to(self.device))
+        self.item_lo = item_lo
+        self._last = None
+
+    u_ids = property(lambda self: self._last[0])
+    i_ids = property(lambda self: self._last[1])
+
+    def _note(self, u_ids: torch.Tensor, i_ids: torch.Tensor):
+        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
+            raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+        self._last = (u_ids.to(self.device, non_blocking=True), i_ids.to(self.device, non_blocking=True))
+        return self._last
+
+    def empty_inputs(self, B: int, with_ids: bool = True):
+        return self.feed.empty_inputs(B, with_ids)
+
+    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None, **kw):
+        """The inner feed's gather of the pairs; the ids are kept for the objective."""
+        u, i = self._note(u_ids, i_ids)
+        return self.feed.gather(u, i, out=out, **kw)
+
+    def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
+        """The model's arguments for the pairs; the ids are kept for the objective."""
+        u, i = self._note(u_ids, i_ids)
+        return self.feed.inputs(u, i, with_ids=with_ids)
+
+
 def _adjacent(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """[a; b] as ONE view when b directly follows a in the same allocation (a write through it lands in a and b)."""
     if not (a.is_contiguous() and b.is_contiguous() and a.dtype == b.dtype and a.shape == b.shape and a.device == b.device

@@ -971,12 +971,17 @@ def _ticket(dev) -> torch.Tensor:
 
 
 def prepare_stream_state(dev) -> None:
-    """Creates the per-(device, stream) state of the CURRENT stream -- the arrival counter of the fused head's MSE reduction --
-    so that its first use does not allocate and zero-fill it.  train_step.GraphedTrainStep /
+    """Creates the per-(device, stream) state of the CURRENT stream -- the arrival counter of the fused head's MSE reduction, and
+    the all-pairs softmax loss's workspace at the largest size any stream of the device has needed so far (the warm-up steps
+    ahead of a recording ran on another stream: they are what sizes it) -- so that its first use does not allocate it.  train_step.GraphedTrainStep /
     GraphedForward call it on their capture stream before recording: a counter buffer created during a capture would live in
     that graph's private memory pool and cost every replay a fill node."""
     dev = torch.device(dev)
     _ticket(dev)
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    need = max((t.numel() for (d, _), t in _PS_WS.items() if d == idx), default=0)
+    if need:
+        _pair_softmax_ws(dev, need)
 
 
 def encode_head_applicable(table, n_docs, L, kernel_sizes, channels, padding_idx) -> bool:
@@ -1315,6 +1320,123 @@ def bpr_loss(pred: torch.Tensor, n_neg: int, valid: Optional[torch.Tensor] = Non
     negative out of the sum and the mean; no valid negative at all gives loss 0 and zero gradients.  Fixed summation order:
     the same bits on every run."""
     return _BprLoss.apply(pred, n_neg, valid)
+
+
+_PS_WS: dict = {}
+
+
+def _pair_softmax_ws(dev, nbytes: int) -> torch.Tensor:
+    """Workspace of rbr_pair_softmax_* (ds [B, B], the row losses, the d_h partials): one per (device, STREAM), as _ticket --
+    launches on one stream are ordered and may share it; it only grows.  prepare_stream_state() creates it ahead of a capture."""
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    key = (idx, torch.cuda.current_stream(idx).cuda_stream)
+    t = _PS_WS.get(key)
+    if t is None or t.numel() < nbytes:
+        t = _PS_WS[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    return t
+
+
+class _PairSoftmaxLoss(torch.autograd.Function):
+    """The in-batch softmax loss over all B x B pairs (rbr_pair_softmax_* in rbr_hip.h) -> (loss, pos).  As _MseLoss: the forward's
+    two launches also write the gradients for an upstream gradient of 1, and a backward that is handed unit_scalar() returns them
+    without a launch; any other root re-runs the two launches with that scalar (and the forward's dropout call number)."""
+
+    @staticmethod
+    def forward(ctx, ul, il, h, row_bias, col_bias, u_ids, i_ids, mode, drop, p_drop, seen, item_lo, logq, inv_temp):
+        code = SCORE_MODES[mode]
+        ul, il = ul.contiguous(), il.contiguous()
+        dev = ul.device
+        B, K = ul.shape
+        ctx.shapes = tuple(None if t is None else t.shape for t in (h, row_bias, col_bias))
+        flat = [None if t is None else t.contiguous().view(-1) for t in (h, row_bias, col_bias, logq)]
+        for t, n, name in zip(flat, (K, B, B, B), ("h", "row_bias", "col_bias", "logq")):
+            if t is not None and t.numel() != n:
+                raise RuntimeError(f"pair_softmax_loss: {name} must hold {n} values, got {t.numel()}")
+        h, row_bias, col_bias, logq = flat
+        u_ids, i_ids = u_ids.contiguous(), i_ids.contiguous()
+        if drop is not None:
+            drop = drop.contiguous()
+            if drop.shape != (B, B, K):
+                raise RuntimeError(f"pair_softmax_loss: drop must be [{B}, {B}, {K}], got {tuple(drop.shape)}")
+        U = 0 if seen is None else seen[0].shape[0] - 1
+        off, items, _, nnz, _ = _exclusion_csr(seen, U, dev)
+        L_ = _lib.lib()
+        # a shape the entry refuses has a workspace of 0 bytes: the call below then returns its error code and text before any launch
+        ws = _pair_softmax_ws(dev, L_.rbr_pair_softmax_ws_bytes(B, K))
+        p_drop = float(p_drop)
+        seed, state = _drop_rng(dev) if p_drop > 0.0 else (0, None)
+        call = torch.empty(1, dtype=I64, device=dev) if p_drop > 0.0 else None
+        loss = torch.empty((), dtype=F32, device=dev)
+        pos = torch.empty(B, dtype=F32, device=dev)
+        grads = any(ctx.needs_input_grad[:5])
+        d_ul = torch.empty_like(ul) if grads else None
+        d_il = torch.empty_like(il) if grads else None
+        d_h = torch.empty_like(h) if grads and h is not None and code == _lib.SCORE_FM else None
+        d_cb = torch.empty_like(col_bias) if grads and col_bias is not None else None
+        d_rb = torch.empty_like(row_bias) if grads and row_bias is not None else None
+        ctx.ops = (code, B, K, dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(h, F32, "h"), dev_ptr(row_bias, F32, "row_bias"),
+                   dev_ptr(col_bias, F32, "col_bias"), dev_ptr(drop, F32, "drop"), p_drop, seed)
+        ctx.ids = (dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"), dev_ptr(off, I64, "seen offsets"),
+                   dev_ptr(items, I32, "seen items"), nnz, U, int(item_lo), dev_ptr(logq, F32, "logq"), float(inv_temp))
+        _call("pair_softmax_fwd", L_.rbr_pair_softmax_fwd, *ctx.ops, None if state is None else state.data_ptr(), *ctx.ids,
+              dev_ptr(loss, F32, "loss"), dev_ptr(pos, F32, "pos"), dev_ptr(d_ul, F32, "d_ul"), dev_ptr(d_il, F32, "d_il"),
+              dev_ptr(d_h, F32, "d_h"), dev_ptr(d_cb, F32, "d_col_bias"), dev_ptr(d_rb, F32, "d_row_bias"),
+              None if call is None else call.data_ptr(), ws.data_ptr(), current_stream())
+        ctx.keep = (ul, il, h, row_bias, col_bias, drop, u_ids, i_ids, off, items, logq, call)      # the pointers of ctx.ops / ctx.ids
+        ctx.unit = (d_ul, d_il, d_h, d_rb, d_cb) if grads else None
+        ctx.mark_non_differentiable(pos)
+        return loss, pos
+
+    @staticmethod
+    def backward(ctx, d_loss, _d_pos):
+        ul, il, h, row_bias, col_bias = ctx.keep[:5]
+        call = ctx.keep[-1]
+        unit = _UNIT.get(ul.device)
+        if unit is not None and ctx.unit is not None and d_loss.data_ptr() == unit.data_ptr():
+            d_ul, d_il, d_h, d_rb, d_cb = ctx.unit
+        else:
+            d_loss = d_loss.contiguous()
+            d_ul, d_il = torch.empty_like(ul), torch.empty_like(il)
+            d_h = torch.empty_like(h) if h is not None and ctx.ops[0] == _lib.SCORE_FM else None
+            d_cb = torch.empty_like(col_bias) if col_bias is not None else None
+            d_rb = torch.empty_like(row_bias) if row_bias is not None else None
+            scratch = torch.empty(ctx.ops[1], dtype=F32, device=ul.device)
+            L_ = _lib.lib()
+            ws = _pair_softmax_ws(ul.device, L_.rbr_pair_softmax_ws_bytes(ctx.ops[1], ctx.ops[2]))
+            _call("pair_softmax_bwd", L_.rbr_pair_softmax_bwd, *ctx.ops, None if call is None else call.data_ptr(), *ctx.ids,
+                  dev_ptr(d_loss, F32, "d_loss"), dev_ptr(scratch, F32, "pos"), dev_ptr(d_ul, F32, "d_ul"), dev_ptr(d_il, F32, "d_il"),
+                  dev_ptr(d_h, F32, "d_h"), dev_ptr(d_cb, F32, "d_col_bias"), dev_ptr(d_rb, F32, "d_row_bias"), ws.data_ptr(),
+                  current_stream())
+        d_h, d_rb, d_cb = (None if t is None else t.view(s) for t, s in zip((d_h, d_rb, d_cb), ctx.shapes))
+        return (d_ul, d_il, d_h, d_rb, d_cb) + (None,) * 9
+
+
+def pair_softmax_loss(ul, il, u_ids, i_ids, mode, h=None, row_bias=None, col_bias=None, drop=None, seen=None, item_lo=1, logq=None,
+                      temperature=1.0, *, p_drop: float = 0.0):
+    """(loss, pos) of the in-batch softmax over ALL B x B pairs of the latent rows ul / il [B, K] (rbr_pair_softmax_fwd): row a's
+    positive is column a, its negatives the other items of the batch -- except an item below item_lo (the pad id), the row's own
+    item again, and an item its user has rated (`seen`: a recommend.SeenItems / (off int64 [U + 1], items int32 sorted within a row),
+    the form of sample_negatives; None = no list).  mode "fm": s = (relu(ul[a] * il[b]) * drop[a, b]) . h + row_bias[a] + col_bias[b]
+    -- pass row_bias = ub[u_ids] + g and col_bias = ib[i_ids] for the model's own score --, mode "dot": s = ul[a] . il[b] + biases.
+    z = s / temperature - logq[b]; loss = mean_a (logsumexp over the allowed b of z[a, b] - z[a, a]); pos [B] = s[a, a], detached.
+    Dropout (fm only): drop [B, B, K] an explicit multiplier, or p_drop > 0: drawn in the kernel, the draw of
+    dropout_multiplier((B, B, K), p_drop, ...) for the same call number.  Autograd through ul, il, h, col_bias; row_bias gets a
+    gradient of exact zeros (a per-user constant cancels in a softmax over items).  Two launches, no float atomics: the same bits
+    on every run; 1 <= B <= 4096, 1 <= K <= 256, there is no fallback."""
+    if mode not in SCORE_MODES:
+        raise ValueError(f"unknown score mode {mode!r}; one of {sorted(SCORE_MODES)}")
+    if ul.dim() != 2 or ul.shape != il.shape:
+        raise RuntimeError(f"pair_softmax_loss: ul / il must be [B, K] each, got {tuple(ul.shape)} / {tuple(il.shape)}")
+    B = ul.shape[0]
+    dev_ptr(ul.detach().contiguous(), F32, "user latents")        # device gate first: a CPU tensor is refused before anything else
+    if u_ids.shape != (B,) or i_ids.shape != (B,):
+        raise RuntimeError(f"pair_softmax_loss: u_ids / i_ids must be [{B}] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+    if seen is not None and len(seen) != 2:
+        raise RuntimeError("seen must be (off [U + 1], items): one row per user id")
+    if not temperature > 0:
+        raise ValueError(f"pair_softmax_loss: temperature must be positive, got {temperature}")
+    return _PairSoftmaxLoss.apply(ul, il, h, row_bias, col_bias, u_ids, i_ids, mode, drop, p_drop, seen, int(item_lo), logq,
+                                  1.0 / float(temperature))
 
 
 # --------------------------------------------------------------------------- NARRE attention pool

@@ -4,7 +4,7 @@ import torch
 import torch.nn as nn
 
 from ... import functional as RF
-from .layers import FM, LastFeat, NgramFeat, WordEmbedding, rating_head
+from .layers import FM, LastFeat, NgramFeat, WordEmbedding, latent_rows, rating_head
 
 
 class DeepCoNNpp(nn.Module):
@@ -94,6 +94,20 @@ class DeepCoNNpp(nn.Module):
             u_rev_feats, i_rev_feats = feats, None          # [2*bz, H], user rows first: the head takes it whole
         preds = rating_head(self.user_feat, self.item_feat, self.fm, u_rev_feats, i_rev_feats, u_ids, i_ids)
         return preds.view(bz)
+
+    def pair_latents(self, u_revs, i_revs, u_rev_masks, i_rev_masks, u_ids, i_ids):
+        """forward's arguments -> (ul, il) [bz, latent_dim] each: the towers' latent rows, under autograd and in the module's own
+        train / eval mode.  The encoder runs once on the stacked 2*bz documents, as in forward; the tail stops at LastFeat, so
+        that a loss over all bz x bz pairs of the batch (functional.pair_softmax_loss) can follow.  forward is untouched."""
+        pad = self.word_embeddings.padding_idx
+        if self.validate_ids:
+            ids, u_ids, i_ids = RF.sanitize_ids([(u_revs, self.vocab_size, pad), (i_revs, self.vocab_size, pad),
+                                                 (u_ids, self.user_size, 0), (i_ids, self.item_size, 0)], stack_first_two=True)
+        else:
+            ids = RF.stack_rows(u_revs, i_revs)
+        masks = RF.stack_rows(u_rev_masks, i_rev_masks)
+        feats = self.ngram.encode(self.word_embeddings.weight, ids, masks, padding_idx=pad)
+        return latent_rows(self.user_feat, self.item_feat, feats, u_ids, i_ids)
 
     # ---- one tower at a time (recommend.Recommender): a tower depends on its own side only, so a catalogue is encoded once
     def _encode_side(self, docs, masks, ids, last):

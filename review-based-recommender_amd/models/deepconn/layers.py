@@ -222,3 +222,13 @@ def rating_head(user_feat: LastFeat, item_feat: LastFeat, fm: FM, u_text_feat, i
                         item_feat.W, item_feat.b, item_feat.ebd.weight,
                         fm.h, fm.g_bias, fm.user_bias.weight, fm.item_bias.weight,
                         drop=drop, pad_u=fm.user_padding_idx, pad_i=fm.item_padding_idx)
+
+
+def latent_rows(user_feat: LastFeat, item_feat: LastFeat, text_feat2, u_ids, i_ids):
+    """(ul, il) [bz, latent_dim] each = LastFeat(user) / LastFeat(item) of the stacked text features [2*bz, H] (user rows first),
+    under autograd: where the two-tower tail stops for a loss over ALL pairs of the batch's latents (the models' pair_latents;
+    functional.pair_softmax_loss).  HIP GEMM + HIP row gather per side; the ids are the caller's range-checked ones."""
+    bz = u_ids.shape[0]
+    ul = RF.linear(text_feat2[:bz], user_feat.W.t(), user_feat.b) + RF.embedding(user_feat.ebd.weight, u_ids, user_feat.padding_idx)
+    il = RF.linear(text_feat2[bz:], item_feat.W.t(), item_feat.b) + RF.embedding(item_feat.ebd.weight, i_ids, item_feat.padding_idx)
+    return ul, il

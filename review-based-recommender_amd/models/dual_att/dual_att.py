@@ -98,6 +98,36 @@ class DualAtt(nn.Module):
             feats = self._fc(RF.block_cat(u_loc, u_glo, i_loc, i_glo))      # [2*bz, hidden_2], user rows first
         return RF.pair_dot(feats).view(-1)                                  # sum(u_feat * i_feat, 1)  (dual_att.py:58)
 
+    def pair_latents(self, u_docs, i_docs):
+        """forward's arguments -> (ul, il) [bz, hidden_size_2] each: the towers' latent rows -- the shared fc over both sides --
+        under autograd and in the module's own train / eval mode (the fc keeps its dropout).  Same encoder pass as forward; the
+        tail stops in front of the inner product, so that a loss over all bz x bz pairs of the batch
+        (functional.pair_softmax_loss) can follow.  forward is untouched."""
+        bz = u_docs.shape[0]
+        pad = self.word_embeddings.padding_idx
+        if self.validate_ids:
+            u_docs, i_docs = RF.sanitize_ids([(u_docs, self.vocab_size, pad), (i_docs, self.vocab_size, pad)])
+        u_par, i_par = self._tower_params(self.u_local_atten, self.u_global_atten), self._tower_params(self.i_local_atten, self.i_global_atten)
+        feats = None
+        if u_docs.shape == i_docs.shape and self.u_local_atten.window_size == self.i_local_atten.window_size:
+            docs2 = RF.stack_rows(u_docs, i_docs)
+            if RF.datt_pair_applies(self.word_embeddings.weight, docs2, u_par[0], u_par[4]):
+                feats = self._fc(RF.datt_towers(self.word_embeddings.weight, docs2, u_par, i_par, padding_idx=pad,
+                                                pad_runs=self.u_local_atten.window_size <= 17))
+        if feats is None:
+            tabs = RF.table_fanout(self.word_embeddings.weight, 8)
+            u_loc, u_glo = self._encode(u_docs, self.u_local_atten, self.u_global_atten, tabs[0:4])
+            i_loc, i_glo = self._encode(i_docs, self.i_local_atten, self.i_global_atten, tabs[4:8])
+            if u_glo is None and i_glo is None:
+                feats = self._fc(RF.stack_rows(u_loc, i_loc))
+            else:
+                if u_glo is None:
+                    u_loc, u_glo = u_loc[:, :self.u_local_atten.out_size], u_loc[:, self.u_local_atten.out_size:]
+                if i_glo is None:
+                    i_loc, i_glo = i_loc[:, :self.i_local_atten.out_size], i_loc[:, self.i_local_atten.out_size:]
+                feats = self._fc(RF.block_cat(u_loc, u_glo, i_loc, i_glo))
+        return feats[:bz], feats[bz:]
+
     # ---- one tower at a time (recommend.Recommender): a tower reads its own documents only, the shared fc included
     def _encode_side(self, docs, local, glob):
         with RF.eval_mode(self):

@@ -8,7 +8,7 @@ import torch
 import torch.nn as nn
 
 from ... import functional as RF
-from ..deepconn.layers import FM, LastFeat, WordEmbedding, rating_head
+from ..deepconn.layers import FM, LastFeat, WordEmbedding, latent_rows, rating_head
 from .layers import NgramFeat
 
 
@@ -89,6 +89,33 @@ class NARRE(nn.Module):
 
         pred = rating_head(self.user_feat, self.item_feat, self.fm, out.view(2 * bz, self.hiddem_dim), None, u_id, i_id)
         return pred.view(-1), u_att_scores, i_att_scores
+
+    def pair_latents(self, u_text, i_text, u_text_masks, i_text_masks, u_id, i_id, reuid, reiid):
+        """forward's arguments -> (ul, il) [bz, latent_dim] each: the towers' latent rows, under autograd and in the module's own
+        train / eval mode (the attention pools keep their dropout).  Encoder and both attention pools run once on the stacked
+        batch, as in forward; the tail stops at LastFeat, so that a loss over all bz x bz pairs of the batch
+        (functional.pair_softmax_loss) can follow.  forward is untouched."""
+        bz = u_text.shape[0]
+        R, T = self.doc_num, self.doc_len
+        if self.validate_ids:
+            wp = self.word_embeddings.padding_idx
+            ids, u_id, i_id, reuid, reiid = RF.sanitize_ids(
+                [(u_text.reshape(-1, T), self.vocab_size, wp), (i_text.reshape(-1, T), self.vocab_size, wp),
+                 (u_id, self.user_size, self.user_feat.padding_idx), (i_id, self.item_size, self.item_feat.padding_idx),
+                 (reuid, self.item_size, self.user_att.padding_idx), (reiid, self.user_size, self.item_att.padding_idx)],
+                stack_first_two=True)
+        else:
+            ids = RF.stack_rows(u_text.reshape(-1, T), i_text.reshape(-1, T))
+        masks = RF.stack_rows(u_text_masks.reshape(-1, T), i_text_masks.reshape(-1, T))
+        feats = self.ngram.encode(self.word_embeddings.weight, ids, masks, padding_idx=self.word_embeddings.padding_idx)
+        ua, ia = self.user_att, self.item_att
+        other = RF.stack_rows(reuid, reiid).view(2, bz, R)
+        drop = RF.dropout_multiplier((2 * bz, self.hiddem_dim), ua.dropout.p, ua.training, feats.device)
+        out, _ = RF.review_attention2(
+            feats.view(2, bz, R, self.hiddem_dim), other,
+            (ua.W_rv, ua.W_id, ua.h, ua.b_1, ua.b_2, ua.ebd_vals.weight), (ia.W_rv, ia.W_id, ia.h, ia.b_1, ia.b_2, ia.ebd_vals.weight),
+            pad_idx=(ua.padding_idx, ia.padding_idx), drop=None if drop is None else drop.view(2, bz, self.hiddem_dim))
+        return latent_rows(self.user_feat, self.item_feat, out.view(2 * bz, self.hiddem_dim), u_id, i_id)
 
     # ---- one tower at a time (recommend.Recommender).  The attention pool of a side is keyed by its reviews' own counterpart
     # ids (reuid / reiid, narre.py:177-178), not by the target pair, so a side's latent row is a function of that side alone.

@@ -6,6 +6,7 @@ import torch.nn as nn
 from ... import functional as RF
 from .layers import (FM, AddictiveAttention, FMWithoutUIBias, LastFeat, MaskedAvgPooling1d, NodeDropout, VariationalDropout,
                      WordEmbedding, rating_head)
+from ..deepconn.layers import latent_rows
 from .utils import get_rev_mask  # noqa: F401  (re-exported as in the reference module)
 
 
@@ -75,6 +76,19 @@ class SimpleSiamese(nn.Module):
         out_logits = rating_head(self.user_last_feat_layer, self.item_last_feat_layer, self.fm, u_rev_feat, i_rev_feat,
                                  u_ids, i_ids)
         return out_logits.view(bz), None, None
+
+    def pair_latents(self, u_revs, i_revs, u_rev_word_masks, i_rev_word_masks, u_rev_masks, i_rev_masks, u_ids, i_ids):
+        """forward's arguments -> (ul, il) [bz, latent_dim] each: the towers' latent rows, under autograd and in the module's own
+        train / eval mode (word and review dropout stay).  The shared tower runs once on the stacked batch, as in forward; the
+        tail stops at LastFeat, so that a loss over all bz x bz pairs of the batch (functional.pair_softmax_loss) can follow.
+        forward is untouched."""
+        if self.validate_ids:
+            stacked, u_ids, i_ids = RF.sanitize_ids([(u_revs, self.vocab_size, 0), (i_revs, self.vocab_size, 0),
+                                                     (u_ids, self.user_size, 0), (i_ids, self.item_size, 0)], stack_first_two=True)
+        else:
+            stacked = RF.stack_rows(u_revs, i_revs)
+        feat = self._tower(stacked, RF.stack_rows(u_rev_word_masks, i_rev_word_masks), RF.stack_rows(u_rev_masks, i_rev_masks))
+        return latent_rows(self.user_last_feat_layer, self.item_last_feat_layer, feat, u_ids, i_ids)
 
     # ---- one tower at a time (recommend.Recommender): the towers share their layers but each reads its own side only
     def _encode_side(self, revs, word_masks, rev_masks, ids, last):

@@ -320,9 +320,12 @@ def _forward_objective_backward(model: nn.Module, batch, objective, optimizer=No
     un-fused), and the root gradient is the cached unit scalar, which functional.bpr_loss answers without a launch."""
     scope = optimizer.row_grad_scope() if isinstance(optimizer, HipClipAdam) else contextlib.nullcontext()
     with scope:
-        out = model(*batch)
-        pred = out[0] if isinstance(out, tuple) else out
-        loss = objective(pred)
+        if hasattr(objective, "forward_loss"):      # an objective over the towers' latents runs the model's forward itself
+            pred, loss = objective.forward_loss(model, batch)
+        else:
+            out = model(*batch)
+            pred = out[0] if isinstance(out, tuple) else out
+            loss = objective(pred)
         loss.backward(RF.unit_scalar(pred.device) if pred.is_cuda else None)
     return pred, loss
 
@@ -341,6 +344,64 @@ class BprObjective:
         if pred.dim() != 1 or pred.shape[0] % (1 + n_neg):
             raise RuntimeError(f"BprObjective: pred {tuple(pred.shape)} is not (1 + {n_neg}) * B scores")
         return RF.bpr_loss(pred, n_neg, self.feed.buffers(pred.shape[0] // (1 + n_neg))[2])
+
+
+class InBatchSoftmaxObjective:
+    """The in-batch softmax ranking objective for a step fed through `feed` (a data.InBatchFeed): the towers' latent rows of the
+    B observed pairs (model.pair_latents), then functional.pair_softmax_loss over ALL B x B pairs -- every user's negatives are
+    the batch's other items, less the pad id, the row's own item again and the items the user has rated (feed.seen) -- scored
+    by the model's own head (score_mode_and_params(): FM with the head's dropout drawn in the kernel, or D-ATT's dot) at
+    `temperature`.  `logq` (f32 [n_items] on the device, or None): the log sampling probability of every item, subtracted from
+    its column's logit (the sampled-softmax correction for popular items).  forward_loss(model, batch) -> (pos, loss) with
+    pos [B] the observed pairs' scores; pass the objective as `objective` to train_step / GraphedTrainStep together with the feed.
+    user_bias and g_bias receive an exactly zero gradient (a per-user constant cancels in a softmax over items)."""
+
+    def __init__(self, model, feed, temperature: float = 1.0, logq=None):
+        for name in ("pair_latents", "score_mode_and_params"):
+            if not hasattr(model, name):
+                raise ValueError(f"InBatchSoftmaxObjective needs a two-tower model with {name}(); {type(model).__name__} has none")
+        if not hasattr(feed, "seen") or not hasattr(feed, "item_lo") or not hasattr(feed, "_last"):
+            raise ValueError("InBatchSoftmaxObjective takes a data.InBatchFeed (the batch's ids, the seen CSR, item_lo)")
+        temperature = float(temperature)
+        if not (temperature > 0.0 and temperature < float("inf")):
+            raise ValueError(f"temperature must be positive and finite, got {temperature}")
+        self.feed, self.temperature = feed, temperature
+        self.logq = None if logq is None else logq.detach().to(torch.float32).contiguous().view(-1, 1)
+
+    def forward_loss(self, model, batch):
+        feed = self.feed
+        if feed._last is None:
+            raise RuntimeError("InBatchSoftmaxObjective: the feed has gathered no batch yet (feed.inputs / feed.gather come first)")
+        u_ids, i_ids = feed.u_ids, feed.i_ids
+        ul, il = model.pair_latents(*batch)
+        if ul.shape[0] != u_ids.shape[0]:
+            raise RuntimeError(f"InBatchSoftmaxObjective: the batch has {ul.shape[0]} pairs, the feed's last gather {u_ids.shape[0]}")
+        mode, h, g, ub, ib = model.score_mode_and_params()
+        row_bias = col_bias = logq = None
+        p_drop = 0.0
+        u_idx, i_idx = u_ids, i_ids
+        if getattr(model, "validate_ids", True) and (ub is not None or ib is not None or self.logq is not None):
+            # ids as indices: range-checked like every other lookup of the model (one launch for both); a caller that has
+            # validated its split and switched the model's check off (the trainer) spares this launch as well
+            u_idx, i_idx = RF.sanitize_ids([(u_ids, ub.shape[0] if ub is not None else (1 << 62), 0),
+                                            (i_ids, ib.shape[0] if ib is not None else self.logq.shape[0], 0)])
+        if mode == "fm":
+            fm = model.fm
+            if fm.training and torch.is_grad_enabled():
+                p_drop = float(fm.dropout.p)
+            if ub is not None:
+                row_bias = RF.embedding(ub, u_idx, fm.user_padding_idx).view(-1) + g
+                col_bias = RF.embedding(ib, i_idx, fm.item_padding_idx).view(-1)
+            else:
+                row_bias = g.expand(ul.shape[0])
+        if self.logq is not None:
+            logq = RF.embedding(self.logq, i_idx, None).view(-1)
+        drop = None
+        if p_drop >= 1.0:
+            drop, p_drop = torch.zeros(ul.shape[0], ul.shape[0], ul.shape[1], dtype=torch.float32, device=ul.device), 0.0
+        loss, pos = RF.pair_softmax_loss(ul, il, u_ids, i_ids, mode, h=h, row_bias=row_bias, col_bias=col_bias, drop=drop,
+                                         seen=feed.seen, item_lo=feed.item_lo, logq=logq, temperature=self.temperature, p_drop=p_drop)
+        return pos, loss
 
 
 def _loss_and_backward(pred: torch.Tensor, ratings: torch.Tensor) -> torch.Tensor:

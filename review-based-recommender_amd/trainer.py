@@ -36,7 +36,13 @@ rating regression: every batch pair is joined by n_neg items its user has not ra
 (data.NegativeFeed), and the step minimises -log sigmoid(score(u, i+) - score(u, i-)) (train_step.BprObjective); the step log line
 keeps its format with the BPR loss under `loss` (its `rmse` field is sqrt of the mean loss then, not an RMSE);
 `select_by: "hr@K" | "ndcg@K" | "mrr"` (default "rmse"; K must be in rank_metrics; required with loss "bpr") makes best_model.pt
-and `patience` follow that validation metric, higher is better, and the rank line ends in `best <metric>: ...`.
+and `patience` follow that validation metric, higher is better, and the rank line ends in `best <metric>: ...`;
+`loss: "softmax"` (same preconditions as "bpr"; `softmax_temperature: 1.0`, `logq_correction: false`; n_neg / neg_seed are
+ignored) trains for ranking with the in-batch softmax: the batch stays the B observed pairs and every user's negatives are the other
+items of the batch -- less the pad id, the pair's own item and the items the user has rated in the training split -- scored from
+the towers' latent rows over all B x B pairs (data.InBatchFeed, train_step.InBatchSoftmaxObjective); logq_correction subtracts
+log((count_i + 1) / (N + I)) of the training examples from item i's logit; the step log line keeps its format with the loss under
+`loss`.
 """
 from __future__ import annotations
 
@@ -74,9 +80,10 @@ class EarlyStop(Exception):
 DEFAULTS = dict(log_dir="logs", dataset="dataset", log=True, log_idx=500, verbose=False, parallel=False, epochs=64,
                 batch_size=50, lr=0.002, max_grad_norm=5.0, patience=5, dropout=0.5, arch="CNN", use_pretrain=False,
                 num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False, eval_from_towers=False,
-                device_reviews=False, rank_metrics=[], loss="mse", n_neg=1, neg_seed=None, select_by="rmse")
+                device_reviews=False, rank_metrics=[], loss="mse", n_neg=1, neg_seed=None, select_by="rmse",
+                softmax_temperature=1.0, logq_correction=False)
 
-LOSSES = ("mse", "bpr")
+LOSSES = ("mse", "bpr", "softmax")
 
 
 def _rank_metric_of(select_by):
@@ -218,6 +225,19 @@ class ReviewExperiment:
             if metric is None:
                 raise ValueError("loss \"bpr\" needs a rank metric in select_by (\"hr@K\", \"ndcg@K\" or \"mrr\"): a "
                                  "pairwise loss does not fit ratings, so the validation RMSE cannot select the model")
+        if args.loss == "softmax":
+            t = args.softmax_temperature
+            if isinstance(t, bool) or not isinstance(t, (int, float)) or not (0.0 < float(t) < math.inf):
+                raise ValueError(f"softmax_temperature must be a positive number, got {t!r}")
+            if not (bool(args.device_cache) or bool(args.device_reviews)):
+                raise ValueError("loss \"softmax\" needs device_cache (--model deepconn or dual_att) or device_reviews (narre or "
+                                 "simple_siamese): the all-pairs loss reads the batch's ids from the id feed")
+            if bool(args.parallel):
+                raise ValueError("loss \"softmax\" is not available with parallel: the item latents of the other processes' "
+                                 "batches are not gathered")
+            if metric is None:
+                raise ValueError("loss \"softmax\" needs a rank metric in select_by (\"hr@K\", \"ndcg@K\" or \"mrr\"): a "
+                                 "ranking loss does not fit ratings, so the validation RMSE cannot select the model")
         self.select_metric = None if metric is None else args.select_by
         self.best_score = -math.inf          # the best select_by metric so far (higher is better); unused with "rmse"
         self.kind, self.args, self.quirks = kind, args, reference_quirks
@@ -259,6 +279,19 @@ class ReviewExperiment:
             self.objective = BprObjective(self.train_feed)
         self._make_dir()
         self.build_model()
+        if args.loss == "softmax":
+            # false negatives are the items the user has rated in the training split: the CSR the validation ranks against
+            from .recommend import Recommender
+            from .train_step import InBatchSoftmaxObjective
+            self._seen = Recommender.seen_from(self.train_set.examples, self.train_set.user_num, self.device)
+            self.train_feed = D.InBatchFeed(self.train_feed, self._seen)
+            logq = None
+            if bool(args.logq_correction):      # log sampling probability of an item as a batch column, add-one smoothed; once, on the host
+                n_items = self.cache.item.shape[0]
+                counts = torch.bincount(torch.tensor([int(e[1]) for e in self.train_set.examples], dtype=torch.int64),
+                                        minlength=n_items)[:n_items].double()
+                logq = torch.log((counts + 1.0) / (counts.sum() + n_items)).float().to(self.device)
+            self.objective = InBatchSoftmaxObjective(self.model, self.train_feed, temperature=float(args.softmax_temperature), logq=logq)
         # both splits were range-checked against their tables when they were loaded (data.validate_ranges): the per-forward
         # device-side check (one launch) is not needed on top
         self.model.validate_ids = False
@@ -416,7 +449,7 @@ class ReviewExperiment:
             key = tuple((t.shape, t.dtype) for t in batch)
             if self._graphed is None:
                 # recording runs warm-up steps: they must not use up the negative sampler's draws either
-                calls = self.train_feed.state.clone() if self.objective is not None else None
+                calls = self.train_feed.state.clone() if hasattr(self.train_feed, "state") else None
                 self._graphed = GraphedTrainStep.from_ids(self.model, self.optimizer, self.train_feed, u_ids, i_ids, ratings,
                                                           a.max_grad_norm, self.grad_sync, with_ids=with_ids,
                                                           objective=self.objective)
