@@ -80,8 +80,7 @@ __device__ __forceinline__ int tensor_of_chunk(const OptTable& T, long chunk) {
 }
 
 __device__ __forceinline__ float block_sum(float x, float* s_red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    x = wave_sum(x);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     __syncthreads();
     if (lane == 0) s_red[wave] = x;

@@ -8,16 +8,12 @@
 // kernel, which scales the token rows while gathering them (csrc/textcnn_fwd.hip, `gate`).
 // One output channel => no GEMM shape; these are HBM/L2-bound row dot products on the VALU.
 #include "rbr_common.h"
+#include "lds_bucket.h"
 
 #include <algorithm>
 
 namespace rbr {
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 typedef float f32x4g __attribute__((ext_vector_type(4)));
 
@@ -53,7 +49,7 @@ __global__ __launch_bounds__(256) void local_gate_fwd_kernel(int B, int L, int E
         float s = 0.f;
         for (int e = lane; e < E; e += 64)
             for (int j = 0; j < win; ++j) s = fmaf(s_rows[(t + j) * E + e], w[(long)e * win + j], s);
-        s = wsum(s);
+        s = wave_sum(s);
         if (lane == 0) gate[(long)b * L + l0 + t] = sigmoidf_(s + bias);
     }
 }
@@ -90,7 +86,7 @@ __device__ __forceinline__ void gate_bwd_dx_kernel(int B, int L, int E, int win,
     const int pad = (win - 1) / 2;
     const int nrow = min(kGWin, L - p0);
 
-    for (int k = tid; k < kGHash; k += 256) { s_hkey[k] = -1; s_hval[k] = kGWin; }
+    bucket_hash_clear<kGHash>(s_hkey, s_hval);
     for (int r = tid; r < kGWin; r += 256) {
         int t = -1;
         // c_out mode keeps the pad token: its row feeds the weight gradient (only its TABLE row gets no gradient)
@@ -107,62 +103,16 @@ __device__ __forceinline__ void gate_bwd_dx_kernel(int B, int L, int E, int win,
         }
     }
     __syncthreads();
-    for (int r = tid; r < kGWin; r += 256) {
-        const int t = s_tok[r];
-        int slot = -1;
-        if (t >= 0) {
-            unsigned hh = ((unsigned)t * 2654435761u) >> 22;
-            for (;;) {
-                const int old = atomicCAS(&s_hkey[hh], -1, t);
-                if (old == -1 || old == t) break;
-                hh = (hh + 1) & (kGHash - 1);
-            }
-            atomicMin(&s_hval[hh], r);
-            slot = (int)hh;
-        }
-        s_leader[r] = (short)slot;
-    }
+    // positions by token (lds_bucket.h): per-token counts and the dense key list
+    bucket_leaders<kGHash, false, true>(s_tok, kGWin, s_hkey, s_hval, s_leader, s_fill);
     __syncthreads();
-    for (int r = tid; r < kGWin; r += 256) {
-        const int slot = s_leader[r];
-        const int lead = slot >= 0 ? s_hval[slot] : -1;
-        s_leader[r] = (short)lead;
-        if (lead >= 0) atomicAdd(&s_fill[lead], 1);
-    }
+    if (wave == 0) bucket_scan<true, false>(lane, s_fill, kGWin, s_start, s_cnt, s_keys, &s_nkeys);
     __syncthreads();
-    if (wave == 0) {   // exclusive scan of the per-token counts, and of the leaders themselves (dense key list)
-        int run = 0, krun = 0;
-        for (int r0 = 0; r0 < kGWin; r0 += 64) {
-            const int r = r0 + lane;
-            const int c = s_fill[r];
-            int inc = c, kinc = c > 0;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int v = __shfl_up(inc, o), kv = __shfl_up(kinc, o);
-                if (lane >= o) { inc += v; kinc += kv; }
-            }
-            s_start[r] = (short)(run + inc - c);
-            s_cnt[r] = (short)c;
-            if (c > 0) s_keys[krun + kinc - 1] = (short)r;
-            run += __shfl(inc, 63);
-            krun += __shfl(kinc, 63);
-        }
-        if (lane == 0) s_nkeys = krun;
-    }
-    __syncthreads();
-    // a token's positions in ascending order (an atomic fill left them in arrival order: the tap sums below rounded differently
-    // from run to run); `lead` is the token's first position, so the walk starts there.  Up to 255 LDS reads for the last
-    // position of a window that holds one token, where the atomic fill took one.  Not measured in isolation; the whole backward
-    // of the token-product gate at the cfg4 tower shape (512 x 1024 Zipf ids, V = 50 k) went from 96 to 101 us with it, the
-    // row maps (rbr_datt_token_rows) from 21.6 to 15.8 us without the contended counter
-    for (int r = tid; r < kGWin; r += 256) {
-        const int lead = s_leader[r];
-        if (lead >= 0) {
-            int rank = 0;
-            for (int q = lead; q < r; ++q) rank += (s_leader[q] == lead);
-            s_sorted[s_start[lead] + rank] = (short)r;
-        }
-    }
+    // a token's positions in ASCENDING order (an atomic fill left them in arrival order: the tap sums below rounded differently
+    // from run to run).  Up to 255 LDS reads for the last position of a window that holds one token, where the atomic fill took
+    // one.  Not measured in isolation; the whole backward of the token-product gate at the cfg4 tower shape (512 x 1024 Zipf ids,
+    // V = 50 k) went from 96 to 101 us with it, the row maps (rbr_datt_token_rows) from 21.6 to 15.8 us without the contended counter
+    bucket_place_ordered(s_leader, kGWin, s_start, s_sorted);
     __syncthreads();
     // The folded rows leave the workgroup thread-parallel: a wave per token walked <= 64 tokens one after the other, each
     // with a dependent L2 read in front of its atomics (latency-bound: 88 us for the tap sums alone at cfg4).
@@ -542,10 +492,7 @@ __device__ __forceinline__ void gp_taps_kernel(int E, int win, int cap, const in
             }
 #pragma unroll
         for (int j = 0; j < kGateWP; ++j)
-            if (j < win) {
-#pragma unroll
-                for (int o = 8; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o);
-            }
+            if (j < win) acc[j] = wave_sum<16>(acc[j]);
         if (live && l < kGateWP) {
             float v = 0.f;
 #pragma unroll
@@ -788,7 +735,7 @@ __device__ __forceinline__ void gp_dw_final_kernel(int cap, int n_out, const int
     const int n_chunks = (min(*counter, cap) + kGpRows - 1) / kGpRows;
     float t = 0.f;
     for (int k = lane; k < n_chunks; k += 64) t += part[(long)k * n_out + o];
-    t = wsum(t);
+    t = wave_sum(t);
     if (lane == 0) { if (o < n_out - 1) dw[o] = t; else db0[0] = t; }
 }
 

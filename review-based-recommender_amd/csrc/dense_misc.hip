@@ -751,8 +751,7 @@ __global__ __launch_bounds__(256) void conv_shift_add_dbias_kernel(const ShiftAd
         const int b = (int)(k / S.L), l = (int)(k - (long)b * S.L);
         acc += d_out[((long)b * S.C + c) * S.L + l];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -11,12 +11,6 @@
 
 namespace rbr {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // d_l of one (pair, k) from the saved latents; the batch-reduction blocks of the backward recompute it with the same function
 __device__ __forceinline__ void head_dl(float su, float si, float dr, float dp, float hk, float& dul, float& dil, float& zdp) {
     const float prod = su * si;
@@ -310,8 +304,7 @@ __global__ __launch_bounds__(256) void head_fwd_pool_kernel(const ConvPlan P, co
         acc += d * d;
         if (mse.d_unit != nullptr) mse.d_unit[i] = d * (2.f / (float)B);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = wave_sum(acc);
     __syncthreads();
     if ((t & 63) == 0) s_l[0][t >> 6] = acc;
     __syncthreads();
@@ -444,8 +437,7 @@ __global__ __launch_bounds__(256) void mse_fwd_kernel(long n, const float* __res
         acc += d * d;
         if (d_unit != nullptr) d_unit[i] = d * (2.f / (float)n);       // d loss / d pred for an upstream gradient of 1
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) *loss = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (float)n;
@@ -485,8 +477,8 @@ __global__ __launch_bounds__(256) void bpr_loss_kernel(int B, int n_neg, const f
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { acc += __shfl_xor(acc, o); cnt += __shfl_xor(cnt, o); }
+    acc = wave_sum(acc);
+    cnt = wave_sum(cnt);
     if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = acc; s_red[1][threadIdx.x >> 6] = cnt; }
     __syncthreads();
     const float total = s_red[0][0] + s_red[0][1] + s_red[0][2] + s_red[0][3];
@@ -679,8 +671,7 @@ __global__ __launch_bounds__(256) void pair_dot_fwd_kernel(int B, int K, const f
     float s = 0.f;
     if (b < B)
         for (int k = l; k < K; k += 16) s = fmaf(x[(long)b * K + k], x[(long)(B + b) * K + k], s);
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    s = wave_sum<16>(s);
     if (b < B && l == 0) out[b] = s;
 }
 

@@ -306,12 +306,6 @@ struct RankArgs {
     int B, Ni, item_lo, S, vec;
 };
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 // Key of pair b's target from score_pair (the bits every other entry gives that pair).  A target outside [0, Ni) is never
 // dereferenced: row 0 stands in (the pair is unranked whatever its key).  false: the target's score is NaN.
 template <int MODE>

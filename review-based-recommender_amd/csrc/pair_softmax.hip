@@ -55,16 +55,14 @@ __device__ __forceinline__ float ps_mult(const PairSoftmax& S, unsigned long lon
 // sum / max over the 256 threads in a fixed order (xor-shuffle tree over 64 lanes, then the four wave results in order);
 // every thread gets the result.  s_w: 4 floats of LDS, free to be reused after the call returns.
 __device__ __forceinline__ float ps_block_sum(float v, float* s_w) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
     __syncthreads();
     return (s_w[0] + s_w[1]) + (s_w[2] + s_w[3]);
 }
 __device__ __forceinline__ float ps_block_max(float v, float* s_w) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    v = wave_max(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -107,8 +105,7 @@ __global__ __launch_bounds__(256) void pair_softmax_rows_kernel(const PairSoftma
                 acc = fmaf(u, v, acc);
             }
         }
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        acc = wave_sum<32>(acc);
         if (kk == 0) {
             float s = acc;
             if (S.row_bias != nullptr) s += rb;

@@ -10,6 +10,7 @@
 
 #include "../../include/rbr_hip.h"
 #include "rbr_launch.h"
+#include "rbr_wave.h"
 
 namespace rbr {
 

@@ -113,8 +113,7 @@ __global__ __launch_bounds__(256) void attn_bwd_sample_kernel(int B, int R, int 
                 const float g = (drop != nullptr) ? d_out[(long)b * H + hh] * drop[(long)b * H + hh] : d_out[(long)b * H + hh];
                 s = fmaf(g, fb[(long)r * H + hh], s);
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            s = wave_sum(s);
             if (lane == 0) s_da[r] = s + ((d_att != nullptr) ? d_att[(long)b * R + r] : 0.f);
         }
     }

@@ -7,6 +7,7 @@
 //     out[b,:] = sum_r s[r] x[r,:].
 // Nothing of shape [reviews, tokens, D] is ever written to HBM (the reference materialises it twice per tower).
 #include "rbr_common.h"
+#include "lds_bucket.h"
 
 #include <rocprim/rocprim.hpp>
 
@@ -31,8 +32,7 @@ __global__ __launch_bounds__(256) void bag_fwd_kernel(int n_rev, int T, int D, c
     const unsigned char* rm = mask ? mask + (long)r * T : nullptr;
     int cnt = 0;
     for (int l = lane; l < T; l += 64) cnt += (rm == nullptr || rm[l]) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    cnt = wave_sum(cnt);
     const float inv = 1.f / ((float)cnt + 1e-8f);
     if (lane == 0) inv_len[r] = inv;
     const bool vec = (D % 4 == 0) && ((((uintptr_t)table) & 15) == 0);
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void bag_bwd_sorted_kernel(long n_pos, int T, 
 }
 
 // Sort-free form (the default): one workgroup per window of kBagWin consecutive token positions buckets them by token in LDS
-// (hash table, as datt_gates.hip's gate backward), sums per distinct token the scaled gradient rows of the reviews it occurs
+// (lds_bucket.h), sums per distinct token the scaled gradient rows of the reviews it occurs
 // in, and adds ONE row per distinct token of the window.  f32 atomics are served per 64-byte request (~25 G/s) and requests
 // to one line queue behind each other (~35 ns): a Zipf-hot token now sends one row per window (~550 of them at the toys
 // shape), not one per occurrence -- and the 18 launches of the capture-safe merge sort are gone.
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(256) void bag_bwd_bucket_kernel(long n_pos, int T, 
     __shared__ int s_nkeys;
     const long p0 = (long)blockIdx.x * kBagWin;
     const int tid = threadIdx.x, lane = tid & 63;
-    for (int k = tid; k < kBagHash; k += 256) { s_hkey[k] = -1; s_hval[k] = kBagWin; }
+    bucket_hash_clear<kBagHash>(s_hkey, s_hval);
     for (int r = tid; r < kBagWin; r += 256) {
         const long k = p0 + r;
         int t = -1, rev = 0;
@@ -182,54 +182,12 @@ __global__ __launch_bounds__(256) void bag_bwd_bucket_kernel(long n_pos, int T, 
         s_tok[r] = t; s_rev[r] = rev; s_inv[r] = inv; s_fill[r] = 0;
     }
     __syncthreads();
-    for (int r = tid; r < kBagWin; r += 256) {
-        const int t = s_tok[r];
-        int slot = -1;
-        if (t >= 0) {
-            unsigned hh = ((unsigned)t * 2654435761u) >> 21;              // kBagHash = 2^11
-            for (;;) {
-                const int old = atomicCAS(&s_hkey[hh], -1, t);
-                if (old == -1 || old == t) break;
-                hh = (hh + 1) & (kBagHash - 1);
-            }
-            atomicMin(&s_hval[hh], r);
-            slot = (int)hh;
-        }
-        s_leader[r] = (short)slot;
-    }
+    // positions by token (lds_bucket.h): per-token counts, dense key list, positions of a token in arrival order
+    bucket_leaders<kBagHash, false, true>(s_tok, kBagWin, s_hkey, s_hval, s_leader, s_fill);
     __syncthreads();
-    for (int r = tid; r < kBagWin; r += 256) {
-        const int slot = s_leader[r];
-        const int lead = slot >= 0 ? s_hval[slot] : -1;
-        s_leader[r] = (short)lead;
-        if (lead >= 0) atomicAdd(&s_fill[lead], 1);
-    }
+    if (tid < 64) bucket_scan<true, true>(lane, s_fill, kBagWin, s_start, s_cnt, s_keys, &s_nkeys);
     __syncthreads();
-    if (tid < 64) {      // exclusive scan of the per-token counts and of the leaders (dense key list)
-        int run = 0, krun = 0;
-        for (int r0 = 0; r0 < kBagWin; r0 += 64) {
-            const int r = r0 + lane;
-            const int c = s_fill[r];
-            int inc = c, kinc = c > 0;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int v = __shfl_up(inc, o), kv = __shfl_up(kinc, o);
-                if (lane >= o) { inc += v; kinc += kv; }
-            }
-            s_start[r] = (short)(run + inc - c);
-            s_cnt[r] = (short)c;
-            s_fill[r] = 0;
-            if (c > 0) s_keys[krun + kinc - 1] = (short)r;
-            run += __shfl(inc, 63);
-            krun += __shfl(kinc, 63);
-        }
-        if (lane == 0) s_nkeys = krun;
-    }
-    __syncthreads();
-    for (int r = tid; r < kBagWin; r += 256) {
-        const int lead = s_leader[r];
-        if (lead >= 0) s_sorted[s_start[lead] + atomicAdd(&s_fill[lead], 1)] = (short)r;
-    }
+    bucket_place_arrival(kBagWin, [&](int r) { return (int)s_leader[r]; }, s_start, s_fill, s_sorted);
     __syncthreads();
     const int total = s_nkeys * D;
     constexpr int kU = 4;                            // items in flight per thread: their first gradient rows before the first atomic

@@ -20,6 +20,7 @@
 //                token in LDS; one wave per token sums them in registers and adds one row to dtable with
 //                256-byte contiguous f32 atomics.
 #include "rbr_common.h"
+#include "lds_bucket.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -428,7 +429,7 @@ __global__ __launch_bounds__(256) void dx_window_kernel(const BwdArgs A, const i
     const int piece = kTile * DC;                 // one channel tile of the packed image
     const int dcstride = A.tiles_total * piece;   // packed[s][dc][tile][slot][dd]
 
-    for (int k = tid; k < kHash; k += 256) { s_hkey[k] = -1; s_hval[k] = kWinMax; }
+    bucket_hash_clear<kHash>(s_hkey, s_hval);
     for (int r = tid; r < kWin; r += 256) {
         const int p = p0 + r;
         int t = -1;
@@ -436,27 +437,9 @@ __global__ __launch_bounds__(256) void dx_window_kernel(const BwdArgs A, const i
         s_tok[r] = t;
     }
     __syncthreads();
-    // leader[r] = first row of the window that carries the same token (hash table, then a min per slot)
-    for (int r = tid; r < kWin; r += 256) {
-        const int t = s_tok[r];
-        int slot = -1;
-        if (t >= 0) {
-            unsigned hh = ((unsigned)t * 2654435761u) >> 22;   // 10 bits
-            for (;;) {
-                const int old = atomicCAS(&s_hkey[hh], -1, t);
-                if (old == -1 || old == t) break;
-                hh = (hh + 1) & (kHash - 1);
-            }
-            atomicMin(&s_hval[hh], r);
-            slot = (int)hh;
-        }
-        s_leader[r] = (short)slot;       // temporarily the hash slot
-    }
-    __syncthreads();
-    for (int r = tid; r < kWin; r += 256) {
-        const int slot = s_leader[r];
-        s_leader[r] = (short)(slot >= 0 ? s_hval[slot] : r);
-    }
+    // leader[r] = first row of the window that carries the same token, once per window (lds_bucket.h); a masked row leads
+    // itself (no item ever names it).  The items of each channel batch are counted and placed below.
+    bucket_leaders<kHash, true, false>(s_tok, kWin, s_hkey, s_hval, s_leader, nullptr);
 
     for (int c0 = 0; c0 < C; c0 += kChanBatch) {
         const int nc = min(kChanBatch, C - c0);
@@ -488,27 +471,9 @@ __global__ __launch_bounds__(256) void dx_window_kernel(const BwdArgs A, const i
             atomicAdd(&s_fill[s_leader[p - p0]], 1);          // per-key item count (int atomics)
         }
         __syncthreads();
-        if (wave == 0) {   // exclusive scan of the per-key counts by one wave
-            int run = 0;
-            for (int r0 = 0; r0 < kWin; r0 += 64) {
-                const int r = r0 + lane;
-                const int c = (r < kWin) ? s_fill[r] : 0;
-                int inc = c;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const int v = __shfl_up(inc, o);
-                    if (lane >= o) inc += v;
-                }
-                if (r < kWin) { s_start[r] = (short)(run + inc - c); s_cnt[r] = (short)c; s_fill[r] = 0; }
-                run += __shfl(inc, 63);
-            }
-        }
+        if (wave == 0) bucket_scan<false, true>(lane, s_fill, kWin, s_start, s_cnt, nullptr, nullptr);
         __syncthreads();
-        const int n = s_count;
-        for (int k = tid; k < n; k += 256) {
-            const int key = s_leader[s_item_row[k]];
-            s_sorted[s_start[key] + atomicAdd(&s_fill[key], 1)] = (short)k;
-        }
+        bucket_place_arrival(s_count, [&](int k) { return (int)s_leader[s_item_row[k]]; }, s_start, s_fill, s_sorted);
         __syncthreads();
         // ---- one wave per token: register accumulation, then one row of atomics -------------------
 #ifdef RBR_DIAG
@@ -562,8 +527,7 @@ __global__ __launch_bounds__(256) void dx_window_kernel(const BwdArgs A, const i
                                 dot += gg[v] * (pr.x + pr.y + pr.z + pr.w);
                             }
                             if (gate != nullptr && dgate != nullptr && q0 + v < cnt) {
-#pragma unroll
-                                for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+                                dot = wave_sum(dot);
                                 if (lane == 0) atomicAdd(dgate + tok[v], dot);
                             }
                         }
@@ -625,8 +589,7 @@ __global__ __launch_bounds__(256) void dx_window_kernel(const BwdArgs A, const i
                         }
                     }
                     if (gate != nullptr && dgate != nullptr) {
-#pragma unroll
-                        for (int o = 32; o > 0; o >>= 1) dot += __shfl_xor(dot, o);
+                        dot = wave_sum(dot);
                         if (lane == 0) atomicAdd(dgate + tok, dot);
                     }
                 }

@@ -110,8 +110,7 @@ __device__ __forceinline__ void compact_pack_kernel(const PackJob& J, int nb_com
             const int4 m = u4[q];
             c += __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+        c = wave_sum(c);
         const int v = below + threadIdx.x;
         const int u = (v < V) ? used[v] : 0;
         const unsigned long long b = __ballot(u);
@@ -482,8 +481,7 @@ __device__ __forceinline__ void g_times_w_kernel(const ProdBwdArgs& A, const int
     }
     if (compact) {            // every workgroup writes its partial (zero when it had no rows): fixed-order reduction later
         __shared__ float s_sq[kWavesPerWG];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+        sq = wave_sum(sq);
         if (lane == 0) s_sq[wave] = sq;
         __syncthreads();
         if (threadIdx.x == 0) sq_part[blockIdx.x] = (s_sq[0] + s_sq[1]) + (s_sq[2] + s_sq[3]);
@@ -579,8 +577,7 @@ __global__ __launch_bounds__(256) void taps_owner_count_kernel(long total, int n
         const int t = tok[k];
         c += (t >= 0 && t % n_sets == rank) ? 1 : 0;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) s_c[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) blk_cnt[blockIdx.x] = (s_c[0] + s_c[1]) + (s_c[2] + s_c[3]);
@@ -603,8 +600,8 @@ __global__ __launch_bounds__(256) void taps_owner_keys_kernel(const ProdBwdArgs 
         all += c;
         if (i < (int)blockIdx.x) before += c;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { before += __shfl_xor(before, o); all += __shfl_xor(all, o); }
+    before = wave_sum(before);
+    all = wave_sum(all);
     if (lane == 0) { s_red[0][wave] = before; s_red[1][wave] = all; }
     __syncthreads();
     before = (s_red[0][0] + s_red[0][1]) + (s_red[0][2] + s_red[0][3]);

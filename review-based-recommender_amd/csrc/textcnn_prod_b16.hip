@@ -210,8 +210,7 @@ __device__ __forceinline__ void prod_gemm_b16_kernel(const B16Gemm& g) {
         }
     }
     if (g.sq_part != nullptr) {          // the rows' share of the gradient norm: lanes by shuffle, waves in wave order
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
+        sq = wave_sum(sq);
         float* s_sq = reinterpret_cast<float*>(smem);
         __builtin_amdgcn_s_barrier();      // every wave is out of the K loop: the ring is free
         if (lane == 0) s_sq[wave] = sq;

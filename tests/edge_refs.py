@@ -1,5 +1,6 @@
-"""Plain float64 restatements, with per-element error bounds, of the ops the edge tests of the rating head, nn.Linear and
-clip + Adam compare the HIP kernels with (tests/test_pair_head_edges_gpu.py, test_linear_edges_gpu.py, test_clip_adam_edges_gpu.py).
+"""Plain float64 restatements, with per-element error bounds, of the ops the edge tests of the rating head, nn.Linear,
+clip + Adam and the SimpleSiamese review bag compare the HIP kernels with (tests/test_pair_head_edges_gpu.py,
+test_linear_edges_gpu.py, test_clip_adam_edges_gpu.py, test_review_bag_edges_gpu.py).
 tests/test_edge_refs_host.py checks every formula here against torch autograd / torch.optim.Adam in float64 on the CPU.
 
 Every function takes f32 (or already float64) CPU tensors and computes in float64.  Beside each value it returns `Abs`, the same
@@ -156,6 +157,34 @@ def head_bwd(uf, itf, uid, iid, P, ul, il, drop, d_pred, pad_u, pad_i):
     for k in val:
         out[k] = (val[k], ab[k], n[k])
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------- review bag
+def review_bag(table, ids, mask, drop, d_out, padding_idx):
+    """SimpleSiamese's bag of embeddings and its table gradient -> {name: (value, Abs, n)}.  With inv_len[r] = 1 / (sum_l mask[r,l]
+    + 1e-8) (mask None: every position counts) and drop None = 1:
+      out[r, :]    = drop[r, :] * inv_len[r] * sum_{l: mask[r,l]} table[ids[r,l], :]               n = unmasked positions of r
+      dtable[t, :] = sum_{(r,l): ids[r,l] = t, mask[r,l], t != padding_idx} d_out[r, :] * inv_len[r] * drop[r, :]
+                                                                                                 n = those occurrences of t
+    A padding token is read like any other in the forward (its table row is what the model keeps there) and gets no gradient.
+    A term's own roundings -- inv_len (the division; the 1e-8 is below f32 resolution from one position on), the products with
+    inv_len and drop -- are the 4 of (n + 4)."""
+    table, drop, d = f64(table), f64(drop), f64(d_out)
+    n_rev, T = ids.shape
+    V, D = table.shape
+    m = torch.ones(n_rev, T, dtype=torch.float64) if mask is None else mask.cpu().double()
+    dr = torch.ones(n_rev, D, dtype=torch.float64) if drop is None else drop
+    inv = 1.0 / (m.sum(1) + 1e-8)
+    rows = table[ids] * m.unsqueeze(2)
+    scale = (inv.unsqueeze(1) * dr)
+    out, aout = rows.sum(1) * scale, rows.abs().sum(1) * scale.abs()
+    live = m if padding_idx is None else m * (ids != padding_idx).double()
+    flat, w = ids.reshape(-1), live.reshape(-1, 1)
+    g = (d * scale).repeat_interleave(T, 0) * w
+    dt = torch.zeros(V, D, dtype=torch.float64).index_add_(0, flat, g)
+    adt = torch.zeros(V, D, dtype=torch.float64).index_add_(0, flat, g.abs())
+    occ = torch.zeros(V, dtype=torch.float64).index_add_(0, flat, w.reshape(-1))
+    return {"out": (out, aout, m.sum(1, keepdim=True)), "dtable": (dt, adt, occ.unsqueeze(1))}
 
 
 # ----------------------------------------------------------------------------------------------------------------- clip + Adam

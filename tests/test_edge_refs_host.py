@@ -1,7 +1,7 @@
-"""The float64 formulas of tests/edge_refs.py -- the references of the GPU edge tests of the rating head, nn.Linear and
-clip + Adam -- against torch on the CPU: the head backward and the linear activation backward from a saved output against
-autograd, the one-step Adam against clip_grad_norm_ + torch.optim.Adam, all in float64 to 1e-12 relative.  Then the bound
-formulas on an f32 CPU computation of the same ops: the reference alone must stay inside them."""
+"""The float64 formulas of tests/edge_refs.py -- the references of the GPU edge tests of the rating head, nn.Linear,
+clip + Adam and the review bag -- against torch on the CPU: the head backward, the linear activation backward from a saved
+output and the review bag against autograd, the one-step Adam against clip_grad_norm_ + torch.optim.Adam, all in float64 to
+1e-12 relative.  Then the bound formulas on an f32 CPU computation of the same ops: the reference alone must stay inside them."""
 import numpy as np
 import pytest
 import torch
@@ -112,6 +112,38 @@ def test_head_reference_matches_autograd(B, H, K, pads, with_drop):
            "dib": torch.zeros(I).index_add_(0, iid, d_pred * (iid != pad_i).float())}
     for k, (val, ab, n) in R.head_bwd(uf, itf, uid, iid, P, ul32, il32, drop, d_pred, pad_u, pad_i).items():
         R.check("host-head", k, got[k], val, R.bound_of(n, ab))
+
+
+# ----------------------------------------------------------------------------------------------------------------- review bag
+def _bag_cases():
+    import test_review_bag_edges_gpu as G
+    return G
+
+
+@pytest.mark.parametrize("name", list(_bag_cases().CASES))
+def test_review_bag_reference_matches_autograd(name):
+    """Every case of tests/test_review_bag_edges_gpu.py: the restatement against autograd, then its bounds on an f32 evaluation."""
+    table, ids, mask, drop, d_out, pad = _bag_cases().inputs(name)
+    n_rev, T = ids.shape
+    leaf = table.double().clone().requires_grad_(True)
+    m = torch.ones(n_rev, T, dtype=torch.float64) if mask is None else mask.double()
+    x = F.embedding(ids, leaf, padding_idx=pad) * m.unsqueeze(2)
+    out = x.sum(1) / (m.sum(1, keepdim=True) + 1e-8) * (1.0 if drop is None else drop.double())
+    (out * d_out.double()).sum().backward()
+    ref = R.review_bag(table, ids, mask, drop, d_out, pad)
+    _close("out", ref["out"][0], out.detach())
+    _close("dtable", ref["dtable"][0], leaf.grad)
+    # f32, operation by operation as the kernels: inv_len once per review, the sums in torch's order
+    m32 = m.float()
+    inv32 = 1.0 / (m32.sum(1) + np.float32(1e-8))
+    dr32 = torch.ones(n_rev, table.shape[1]) if drop is None else drop
+    out32 = (table[ids] * m32.unsqueeze(2)).sum(1) * inv32.unsqueeze(1) * dr32
+    live = m32 if pad is None else m32 * (ids != pad).float()
+    g32 = (d_out * inv32.unsqueeze(1) * dr32).repeat_interleave(T, 0) * live.reshape(-1, 1)
+    dt32 = torch.zeros_like(table).index_add_(0, ids.reshape(-1), g32)
+    assert out32.dtype == dt32.dtype == torch.float32
+    for k, got in (("out", out32), ("dtable", dt32)):
+        R.check("host-bag", f"{name} {k}", got, ref[k][0], R.bound_of(ref[k][2], ref[k][1]))
 
 
 # ----------------------------------------------------------------------------------------------------------------- clip + Adam
