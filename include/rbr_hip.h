@@ -182,6 +182,22 @@ struct rbr_id_set;
 int rbr_textcnn_prod_prepare_ids(const rbr_textcnn_desc* d, int32_t n_sets, const struct rbr_id_set* sets, int64_t* err,
                                  const int64_t* ids, const uint8_t* mask, const float* const* W, int32_t* pidx, void* ws,
                                  void* stream);
+/*   prod_prepare_ids_kept: the same stage in TWO launches, for a caller that keeps `ws` from call to call.  Contract: the LIST
+ *            STATE of `ws` that a call needs zero -- the token marks and two words of the token list's counter block (an arrival
+ *            ticket and the slab scan's counter) -- is zero on entry (a workspace zero-filled once when it was allocated is), and
+ *            every call that returns 0 leaves it zero: launch A checks, cleans and marks the token ids and scans the slabs, launch
+ *            B builds the list, writes the WHOLE row mask and the other counters (so they need no clearing), publishes the slab
+ *            count and clears the marks behind their last reader.  After a non-zero return the state is undefined: zero-fill `ws` again before the next
+ *            call.  Calls on one `ws` must be ordered (one stream, or events).  The token sets' limit must not exceed d->V.
+ *            Results (list, maps, counts, clean ids, err, work list as a set) are those of prod_prepare_ids.  Not available inside
+ *            a pair region.  rbr_textcnn_prod_prepare[_ids] stay self-initialising and take any workspace. */
+int rbr_textcnn_prod_prepare_ids_kept(const rbr_textcnn_desc* d, int32_t n_sets, const struct rbr_id_set* sets, int64_t* err,
+                                      const int64_t* ids, const uint8_t* mask, const float* const* W, int32_t* pidx, void* ws,
+                                      void* stream);
+/* Byte offsets of the list state inside a forward workspace, for the owner's checks and tests: off[0..1] = marks (offset, bytes),
+ * off[2..3] = row mask, off[4..5] = the two counter words that must be zero between calls.  Returns 0, or an error when the
+ * product formulation does not apply. */
+int rbr_textcnn_prod_list_state(const rbr_textcnn_desc* d, int64_t off[6]);
 
 /* Stage 3: reduce the slabs of each document, add the conv bias, apply the activation.
  * feat[n_docs, C] (C = sum ch[w]); argmax[n_docs, C] = first position attaining the max.
@@ -363,7 +379,8 @@ int rbr_pair_head_fwd_train(int32_t B, int32_t H, int32_t K, const float* u_feat
  * batch were blanked and not encoded); feat / argmax rows of r are then copies of first[r]'s.  ticket: one int32
  * in device memory, zero before the first call (the launch re-arms it); calls that may be in flight at the same time (different
  * streams) need a ticket each -- the binding keeps one per (device, stream).  RBR_ERR_UNSUPPORTED when the conv has more than
- * 256 channel slots. */
+ * 256 channel slots.  (rbr_pair_head_fwd_pool_ex with d_feat_unit accepts a NULL ticket: then loss / d_pred_unit are NOT written
+ * by this launch -- rbr_pair_head_bwd_ex computes them.) */
 int rbr_pair_head_fwd_pool(const rbr_textcnn_desc* d, const float* pval, const int32_t* pidx, const float* const* bias,
                            float* feat, int32_t* argmax, const int64_t* first, int32_t K, const int64_t* u_id, const int64_t* i_id,
                            const rbr_head_params* p, const float* drop, float p_drop, uint64_t seed, uint64_t* rng_state,
@@ -395,6 +412,18 @@ int rbr_pair_head_bwd(int32_t B, int32_t H, int32_t K, const float* u_feat, cons
                       const int64_t* u_id, const int64_t* i_id, const rbr_head_params* p, const float* drop,
                       const float* ul, const float* il, const float* d_pred, int32_t pad_u, int32_t pad_i,
                       const rbr_head_grads* g, float* d_ufeat, float* d_ifeat, float* ws, void* stream);
+/* The same launch with the trainers' MSE in it, for a step whose forward ran rbr_pair_head_fwd_pool_ex with d_feat_unit and a NULL
+ * ticket (that launch then stores pred and ends: no loss, no ticket, no fences).  d_pred NULL: the upstream gradient is
+ * d loss / d pred[b] = (pred[b] - target[b]) * 2/B, computed where it is used (the bits of rbr_mse_loss_fwd's d_pred_unit), and one
+ * more workgroup writes loss[0] -- and d_pred_unit [B] unless NULL -- with rbr_mse_loss_fwd's thread -> element mapping and
+ * reduction order: the same bits.  The loss is an output nothing in the step waits for; here it is computed beside the batch
+ * reductions instead of at the end of the forward's serial chain.  d_pred != NULL: exactly rbr_pair_head_bwd (pred, target, loss,
+ * d_pred_unit are ignored). */
+int rbr_pair_head_bwd_ex(int32_t B, int32_t H, int32_t K, const float* u_feat, const float* i_feat,
+                         const int64_t* u_id, const int64_t* i_id, const rbr_head_params* p, const float* drop,
+                         const float* ul, const float* il, const float* d_pred, int32_t pad_u, int32_t pad_i,
+                         const rbr_head_grads* g, float* d_ufeat, float* d_ifeat, const float* pred, const float* target,
+                         float* loss, float* d_pred_unit, void* stream);
 /* ---- nn.Dropout multiplier (deepconn/layers.py:202, narre.py:73, dual_att/dual_att.py:33, simple_siamese/layers.py:7-68):
  *   out[i] = 0 with probability p, else 1/(1-p), i < n.  Philox4x32-10 keyed by `seed`, counter (i/4, call number).
  *   state: 2 x uint64 in device memory, zero-initialised by the caller once; state[0] is the call number, advanced by

@@ -291,6 +291,9 @@ __global__ __launch_bounds__(256) void head_fwd_pool_kernel(const ConvPlan P, co
         head_pair_dfeat(P.C, K, s_bwd, s_bwd + K4, s_bwd + 2 * K4, s_dp, p, s_bwd, s_bwd + K4, d_feat_unit + (long)b * P.C,
                         d_feat_unit + (long)(B + b) * P.C);
     }
+    // No ticket: the loss is not computed here but by rbr_pair_head_bwd_ex's loss workgroup, off the step's serial chain (nothing
+    // on the chain reads it since d_feat_unit exists).  pred[b] is stored and the block ends: no fences, no last-block pass.
+    if (mse.ticket == nullptr) return;                          // kernel argument: uniform over the launch
     if (t == 0) {
         __threadfence();                                        // pred[b] is visible before the ticket is taken
         s_last = atomicAdd(mse.ticket, 1) == B - 1;
@@ -319,13 +322,24 @@ __global__ __launch_bounds__(256) void head_fwd_pool_kernel(const ConvPlan P, co
 // reductions dW = feat^T @ d_l, db, dh, dg, one workgroup per output row (side, r), 8 thread groups striding the batch in a
 // fixed partition and order (bitwise reproducible); they recompute d_l from ul / il / drop / d_pred (a few flops) instead
 // of waiting for the pair blocks to publish it, so both halves run side by side.
+// FROM_PRED (rbr_pair_head_bwd_ex with d_pred NULL): the upstream gradient is the MSE's for a root gradient of 1, taken from
+// pred / target with the operations of mse_fwd_kernel (the bits of its d_unit[b]).
+struct HeadLoss {
+    const float* pred;         // [B]
+    const float* target;       // [B]
+    float* loss;               // [1], written by the loss workgroup (the block behind the reduction blocks)
+    float* d_unit;             // [B] or NULL
+};
+// FROM_PRED is a template argument, not a test of d_pred: behind a run-time branch the reduction blocks' 40 loads per round no
+// longer leave together and the launch takes twice as long (23.3 us against 11.9 at cfg2).
+template <bool FROM_PRED>
 __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int H, int K, const float* __restrict__ uf,
                                                        const float* __restrict__ itf, const long long* __restrict__ uid,
                                                        const long long* __restrict__ iid, const rbr_head_params p,
                                                        const float* __restrict__ drop, const float* __restrict__ ul,
                                                        const float* __restrict__ il, const float* __restrict__ d_pred,
                                                        int pad_u, int pad_i, const rbr_head_grads g,
-                                                       float* __restrict__ d_uf, float* __restrict__ d_if) {
+                                                       float* __restrict__ d_uf, float* __restrict__ d_if, const HeadLoss lj) {
     // (Measured and dropped in round 3: clearing the conv backward's G with extra workgroups of this launch instead of the
     // zero_g_rows launch -- the step got 19 us SLOWER: the weight-gradient branch then starts beside the L2-bound sparse product
     // instead of beside the zero fill and the atomics-bound G build, and both crawl.  Round 4, the same 64 MB cleared by extra
@@ -340,7 +354,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int H, int K, cons
         float* s_dul = sm;
         float* s_dil = sm + K4;
         const long u = uid[b], it = iid[b];
-        const float dp = d_pred[b];
+        // (__fmul_rn: the product is rounded here, as the stored d_unit[b] is, whatever sum it enters below)
+        const float dp = FROM_PRED ? __fmul_rn(lj.pred[b] - lj.target[b], 2.f / (float)B) : d_pred[b];
         // d_uf NULL: the forward launch already wrote d_feat (rbr_pair_head_fwd_pool_ex's d_feat_unit); the atomics remain
         head_pair_dfeat(H, K, ul + (long)b * K, il + (long)b * K, drop != nullptr ? drop + (long)b * K : nullptr, dp, p, s_dul, s_dil,
                         d_uf != nullptr ? d_uf + (long)b * H : nullptr, d_uf != nullptr ? d_if + (long)b * H : nullptr);
@@ -357,6 +372,24 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int H, int K, cons
     float (*red)[8][32] = reinterpret_cast<float (*)[8][32]>(sm);
     const int rows = H + 1;                 // row H holds the bias / h / g reductions
     const int rb = blockIdx.x - B;
+    if (FROM_PRED && rb == 2 * rows) {
+        // Loss role (one workgroup, launched only with lj.loss): nn.MSELoss(mean) as mse_fwd_kernel computes it -- the same thread ->
+        // element mapping and reduction order, the same bits -- here, on the weight-gradient branch, where nothing waits for it,
+        // instead of behind a ticket and two agent-scope fences at the end of the forward's head launch.
+        // RBR_LOSS_IN_BWD=0 (functional.py) restores the ticketed tail.  Measured at cfg2: head_fwd_pool
+        // 28.6 -> 22.3 us on the chain, this launch 11.9 -> 16.6 us off it (it still ends 3 us before g_times_w does).
+        float acc = 0.f;
+        for (int i = t; i < B; i += 256) {
+            const float d = lj.pred[i] - lj.target[i];
+            acc += d * d;
+            if (lj.d_unit != nullptr) lj.d_unit[i] = d * (2.f / (float)B);
+        }
+        acc = wave_sum(acc);
+        if ((t & 63) == 0) sm[t >> 6] = acc;
+        __syncthreads();
+        if (t == 0) *lj.loss = (sm[0] + sm[1] + sm[2] + sm[3]) / (float)B;
+        return;
+    }
     const int side = rb / rows, r = rb % rows;
     const int kk = t & 31, grp = t >> 5;
     const float* ft = side ? itf : uf;
@@ -368,7 +401,8 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int H, int K, cons
             // 8 batch rows per round: their 40 loads are issued together (a row past the batch repeats row `grp` with
             // d_pred = 0, which contributes exact zeros)
             for (int b0 = grp; b0 < B; b0 += 64) {
-                float vu[8], vi[8], vd[8], vp[8], vf[8];
+                float vu[8], vi[8], vd[8], vp[8], vf[8], vt[8];
+                const float* pp = FROM_PRED ? lj.pred : d_pred;
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
                     const int b = b0 + 8 * u;
@@ -377,8 +411,13 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(int B, int H, int K, cons
                     vu[u] = ul[bb * K + k];
                     vi[u] = il[bb * K + k];
                     vd[u] = (drop != nullptr) ? drop[bb * K + k] : 1.f;
-                    vp[u] = ok ? d_pred[bb] : 0.f;
+                    vp[u] = ok ? pp[bb] : 0.f;
+                    vt[u] = (FROM_PRED && ok) ? lj.target[bb] : 0.f;
                     vf[u] = (r < H) ? ft[bb * H + r] : 0.f;
+                }
+                if (FROM_PRED) {      // d loss / d pred as mse_fwd_kernel writes it (a row past the batch: (0 - 0) * 2/B = 0)
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) vp[u] = __fmul_rn(vp[u] - vt[u], 2.f / (float)B);      // rounded here: no FMA into gs
                 }
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {
@@ -613,7 +652,9 @@ extern "C" int rbr_pair_head_fwd_pool_ex(const rbr_textcnn_desc* d, const float*
     if (!(p_drop >= 0.f && p_drop < 1.f)) { set_error("pair_head_fwd_pool: p_drop=%f outside [0,1)", (double)p_drop); return RBR_ERR_BAD_ARG; }
     if (p_drop > 0.f && (!rng_state || !drop_out)) { set_error("pair_head_fwd_pool: dropout needs rng_state and drop_out"); return RBR_ERR_BAD_ARG; }
     if (zero_n < 0 || (zero_n > 0 && !zero_buf)) { set_error("pair_head_fwd_pool: bad zero buffer"); return RBR_ERR_BAD_ARG; }
-    if (target != nullptr && (!loss || !ticket)) { set_error("pair_head_fwd_pool: the loss needs loss and ticket"); return RBR_ERR_BAD_ARG; }
+    // ticket NULL with d_feat_unit: no loss in this launch (rbr_pair_head_bwd_ex computes it); loss / d_pred_unit are not written
+    if (target != nullptr && ticket == nullptr && d_feat_unit == nullptr) { set_error("pair_head_fwd_pool: the loss needs loss and ticket"); return RBR_ERR_BAD_ARG; }
+    if (target != nullptr && ticket != nullptr && !loss) { set_error("pair_head_fwd_pool: the loss needs loss and ticket"); return RBR_ERR_BAD_ARG; }
     if (d_feat_unit != nullptr && !target) { set_error("pair_head_fwd_pool: d_feat_unit needs the loss target"); return RBR_ERR_BAD_ARG; }
     HeadTrain tr{};
     tr.p_drop = p_drop; tr.seed = seed;
@@ -644,22 +685,52 @@ extern "C" int rbr_pair_head_fwd_pool(const rbr_textcnn_desc* d, const float* pv
 
 extern "C" size_t rbr_pair_head_bwd_ws_floats(int32_t B, int32_t K) { (void)B; (void)K; return 0; }
 
+// d_pred NULL: the MSE's own gradient for a root gradient of 1, from pred / target, and one more workgroup writes the loss
+// (and d_pred_unit) -- see rbr_pair_head_bwd_ex in rbr_hip.h.
+static int head_bwd_launch(int32_t B, int32_t H, int32_t K, const float* u_feat, const float* i_feat, const int64_t* u_id,
+                           const int64_t* i_id, const rbr_head_params* p, const float* drop, const float* ul, const float* il,
+                           const float* d_pred, int32_t pad_u, int32_t pad_i, const rbr_head_grads* g, float* d_ufeat, float* d_ifeat,
+                           const HeadLoss& lj, void* stream) {
+    if (!head_args_ok(B, H, K)) return RBR_ERR_BAD_ARG;
+    if (!u_feat || !i_feat || !u_id || !i_id || !p || !ul || !il || !g || (!d_ufeat != !d_ifeat)) {
+        set_error("null pointer");
+        return RBR_ERR_BAD_ARG;
+    }
+    if (d_pred == nullptr && (!lj.pred || !lj.target || !lj.loss)) {
+        set_error("pair_head_bwd: without d_pred the loss role needs pred, target and loss");
+        return RBR_ERR_BAD_ARG;
+    }
+    const bool loss_role = d_pred == nullptr;
+    const size_t lds = std::max((size_t)2 * ((K + 3) & ~3), (size_t)3 * 8 * 32) * sizeof(float);
+    if (loss_role)
+        hipLaunchKernelGGL(head_bwd_kernel<true>, dim3((unsigned)(B + 2 * (H + 1) + 1)), dim3(256), lds, (hipStream_t)stream,
+                           B, H, K, u_feat, i_feat, reinterpret_cast<const long long*>(u_id), reinterpret_cast<const long long*>(i_id), *p,
+                           drop, ul, il, d_pred, pad_u, pad_i, *g, d_ufeat, d_ifeat, lj);
+    else
+        hipLaunchKernelGGL(head_bwd_kernel<false>, dim3((unsigned)(B + 2 * (H + 1))), dim3(256), lds, (hipStream_t)stream,
+                           B, H, K, u_feat, i_feat, reinterpret_cast<const long long*>(u_id), reinterpret_cast<const long long*>(i_id), *p,
+                           drop, ul, il, d_pred, pad_u, pad_i, *g, d_ufeat, d_ifeat, HeadLoss{});
+    RBR_CHECK_LAUNCH("pair_head_bwd launch");
+    return 0;
+}
+
 extern "C" int rbr_pair_head_bwd(int32_t B, int32_t H, int32_t K, const float* u_feat, const float* i_feat,
                                  const int64_t* u_id, const int64_t* i_id, const rbr_head_params* p, const float* drop,
                                  const float* ul, const float* il, const float* d_pred, int32_t pad_u, int32_t pad_i,
                                  const rbr_head_grads* g, float* d_ufeat, float* d_ifeat, float* ws, void* stream) {
-    if (!head_args_ok(B, H, K)) return RBR_ERR_BAD_ARG;
-    if (!u_feat || !i_feat || !u_id || !i_id || !p || !ul || !il || !d_pred || !g || (!d_ufeat != !d_ifeat)) {
-        set_error("null pointer");
-        return RBR_ERR_BAD_ARG;
-    }
+    if (!d_pred) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
     (void)ws;      // no longer needed: the reduction blocks recompute d_l instead of reading it back
-    const size_t lds = std::max((size_t)2 * ((K + 3) & ~3), (size_t)3 * 8 * 32) * sizeof(float);
-    hipLaunchKernelGGL(head_bwd_kernel, dim3((unsigned)(B + 2 * (H + 1))), dim3(256), lds, (hipStream_t)stream, B, H, K, u_feat,
-                       i_feat, reinterpret_cast<const long long*>(u_id), reinterpret_cast<const long long*>(i_id), *p, drop,
-                       ul, il, d_pred, pad_u, pad_i, *g, d_ufeat, d_ifeat);
-    RBR_CHECK_LAUNCH("pair_head_bwd launch");
-    return 0;
+    return head_bwd_launch(B, H, K, u_feat, i_feat, u_id, i_id, p, drop, ul, il, d_pred, pad_u, pad_i, g, d_ufeat, d_ifeat, HeadLoss{},
+                           stream);
+}
+
+extern "C" int rbr_pair_head_bwd_ex(int32_t B, int32_t H, int32_t K, const float* u_feat, const float* i_feat,
+                                    const int64_t* u_id, const int64_t* i_id, const rbr_head_params* p, const float* drop,
+                                    const float* ul, const float* il, const float* d_pred, int32_t pad_u, int32_t pad_i,
+                                    const rbr_head_grads* g, float* d_ufeat, float* d_ifeat, const float* pred, const float* target,
+                                    float* loss, float* d_pred_unit, void* stream) {
+    return head_bwd_launch(B, H, K, u_feat, i_feat, u_id, i_id, p, drop, ul, il, d_pred, pad_u, pad_i, g, d_ufeat, d_ifeat,
+                           HeadLoss{pred, target, loss, d_pred_unit}, stream);
 }
 
 // ---- D-ATT's rating: ratings[b] = sum_k u[b,k] * i[b,k] (dual_att.py:58) over a STACKED [2B, K] feature block (user rows

@@ -133,7 +133,8 @@ struct IdSets {
 // host: rbr_id_set[] -> IdSets (validated); returns 0 or RBR_ERR_BAD_ARG
 int fill_id_sets(int n_sets, const rbr_id_set* sets, IdSets& S);
 // element k of the launch: out = in where 0 <= in < limit, else `replace` + a record in err (err[0] count, err[1] value, err[2] set)
-__device__ __forceinline__ void sanitize_id(const IdSets& S, long long k, long long* __restrict__ err) {
+// (returns the clean id)
+__device__ __forceinline__ long long sanitize_id(const IdSets& S, long long k, long long* __restrict__ err) {
     int s = 0;
 #pragma unroll
     for (int q = 1; q < RBR_MAX_ID_SETS; ++q)
@@ -147,17 +148,21 @@ __device__ __forceinline__ void sanitize_id(const IdSets& S, long long k, long l
         v = S.replace[s];
     }
     S.out[s][e] = v;
+    return v;
 }
 
 // Work-list scan of 256 wave-tiles (block `blk` of the scan grid): flags[wt], and the active tiles appended to the
 // list in any order.  sched = flags[total_wt] | list[total_wt] | counters; the counters must be zero beforehand.
+// count (optional): the list's arrival counter when it is not sched's own -- the prepare stage that keeps its list state zero
+// counts in its workspace and publishes the total one launch later.
 // flags: 1 = computed; 0 = all tokens masked (its conv sums are exactly 0: the finalize kernels count it as that);
 // kSlabDup = un-masked slab of pure padding behind another one (P.pad_runs): position for position the values of its
 // predecessor, so it can change neither a maximum nor a FIRST argmax -- neither computed nor looked at.
 constexpr int kSlabDup = 2;
 constexpr int kPadRunHalo = 8;
 __device__ __forceinline__ void tile_scan_block(const ConvPlan& P, const unsigned char* __restrict__ mask,
-                                                int* __restrict__ sched, int blk, const long long* __restrict__ ids = nullptr) {
+                                                int* __restrict__ sched, int blk, const long long* __restrict__ ids = nullptr,
+                                                int* __restrict__ count = nullptr) {
     const int wt = blk * 256 + threadIdx.x;
     int act = 0;
     if (wt < P.total_wt) {
@@ -225,7 +230,7 @@ __device__ __forceinline__ void tile_scan_block(const ConvPlan& P, const unsigne
     act = act == 1;
     const int lane = threadIdx.x & 63;
     int base = 0;
-    if (lane == 0 && b) base = atomicAdd(sched + 2 * (long)P.total_wt, __popcll(b));
+    if (lane == 0 && b) base = atomicAdd(count != nullptr ? count : sched + 2 * (long)P.total_wt, __popcll(b));
     base = __shfl(base, 0);
     if (act) sched[(long)P.total_wt + base + __popcll(b & ((1ull << lane) - 1))] = wt;
 }

@@ -71,6 +71,50 @@ __global__ __launch_bounds__(256) void prep_kernel(const IdSets S, long long* __
     }
 }
 
+// The prepare stage that KEEPS its list state zero (rbr_textcnn_prod_prepare_ids_kept): two launches instead of three.  The
+// workspace's token marks, its compaction ticket and its slab counter are zero on entry and every call leaves them zero, so
+// no launch has to clear them first.  Measured at cfg2: prep 6.1 + mark_scan 6.1 + compact_pack 8.8 us
+// -> 6.4 + 9.9 us, the GEMM starts 3.7 us earlier in the step; with RBR_PREP_TWO_LAUNCH=0 the step is 0.3442 / 0.3477 ms
+// against 0.3374 - 0.3425.
+// Two spare slots of the token list's counter block (kSchedCounters = 64 ints; [0] rows, [1 + g] the GEMM's item counters,
+// g < kMaxGroups = 32) hold the state that must survive from launch to launch:
+constexpr int kKeptTicket = 62;      // arrivals of the compaction blocks; the last one clears the marks and re-arms it
+constexpr int kKeptSlabs = 63;       // arrival counter of the slab scan; the compaction launch publishes and clears it
+struct KeptState {                   // all NULL: the self-initialising chain
+    int* ticket;                     // counter block of the workspace + kKeptTicket
+    int* slabs;                      // counter block of the workspace + kKeptSlabs
+    int* doc_counters;               // the documents' work list: its kSchedCounters counters (tail of pidx; [0] = active slabs)
+    int* gemm_counters;              // counter block of the workspace ([1, kKeptTicket) are cleared for the GEMM)
+    int used_words;                  // the marks as 16-byte words (align256(V) / 16)
+    int mask_bytes;                  // the row mask (align256(cap))
+};
+
+// Launch A: blocks [0, nb_scan) the slab scan (counting in the workspace: `slabs`), blocks [nb_scan, nb_scan + nb_mark) check,
+// clean and mark the token ids -- the check and the mark of an id in one thread, so no mark can land outside used[] --, the rest
+// check the id sets that are not conv tokens.  The scan reads no ids: the entry refuses convs whose scan would (RBR_CONV_PAD_RUNS
+// without a mask), because the clean ids are only being written beside it.
+__global__ __launch_bounds__(256) void mark_scan_ids_kernel(const ConvPlan P, int nb_scan, int nb_mark, long n_tok, const IdSets S,
+                                                            long long* __restrict__ err, const unsigned char* __restrict__ mask,
+                                                            int* __restrict__ sched, int* __restrict__ slabs,
+                                                            unsigned char* __restrict__ used, int V) {
+    if ((int)blockIdx.x < nb_scan) {
+        tile_scan_block(P, mask, sched, blockIdx.x, nullptr, slabs);
+        return;
+    }
+    if ((int)blockIdx.x < nb_scan + nb_mark) {
+        for (long k = (long)(blockIdx.x - nb_scan) * 256 + threadIdx.x; k < n_tok; k += (long)nb_mark * 256) {
+            const long long v = sanitize_id(S, k, err);
+            // (v < V always: prepare_ids_kept refuses token sets whose limit or replacement lies outside the table)
+            if ((mask == nullptr || mask[k]) && (unsigned long long)v < (unsigned long long)V) used[v] = 1;
+        }
+        return;
+    }
+    const long long total = S.first[S.count];
+    const long nb = gridDim.x - nb_scan - nb_mark;
+    for (long long k = n_tok + (long long)(blockIdx.x - nb_scan - nb_mark) * 256 + threadIdx.x; k < total; k += (long long)nb * 256)
+        sanitize_id(S, k, err);
+}
+
 struct PackJob {        // weight images of the product formulation, both derived from the torch-layout conv weights
     ConvPlan P;         // plan of the token pseudo-document (one kz = 1 bank of Cp channels): forward image [dc][tile][slot][dd]
     int n_widths, D, cp_real;
@@ -85,6 +129,36 @@ __device__ __forceinline__ float prod_weight(const PackJob& J, const PtrArray& W
     const int rel = pc - J.poff[w];
     const int j = rel / J.ch[w], cl = rel - j * J.ch[w];
     return W.p[w][((long)cl * J.D + d) * J.kz[w] + j];
+}
+
+// The pack role of launch 3 (blocks [nb_compact, gridDim.x)): the product weight image of the forward GEMM and the row-major
+// Wprod^T the backward's sparse product reads.
+__device__ __forceinline__ void pack_blocks(const PackJob& J, int nb_compact, const PtrArray& W, float* __restrict__ packed,
+                                            float* __restrict__ WT, const B16Pack& JB, unsigned char* __restrict__ bimg) {
+    const long nb = gridDim.x - nb_compact, b0 = blockIdx.x - nb_compact;
+    const ConvPlan& P = J.P;
+    const int DC = P.DC;
+    const long n_img = packed != nullptr ? (long)P.nchunks * P.tiles_total * kTile * DC : 0;     // bf16-plane GEMM: no f32 image
+    const long n_wt = (long)J.cp_real * J.D;
+    const long n_b16 = bimg != nullptr ? b16_pack_items(JB) : 0;                                 // bf16-plane GEMM: its weight planes
+    for (long idx = b0 * 256 + threadIdx.x; idx < n_img + n_wt + n_b16; idx += nb * 256) {
+        if (idx >= n_img + n_wt) {
+            b16_pack_item(JB, W, bimg, idx - n_img - n_wt);
+        } else if (idx < n_img) {
+            long r = idx;
+            const int dd = (int)(r % DC); r /= DC;
+            const int slot = (int)(r % kTile); r /= kTile;
+            const int t = (int)(r % P.tiles_total);
+            const int dc = (int)(r / P.tiles_total);
+            const int pc = t * kTile + slot;          // product channel
+            const int d = dc * DC + dd;
+            packed[idx] = (pc < J.cp_real && d < J.D) ? prod_weight(J, W, pc, d) : 0.f;
+        } else {
+            const long e = idx - n_img;
+            const int pc = (int)(e / J.D), d = (int)(e - (long)pc * J.D);
+            WT[e] = prod_weight(J, W, pc, d);         // WT[(w, j, cl)][d] = W_w[cl, d, j]
+        }
+    }
 }
 
 // Launch 3: blocks [0, nb_compact) turn the marks into the token list (row_of_token[v] = dense row or -1,
@@ -130,30 +204,78 @@ __device__ __forceinline__ void compact_pack_kernel(const PackJob& J, int nb_com
             *counter = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]) + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
         return;
     }
-    const long nb = gridDim.x - nb_compact, b0 = blockIdx.x - nb_compact;
-    const ConvPlan& P = J.P;
-    const int DC = P.DC;
-    const long n_img = packed != nullptr ? (long)P.nchunks * P.tiles_total * kTile * DC : 0;     // bf16-plane GEMM: no f32 image
-    const long n_wt = (long)J.cp_real * J.D;
-    const long n_b16 = bimg != nullptr ? b16_pack_items(JB) : 0;                                 // bf16-plane GEMM: its weight planes
-    for (long idx = b0 * 256 + threadIdx.x; idx < n_img + n_wt + n_b16; idx += nb * 256) {
-        if (idx >= n_img + n_wt) {
-            b16_pack_item(JB, W, bimg, idx - n_img - n_wt);
-        } else if (idx < n_img) {
-            long r = idx;
-            const int dd = (int)(r % DC); r /= DC;
-            const int slot = (int)(r % kTile); r /= kTile;
-            const int t = (int)(r % P.tiles_total);
-            const int dc = (int)(r / P.tiles_total);
-            const int pc = t * kTile + slot;          // product channel
-            const int d = dc * DC + dd;
-            packed[idx] = (pc < J.cp_real && d < J.D) ? prod_weight(J, W, pc, d) : 0.f;
-        } else {
-            const long e = idx - n_img;
-            const int pc = (int)(e / J.D), d = (int)(e - (long)pc * J.D);
-            WT[e] = prod_weight(J, W, pc, d);         // WT[(w, j, cl)][d] = W_w[cl, d, j]
-        }
+    pack_blocks(J, nb_compact, W, packed, WT, JB, bimg);
+}
+
+// The compaction of the kept form (see KeptState), block blockIdx.x < nb_compact.
+__device__ __forceinline__ void compact_kept_block(int nb_compact, int V, int cap, unsigned char* used, int* __restrict__ row_of_token,
+                                                   long long* __restrict__ tok_of_row, unsigned char* __restrict__ row_mask,
+                                                   int* __restrict__ counter, float* __restrict__ zero_row, int pitch,
+                                                   const KeptState& KS) {
+    // Rows, list and count exactly as compact_pack_kernel's; in addition every block counts ALL marks, so that
+    // it knows the list's length and can write its 256 bytes of the row mask outright (1 below the count, 0 above: the mask
+    // needs no clearing), block 0 publishes the slab count and clears the counters the GEMM pulls from, and the block that
+    // arrives LAST at the ticket clears the marks and re-arms the ticket.  No fence: every block has consumed its mark values
+    // (they are in LDS behind a barrier) before its ticket atomic is issued, and the clearing becomes visible at the kernel
+    // boundary -- the reasoning of head_rng_ticket.
+    if (blockIdx.x == 0)
+        for (int k = threadIdx.x; k < pitch; k += 256) zero_row[k] = 0.f;
+    __shared__ int s_cnt[4], s_all[4], s_wave[4], s_last;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int below = blockIdx.x * 256;
+    int c = 0, call = 0;
+    const int4* u4 = reinterpret_cast<const int4*>(used);
+    for (int q = threadIdx.x; q < KS.used_words; q += 256) {
+        const int4 m = u4[q];
+        const int n = __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w);
+        call += n;
+        if (q < below / 16) c += n;
     }
+    c = wave_sum(c);
+    call = wave_sum(call);
+    const int v = below + threadIdx.x;
+    const int u = (v < V) ? used[v] : 0;
+    const unsigned long long b = __ballot(u);
+    if (lane == 0) { s_cnt[wave] = c; s_all[wave] = call; s_wave[wave] = __popcll(b); }
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = atomicAdd(KS.ticket, 1) == nb_compact - 1;
+    int base = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    for (int k = 0; k < wave; ++k) base += s_wave[k];
+    const int total = (s_all[0] + s_all[1]) + (s_all[2] + s_all[3]);
+    if (v < V) {
+        int row = -1;
+        if (u) {
+            row = base + __popcll(b & ((1ull << lane) - 1));
+            if (row < cap) tok_of_row[row] = v; else row = -1;
+        }
+        row_of_token[v] = row;
+    }
+    if (v < KS.mask_bytes) row_mask[v] = v < min(total, cap) ? 1 : 0;
+    if ((int)blockIdx.x == nb_compact - 1 && threadIdx.x == 0) *counter = total;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) { KS.doc_counters[0] = *KS.slabs; *KS.slabs = 0; }
+        else if (threadIdx.x < kSchedCounters) KS.doc_counters[threadIdx.x] = 0;
+        if (threadIdx.x >= 1 && threadIdx.x < kKeptTicket) KS.gemm_counters[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    if (s_last) {          // workgroup-uniform
+        int4* w4 = reinterpret_cast<int4*>(used);
+        for (int q = threadIdx.x; q < KS.used_words; q += 256) w4[q] = make_int4(0, 0, 0, 0);
+        if (threadIdx.x == 0) *KS.ticket = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void compact_pack_kept_kernel(const PackJob J, int nb_compact, int V, int cap, unsigned char* used,
+                                                                int* __restrict__ row_of_token, long long* __restrict__ tok_of_row,
+                                                                unsigned char* __restrict__ row_mask, int* __restrict__ counter,
+                                                                float* __restrict__ zero_row, int pitch, const PtrArray W,
+                                                                float* __restrict__ packed, float* __restrict__ WT, const B16Pack JB,
+                                                                unsigned char* __restrict__ bimg, const KeptState KS) {
+    if ((int)blockIdx.x < nb_compact) {
+        compact_kept_block(nb_compact, V, cap, used, row_of_token, tok_of_row, row_mask, counter, zero_row, pitch, KS);
+        return;
+    }
+    pack_blocks(J, nb_compact, W, packed, WT, JB, bimg);
 }
 
 // ---------------------------------------------------------------------------------- gather + pool
@@ -1447,9 +1569,12 @@ int prod_state(const rbr_textcnn_desc* d, void* ws, ProdState& S) {
 }  // namespace
 
 // Stage 1: work list of the real documents (tail of `pidx`), distinct-token list of the batch, product weight
-// images.  Three launches: zero the state | mark + scan | compact + pack.
+// images.  Three launches: zero the state | mark + scan | compact + pack.  kept (needs id_sets): the two launches of the form
+// that finds the list state zero and leaves it zero (KeptState) -- check + mark + scan | compact + pack.
+// (The weight images stay in the second launch.  Moving them into the first was NOT measured: at cfg2 the first launch is 6.4 us
+// and the second 9.9 us, of which the compaction alone was 8.2 us before)
 static int prod_prepare(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* const* W, int32_t* pidx,
-                        void* ws, void* stream, const IdSets* id_sets, int64_t* err) {
+                        void* ws, void* stream, const IdSets* id_sets, int64_t* err, bool kept = false) {
     ConvPlan plans[kMaxGroups];
     if (!build_plans(d, plans)) return RBR_ERR_BAD_ARG;
     if (!ids || !W || !pidx) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
@@ -1461,7 +1586,20 @@ static int prod_prepare(const rbr_textcnn_desc* d, const int64_t* ids, const uin
     ZeroRegions zr{{reinterpret_cast<int*>(S.base + S.Lo.used), S.sched_p + 2 * (size_t)S.pp[0].total_wt,
                     sched + 2 * (size_t)plans[0].total_wt},
                    {(long)((S.Lo.row_of_token - S.Lo.used) / sizeof(int)), kSchedCounters, kSchedCounters}};
-    if (id_sets != nullptr) {
+    const long n_tok = (long)d->n_docs * d->L;
+    const int nb_scan = (plans[0].total_wt + 255) / 256;
+    const int nb_mark = (int)std::min<long>((n_tok + 255) / 256, 2048);
+    if (kept) {
+        if (mask == nullptr && plans[0].pad_runs >= 0) {
+            set_error("prod_prepare_ids_kept: an un-masked conv with RBR_CONV_PAD_RUNS scans the clean ids (use prod_prepare_ids)");
+            return RBR_ERR_UNSUPPORTED;
+        }
+        const long long rest = id_sets->first[id_sets->count] - n_tok;
+        const int nb_rest = (int)std::min<long long>((rest + 255) / 256, 2048);
+        hipLaunchKernelGGL(mark_scan_ids_kernel, dim3(nb_scan + nb_mark + nb_rest), dim3(256), 0, st, plans[0], nb_scan, nb_mark, n_tok,
+                           *id_sets, reinterpret_cast<long long*>(err), mask, sched, S.counter + kKeptSlabs, S.used, d->V);
+        RBR_CHECK_LAUNCH("textcnn mark_scan_ids launch");
+    } else if (id_sets != nullptr) {
         const long long total = id_sets->first[id_sets->count];
         const int nb_ids = (int)std::min<long long>((total + 255) / 256, 2048);
         const long nz = zr.n[0] + zr.n[1] + zr.n[2];
@@ -1471,10 +1609,8 @@ static int prod_prepare(const rbr_textcnn_desc* d, const int64_t* ids, const uin
     } else if (int e = zero_regions(zr, st)) {
         return e;
     }
-    const long n_tok = (long)d->n_docs * d->L;
-    const int nb_scan = (plans[0].total_wt + 255) / 256;
-    const int nb_mark = (int)std::min<long>((n_tok + 255) / 256, 2048);
-    if (int e_ = rbr::launch<mark_scan_kernel, 256>(dim3(nb_scan + nb_mark), dim3(256), 0, st, "textcnn mark_scan launch", plans[0], nb_scan, n_tok, reinterpret_cast<const long long*>(ids), mask, sched, S.used)) return e_;
+    if (!kept)
+        if (int e_ = rbr::launch<mark_scan_kernel, 256>(dim3(nb_scan + nb_mark), dim3(256), 0, st, "textcnn mark_scan launch", plans[0], nb_scan, n_tok, reinterpret_cast<const long long*>(ids), mask, sched, S.used)) return e_;
     PackJob J{};
     J.P = S.pp[0]; J.n_widths = d->n_widths; J.D = d->D; J.cp_real = S.A.cp_real;
     for (int w = 0; w < d->n_widths; ++w) { J.kz[w] = d->kz[w]; J.ch[w] = d->ch[w]; J.poff[w] = S.A.poff[w]; }
@@ -1488,6 +1624,18 @@ static int prod_prepare(const rbr_textcnn_desc* d, const int64_t* ids, const uin
                         (long)S.A.cp_real * d->D;
     const int nb_pack = (int)std::min<long>((n_pack + 255) / 256, 2048);
     // (bf16-plane GEMM: the weight planes in MFMA-fragment order instead of the f32 tile image)
+    if (kept) {
+        const bool tb16 = prod_t_bf16(d);
+        float* zero_row = tb16 ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(S.T) + (size_t)S.Lo.cap * S.A.pitch)
+                               : S.T + (size_t)S.Lo.cap * S.A.pitch;
+        const KeptState KS{S.counter + kKeptTicket, S.counter + kKeptSlabs, sched + 2 * (size_t)plans[0].total_wt, S.counter,
+                           (int)(align256((size_t)d->V) / 16), (int)align256((size_t)S.Lo.cap)};
+        hipLaunchKernelGGL(compact_pack_kept_kernel, dim3(nb_compact + nb_pack), dim3(256), 0, st, J, nb_compact, d->V, S.Lo.cap, S.used,
+                           S.row_of_token, S.tok_of_row, S.row_mask, S.counter, zero_row, tb16 ? S.A.pitch / 2 : S.A.pitch, wp,
+                           b16 ? nullptr : S.packed_p, S.WT, JB, b16 ? reinterpret_cast<unsigned char*>(S.base + S.Lo.bimg) : nullptr, KS);
+        RBR_CHECK_LAUNCH("textcnn compact_pack_kept launch");
+        return 0;
+    }
     if (int e_ = rbr::launch<compact_pack_kernel, 256>(dim3(nb_compact + nb_pack), dim3(256), 0, st, "textcnn compact_pack launch", J, nb_compact, d->V, S.Lo.cap, S.used, S.row_of_token, S.tok_of_row, S.row_mask, S.counter, prod_t_bf16(d) ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(S.T) + (size_t)S.Lo.cap * S.A.pitch)
                                       : S.T + (size_t)S.Lo.cap * S.A.pitch, prod_t_bf16(d) ? S.A.pitch / 2 : S.A.pitch, wp, b16 ? nullptr : S.packed_p, S.WT, JB, b16 ? reinterpret_cast<unsigned char*>(S.base + S.Lo.bimg) : nullptr)) return e_;
     return 0;
@@ -1512,6 +1660,39 @@ extern "C" int rbr_textcnn_prod_prepare_ids(const rbr_textcnn_desc* d, int32_t n
     const bool two = n_sets >= 2 && sets[0].out == ids && sets[1].out == sets[0].out + sets[0].n && sets[0].n + sets[1].n == n_tok;
     if (!one && !two) { set_error("prod_prepare_ids: `ids` is not the clean copy of the first id set(s)"); return RBR_ERR_BAD_ARG; }
     return prod_prepare(d, ids, mask, W, pidx, ws, stream, &S, err);
+}
+
+// The same stage in TWO launches for a caller that owns `ws` from call to call (see rbr_hip.h): the list state is zero on entry
+// and every successful call leaves it zero.
+extern "C" int rbr_textcnn_prod_prepare_ids_kept(const rbr_textcnn_desc* d, int32_t n_sets, const rbr_id_set* sets, int64_t* err,
+                                                 const int64_t* ids, const uint8_t* mask, const float* const* W, int32_t* pidx,
+                                                 void* ws, void* stream) {
+    if (!err) { set_error("null err"); return RBR_ERR_BAD_ARG; }
+    if (pair_region_open()) { set_error("prod_prepare_ids_kept: not inside a pair region"); return RBR_ERR_UNSUPPORTED; }
+    IdSets S;
+    if (int e = fill_id_sets(n_sets, sets, S)) return e;
+    const long long n_tok = (long long)d->n_docs * d->L;
+    const bool one = sets[0].out == ids && sets[0].n == n_tok;
+    const bool two = n_sets >= 2 && sets[0].out == ids && sets[1].out == sets[0].out + sets[0].n && sets[0].n + sets[1].n == n_tok;
+    if (!one && !two) { set_error("prod_prepare_ids_kept: `ids` is not the clean copy of the first id set(s)"); return RBR_ERR_BAD_ARG; }
+    for (int s = 0; s < (one ? 1 : 2); ++s)      // a clean token id indexes the marks: it must lie inside the table
+        if (S.limit[s] > d->V || S.replace[s] < 0 || S.replace[s] >= d->V) {
+            set_error("prod_prepare_ids_kept: token set %d has limit %lld / replacement %lld outside the table of %d rows", s,
+                      S.limit[s], S.replace[s], d->V);
+            return RBR_ERR_BAD_ARG;
+        }
+    return prod_prepare(d, ids, mask, W, pidx, ws, stream, &S, err, true);
+}
+
+extern "C" int rbr_textcnn_prod_list_state(const rbr_textcnn_desc* d, int64_t off[6]) {
+    if (!off) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
+    if (!prod_applicable(d)) { set_error("token-product path does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
+    ProdLayout Lo;
+    if (!prod_layout(d, Lo)) return RBR_ERR_BAD_ARG;
+    off[0] = (int64_t)Lo.used; off[1] = (int64_t)align256((size_t)d->V);
+    off[2] = (int64_t)Lo.row_mask; off[3] = (int64_t)align256((size_t)Lo.cap);
+    off[4] = (int64_t)(Lo.counter + kKeptTicket * sizeof(int)); off[5] = (int64_t)((kKeptSlabs - kKeptTicket + 1) * sizeof(int));
+    return 0;
 }
 
 // ---- dense formulation's table gradient through a token list built for the purpose (no product table T: un-gated convs)

@@ -344,10 +344,104 @@ def _conv_operands(table, ids, mask, weights, pad_mode, act, padding_idx, flags:
     return table_c, ids, mask8, ws, _conv_desc(table_c, ids.shape[0], ids.shape[1], ws, pad_mode, act, padding_idx, flags)
 
 
-def _conv_fwd_buffers(rec, desc, dev, feat=None, argmax=None):
+# ---- forward workspaces that are KEPT from call to call: the two-launch prepare stage (rbr_textcnn_prod_prepare_ids_kept) -------
+# That entry finds the workspace's list state zero and leaves it zero, so somebody has to own the workspace between calls.
+# Eager calls: a free list per (device, stream) -- calls on one stream are ordered --; a workspace is out on loan for as long as
+# anything holds the tensor a checkout returned (the forward's record, the row-form gradient that still reads its token list).
+# Recorded steps: the graph keeps the workspace's ADDRESS, so the workspace must live as long as the graph and serve nobody else:
+# the recording object opens kept_ws_owner(list) around its capture and the workspaces move into that list.  A capture without
+# an owner, or without a free workspace on its stream (prepare_stream_state creates them ahead of a recording: a buffer made during
+# a capture would sit in the graph's private pool, where a later tensor may be laid over it), gets None: the three-launch chain.
+# RBR_PREP_TWO_LAUNCH=0 switches the whole thing off (the A/B of DESIGN.md section 4.14: 0.3442 / 0.3477 ms per cfg2 step with
+# the switch off against 0.3374 - 0.3425 with it on; the prepare stage 21.0 -> 16.2 us).
+_KEPT_WS: dict = {}          # (device index, stream handle) -> [_KeptWs]
+_KEPT_OWNER: list = []       # innermost kept_ws_owner() list
+
+
+def _kept_state(desc):
+    """((offset, bytes) x 3) of a forward workspace's list state: marks, row mask, the two kept counter words."""
+    off = (C.c_int64 * 6)()
+    check(_lib.lib().rbr_textcnn_prod_list_state(C.byref(desc), off), "rbr_textcnn_prod_list_state")
+    return tuple((int(off[k]), int(off[k + 1])) for k in (0, 2, 4))
+
+
+class _KeptWs:
+    def __init__(self, state, nbytes, dev):
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.busy, self.state = False, state          # (workspaces of one size and one state layout are interchangeable)
+        self.zero()
+
+    def fits(self, state, nbytes) -> bool:
+        return self.buf.numel() == nbytes and self.state == state
+
+    def zero(self):
+        for o, n in self.state:
+            self.buf[o:o + n].zero_()
+        self.dirty = False
+
+
+class _KeptLease:
+    def __init__(self, ws):
+        self.ws = ws
+        ws.busy = True
+
+    def __del__(self):
+        self.ws.busy = False
+
+
+@contextlib.contextmanager
+def kept_ws_owner(owned: list):
+    """with kept_ws_owner(self._kept): <capture> -- forward workspaces a recording takes are appended to `owned`, which must
+    live as long as the recorded graph (train_step.GraphedTrainStep / GraphedForward)."""
+    _KEPT_OWNER.append(owned)
+    try:
+        yield owned
+    finally:
+        _KEPT_OWNER.pop()
+
+
+def _kept_ws_checkout(desc, nbytes, dev):
+    """A workspace of `nbytes` whose list state is zero, as a tensor that carries its loan, or None (see above)."""
+    if os.environ.get("RBR_PREP_TWO_LAUNCH", "1") == "0":
+        return None
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    free = _KEPT_WS.setdefault((idx, torch.cuda.current_stream(idx).cuda_stream), [])
+    capturing = torch.cuda.is_current_stream_capturing()
+    if capturing and not _KEPT_OWNER:
+        return None
+    state = _kept_state(desc)
+    ws = next((w for w in free if not w.busy and w.fits(state, nbytes) and not (capturing and w.dirty)), None)
+    if ws is None:
+        if capturing:
+            return None
+        ws = _KeptWs(state, nbytes, dev)
+        free.append(ws)
+    elif ws.dirty:
+        ws.zero()
+    t = ws.buf[:]                    # a tensor object of this checkout's own: the loan lives and dies with it
+    t._kept = ws
+    if capturing:
+        free.remove(ws)
+        _KEPT_OWNER[-1].append(ws)
+    else:
+        t._kept_lease = _KeptLease(ws)
+    return t
+
+
+def _kept_ws_prepare_stream(dev, idx) -> None:
+    """For every (size, descriptor) a stream of the device has used: a free workspace on the CURRENT stream."""
+    cur = _KEPT_WS.setdefault((idx, torch.cuda.current_stream(idx).cuda_stream), [])
+    seen = {(w.buf.numel(), w.state) for (d, _), lst in list(_KEPT_WS.items()) if d == idx for w in lst}
+    for n, state in seen:
+        if not any(c.fits(state, n) and not c.busy and not c.dirty for c in cur):
+            cur.append(_KeptWs(state, n, dev))
+
+
+def _conv_fwd_buffers(rec, desc, dev, feat=None, argmax=None, kept=False):
     """Plan queries and output buffers of a conv forward, left on the record `rec` -- allocations only, nothing launches: pval /
     pidx (the pool's per-slab partials), feat / argmax [n_docs, C] (or the caller's views) and prod_ws, the workspace of the
-    token-product formulation (None: it does not apply to this shape, the dense formulation runs)."""
+    token-product formulation (None: it does not apply to this shape, the dense formulation runs).  kept: prod_ws from the kept
+    workspaces when one is to be had (its tensor then has `_kept`: _prod_forward takes the two-launch prepare stage)."""
     L_ = _lib.lib()
     n_part = L_.rbr_textcnn_partial_elems(C.byref(desc))
     if not n_part:
@@ -358,7 +452,9 @@ def _conv_fwd_buffers(rec, desc, dev, feat=None, argmax=None):
     rec.pidx = torch.empty(n_part, dtype=I32, device=dev)
     rec.feat = feat if feat is not None else torch.empty(desc.n_docs, Ctot, dtype=F32, device=dev)
     rec.argmax = argmax if argmax is not None else torch.empty(desc.n_docs, Ctot, dtype=I32, device=dev)
-    rec.prod_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    rec.prod_ws = (_kept_ws_checkout(desc, ws_bytes, dev) if kept else None) if ws_bytes else None
+    if rec.prod_ws is None and ws_bytes:
+        rec.prod_ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     return rec
 
 
@@ -370,7 +466,17 @@ def _prod_forward(desc, rec, table, ids, mask8, gate, ws, st, *, id_sets=None, p
     L_ = _lib.lib()
     d, wsp = C.byref(desc), rec.prod_ws.data_ptr()
     ids_p, mask_p, pidx_p = dev_ptr(ids, I64, "ids"), dev_ptr(mask8, U8, "mask"), dev_ptr(rec.pidx, I32, "pidx")
-    if id_sets is not None:
+    kept = getattr(rec.prod_ws, "_kept", None) if id_sets is not None else None
+    if kept is not None:
+        # two launches (check + mark + scan | list + weight images) on a workspace whose list state stays zero; after an error the
+        # state is undefined: the owner clears it before the next use
+        try:
+            _call(prepare_key, L_.rbr_textcnn_prod_prepare_ids_kept, d, *id_sets, ids_p, mask_p, ptr_array(ws, F32, "conv weight"),
+                  pidx_p, wsp, st)
+        except Exception:
+            kept.dirty = True
+            raise
+    elif id_sets is not None:
         _call(prepare_key, L_.rbr_textcnn_prod_prepare_ids, d, *id_sets, ids_p, mask_p, ptr_array(ws, F32, "conv weight"), pidx_p,
               wsp, st)
     else:
@@ -928,10 +1034,12 @@ def pair_head(u_feat, i_feat, u_id, i_id, Wu, bu, Eu, Wi, bi, Ei, h, g, ub, ib, 
 # --------------------------------------------------------------------------- encoder + head of a two-tower model, fused
 class _LossRequest:
     """fused_loss(target): the trainer's nn.MSELoss target, announced to the model's forward so that a fused head launch can
-    compute the loss as well; loss_for(pred) hands it out (None: the forward did not take the offer)."""
+    compute the loss as well; loss_for(pred) hands it out (None: the forward did not take the offer).  after_backward: the
+    caller reads the loss VALUE only after loss.backward() has run (train_step does) -- the forward may then leave computing it to
+    the backward (_EncodeHead: RBR_LOSS_IN_BWD)."""
 
-    def __init__(self, target):
-        self.target, self.pred_ptr, self.loss = target, None, None
+    def __init__(self, target, after_backward: bool = False):
+        self.target, self.pred_ptr, self.loss, self.after_backward = target, None, None, bool(after_backward)
 
     def loss_for(self, pred: torch.Tensor):
         if self.loss is not None and self.pred_ptr == pred.data_ptr() and pred.numel() == self.target.numel():
@@ -943,11 +1051,13 @@ _LOSS_REQUEST: list = []
 
 
 @contextlib.contextmanager
-def fused_loss(target: torch.Tensor):
+def fused_loss(target: torch.Tensor, after_backward: bool = False):
     """with fused_loss(ratings) as fl: pred = model(*batch); loss = fl.loss_for(pred) -- the mean-squared error against
     `target` (trainer/train_deepconn_pp.py:164) out of the model's last launch when the model supports it (DeepCoNN's fused
-    encoder + head), else None and the caller computes mse_loss(pred, target) itself."""
-    req = _LossRequest(target)
+    encoder + head), else None and the caller computes mse_loss(pred, target) itself.  after_backward=True: a promise that the
+    loss tensor is not READ before loss.backward() has been issued; DeepCoNN's fused head then writes it from its backward launch,
+    off the step's serial chain, and until then the tensor holds no value."""
+    req = _LossRequest(target, after_backward)
     _LOSS_REQUEST.append(req)
     try:
         yield req
@@ -982,6 +1092,7 @@ def prepare_stream_state(dev) -> None:
     need = max((t.numel() for (d, _), t in _PS_WS.items() if d == idx), default=0)
     if need:
         _pair_softmax_ws(dev, need)
+    _kept_ws_prepare_stream(dev, idx)
 
 
 def encode_head_applicable(table, n_docs, L, kernel_sizes, channels, padding_idx) -> bool:
@@ -1006,7 +1117,9 @@ class _EncodeHead(torch.autograd.Function):
     atomics, batch reductions) behind dW on the weight-gradient branch.  RBR_HEAD_BWD_IN_FWD=0 restores the old order."""
 
     @staticmethod
-    def forward(ctx, table, id_sets, ids, mask, u_id, i_id, drop, target, padding_idx, pad_u, pad_i, n_widths, first, *params):
+    def forward(ctx, table, id_sets, ids, mask, u_id, i_id, drop, target, padding_idx, pad_u, pad_i, n_widths, first, opts,
+                *params):
+        defer_loss, own_ws = opts
         bs_ = [b.contiguous() for b in params[n_widths:2 * n_widths]]
         head = [t.contiguous() for t in params[2 * n_widths:]]
         L_ = _lib.lib()
@@ -1033,7 +1146,7 @@ class _EncodeHead(torch.autograd.Function):
             u_id, i_id = u_id.contiguous(), i_id.contiguous()
         table_c, ids, mask8, ws_, desc = _conv_operands(table, ids, mask, params[:n_widths], PAD_SAME, ACT_RELU, padding_idx)
         B = ids.shape[0] // 2
-        conv = _conv_fwd_buffers(_ConvSaved(), desc, dev)
+        conv = _conv_fwd_buffers(_ConvSaved(), desc, dev, kept=own_ws and sets is not None)
         if conv.prod_ws is None:
             check(-1, "encode_head plan (encode_head_applicable() was not consulted)")
         pval, pidx, feat, argmax = conv.pval, conv.pidx, conv.feat, conv.argmax
@@ -1066,6 +1179,15 @@ class _EncodeHead(torch.autograd.Function):
             if training and first is None and os.environ.get("RBR_HEAD_BWD_IN_FWD", "1") != "0" \
                     and L_.rbr_pair_head_fwd_pool_lds_bytes(C.byref(desc), K, 1):
                 d_feat_unit = torch.empty(2 * B, feat.shape[1], dtype=F32, device=dev)
+        # The loss off the serial chain: with d_feat_unit nothing in the step reads the loss, so a caller that promised to read it
+        # only after the backward (fused_loss(after_backward=True)) gets a head launch without the MSE ticket, its two agent-scope
+        # fences and the last-block pass; rbr_pair_head_bwd_ex writes loss and d_unit from one more workgroup on the
+        # weight-gradient branch.  RBR_LOSS_IN_BWD=0 keeps the ticketed tail.  Measured at cfg2: the head
+        # launch 28.6 -> 22.3 us; with the switch off the step is 0.3454 / 0.3416 ms against 0.3374 - 0.3425 with it on.
+        ctx.deferred = None
+        if d_feat_unit is not None and defer_loss and os.environ.get("RBR_LOSS_IN_BWD", "1") != "0":
+            ctx.deferred = (pred.detach(), target, loss.detach())
+        ticketed = target is not None and ctx.deferred is None
         _call("pair_head_fwd_pool", L_.rbr_pair_head_fwd_pool_ex, C.byref(desc), dev_ptr(pval, F32, "pval"), dev_ptr(pidx, I32, "pidx"),
               ptr_array(bs_, F32, "conv bias"), dev_ptr(feat, F32, "feat"), dev_ptr(argmax, I32, "argmax"),
               dev_ptr(first, I64, "first"), K, dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp),
@@ -1074,7 +1196,7 @@ class _EncodeHead(torch.autograd.Function):
               dev_ptr(drop_t, F32, "drop") if p_drop > 0.0 else None, dev_ptr(flat_zero, F32, "zero_buf"),
               acc_n, dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(pred, F32, "pred"),
               dev_ptr(target, F32, "target"), dev_ptr(loss, F32, "loss"), dev_ptr(d_unit, F32, "d_unit"),
-              _ticket(dev).data_ptr() if target is not None else None, dev_ptr(d_feat_unit, F32, "d_feat_unit"), st)
+              _ticket(dev).data_ptr() if ticketed else None, dev_ptr(d_feat_unit, F32, "d_feat_unit"), st)
         ctx.d_feat_unit = d_feat_unit
         ctx.conv = _ConvSaved(table=table_c, ids=ids, packed=None, feat=feat, argmax=argmax, mask8=mask8, gate=None, ws=ws_,
                               desc=desc, prod_ws=conv.prod_ws, fanout_acc=None)
@@ -1094,11 +1216,18 @@ class _EncodeHead(torch.autograd.Function):
         S = ctx.conv
         dev = S.table.device
         L_ = _lib.lib()
-        need_conv = any(ctx.needs_input_grad[13:13 + 2 * n_widths]) or ctx.needs_input_grad[0]
+        need_conv = any(ctx.needs_input_grad[14:14 + 2 * n_widths]) or ctx.needs_input_grad[0]
         unit = _UNIT.get(dev)
         # the forward launch wrote d_feat for exactly this upstream gradient: the conv backward does not wait for head_bwd
         early = (ctx.d_feat_unit is not None and need_conv and d_pred is None and ctx.first is None and d_loss is not None
                  and unit is not None and d_loss.data_ptr() == unit.data_ptr())
+        deferred = ctx.deferred
+        if deferred is not None and not early:
+            # any other upstream gradient: the loss and d loss / d pred the forward launch left out, by the launch of their own
+            # (rbr_mse_loss_fwd: the same bits), then the old order
+            _call(None, L_.rbr_mse_loss_fwd, B, dev_ptr(deferred[0], F32, "pred"), dev_ptr(deferred[1], F32, "target"),
+                  dev_ptr(deferred[2], F32, "loss"), dev_ptr(d_unit, F32, "d_pred_unit"), current_stream())
+            deferred = None
         if d_loss is not None:                  # the fused loss: d loss / d pred was written by the forward launch
             g = d_unit if (unit is not None and d_loss.data_ptr() == unit.data_ptr()) else d_unit * d_loss
             d_pred = g if d_pred is None else d_pred + g
@@ -1117,6 +1246,13 @@ class _EncodeHead(torch.autograd.Function):
         feat = S.feat
 
         def head_bwd():          # early: the pair blocks only accumulate the id-row gradients
+            if deferred is not None:      # ... and one more workgroup writes the loss and d_unit (d_pred is taken from pred / target)
+                _call(None, L_.rbr_pair_head_bwd_ex, B, H, K, dev_ptr(feat[:B], F32, "u_feat"), dev_ptr(feat[B:], F32, "i_feat"),
+                      dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp), dev_ptr(drop_t, F32, "drop"),
+                      dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), None, pad_u, pad_i, C.byref(hg), None, None,
+                      dev_ptr(deferred[0], F32, "pred"), dev_ptr(deferred[1], F32, "target"), dev_ptr(deferred[2], F32, "loss"),
+                      dev_ptr(d_unit, F32, "d_pred_unit"), current_stream())
+                return
             _call(None, L_.rbr_pair_head_bwd, B, H, K, dev_ptr(feat[:B], F32, "u_feat"), dev_ptr(feat[B:], F32, "i_feat"),
                   dev_ptr(u_id, I64, "u_id"), dev_ptr(i_id, I64, "i_id"), C.byref(hp), dev_ptr(drop_t, F32, "drop"),
                   dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"), dev_ptr(d_pred, F32, "d_pred"), pad_u, pad_i, C.byref(hg),
@@ -1125,7 +1261,7 @@ class _EncodeHead(torch.autograd.Function):
 
         if early:
             dtable, _, dWs, dbs = _textcnn_backward(S, d_pair, ctx.needs_input_grad[0], False, side_job=head_bwd)
-            return (dtable, None, None, None, None, None, None, None, None, None, None, None, None, *dWs, *dbs, *grads)
+            return (dtable, None, None, None, None, None, None, None, None, None, None, None, None, None, *dWs, *dbs, *grads)
         head_bwd()
         if need_conv and ctx.first is not None:      # in-batch dedup: the repeated documents' gradient rows onto their first occurrence
             _call(None, L_.rbr_dedup_fold_rows, 2 * B, H, dev_ptr(ctx.first, I64, "first"), dev_ptr(d_pair, F32, "d_feat"),
@@ -1134,17 +1270,19 @@ class _EncodeHead(torch.autograd.Function):
             dtable, _, dWs, dbs = _textcnn_backward(S, d_pair, ctx.needs_input_grad[0], False)
         else:
             dtable, dWs, dbs = None, [None] * n_widths, [None] * n_widths
-        return (dtable, None, None, None, None, None, None, None, None, None, None, None, None, *dWs, *dbs, *grads)
+        return (dtable, None, None, None, None, None, None, None, None, None, None, None, None, None, *dWs, *dbs, *grads)
 
 
 def encode_head(table, ids, mask, u_id, i_id, conv_weights, conv_biases, head_params, *, id_sets=None, drop=None,
-                padding_idx=0, pad_u=0, pad_i=0, first=None):
+                padding_idx=0, pad_u=0, pad_i=0, first=None, own_workspace=False):
     """DeepCoNN++'s forward from token ids to predictions in one autograd function (see _EncodeHead).  ids / mask: the stacked
     [2B, L] towers (user rows first) -- or id_sets = [(u_docs, V, pad), (i_docs, V, pad), (u_ids, U, 0), (i_ids, I, 0)], the raw
     id tensors, whose range check then rides in the prepare stage's first launch (ids / u_id / i_id are ignored).
     head_params: (Wu, bu, Eu, Wi, bi, Ei, h, g, ub, ib).  drop: None, a [B, K] multiplier, or the dropout probability of a
     training forward.  first [2B] (dedup_rows; `mask` then carries the blanked rows): document r's features are document
-    first[r]'s -- the in-batch dedup by id, inside the fused step.  Inside `with fused_loss(target)` the MSE against target is computed by the head launch as well."""
+    first[r]'s -- the in-batch dedup by id, inside the fused step.  Inside `with fused_loss(target)` the MSE against target is computed by the head launch as well.
+    own_workspace (with id_sets): the conv's forward workspace comes from the kept workspaces (_kept_ws_checkout) and the prepare
+    stage runs in two launches instead of three."""
     req = _LOSS_REQUEST[-1] if _LOSS_REQUEST else None
     target = None
     if req is not None and req.loss is None and req.target.is_cuda and req.target.dtype == F32 and req.target.dim() == 1 \
@@ -1153,7 +1291,8 @@ def encode_head(table, ids, mask, u_id, i_id, conv_weights, conv_biases, head_pa
         if req.target.shape[0] == B:
             target = req.target
     pred, loss = _EncodeHead.apply(table, id_sets, ids, mask, u_id, i_id, drop, target, padding_idx, pad_u, pad_i,
-                                   len(conv_weights), first, *conv_weights, *conv_biases, *head_params)
+                                   len(conv_weights), first, (target is not None and req.after_backward, bool(own_workspace)),
+                                   *conv_weights, *conv_biases, *head_params)
     if target is not None:
         req.pred_ptr, req.loss = pred.data_ptr(), loss
     return pred

@@ -68,7 +68,7 @@ class DeepCoNNpp(nn.Module):
                         (i_ids, self.item_size, 0)]
                 preds = RF.encode_head(self.word_embeddings.weight, None, masks, None, None, conv.weights(), conv.biases(), head,
                                        id_sets=sets, drop=drop, padding_idx=pad, pad_u=fm.user_padding_idx, pad_i=fm.item_padding_idx,
-                                       first=first)
+                                       first=first, own_workspace=True)      # (two-launch prepare stage on a kept workspace)
             else:
                 preds = RF.encode_head(self.word_embeddings.weight, RF.stack_rows(u_revs, i_revs), masks, u_ids, i_ids,
                                        conv.weights(), conv.biases(), head, drop=drop, padding_idx=pad,

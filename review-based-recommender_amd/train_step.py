@@ -305,7 +305,8 @@ def _forward_loss_backward(model: nn.Module, batch, ratings: torch.Tensor, optim
     scope = optimizer.row_grad_scope() if isinstance(optimizer, HipClipAdam) else contextlib.nullcontext()
     fusable = ratings.is_cuda and ratings.dtype == torch.float32
     with scope:
-        with (RF.fused_loss(ratings) if fusable else contextlib.nullcontext()) as req:
+        # (after_backward: the loss is read only once the backward below has been issued, so the forward may leave it to it)
+        with (RF.fused_loss(ratings, after_backward=True) if fusable else contextlib.nullcontext()) as req:
             out = model(*batch)
             pred = out[0] if isinstance(out, tuple) else out
             loss = req.loss_for(pred) if req is not None else None
@@ -507,7 +508,8 @@ class GraphedForward:
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         self._capture_stream = _capture_stream(batch[0].device)
-        with torch.no_grad(), _lib_mod().capture_guard(self._capture_stream), \
+        self._kept_ws = []           # forward workspaces the graph keeps the addresses of (functional.kept_ws_owner)
+        with torch.no_grad(), _lib_mod().capture_guard(self._capture_stream), RF.kept_ws_owner(self._kept_ws), \
                 torch.cuda.graph(self.graph, stream=self._capture_stream, capture_error_mode=capture_error_mode):
             self._prologue()
             out = model(*self.batch)
@@ -665,17 +667,24 @@ class GraphedTrainStep:
         mode = capture_error_mode or ("thread_local" if grad_sync is not None else "global")
         self._capture_stream = _capture_stream(ratings.device)
         cs = self._capture_stream
+        self._kept_ws = []           # forward workspaces the graphs keep the addresses of (functional.kept_ws_owner)
         for sl in self._slots:
+            if sl is not first:      # every recording takes its own kept workspaces: one more set on the capture stream
+                with torch.cuda.stream(cs):
+                    RF.prepare_stream_state(ratings.device)
+                torch.cuda.synchronize(ratings.device)
             optimizer.zero_grad(set_to_none=True)
             sl.g_fwd_bwd = torch.cuda.CUDAGraph(keep_graph=True) if self._keep_graph else torch.cuda.CUDAGraph()
             if grad_sync is None:
-                with _lib_mod().capture_guard(cs), torch.cuda.graph(sl.g_fwd_bwd, stream=cs, capture_error_mode=mode):
+                with _lib_mod().capture_guard(cs), RF.kept_ws_owner(self._kept_ws), \
+                        torch.cuda.graph(sl.g_fwd_bwd, stream=cs, capture_error_mode=mode):
                     self._prologue(sl)
                     sl.loss, sl.gnorm, sl.pred = train_step(model, optimizer, sl.batch, sl.ratings, max_grad_norm,
                                                             objective=objective)
                 sl.static_grads = [(p, p.grad) for p in model.parameters()]
             else:
-                with _lib_mod().capture_guard(cs), torch.cuda.graph(sl.g_fwd_bwd, stream=cs, capture_error_mode=mode):
+                with _lib_mod().capture_guard(cs), RF.kept_ws_owner(self._kept_ws), \
+                        torch.cuda.graph(sl.g_fwd_bwd, stream=cs, capture_error_mode=mode):
                     self._prologue(sl)
                     optimizer.zero_grad()
                     pred, loss = _forward_loss_backward(model, sl.batch, sl.ratings)
