@@ -719,6 +719,34 @@ int rbr_sample_negatives(int32_t B, int32_t n_neg, int32_t I, int32_t item_lo, c
                          uint64_t* state, int32_t max_tries, int64_t replace_id, int64_t* u_out, int64_t* i_out, float* valid,
                          void* stream);
 
+/* ---- dynamic negative sampling (DNS; Zhang et al., SIGIR 2013) for the same objective: every negative is the best-scoring of
+ *      n_cand (1..64) draws, scored from cached tower latents by the arithmetic of the pair_score entries below.  Arguments,
+ *      outputs (u_out / i_out / valid, slab-major) and state are those of rbr_sample_negatives, except that U >= 1 is ALSO the
+ *      row count of ul / ub (seen_off, when given, is [U + 1]).  mode RBR_SCORE_FM / RBR_SCORE_DOT, ul f32 [U, K], il f32 [I, K]
+ *      (K >= 1, nothing assumed beyond 4-byte alignment), h [K], g [1] (FM), ub [U] / ib [I] or NULL: as rbr_pair_score_ids
+ *      takes them.
+ *      THE DRAW.  Candidate m in [0, n_cand) of negative j of pair b is drawn exactly as rbr_sample_negatives draws, with draw
+ *      index d' = (b * n_neg + j) * n_cand + m in place of d: counter (d' * 16 + (t >> 2), state[0]), key seed, word t & 3, the
+ *      same candidate mapping, rejection against i_ids[b] and the user's seen row, and the same cyclic walk after max_tries
+ *      rejections.  With n_cand = 1 the three outputs equal rbr_sample_negatives' byte for byte.
+ *      THE CHOICE.  Candidate c scores s = score(u_ids[b], c), bit for bit what rbr_pair_score_ids returns for that pair;
+ *      key(m) = 0 where s is NaN, else (order-preserving bits of s) << 32 | (2^32 - 1 - c), the key of rbr_pair_score_topk.  The
+ *      negative is the candidate of the largest key -- score descending, then the lower item id -- and candidate 0 where every
+ *      key is 0.  A u_id outside [0, U) never indexes ul / ub: row 0 stands in (its seen row is empty; the feed's own id check
+ *      reports it).  Where no item is acceptable for (u, i+), which holds for all candidates or none, i_out = replace_id and
+ *      valid = 0 as in rbr_sample_negatives.
+ *      cand_out int64 / cand_score f32 [n_neg * B * n_cand] (each may be NULL), entry (j * B + b) * n_cand + m: every candidate
+ *      (replace_id where none is acceptable) and its score, for tests and tools.
+ *      One launch, one lane per candidate: a draw is W = 2^ceil(log2 n_cand) consecutive lanes and its maximum an xor butterfly
+ *      over them, no atomics but the ticket, no LDS, plain stores: graph-capturable, a new set on every replay.
+ *      B * n_neg * n_cand <= 2^30.                                                                                       ---- */
+int rbr_sample_hard_negatives(int32_t B, int32_t n_neg, int32_t n_cand, int32_t I, int32_t item_lo, const int64_t* u_ids,
+                              const int64_t* i_ids, const int64_t* seen_off, const int32_t* seen_item, int64_t seen_nnz,
+                              int32_t U, int32_t mode, int32_t K, const float* ul, const float* il, const float* h,
+                              const float* g, const float* ub, const float* ib, uint64_t seed, uint64_t* state,
+                              int32_t max_tries, int64_t replace_id, int64_t* u_out, int64_t* i_out, float* valid,
+                              int64_t* cand_out, float* cand_score, void* stream);
+
 /* ---- scoring and top-K recommendation from cached tower latents.  Every tower depends on its own side only, so a catalogue is
  *      encoded once into latent tables ul [U, K] / il [I, K] and a (user, item) score is the pair-dependent tail:
  *        RBR_SCORE_FM : relu(ul[u,:] * il[i,:]) . h + ub[u] + ib[i] + g    FM.forward in eval mode, no dropout

@@ -187,6 +187,9 @@ SIGNATURES = {
                                        c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, c_stream]),
     "rbr_sample_negatives": (C.c_int, [i32, i32, i32, i32, c_i64p, c_i64p, c_i64p, c_i32p, C.c_int64, i32, C.c_uint64, C.c_void_p,
                                        i32, C.c_int64, c_i64p, c_i64p, c_f32p, c_stream]),
+    "rbr_sample_hard_negatives": (C.c_int, [i32, i32, i32, i32, i32, c_i64p, c_i64p, c_i64p, c_i32p, C.c_int64, i32, i32, i32, c_f32p,
+                                            c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_uint64, C.c_void_p, i32, C.c_int64, c_i64p,
+                                            c_i64p, c_f32p, c_i64p, c_f32p, c_stream]),
     "rbr_review_attn_fwd": (C.c_int, [i32, i32, i32, i32, c_f32p, c_i64p, C.POINTER(AttnParams), c_f32p, c_f32p, c_f32p,
                                       c_f32p, c_stream]),
     "rbr_review_attn_bwd_ws_floats": (C.c_size_t, [i32, i32, i32, i32]),

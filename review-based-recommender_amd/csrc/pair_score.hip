@@ -4,7 +4,7 @@
 //                                                                      ub / ib NULL = FMWithoutUIBias)
 //   RBR_SCORE_DOT: sum_k ul[u,k] * il[i,k]                             D-ATT (dual_att/dual_att.py:58)
 // The FM score is not a GEMM (the ReLU sits between the product and the sum over k).  Four entries share ONE arithmetic,
-// score_step / score_finish below -- explicit fmaf / __fmul_rn, k ascending -- so they agree bit for bit on the same pair:
+// score_step / score_finish of pair_score_math.h -- explicit fmaf / __fmul_rn, k ascending -- so they agree bit for bit on the same pair:
 //   rbr_pair_score_ids  : B pairs gathered by id (validation from the tables instead of two document encodes per pair)
 //   rbr_pair_score_dense: the [Nu, Ni] matrix (tests, small catalogues)
 //   rbr_pair_score_topk : the k best items of every user row WITHOUT the [Nu, Ni] matrix, two launches:
@@ -28,6 +28,7 @@
 //        after the sweep, not a binary search per (pair, item) inside it.
 //   All counts are integers: the same bytes on every run.
 #include "rbr_common.h"
+#include "pair_score_math.h"
 
 #include <cmath>
 #include <cstdint>
@@ -41,22 +42,7 @@ constexpr int kMaxSplits = 64;       // item slices
 constexpr int kTargetWaves = 2048;   // slice-kernel waves aimed at: 8 per CU.  Fewer, longer slices keep the insertions (about
                                      // k * ln(slice / k) per user and slice) small beside the 3 * K * slice instructions of scoring
 
-// ---- the one arithmetic of all three entries
-template <int MODE> __device__ __forceinline__ float score_step(float acc, float u, float i, float h) {
-    if (MODE == RBR_SCORE_FM) return fmaf(fmaxf(__fmul_rn(u, i), 0.f), h, acc);
-    return fmaf(u, i, acc);
-}
-template <int MODE> __device__ __forceinline__ float score_finish(float acc, float ub, float ib, float g) {
-    if (MODE == RBR_SCORE_FM) return __fadd_rn(__fadd_rn(__fadd_rn(acc, ub), ib), g);
-    return acc;
-}
-template <int MODE>
-__device__ __forceinline__ float score_pair(const float* __restrict__ u, const float* __restrict__ i, const float* __restrict__ h, int K,
-                                            float ub, float ib, float g) {
-    float acc = 0.f;
-    for (int k = 0; k < K; ++k) acc = score_step<MODE>(acc, u[k], i[k], MODE == RBR_SCORE_FM ? h[k] : 0.f);
-    return score_finish<MODE>(acc, ub, ib, g);
-}
+// ---- the one arithmetic of all entries (score_step / score_finish / score_pair) and the key: pair_score_math.h
 
 struct ScoreParams {
     const float* ul; const float* il;     // [U, K] / [I, K]
@@ -101,17 +87,7 @@ __global__ __launch_bounds__(256) void pair_score_dense_kernel(const ScoreParams
 }
 
 // ---------------------------------------------------------------------------------------------------------------- top-k
-__device__ __forceinline__ unsigned long long make_key(float s, int item) {
-    unsigned b = __float_as_uint(s);
-    b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((unsigned long long)b << 32) | (0xFFFFFFFFu - (unsigned)item);
-}
-__device__ __forceinline__ float key_score(unsigned long long key) {
-    unsigned b = (unsigned)(key >> 32);
-    b = (b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b;
-    return __uint_as_float(b);
-}
-__device__ __forceinline__ int key_item(unsigned long long key) { return (int)(0xFFFFFFFFu - (unsigned)key); }
+// (make_key / key_score / key_item: pair_score_math.h)
 
 // Lst[0 .. k): keys descending, 0 = empty slot.  All 64 lanes of the (single-wave) workgroup insert the same key x, which is
 // in no slot yet: slot p keeps its key when that is larger, takes x when its predecessor is larger, else its predecessor's key.

@@ -505,30 +505,61 @@ class NegativeFeed:
     negatives.  A review feed applies its leave-one-out rule to every expanded pair as to any pair (a negative's pair has no
     review of its own to leave out).
 
+    n_cand > 1 is dynamic negative sampling (functional.sample_hard_negatives): every negative is the best-scoring of n_cand such
+    draws under latent tables handed over with set_tables(); only the winner is gathered and encoded.  The feed keeps its OWN
+    static copies of the tables, so a recorded step holds valid pointers across refreshes; the head's parameters are the model's
+    live ones.  n_cand = 1 (the default) is the uniform sampler, call for call.
+
     The expanded ids and the `valid` flags (f32 [n_neg * B]: 0 where a user has no unrated item) live in static buffers, one
     set per batch size B (`buffers(B)`; `u_out` / `i_out` / `valid` are those of the last gather); `state` is the sampler's
     [call number, ticket] on the device.  reseed(seed, call) restarts the sequence: (seed, call) fixes a draw exactly."""
 
-    def __init__(self, feed, seen, n_items: int, n_neg: int = 1, seed: int = 0, item_lo: int = 1, max_tries: int = 16):
+    def __init__(self, feed, seen, n_items: int, n_neg: int = 1, seed: int = 0, item_lo: int = 1, max_tries: int = 16,
+                 n_cand: int = 1):
         if isinstance(n_neg, bool) or not isinstance(n_neg, int) or n_neg < 1:
             raise ValueError(f"n_neg must be an integer >= 1, got {n_neg!r}")
         if not 0 <= int(item_lo) < int(n_items):
             raise ValueError(f"item_lo {item_lo} leaves no item of [0, {n_items})")
         if not 1 <= int(max_tries) <= 64:
             raise ValueError(f"max_tries must be in [1, 64], got {max_tries}")
+        if isinstance(n_cand, bool) or not isinstance(n_cand, int) or not 1 <= n_cand <= 64:
+            raise ValueError(f"n_cand must be an integer in [1, 64], got {n_cand!r}")
         self.feed, self.device = feed, torch.device(feed.device)
         self.seen = None if seen is None else (seen[0].to(self.device), seen[1].to(self.device))
         self.n_items, self.n_neg, self.item_lo, self.max_tries = int(n_items), n_neg, int(item_lo), int(max_tries)
+        self.n_cand = n_cand
         self.seed = int(seed)
         self.state = torch.zeros(2, dtype=torch.int64, device=self.device)
         self._buffers = {}
         self._last = None
+        self._tables = None          # (mode, ul, il, h, g, ub, ib) of set_tables: ul / il the feed's own copies
 
     def reseed(self, seed: int, call: int = 0) -> None:
         """The next draw is call number `call` under `seed` (no host synchronisation: one small copy on the current stream).
         A recorded step holds the seed it was recorded with: reseed it with that seed, to move the call number only."""
         self.seed = int(seed)
         self.state.copy_(torch.tensor([int(call), 0], dtype=torch.int64), non_blocking=True)
+
+    def set_tables(self, mode, ul, il, h=None, g=None, ub=None, ib=None) -> None:
+        """The latent tables ul [U, K] / il [n_items, K] and the head (`mode`, h, g, ub, ib: model.score_mode_and_params()) that
+        score the candidates of n_cand > 1.  The first call allocates the feed's own f32 copies of ul / il; later calls copy into
+        them (same shapes), on the current stream: a step recorded in between keeps its pointers and draws from the new values.
+        h, g, ub, ib are kept as given -- the model's live parameters, not copies."""
+        if ul.dim() != 2 or il.dim() != 2 or ul.shape[1] != il.shape[1] or il.shape[0] != self.n_items:
+            raise ValueError(f"latent tables must be [U, K] / [{self.n_items}, K], got {tuple(ul.shape)} / {tuple(il.shape)}")
+        if self._tables is None:
+            own_ul = ul.detach().to(self.device, torch.float32, copy=True).contiguous()
+            own_il = il.detach().to(self.device, torch.float32, copy=True).contiguous()
+        else:
+            own_ul, own_il = self._tables[1], self._tables[2]
+            if own_ul.shape != ul.shape or own_il.shape != il.shape:
+                raise ValueError(f"latent tables changed shape: {tuple(own_ul.shape)} / {tuple(own_il.shape)} were set, got "
+                                 f"{tuple(ul.shape)} / {tuple(il.shape)}")
+            own_ul.copy_(ul.detach())
+            own_il.copy_(il.detach())
+        self._tables = (mode, own_ul, own_il, h, g, ub, ib)
+
+    tables = property(lambda self: None if self._tables is None else self._tables[1:3], doc="the feed's own (ul, il), or None")
 
     def buffers(self, B: int):
         """(u_out, i_out, valid) of batch size B: the sampler's static outputs."""
@@ -547,10 +578,19 @@ class NegativeFeed:
     def sample(self, u_ids: torch.Tensor, i_ids: torch.Tensor):
         """Draws the negatives of the pairs into buffers(B) and returns them."""
         from . import functional as RF
+        if self.n_cand > 1 and self._tables is None:
+            raise RuntimeError("NegativeFeed(n_cand > 1) scores its candidates from latent tables: call set_tables() first")
         u_ids, i_ids = u_ids.to(self.device, non_blocking=True), i_ids.to(self.device, non_blocking=True)
-        self._last = RF.sample_negatives(u_ids, i_ids, self.n_neg, self.n_items, self.seen, state=self.state, seed=self.seed,
-                                         item_lo=self.item_lo, max_tries=self.max_tries, replace_id=self.item_lo,
-                                         out=self.buffers(u_ids.shape[0]))
+        if self.n_cand == 1:
+            self._last = RF.sample_negatives(u_ids, i_ids, self.n_neg, self.n_items, self.seen, state=self.state, seed=self.seed,
+                                             item_lo=self.item_lo, max_tries=self.max_tries, replace_id=self.item_lo,
+                                             out=self.buffers(u_ids.shape[0]))
+        else:
+            mode, ul, il, h, g, ub, ib = self._tables
+            self._last = RF.sample_hard_negatives(u_ids, i_ids, self.n_neg, self.n_items, self.seen, n_cand=self.n_cand, mode=mode,
+                                                  ul=ul, il=il, h=h, g=g, ub=ub, ib=ib, state=self.state, seed=self.seed,
+                                                  item_lo=self.item_lo, max_tries=self.max_tries, replace_id=self.item_lo,
+                                                  out=self.buffers(u_ids.shape[0]))
         return self._last
 
     def empty_inputs(self, B: int, with_ids: bool = True):

@@ -2542,16 +2542,9 @@ def pair_score_rank(mode, ul, il, targets, h=None, g=None, ub=None, ib=None, *, 
 
 
 # --------------------------------------------------------------------------- negatives for a pairwise objective
-def sample_negatives(u_ids, i_ids, n_neg: int, n_items: int, seen=None, *, state, seed: int = 0, item_lo: int = 1,
-                     max_tries: int = 16, replace_id: int = 0, out=None):
-    """(u_out int64 [(1 + n_neg) * B], i_out int64 [(1 + n_neg) * B], valid f32 [n_neg * B]) for the observed pairs (u_ids[b],
-    i_ids[b]) (rbr_sample_negatives, one launch): rows [0, B) are the pairs themselves, rows [(j+1)B, (j+2)B) pair b's j-th
-    negative -- an item of [item_lo, n_items) that is neither i_ids[b] nor in the user's row of `seen`, with replacement across j;
-    valid[j*B + b] = 0 (and item replace_id) where a user has no such item.  `seen`: a recommend.SeenItems / (off int64 [U + 1],
-    items int32 sorted within a row) over all user ids -- the first exclusion form of pair_score_topk -- or None.
-    `state`: int64 [2] on the device, [call number, 0]; the launch advances the call number itself, so two calls (or two replays of
-    a recorded call) draw different sets, and (seed, call number) fixes a set exactly (the draw is stated in include/rbr_hip.h).
-    `out`: the three tensors to write into.  No autograd, no host synchronisation, no allocation with `out`: graph-capturable."""
+def _sampler_operands(u_ids, i_ids, n_neg, seen, state, out):
+    """The operands both samplers share, checked: contiguous ids, B, n_neg, the seen CSR (U rows, offsets, items, nnz) and the
+    three output tensors (allocated where `out` is None)."""
     u_ids, i_ids = u_ids.contiguous(), i_ids.contiguous()
     if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
         raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
@@ -2569,10 +2562,60 @@ def sample_negatives(u_ids, i_ids, n_neg: int, n_items: int, seen=None, *, state
     u_out, i_out, valid = out
     if u_out.shape != (rows,) or i_out.shape != (rows,) or valid.shape != (rows - B,):
         raise RuntimeError(f"out must be u_out [{rows}], i_out [{rows}], valid [{rows - B}]")
+    return u_ids, i_ids, B, n_neg, U, off, items, nnz, (u_out, i_out, valid)
+
+
+def sample_negatives(u_ids, i_ids, n_neg: int, n_items: int, seen=None, *, state, seed: int = 0, item_lo: int = 1,
+                     max_tries: int = 16, replace_id: int = 0, out=None):
+    """(u_out int64 [(1 + n_neg) * B], i_out int64 [(1 + n_neg) * B], valid f32 [n_neg * B]) for the observed pairs (u_ids[b],
+    i_ids[b]) (rbr_sample_negatives, one launch): rows [0, B) are the pairs themselves, rows [(j+1)B, (j+2)B) pair b's j-th
+    negative -- an item of [item_lo, n_items) that is neither i_ids[b] nor in the user's row of `seen`, with replacement across j;
+    valid[j*B + b] = 0 (and item replace_id) where a user has no such item.  `seen`: a recommend.SeenItems / (off int64 [U + 1],
+    items int32 sorted within a row) over all user ids -- the first exclusion form of pair_score_topk -- or None.
+    `state`: int64 [2] on the device, [call number, 0]; the launch advances the call number itself, so two calls (or two replays of
+    a recorded call) draw different sets, and (seed, call number) fixes a set exactly (the draw is stated in include/rbr_hip.h).
+    `out`: the three tensors to write into.  No autograd, no host synchronisation, no allocation with `out`: graph-capturable."""
+    u_ids, i_ids, B, n_neg, U, off, items, nnz, (u_out, i_out, valid) = _sampler_operands(u_ids, i_ids, n_neg, seen, state, out)
     if B == 0 and n_neg >= 1:
         return u_out, i_out, valid
     _call("sample_negatives", _lib.lib().rbr_sample_negatives, B, n_neg, int(n_items), int(item_lo), dev_ptr(u_ids, I64, "u_ids"),
           dev_ptr(i_ids, I64, "i_ids"), dev_ptr(off, I64, "seen offsets"), dev_ptr(items, I32, "seen items"), nnz, U,
           int(seed) & 0xFFFFFFFFFFFFFFFF, dev_ptr(state, I64, "state"), int(max_tries), int(replace_id), dev_ptr(u_out, I64, "u_out"),
           dev_ptr(i_out, I64, "i_out"), dev_ptr(valid, F32, "valid"), current_stream())
+    return u_out, i_out, valid
+
+
+def sample_hard_negatives(u_ids, i_ids, n_neg: int, n_items: int, seen=None, *, n_cand: int, mode, ul, il, h=None, g=None, ub=None,
+                          ib=None, state, seed: int = 0, item_lo: int = 1, max_tries: int = 16, replace_id: int = 0, out=None,
+                          return_candidates: bool = False):
+    """sample_negatives with dynamic negative sampling (rbr_sample_hard_negatives, one launch): every negative is the best-scoring
+    of n_cand (1..64) draws of sample_negatives' kind -- candidate m of draw d uses draw index d * n_cand + m -- scored from the
+    latent tables ul [U, K] / il [I, K] with the arithmetic and the operands of pair_score (`mode`, h, g, ub, ib), bit for bit;
+    score descending, ties by the lower item id, a NaN score never wins while another candidate has a number.  n_cand = 1 gives
+    sample_negatives' outputs byte for byte.  U is the row count of ul AND of `seen`; a user id outside [0, U) scores as row 0.
+    Returns (u_out, i_out, valid) in sample_negatives' layout; with return_candidates also (cand int64, cand_score f32), each
+    [n_neg, B, n_cand]: every candidate (replace_id where a user has no acceptable item) and its score.  The tables and the head's
+    parameters are read through their pointers at every launch: a recorded call sees what they hold at replay time.  No autograd,
+    no host synchronisation, no allocation with `out` and without return_candidates: graph-capturable."""
+    u_ids, i_ids, B, n_neg, seen_rows, off, items, nnz, (u_out, i_out, valid) = _sampler_operands(u_ids, i_ids, n_neg, seen, state, out)
+    code, ul, il, h, g, ub, ib = _score_operands(mode, ul, il, h, g, ub, ib)
+    U, n_cand = ul.shape[0], int(n_cand)
+    if seen is not None and seen_rows != U:
+        raise RuntimeError(f"seen must hold one row per row of ul ({U}), got {seen_rows}")
+    if il.shape[0] != int(n_items):
+        raise RuntimeError(f"il must hold n_items = {int(n_items)} rows, got {il.shape[0]}")
+    cand = cand_score = None
+    if return_candidates:
+        cand = torch.empty(max(n_neg, 0), B, max(n_cand, 0), dtype=I64, device=u_ids.device)
+        cand_score = torch.empty(max(n_neg, 0), B, max(n_cand, 0), dtype=F32, device=u_ids.device)
+    if not (B == 0 and n_neg >= 1 and 1 <= n_cand <= 64):
+        _call("sample_hard_negatives", _lib.lib().rbr_sample_hard_negatives, B, n_neg, n_cand, int(n_items), int(item_lo),
+              dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"), dev_ptr(off, I64, "seen offsets"),
+              dev_ptr(items, I32, "seen items"), nnz, U, code, ul.shape[1], dev_ptr(ul, F32, "ul"), dev_ptr(il, F32, "il"),
+              dev_ptr(h, F32, "h"), dev_ptr(g, F32, "g"), dev_ptr(ub, F32, "ub"), dev_ptr(ib, F32, "ib"),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, dev_ptr(state, I64, "state"), int(max_tries), int(replace_id),
+              dev_ptr(u_out, I64, "u_out"), dev_ptr(i_out, I64, "i_out"), dev_ptr(valid, F32, "valid"),
+              dev_ptr(cand, I64, "cand"), dev_ptr(cand_score, F32, "cand_score"), current_stream())
+    if return_candidates:
+        return u_out, i_out, valid, cand, cand_score
     return u_out, i_out, valid

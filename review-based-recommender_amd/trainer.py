@@ -42,7 +42,14 @@ ignored) trains for ranking with the in-batch softmax: the batch stays the B obs
 items of the batch -- less the pad id, the pair's own item and the items the user has rated in the training split -- scored from
 the towers' latent rows over all B x B pairs (data.InBatchFeed, train_step.InBatchSoftmaxObjective); logq_correction subtracts
 log((count_i + 1) / (N + I)) of the training examples from item i's logit; the step log line keeps its format with the loss under
-`loss`.
+`loss`;
+`neg_candidates: M` (1..64, default 1 = the uniform sampler, call for call; above 1 needs loss "bpr") is dynamic negative sampling:
+every negative is the best-scoring of M uniform draws, scored on the device from the latent tables of the validation's
+recommend.Recommender under the model's live head parameters (functional.sample_hard_negatives), and only the winner is encoded.
+The tables are a snapshot: encoded once before the first training step and taken over from every validation pass's refresh for the
+next epoch, and with `neg_refresh_steps: N` (default 0 = never) also re-encoded every N updates within an epoch; the feed keeps its
+own copies (data.NegativeFeed.set_tables), so a recorded step stays valid across refreshes.  A small M is advised: the arg-max of
+many candidates is often an item the user would rate well but has not rated in the training split.  The log format is unchanged.
 """
 from __future__ import annotations
 
@@ -81,7 +88,7 @@ DEFAULTS = dict(log_dir="logs", dataset="dataset", log=True, log_idx=500, verbos
                 batch_size=50, lr=0.002, max_grad_norm=5.0, patience=5, dropout=0.5, arch="CNN", use_pretrain=False,
                 num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False, eval_from_towers=False,
                 device_reviews=False, rank_metrics=[], loss="mse", n_neg=1, neg_seed=None, select_by="rmse",
-                softmax_temperature=1.0, logq_correction=False)
+                softmax_temperature=1.0, logq_correction=False, neg_candidates=1, neg_refresh_steps=0)
 
 LOSSES = ("mse", "bpr", "softmax")
 
@@ -225,6 +232,16 @@ class ReviewExperiment:
             if metric is None:
                 raise ValueError("loss \"bpr\" needs a rank metric in select_by (\"hr@K\", \"ndcg@K\" or \"mrr\"): a "
                                  "pairwise loss does not fit ratings, so the validation RMSE cannot select the model")
+        nc, nr = args.neg_candidates, args.neg_refresh_steps
+        if isinstance(nc, bool) or not isinstance(nc, int) or not 1 <= nc <= 64:
+            raise ValueError(f"neg_candidates must be an integer in [1, 64], got {nc!r}")
+        if nc > 1 and args.loss != "bpr":
+            raise ValueError(f"neg_candidates {nc} needs loss \"bpr\": the candidates are negatives of the pairwise step, and loss "
+                             f"{args.loss!r} draws none")
+        if isinstance(nr, bool) or not isinstance(nr, int) or nr < 0:
+            raise ValueError(f"neg_refresh_steps must be an integer >= 0, got {nr!r}")
+        if nr > 0 and nc == 1:
+            raise ValueError(f"neg_refresh_steps {nr} needs neg_candidates > 1: the uniform sampler reads no latent tables")
         if args.loss == "softmax":
             t = args.softmax_temperature
             if isinstance(t, bool) or not isinstance(t, (int, float)) or not (0.0 < float(t) < math.inf):
@@ -275,7 +292,8 @@ class ReviewExperiment:
             from .train_step import BprObjective
             self._seen = Recommender.seen_from(self.train_set.examples, self.train_set.user_num, self.device)
             seed = args.seed if args.neg_seed is None else args.neg_seed
-            self.train_feed = D.NegativeFeed(self.train_feed, self._seen, self.cache.item.shape[0], n_neg=args.n_neg, seed=int(seed))
+            self.train_feed = D.NegativeFeed(self.train_feed, self._seen, self.cache.item.shape[0], n_neg=args.n_neg, seed=int(seed),
+                                             n_cand=args.neg_candidates)
             self.objective = BprObjective(self.train_feed)
         self._make_dir()
         self.build_model()
@@ -380,7 +398,12 @@ class ReviewExperiment:
         steps = count = 0
         start = time.time()
         self.model.train()
+        hard = a.neg_candidates > 1
+        if hard and self.train_feed.tables is None:
+            self._refresh_negative_tables()              # before the first training step; later epochs use the validation's tables
         for i, batch in enumerate(loader):
+            if hard and a.neg_refresh_steps > 0 and i > 0 and i % a.neg_refresh_steps == 0:
+                self._refresh_negative_tables()
             staged = self._step_from_host(batch)
             if staged is not None:
                 loss, gnorm, ratings = staged
@@ -498,6 +521,23 @@ class ReviewExperiment:
         out = self.model(*inputs)
         return out[0] if isinstance(out, tuple) else out
 
+    def _negative_towers(self):
+        """The one Recommender of this experiment: the validation's latent tables, and with neg_candidates > 1 the sampler's."""
+        if getattr(self, "_towers", None) is None:
+            from .recommend import Recommender
+            self._towers = Recommender(self.model, self.cache)
+        return self._towers
+
+    def _hand_tables_to_feed(self, towers):
+        """neg_candidates > 1: the feed copies the tables (a recorded step keeps its pointers); the head's parameters stay live."""
+        mode, h, g, ub, ib = self.model.score_mode_and_params()
+        self.train_feed.set_tables(mode, towers.user_latents, towers.item_latents, h, g, ub, ib)
+
+    def _refresh_negative_tables(self):
+        """Encodes the catalogue with the parameters as they are now and hands the tables to the negative sampler (the model's
+        train / eval mode is as before afterwards: Recommender.refresh restores it)."""
+        self._hand_tables_to_feed(self._negative_towers().refresh())
+
     def valid_one_epoch(self):
         loader = self.valid_loader
         sq_err = torch.zeros((), device=self.device, dtype=torch.float64)
@@ -509,11 +549,10 @@ class ReviewExperiment:
         if self.args.eval_from_towers:
             # every user / item document encoded ONCE into latent tables (the parameters changed since the last epoch), then a
             # pair is two row gathers and the head's arithmetic instead of two document encodes (recommend.Recommender)
-            if getattr(self, "_towers", None) is None:
-                from .recommend import Recommender
-                self._towers = Recommender(self.model, self.cache)
-            towers = self._towers
+            towers = self._negative_towers()
             towers.refresh()
+            if self.args.neg_candidates > 1:
+                self._hand_tables_to_feed(towers)          # the next epoch's candidates are scored from this pass's tables
         ranks = []
         if self.args.rank_metrics and getattr(self, "_seen", None) is None:
             # what a validation item competes against: every item its user has not rated in the training split
