@@ -471,8 +471,8 @@ int rbr_bpr_loss_bwd(int32_t B, int32_t n_neg, const float* pred, const float* v
  *     dropout (FM only): drop [B, B, K] an explicit multiplier, OR p_drop > 0 with seed and rng_state: element (a, b, k) gets
  *     exactly what rbr_dropout_multiplier(B*B*K, p_drop, seed, rng_state, ...) writes at (a*B + b)*K + k for the same call number
  *     (both launches read the call number before the second advances it, once); u_id, i_id int64 [B]; the seen-items CSR of
- *     rbr_sample_negatives (seen_off int64 [U + 1], seen_item int32 [seen_nnz] sorted within a row; both NULL = none; offsets
- *     clamped to [0, seen_nnz]; a u_id outside [0, U) has an empty row); item_lo; logq [B] or NULL (log sampling probability of
+ *     rbr_sample_negatives (seen_off int64 [U + 1], seen_item int32 [seen_nnz] sorted within a row; both NULL = none; a malformed
+ *     list and a u_id outside [0, U) are read by the one rule stated at rbr_pair_score_topk); item_lo; logq [B] or NULL (log sampling probability of
  *     column b's item); inv_temp > 0.
  *       core(a,b)    = FM: sum_k relu(ul[a,k] * il[b,k]) * drop[a,b,k] * h[k]      DOT: sum_k ul[a,k] * il[b,k]
  *       s[a,b]       = core(a,b) + row_bias[a] + col_bias[b]
@@ -697,8 +697,8 @@ int rbr_review_gather(int32_t B, int32_t R, int32_t T, const int64_t* u_ids, con
 /* ---- negatives for a pairwise objective, in front of either id feed: for each of the B observed pairs (u_ids[b], i_ids[b]),
  *      n_neg >= 1 items of [item_lo, I) that are neither i_ids[b] nor in the user's seen row, with replacement across j.
  *      seen_off int64 [U + 1] / seen_item int32 [seen_nnz]: the CSR rbr_pair_score_topk takes for its exclusion (sorted within a
- *      row; both NULL and seen_nnz 0 for none; offsets outside [0, seen_nnz] are clamped).  A u_id outside [0, U) has an empty
- *      seen row (the feed's own id check reports it).
+ *      row; both NULL and seen_nnz 0 for none), read by the one rule stated there: a malformed offset is clamped, and a u_id
+ *      outside [0, U) has an empty seen row (the feed's own id check reports it).
  *      Outputs, slab-major, row r = j * B + b: u_out / i_out int64 [(1 + n_neg) * B] -- slab 0 holds the observed pairs
  *      (i_out[b] = i_ids[b]), slab 1 + j the j-th negatives, u_out[j*B + b] = u_ids[b] in every slab; valid f32 [n_neg * B],
  *      valid[j*B + b] = 1 when pair b's j-th negative (row (j+1)*B + b) was drawn, 0 when no item is acceptable.
@@ -761,7 +761,8 @@ int rbr_sample_hard_negatives(int32_t B, int32_t n_neg, int32_t n_cand, int32_t 
  *      pair_score_topk : for each of the Nu user rows the k best items of [item_lo, Ni): out_item int64 [Nu, k], out_score
  *        [Nu, k], score descending, ties by the lower item id; the same bytes on every run.  excl_off int64 [Nu + 1] /
  *        excl_item int32 [excl_nnz] (CSR, sorted within a row; both NULL and excl_nnz 0 for none) lists items that never appear;
- *        offsets outside [0, excl_nnz] are clamped.  excl_row int64 [Nu] (or NULL): user row r takes row excl_row[r] of a CSR of
+ *        THE RULE for every entry that takes such a list (csrc/item_csr.h): a row's offsets are clamped to [0, excl_nnz] and its end
+ *        raised to its start, so nothing outside excl_item is read, and a row outside the CSR lists nothing.  excl_row int64 [Nu] (or NULL): user row r takes row excl_row[r] of a CSR of
  *        excl_rows rows instead of row r (a CSR over all user ids serving a block of users; a row outside it excludes nothing).
  *        A row with fewer than k candidates ends in item -1, score -inf.  NaN scores
  *        are never returned.  1 <= k <= 128 and K <= 4096, else RBR_ERR_UNSUPPORTED.  [Nu, Ni] is never materialised:

@@ -808,7 +808,6 @@ namespace rbr {
 __global__ __launch_bounds__(256) void dropout_mult_kernel(long n, float p, unsigned long long seed,
                                                            unsigned long long* __restrict__ state, float* __restrict__ out) {
     const unsigned long long call = state[0];
-    const float keep = 1.f / (1.f - p);
     const long nquads = (n + 3) >> 2;
     for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nquads; q += (long)gridDim.x * 256) {
         unsigned c0, c1, c2, c3;
@@ -817,16 +816,11 @@ __global__ __launch_bounds__(256) void dropout_mult_kernel(long n, float p, unsi
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const long i = 4 * q + e;
-            if (i < n) out[i] = dropout_keep(w[e], p) ? keep : 0.f;
+            if (i < n) out[i] = dropout_word_mult(w[e], p);
         }
     }
     __syncthreads();
-    if (threadIdx.x == 0) {       // (no fence needed: the call number was consumed before this atomic is issued)
-        if (atomicAdd(state + 1, 1ull) == (unsigned long long)gridDim.x - 1) {      // every workgroup has read state[0]
-            state[1] = 0;
-            state[0] = call + 1;
-        }
-    }
+    if (threadIdx.x == 0) rng_advance_call(state, call);
 }
 
 }  // namespace rbr

@@ -13,6 +13,7 @@
 // descending, then item ascending -- is the negative.  One lane per candidate, a draw is a group of W = 2^ceil(log2 n_cand)
 // consecutive lanes, the group's maximum an xor butterfly on the two halves of the key; only the winner is encoded afterwards.
 #include "rbr_common.h"
+#include "item_csr.h"
 #include "pair_score_math.h"
 
 namespace rbr {
@@ -20,44 +21,25 @@ namespace rbr {
 struct NegSample {
     const long long* u_ids;
     const long long* i_ids;
-    const long long* seen_off;     // [U + 1] or null
-    const int* seen_item;          // sorted within a user
-    long long seen_nnz;
+    ItemCsr seen;                  // row u: the items user u has seen (item_csr.h)
     long long* u_out;              // [(1 + n_neg) * B]
     long long* i_out;
     float* valid;                  // [n_neg * B]
     unsigned long long seed;
     long long replace;
-    int B, n_neg, I, item_lo, U, max_tries;
+    int B, n_neg, I, item_lo, max_tries;
 };
-
-// [a, e) of seen_item that serves user u; an id outside [0, U) has no row, and a malformed CSR cannot send a reader outside
-// seen_item (offsets clamped to [0, seen_nnz], as rbr_pair_score_topk clamps them)
-__device__ __forceinline__ void seen_bounds(const NegSample& S, long long u, long long& a, long long& e) {
-    a = e = 0;
-    if (S.seen_off == nullptr || (unsigned long long)u >= (unsigned long long)S.U) return;
-    a = S.seen_off[u]; e = S.seen_off[u + 1];
-    a = a < 0 ? 0 : a;
-    e = e > S.seen_nnz ? S.seen_nnz : e;
-    if (e < a) e = a;
-}
 
 // a negative may be any item but the pair's own and those of the user's seen row [a, e)
 __device__ __forceinline__ bool neg_acceptable(const int* __restrict__ seen_item, long long c, long long pos, long long a, long long e) {
-    if (c == pos) return false;
-    long long lo = a, hi = e;
-    while (lo < hi) {
-        const long long mid = (lo + hi) >> 1;
-        if ((long long)seen_item[mid] < c) lo = mid + 1; else hi = mid;
-    }
-    return !(lo < e && (long long)seen_item[lo] == c);
+    return c != pos && !csr_has(seen_item, a, e, c);
 }
 
 // THE DRAW of include/rbr_hip.h for draw index d under call number `call`: the item, and whether it is acceptable at all
 __device__ __forceinline__ bool draw_negative(const NegSample& S, unsigned long long d, unsigned long long call, long long u, long long pos,
                                               long long& c) {
     long long a, e;
-    seen_bounds(S, u, a, e);
+    csr_row(S.seen, u, a, e);
     const unsigned long long range = (unsigned long long)(S.I - S.item_lo);
     c = S.item_lo;
     bool found = false;
@@ -66,25 +48,14 @@ __device__ __forceinline__ bool draw_negative(const NegSample& S, unsigned long 
         if ((t & 3) == 0) philox4x32_10(d * 16ull + (unsigned long long)(t >> 2), call, S.seed, w0, w1, w2, w3);
         const unsigned word = (t & 3) == 0 ? w0 : (t & 3) == 1 ? w1 : (t & 3) == 2 ? w2 : w3;
         c = (long long)S.item_lo + (long long)(((unsigned long long)word * range) >> 32);
-        found = neg_acceptable(S.seen_item, c, pos, a, e);
+        found = neg_acceptable(S.seen.item, c, pos, a, e);
     }
     // crowded row: walk on from the last candidate, cyclically, to the first acceptable item (`range` steps visit every item)
     for (unsigned long long s = 0; s < range && !found; ++s) {
         c = (long long)S.item_lo + (long long)(((unsigned long long)(c - S.item_lo) + 1ull) % range);
-        found = neg_acceptable(S.seen_item, c, pos, a, e);
+        found = neg_acceptable(S.seen.item, c, pos, a, e);
     }
     return found;
-}
-
-// the last workgroup to get here advances the call number (no fence needed: every lane consumed it before this atomic is issued)
-__device__ __forceinline__ void advance_call(unsigned long long* __restrict__ state, unsigned long long call) {
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (atomicAdd(state + 1, 1ull) == (unsigned long long)gridDim.x - 1) {      // every workgroup has read state[0]
-            state[1] = 0;
-            state[0] = call + 1;
-        }
-    }
 }
 
 __global__ __launch_bounds__(256) void sample_negatives_kernel(const NegSample S, unsigned long long* __restrict__ state) {
@@ -105,16 +76,18 @@ __global__ __launch_bounds__(256) void sample_negatives_kernel(const NegSample S
             S.i_out[b] = pos;
         }
     }
-    advance_call(state, call);
+    __syncthreads();
+    if (threadIdx.x == 0) rng_advance_call(state, call);
 }
 
 struct HardNeg {
-    NegSample S;                   // S.U: rows of ul / ub AND of the seen CSR
+    NegSample S;
     const float* ul; const float* il;     // [U, K] / [I, K]
     const float* h; const float* g;       // [K], [1] (FM)
     const float* ub; const float* ib;     // [U], [I] or null (FM)
     long long* cand_out;           // [n_neg * B * n_cand] or null
     float* cand_score;             // [n_neg * B * n_cand] or null
+    int U;                         // rows of ul / ub AND of the seen CSR
     int K, n_cand, log_w;          // a draw is 1 << log_w consecutive lanes, the first n_cand of them live
 };
 
@@ -136,7 +109,7 @@ __global__ __launch_bounds__(256) void sample_hard_negatives_kernel(const HardNe
         u = S.u_ids[b];
         found = draw_negative(S, (unsigned long long)d * (unsigned long long)A.n_cand + (unsigned long long)m, call, u, S.i_ids[b], c);
         if (!found) c = S.replace;                  // nothing is acceptable for (u, i+): so says every candidate of the draw
-        const size_t ur = (unsigned long long)u < (unsigned long long)S.U ? (size_t)u : 0;      // an id outside the table: row 0
+        const size_t ur = (unsigned long long)u < (unsigned long long)A.U ? (size_t)u : 0;      // an id outside the table: row 0
         const float ub = (MODE == RBR_SCORE_FM && A.ub) ? A.ub[ur] : 0.f, ib = (MODE == RBR_SCORE_FM && A.ib) ? A.ib[c] : 0.f;
         const float s = score_pair<MODE>(A.ul + ur * A.K, A.il + (size_t)c * A.K, A.h, A.K, ub, ib, MODE == RBR_SCORE_FM ? A.g[0] : 0.f);
         key = s != s ? 0ull : make_key(s, (int)c);
@@ -160,7 +133,8 @@ __global__ __launch_bounds__(256) void sample_hard_negatives_kernel(const HardNe
             S.i_out[b] = S.i_ids[b];
         }
     }
-    advance_call(state, call);
+    __syncthreads();
+    if (threadIdx.x == 0) rng_advance_call(state, call);
 }
 
 }  // namespace rbr
@@ -176,10 +150,7 @@ extern "C" int rbr_sample_negatives(int32_t B, int32_t n_neg, int32_t I, int32_t
     }
     if (item_lo < 0 || item_lo >= I) { set_error("rbr_sample_negatives: item_lo=%d leaves no item of [0, %d)", item_lo, I); return RBR_ERR_BAD_ARG; }
     if (!u_ids || !i_ids || !state || !u_out || !i_out || !valid) { set_error("rbr_sample_negatives: null pointer"); return RBR_ERR_BAD_ARG; }
-    if ((seen_off != nullptr) != (seen_item != nullptr) || seen_nnz < 0 || (!seen_off && seen_nnz != 0) || (seen_off && U <= 0)) {
-        set_error("rbr_sample_negatives: the seen list is seen_off [U + 1] AND seen_item [seen_nnz] with U >= 1, or neither");
-        return RBR_ERR_BAD_ARG;
-    }
+    if (int e = item_csr_ok("rbr_sample_negatives", true, seen_off, seen_item, seen_nnz, nullptr, U)) return e;
     if (max_tries < 1 || max_tries > 64) { set_error("rbr_sample_negatives: max_tries=%d outside [1, 64]", max_tries); return RBR_ERR_BAD_ARG; }
     if (replace_id < 0 || replace_id >= I) {
         set_error("rbr_sample_negatives: replace_id %lld is not an item of [0, %d)", (long long)replace_id, I);
@@ -187,10 +158,10 @@ extern "C" int rbr_sample_negatives(int32_t B, int32_t n_neg, int32_t I, int32_t
     }
     NegSample S;
     S.u_ids = reinterpret_cast<const long long*>(u_ids); S.i_ids = reinterpret_cast<const long long*>(i_ids);
-    S.seen_off = reinterpret_cast<const long long*>(seen_off); S.seen_item = seen_item; S.seen_nnz = seen_nnz;
+    S.seen = item_csr(seen_off, seen_item, nullptr, seen_nnz, U);
     S.u_out = reinterpret_cast<long long*>(u_out); S.i_out = reinterpret_cast<long long*>(i_out); S.valid = valid;
     S.seed = seed; S.replace = replace_id;
-    S.B = B; S.n_neg = n_neg; S.I = I; S.item_lo = item_lo; S.U = U; S.max_tries = max_tries;
+    S.B = B; S.n_neg = n_neg; S.I = I; S.item_lo = item_lo; S.max_tries = max_tries;
     const unsigned grid = (unsigned)(((long long)B * n_neg + 255) / 256);
     hipLaunchKernelGGL(sample_negatives_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, S,
                        reinterpret_cast<unsigned long long*>(state));
@@ -219,10 +190,7 @@ extern "C" int rbr_sample_hard_negatives(int32_t B, int32_t n_neg, int32_t n_can
     if (!u_ids || !i_ids || !state || !u_out || !i_out || !valid) { set_error("rbr_sample_hard_negatives: null pointer"); return RBR_ERR_BAD_ARG; }
     if (!ul || !il) { set_error("rbr_sample_hard_negatives: null latent table"); return RBR_ERR_BAD_ARG; }
     if (mode == RBR_SCORE_FM && (!h || !g)) { set_error("rbr_sample_hard_negatives: RBR_SCORE_FM needs h and g"); return RBR_ERR_BAD_ARG; }
-    if ((seen_off != nullptr) != (seen_item != nullptr) || seen_nnz < 0 || (!seen_off && seen_nnz != 0)) {
-        set_error("rbr_sample_hard_negatives: the seen list is seen_off [U + 1] AND seen_item [seen_nnz], or neither");
-        return RBR_ERR_BAD_ARG;
-    }
+    if (int e = item_csr_ok("rbr_sample_hard_negatives", true, seen_off, seen_item, seen_nnz, nullptr, U)) return e;
     if (max_tries < 1 || max_tries > 64) { set_error("rbr_sample_hard_negatives: max_tries=%d outside [1, 64]", max_tries); return RBR_ERR_BAD_ARG; }
     if (replace_id < 0 || replace_id >= I) {
         set_error("rbr_sample_hard_negatives: replace_id %lld is not an item of [0, %d)", (long long)replace_id, I);
@@ -231,13 +199,13 @@ extern "C" int rbr_sample_hard_negatives(int32_t B, int32_t n_neg, int32_t n_can
     HardNeg A;
     NegSample& S = A.S;
     S.u_ids = reinterpret_cast<const long long*>(u_ids); S.i_ids = reinterpret_cast<const long long*>(i_ids);
-    S.seen_off = reinterpret_cast<const long long*>(seen_off); S.seen_item = seen_item; S.seen_nnz = seen_nnz;
+    S.seen = item_csr(seen_off, seen_item, nullptr, seen_nnz, U);
     S.u_out = reinterpret_cast<long long*>(u_out); S.i_out = reinterpret_cast<long long*>(i_out); S.valid = valid;
     S.seed = seed; S.replace = replace_id;
-    S.B = B; S.n_neg = n_neg; S.I = I; S.item_lo = item_lo; S.U = U; S.max_tries = max_tries;
+    S.B = B; S.n_neg = n_neg; S.I = I; S.item_lo = item_lo; S.max_tries = max_tries;
     A.ul = ul; A.il = il; A.h = h; A.g = g; A.ub = ub; A.ib = ib;
     A.cand_out = reinterpret_cast<long long*>(cand_out); A.cand_score = cand_score;
-    A.K = K; A.n_cand = n_cand;
+    A.U = U; A.K = K; A.n_cand = n_cand;
     A.log_w = 0;
     while ((1 << A.log_w) < n_cand) ++A.log_w;
     const unsigned grid = (unsigned)(((((long long)B * n_neg) << A.log_w) + 255) / 256);

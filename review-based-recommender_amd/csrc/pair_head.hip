@@ -65,17 +65,6 @@ struct HeadTrain {               // rbr_pair_head_fwd_train extras; all zero for
     long zero_n;
 };
 
-// the last workgroup of the launch advances the call number (every pair block has read it by then)
-__device__ __forceinline__ void head_rng_ticket(const HeadTrain& tr, unsigned long long call) {
-    if (tr.rng_state == nullptr) return;
-    // no fence: the call number was consumed (its value used) before this atomic is issued, and nothing else is published
-    if (atomicAdd(tr.rng_state + 1, 1ull) == (unsigned long long)gridDim.x - 1) {
-        tr.rng_state[1] = 0;
-        tr.rng_state[0] = tr.rng_state[0] + 1;
-    }
-    (void)call;
-}
-
 // MSE of the trainers folded into the head's training launch (rbr_pair_head_fwd_pool): the pair block that arrives LAST at
 // the ticket sees every prediction and computes nn.MSELoss(mean) and d loss / d pred exactly as mse_fwd_kernel does (same
 // thread -> element mapping, same reduction order: the same bits), then re-arms the ticket.
@@ -95,10 +84,9 @@ __device__ __forceinline__ float head_pair(int b, int B, int H, int K, const flo
                                           const long long* __restrict__ uid, const long long* __restrict__ iid,
                                           const rbr_head_params& p, const float* __restrict__ drop, float* __restrict__ ul,
                                           float* __restrict__ il, float* __restrict__ pred, const HeadTrain& tr,
-                                          float (*s_part)[4][32], float (*s_l)[32], float* s_bwd = nullptr) {
+                                          unsigned long long call, float (*s_part)[4][32], float (*s_l)[32], float* s_bwd = nullptr) {
     const int t = threadIdx.x;
     const int K4 = (K + 3) & ~3;
-    const unsigned long long call = (tr.p_drop > 0.f) ? tr.rng_state[0] : 0;
     const int side = t >> 7, hp = (t >> 5) & 3, kk = t & 31;
     const long id = side ? iid[b] : uid[b];
     const float* ft = side ? ft1 : ft0;
@@ -139,9 +127,7 @@ __device__ __forceinline__ float head_pair(int b, int B, int H, int K, const flo
             float m = 1.f;
             if (tr.p_drop > 0.f) {       // the draw rbr_dropout_multiplier would make for element (b, k) of this call
                 const unsigned long long e = (unsigned long long)b * K + k;
-                unsigned w[4];
-                philox4x32_10(e >> 2, call, tr.seed, w[0], w[1], w[2], w[3]);
-                m = dropout_keep(w[e & 3], tr.p_drop) ? 1.f / (1.f - tr.p_drop) : 0.f;
+                m = dropout_draw(e, call, tr.seed, tr.p_drop);
                 tr.drop_out[e] = m;
                 z *= m;
             } else if (drop != nullptr) {
@@ -157,7 +143,6 @@ __device__ __forceinline__ float head_pair(int b, int B, int H, int K, const flo
         part = wave_sum(part);
         if (t == 0) pred[b] = pr = part + p.ub[uid[b]] + p.ib[iid[b]] + p.g[0];
     }
-    if (t == 0 && tr.rng_state != nullptr) head_rng_ticket(tr, call);
     (void)B;
     return pr;
 }
@@ -171,12 +156,13 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(int B, int H, int K, cons
     __shared__ float s_part[2][4][32];
     __shared__ float s_l[2][32];
     const int b = blockIdx.x, t = threadIdx.x;
+    const unsigned long long call = tr.rng_state != nullptr ? tr.rng_state[0] : 0;      // every workgroup, first (rbr_rng.h)
     if (b >= B) {                 // training launch only: blocks past the pairs clear the buffer the backward accumulates into
         for (long k = (long)(b - B) * 256 + t; k < tr.zero_n; k += (long)(gridDim.x - B) * 256) tr.zero_buf[k] = 0.f;
-        if (t == 0) head_rng_ticket(tr, 0);
-        return;
+    } else {
+        head_pair(b, B, H, K, uf + (long)b * H, itf + (long)b * H, uid, iid, p, drop, ul, il, pred, tr, call, s_part, s_l);
     }
-    head_pair(b, B, H, K, uf + (long)b * H, itf + (long)b * H, uid, iid, p, drop, ul, il, pred, tr, s_part, s_l);
+    if (t == 0 && tr.rng_state != nullptr) rng_advance_call(tr.rng_state, call);      // (head_pair's barriers lie in between)
 }
 
 // The head forward with the encoder's pool epilogue in front and the trainer's loss behind (one launch instead of
@@ -204,9 +190,10 @@ __global__ __launch_bounds__(256) void head_fwd_pool_kernel(const ConvPlan P, co
     __shared__ float s_dp;
     extern __shared__ __attribute__((aligned(16))) float s_feat[];      // [2][C]
     const int b = blockIdx.x, t = threadIdx.x;
+    const unsigned long long call = tr.rng_state != nullptr ? tr.rng_state[0] : 0;      // every workgroup, first (rbr_rng.h)
     if (b >= B) {
         for (long k = (long)(b - B) * 256 + t; k < tr.zero_n; k += (long)(gridDim.x - B) * 256) tr.zero_buf[k] = 0.f;
-        if (t == 0) head_rng_ticket(tr, 0);
+        if (t == 0 && tr.rng_state != nullptr) rng_advance_call(tr.rng_state, call);
         return;
     }
     // Pool epilogue of this pair's two documents in three memory round trips: (1) the slabs' activity flags, (2) EVERY slab
@@ -278,7 +265,8 @@ __global__ __launch_bounds__(256) void head_fwd_pool_kernel(const ConvPlan P, co
     __syncthreads();
     // d_feat_unit: the pair's ul / il / multiplier stay in LDS behind the slab partials (offset rounded to 16 bytes)
     float* s_bwd = d_feat_unit != nullptr ? s_feat + ((2 * P.C + 2 * wpd * nslots + 2 * wpd + 3) & ~3) : nullptr;
-    const float pr = head_pair(b, B, P.C, K, s_feat, s_feat + P.C, uid, iid, p, drop, ul, il, pred, tr, s_part, s_l, s_bwd);
+    const float pr = head_pair(b, B, P.C, K, s_feat, s_feat + P.C, uid, iid, p, drop, ul, il, pred, tr, call, s_part, s_l, s_bwd);
+    if (t == 0 && tr.rng_state != nullptr) rng_advance_call(tr.rng_state, call);      // (head_pair's barriers lie in between)
     if (mse.target == nullptr) return;
     if (d_feat_unit != nullptr) {
         // The pair role of the backward for an upstream gradient of 1, from this pair's own prediction: d loss / d pred[b] with the

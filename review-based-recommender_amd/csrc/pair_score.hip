@@ -28,6 +28,7 @@
 //        after the sweep, not a binary search per (pair, item) inside it.
 //   All counts are integers: the same bytes on every run.
 #include "rbr_common.h"
+#include "item_csr.h"
 #include "pair_score_math.h"
 
 #include <cmath>
@@ -121,38 +122,11 @@ __device__ __forceinline__ unsigned long long list_offer(unsigned long long* Lst
 
 struct TopKArgs {
     ScoreParams P;
-    const long long* excl_off;     // [Nu + 1] or null
-    const int* excl_item;          // sorted within a user
-    const long long* excl_row;     // [Nu] row of excl_off that serves user row r, or null (= r)
-    long long excl_nnz;
-    int excl_rows;                 // rows of excl_off
+    ItemCsr excl;                  // user row r: the items it must never get (item_csr.h)
     unsigned long long* ws;        // [Nu, S, k] keys
     long long per;                 // items per slice (a multiple of 64)
     int Nu, Ni, k, item_lo, S, vec;
 };
-
-// [a, e) of excl_item that serves user row urow, false when the row has no list; a malformed CSR cannot send a reader outside
-// excl_item
-__device__ __forceinline__ bool excl_bounds(const long long* __restrict__ excl_off, const long long* __restrict__ excl_row, int excl_rows,
-                                            long long excl_nnz, int urow, long long& a, long long& e) {
-    const long long row = excl_row ? excl_row[urow] : (long long)urow;
-    if ((unsigned long long)row >= (unsigned long long)excl_rows) return false;
-    a = excl_off[row]; e = excl_off[row + 1];
-    a = a < 0 ? 0 : a;
-    e = e > excl_nnz ? excl_nnz : e;
-    return true;
-}
-
-__device__ __forceinline__ bool excluded(const TopKArgs& A, int urow, int item) {
-    long long a, e;
-    if (!excl_bounds(A.excl_off, A.excl_row, A.excl_rows, A.excl_nnz, urow, a, e)) return false;      // no list for this row
-    long long b = e;
-    while (a < b) {
-        const long long mid = a + ((b - a) >> 1);
-        if (A.excl_item[mid] < item) a = mid + 1; else b = mid;
-    }
-    return a < e && A.excl_item[a] == item;
-}
 
 // KC latents of the lane's item against the kTU user rows of the tile: k0 .. k0 + KC of every accumulator, k ascending
 template <int MODE, int KC>
@@ -228,7 +202,8 @@ __global__ __launch_bounds__(64) void topk_slice_kernel(const TopKArgs A) {
             unsigned long long tk = Lu[k - 1];
             const unsigned long long key = make_key(sc, item);
             bool c = valid && sc >= thr[u] && key > tk;
-            if (c && A.excl_off) c = !excluded(A, u0 + u, item);
+            long long xa, xe;
+            if (c && csr_row(A.excl, u0 + u, xa, xe)) c = !csr_has(A.excl.item, xa, xe, item);
             const unsigned long long tk1 = list_offer(Lu, k, key, c, tk, lane);
             if (tk1 != tk) {
                 if (lane == 0) thr[u] = key_score(tk1);
@@ -272,9 +247,7 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const unsigned long long
 struct RankArgs {
     ScoreParams P;                 // P.ul [B, K] / P.ub [B]: the user rows gathered per pair
     const long long* tgt;          // [B] target item ids
-    const long long* excl_off; const int* excl_item; const long long* excl_row;      // as in TopKArgs
-    long long excl_nnz;
-    int excl_rows;
+    ItemCsr excl;                  // as in TopKArgs, a row per pair
     int2* ws;                      // [B, S] (items of the slice that beat the target, NaN items of the slice)
     int* rank; int* n_cand;        // [B]
     long long* err;                // the int64[4] record of rbr_sanitize_ids, or null
@@ -362,12 +335,12 @@ __global__ __launch_bounds__(64) void rank_finish_kernel(const RankArgs A) {
         beats += p.x; gone += p.y;
     }
     long long a, e;
-    if (A.excl_off && excl_bounds(A.excl_off, A.excl_row, A.excl_rows, A.excl_nnz, b, a, e)) {
+    if (csr_row(A.excl, b, a, e)) {
         const float ub = (MODE == RBR_SCORE_FM && A.P.ub) ? A.P.ub[b] : 0.f, g = MODE == RBR_SCORE_FM ? A.P.g[0] : 0.f;
         for (long long q = a + lane; q < e; q += 64) {
-            const int j = A.excl_item[q];
+            const int j = A.excl.item[q];
             // outside the sweep, the target itself (never excluded), or the entry before it again
-            if (j < A.item_lo || j >= A.Ni || (in_table && j == t) || (q > a && A.excl_item[q - 1] == j)) continue;
+            if (j < A.item_lo || j >= A.Ni || (in_table && j == t) || (q > a && A.excl.item[q - 1] == j)) continue;
             const float ib = (MODE == RBR_SCORE_FM && A.P.ib) ? A.P.ib[j] : 0.f;
             const float sc = score_pair<MODE>(A.P.ul + (size_t)b * K, A.P.il + (size_t)j * K, A.P.h, K, ub, ib, g);
             if (sc != sc) continue;                   // the sweep has it among the NaNs already
@@ -472,18 +445,10 @@ extern "C" int rbr_pair_score_topk(int32_t mode, int32_t Nu, int32_t Ni, int32_t
     if (int e = score_args_ok("rbr_pair_score_topk", mode, K, ul, il, h, g)) return e;
     if (item_lo < 0 || item_lo >= Ni) { set_error("rbr_pair_score_topk: item_lo=%d outside [0, %d)", item_lo, Ni); return RBR_ERR_BAD_ARG; }
     if (!out_item || !out_score || !ws) { set_error("rbr_pair_score_topk: null output or workspace"); return RBR_ERR_BAD_ARG; }
-    if ((excl_off != nullptr) != (excl_item != nullptr) || excl_nnz < 0 || (!excl_off && (excl_nnz != 0 || excl_row))) {
-        set_error("rbr_pair_score_topk: the exclusion list is excl_off [rows + 1] AND excl_item [excl_nnz], or neither");
-        return RBR_ERR_BAD_ARG;
-    }
-    if (excl_row && excl_rows <= 0) { set_error("rbr_pair_score_topk: excl_row with excl_rows=%d", excl_rows); return RBR_ERR_BAD_ARG; }
+    if (int e = item_csr_ok("rbr_pair_score_topk", false, excl_off, excl_item, excl_nnz, excl_row, excl_rows)) return e;
     TopKArgs A;
     A.P = ScoreParams{ul, il, h, g, ub, ib, K};
-    A.excl_off = reinterpret_cast<const long long*>(excl_off);
-    A.excl_item = excl_item;
-    A.excl_nnz = excl_nnz;
-    A.excl_row = reinterpret_cast<const long long*>(excl_row);
-    A.excl_rows = excl_row ? excl_rows : Nu;
+    A.excl = item_csr(excl_off, excl_item, excl_row, excl_nnz, excl_row ? excl_rows : Nu);
     A.ws = static_cast<unsigned long long*>(ws);
     A.Nu = Nu; A.Ni = Ni; A.k = k; A.item_lo = item_lo;
     A.S = topk_splits(Nu, Ni);
@@ -519,19 +484,11 @@ extern "C" int rbr_pair_score_rank(int32_t mode, int32_t B, int32_t Ni, int32_t 
     if (int e = score_args_ok("rbr_pair_score_rank", mode, K, ul, il, h, g)) return e;
     if (item_lo < 0 || item_lo >= Ni) { set_error("rbr_pair_score_rank: item_lo=%d outside [0, %d)", item_lo, Ni); return RBR_ERR_BAD_ARG; }
     if (!tgt || !rank || !n_cand || !ws) { set_error("rbr_pair_score_rank: null targets, output or workspace"); return RBR_ERR_BAD_ARG; }
-    if ((excl_off != nullptr) != (excl_item != nullptr) || excl_nnz < 0 || (!excl_off && (excl_nnz != 0 || excl_row))) {
-        set_error("rbr_pair_score_rank: the exclusion list is excl_off [rows + 1] AND excl_item [excl_nnz], or neither");
-        return RBR_ERR_BAD_ARG;
-    }
-    if (excl_row && excl_rows <= 0) { set_error("rbr_pair_score_rank: excl_row with excl_rows=%d", excl_rows); return RBR_ERR_BAD_ARG; }
+    if (int e = item_csr_ok("rbr_pair_score_rank", false, excl_off, excl_item, excl_nnz, excl_row, excl_rows)) return e;
     RankArgs A;
     A.P = ScoreParams{ul, il, h, g, ub, ib, K};
     A.tgt = reinterpret_cast<const long long*>(tgt);
-    A.excl_off = reinterpret_cast<const long long*>(excl_off);
-    A.excl_item = excl_item;
-    A.excl_row = reinterpret_cast<const long long*>(excl_row);
-    A.excl_nnz = excl_nnz;
-    A.excl_rows = excl_row ? excl_rows : B;
+    A.excl = item_csr(excl_off, excl_item, excl_row, excl_nnz, excl_row ? excl_rows : B);
     A.ws = static_cast<int2*>(ws);
     A.rank = rank; A.n_cand = n_cand;
     A.err = reinterpret_cast<long long*>(err);

@@ -15,6 +15,7 @@
 //
 // No float atomics; every output element has one owner that adds its terms in a fixed order: the same bits on every run.
 #include "rbr_common.h"
+#include "item_csr.h"
 
 #include <cmath>
 
@@ -25,9 +26,9 @@ constexpr int kPsMaxK = 256;
 
 struct PairSoftmax {
     const float *ul, *il, *h, *row_bias, *col_bias, *drop, *logq, *d_loss;
-    const long long *u_id, *i_id, *seen_off;
-    const int* seen_item;
-    long long seen_nnz, item_lo;
+    const long long *u_id, *i_id;
+    ItemCsr seen;                       // row u: the items user u has rated (item_csr.h)
+    long long item_lo;
     const unsigned long long* call;     // call number of the in-kernel draw (rng_state, or the forward's saved one); NULL: none
     unsigned long long* rng_state;      // non-NULL: launch 2 advances the call number
     unsigned long long* call_out;       // the call number this call drew with (for rbr_pair_softmax_bwd)
@@ -35,21 +36,14 @@ struct PairSoftmax {
     float p_drop, inv_temp;
     float *loss, *pos, *d_ul, *d_il, *d_h, *d_col_bias, *d_row_bias;
     float *ds, *row_loss, *dh_part;     // workspace: [B, B], [B], [B, K]
-    int mode, B, K, U, grads, col_blocks;
+    int mode, B, K, grads, col_blocks;
 };
 
 // the head's dropout multiplier of element e = (a * B + b) * K + k: the explicit one, or the draw rbr_dropout_multiplier makes
-// for element e of call `call` (word e & 3 of the Philox block with counter (e >> 2, call))
+// for element e of call `call` (rbr_rng.h)
 __device__ __forceinline__ float ps_mult(const PairSoftmax& S, unsigned long long call, long long e) {
     if (S.drop != nullptr) return S.drop[e];
-    if (S.p_drop > 0.f) {
-        unsigned w0, w1, w2, w3;
-        philox4x32_10((unsigned long long)e >> 2, call, S.seed, w0, w1, w2, w3);
-        const int q = (int)(e & 3);
-        const unsigned w = q == 0 ? w0 : q == 1 ? w1 : q == 2 ? w2 : w3;
-        return dropout_keep(w, S.p_drop) ? 1.f / (1.f - S.p_drop) : 0.f;
-    }
-    return 1.f;
+    return S.p_drop > 0.f ? dropout_draw((unsigned long long)e, call, S.seed, S.p_drop) : 1.f;
 }
 
 // sum / max over the 256 threads in a fixed order (xor-shuffle tree over 64 lanes, then the four wave results in order);
@@ -78,15 +72,9 @@ __global__ __launch_bounds__(256) void pair_softmax_rows_kernel(const PairSoftma
     const bool fm = S.mode == RBR_SCORE_FM;
     const unsigned long long call = S.call != nullptr ? S.call[0] : 0ull;
     for (int k = t; k < K; k += 256) s_u[k] = S.ul[(long)a * K + k];
-    // the user's seen row [sa, se): an id outside [0, U) has none; offsets clamped as rbr_sample_negatives clamps them
-    const long long ia = S.i_id[a], ua = S.u_id[a];
-    long long sa = 0, se = 0;
-    if (S.seen_off != nullptr && (unsigned long long)ua < (unsigned long long)S.U) {
-        sa = S.seen_off[ua]; se = S.seen_off[ua + 1];
-        sa = sa < 0 ? 0 : sa;
-        se = se > S.seen_nnz ? S.seen_nnz : se;
-        if (se < sa) se = sa;
-    }
+    const long long ia = S.i_id[a];
+    long long sa, se;                       // the user's seen row
+    csr_row(S.seen, S.u_id[a], sa, se);
     const float rb = S.row_bias != nullptr ? S.row_bias[a] : 0.f;
     __syncthreads();
 
@@ -116,15 +104,7 @@ __global__ __launch_bounds__(256) void pair_softmax_rows_kernel(const PairSoftma
             bool ok = b == a;
             if (!ok) {
                 const long long ib = S.i_id[b];
-                ok = ib >= S.item_lo && ib != ia;
-                if (ok) {
-                    long long lo = sa, hi = se;
-                    while (lo < hi) {
-                        const long long mid = (lo + hi) >> 1;
-                        if ((long long)S.seen_item[mid] < ib) lo = mid + 1; else hi = mid;
-                    }
-                    ok = !(lo < se && (long long)S.seen_item[lo] == ib);
-                }
+                ok = ib >= S.item_lo && ib != ia && !csr_has(S.seen.item, sa, se, ib);
             }
             s_z[b] = ok ? z : -INFINITY;
         }
@@ -251,10 +231,7 @@ __global__ __launch_bounds__(256) void pair_softmax_cols_kernel(const PairSoftma
     }
     if (S.rng_state != nullptr) {       // the last workgroup to finish advances the call number: every one has read it
         __syncthreads();
-        if (t == 0 && atomicAdd(S.rng_state + 1, 1ull) == (unsigned long long)gridDim.x - 1) {
-            S.rng_state[1] = 0;
-            S.rng_state[0] = call + 1;
-        }
+        if (t == 0) rng_advance_call(S.rng_state, call);
     }
 }
 
@@ -279,11 +256,7 @@ static int ps_check(const char* who, int mode, int B, int K, const float* ul, co
     if (drop && p_drop > 0.f) { set_error("%s: an explicit drop multiplier AND p_drop > 0: one of them", who); return RBR_ERR_BAD_ARG; }
     if (mode == RBR_SCORE_DOT && (drop || p_drop > 0.f)) { set_error("%s: the dot score has no dropout", who); return RBR_ERR_BAD_ARG; }
     if (p_drop > 0.f && !rng) { set_error("%s: p_drop > 0 needs the call number in device memory", who); return RBR_ERR_BAD_ARG; }
-    if ((seen_off != nullptr) != (seen_item != nullptr) || seen_nnz < 0 || (!seen_off && seen_nnz != 0) || (seen_off && U <= 0)) {
-        set_error("%s: the seen list is seen_off [U + 1] AND seen_item [seen_nnz] with U >= 1, or neither", who);
-        return RBR_ERR_BAD_ARG;
-    }
-    return 0;
+    return item_csr_ok(who, true, seen_off, seen_item, seen_nnz, nullptr, U);
 }
 
 static int ps_run(PairSoftmax& S, void* ws, hipStream_t st, const char* who) {
@@ -330,13 +303,13 @@ extern "C" int rbr_pair_softmax_fwd(int32_t mode, int32_t B, int32_t K, const fl
     PairSoftmax S{};
     S.ul = ul; S.il = il; S.h = h; S.row_bias = row_bias; S.col_bias = col_bias; S.drop = drop; S.logq = logq; S.d_loss = nullptr;
     S.u_id = reinterpret_cast<const long long*>(u_id); S.i_id = reinterpret_cast<const long long*>(i_id);
-    S.seen_off = reinterpret_cast<const long long*>(seen_off); S.seen_item = seen_item; S.seen_nnz = seen_nnz; S.item_lo = item_lo;
+    S.seen = item_csr(seen_off, seen_item, nullptr, seen_nnz, U); S.item_lo = item_lo;
     S.rng_state = p_drop > 0.f ? reinterpret_cast<unsigned long long*>(rng_state) : nullptr;
     S.call = S.rng_state;
     S.call_out = reinterpret_cast<unsigned long long*>(call_out);
     S.seed = seed; S.p_drop = p_drop; S.inv_temp = inv_temp;
     S.loss = loss; S.pos = pos; S.d_ul = d_ul; S.d_il = d_il; S.d_h = d_h; S.d_col_bias = d_col_bias; S.d_row_bias = d_row_bias;
-    S.mode = mode; S.B = B; S.K = K; S.U = U; S.grads = grads ? 1 : 0;
+    S.mode = mode; S.B = B; S.K = K; S.grads = grads ? 1 : 0;
     return ps_run(S, ws, (hipStream_t)stream, who);
 }
 
@@ -359,12 +332,12 @@ extern "C" int rbr_pair_softmax_bwd(int32_t mode, int32_t B, int32_t K, const fl
     PairSoftmax S{};
     S.ul = ul; S.il = il; S.h = h; S.row_bias = row_bias; S.col_bias = col_bias; S.drop = drop; S.logq = logq; S.d_loss = d_loss;
     S.u_id = reinterpret_cast<const long long*>(u_id); S.i_id = reinterpret_cast<const long long*>(i_id);
-    S.seen_off = reinterpret_cast<const long long*>(seen_off); S.seen_item = seen_item; S.seen_nnz = seen_nnz; S.item_lo = item_lo;
+    S.seen = item_csr(seen_off, seen_item, nullptr, seen_nnz, U); S.item_lo = item_lo;
     S.rng_state = nullptr;       // the forward advanced the call number; this launch re-draws the forward's set from the saved one
     S.call = p_drop > 0.f ? reinterpret_cast<const unsigned long long*>(call) : nullptr;
     S.call_out = nullptr;
     S.seed = seed; S.p_drop = p_drop; S.inv_temp = inv_temp;
     S.loss = nullptr; S.pos = pos_scratch; S.d_ul = d_ul; S.d_il = d_il; S.d_h = d_h; S.d_col_bias = d_col_bias; S.d_row_bias = d_row_bias;
-    S.mode = mode; S.B = B; S.K = K; S.U = U; S.grads = 1;
+    S.mode = mode; S.B = B; S.K = K; S.grads = 1;
     return ps_run(S, ws, (hipStream_t)stream, who);
 }

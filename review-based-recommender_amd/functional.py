@@ -1481,7 +1481,7 @@ class _PairSoftmaxLoss(torch.autograd.Function):
     without a launch; any other root re-runs the two launches with that scalar (and the forward's dropout call number)."""
 
     @staticmethod
-    def forward(ctx, ul, il, h, row_bias, col_bias, u_ids, i_ids, mode, drop, p_drop, seen, item_lo, logq, inv_temp):
+    def forward(ctx, ul, il, h, row_bias, col_bias, u_ids, i_ids, mode, drop, p_drop, seen_csr, item_lo, logq, inv_temp):
         code = SCORE_MODES[mode]
         ul, il = ul.contiguous(), il.contiguous()
         dev = ul.device
@@ -1497,8 +1497,7 @@ class _PairSoftmaxLoss(torch.autograd.Function):
             drop = drop.contiguous()
             if drop.shape != (B, B, K):
                 raise RuntimeError(f"pair_softmax_loss: drop must be [{B}, {B}, {K}], got {tuple(drop.shape)}")
-        U = 0 if seen is None else seen[0].shape[0] - 1
-        off, items, _, nnz, _ = _exclusion_csr(seen, U, dev)
+        off, items, nnz, U = seen_csr
         L_ = _lib.lib()
         # a shape the entry refuses has a workspace of 0 bytes: the call below then returns its error code and text before any launch
         ws = _pair_softmax_ws(dev, L_.rbr_pair_softmax_ws_bytes(B, K))
@@ -1570,11 +1569,10 @@ def pair_softmax_loss(ul, il, u_ids, i_ids, mode, h=None, row_bias=None, col_bia
     dev_ptr(ul.detach().contiguous(), F32, "user latents")        # device gate first: a CPU tensor is refused before anything else
     if u_ids.shape != (B,) or i_ids.shape != (B,):
         raise RuntimeError(f"pair_softmax_loss: u_ids / i_ids must be [{B}] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
-    if seen is not None and len(seen) != 2:
-        raise RuntimeError("seen must be (off [U + 1], items): one row per user id")
+    seen_csr = _seen_csr(seen, ul.device)
     if not temperature > 0:
         raise ValueError(f"pair_softmax_loss: temperature must be positive, got {temperature}")
-    return _PairSoftmaxLoss.apply(ul, il, h, row_bias, col_bias, u_ids, i_ids, mode, drop, p_drop, seen, int(item_lo), logq,
+    return _PairSoftmaxLoss.apply(ul, il, h, row_bias, col_bias, u_ids, i_ids, mode, drop, p_drop, seen_csr, int(item_lo), logq,
                                   1.0 / float(temperature))
 
 
@@ -2486,6 +2484,18 @@ def _exclusion_csr(exclude, Nu, dev):
     return off, items, rows, nnz, n_rows if rows is not None else 0
 
 
+def _seen_csr(seen, dev):
+    """(off, items, nnz, U) of the `seen` argument of the samplers and pair_softmax_loss -- (off int64 [U + 1], items int32), the
+    two-array form of `exclude` with one row per user id; None, None, 0, 0 for no list."""
+    if seen is None:
+        return None, None, 0, 0
+    if len(seen) != 2:
+        raise RuntimeError("seen must be (off [U + 1], items): one row per user id")
+    U = seen[0].shape[0] - 1
+    off, items, _, nnz, _ = _exclusion_csr(seen, U, dev)
+    return off, items, nnz, U
+
+
 def pair_score_topk(mode, ul, il, k, h=None, g=None, ub=None, ib=None, *, item_lo=0, exclude=None):
     """(items int64 [Nu, k], scores f32 [Nu, k]): for every user row of ul [Nu, K] the k best items of [item_lo, Ni), score
     descending, ties by the lower item id, the same bytes on every run (rbr_pair_score_topk; 1 <= k <= 128).  `exclude` lists
@@ -2549,10 +2559,7 @@ def _sampler_operands(u_ids, i_ids, n_neg, seen, state, out):
     if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
         raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
     B, n_neg, dev = u_ids.shape[0], int(n_neg), u_ids.device
-    if seen is not None and len(seen) != 2:
-        raise RuntimeError("seen must be (off [U + 1], items): one row per user id")
-    U = 0 if seen is None else seen[0].shape[0] - 1
-    off, items, _, nnz, _ = _exclusion_csr(seen, U, dev)
+    off, items, nnz, U = _seen_csr(seen, dev)
     if state.shape != (2,) or state.dtype != I64:
         raise RuntimeError(f"state must be int64 [2], got {state.dtype} {tuple(state.shape)}")
     rows = (1 + max(n_neg, 0)) * B

@@ -1,5 +1,5 @@
 """Integer restatement of rbr_sample_negatives' draw (include/rbr_hip.h) in numpy, shared by the sampler's host and GPU tests:
-Philox4x32-10 as csrc/rbr_common.h states it, the candidate mapping, the accept rule and the cyclic walk."""
+Philox4x32-10 as csrc/rbr_rng.h states it, the candidate mapping, the accept rule and the cyclic walk."""
 import numpy as np
 
 M0, M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
