@@ -14,12 +14,16 @@
 //   2. mark_scan                     : marks of the tokens that occur + work list of the documents' 32-token slabs
 //   3. compact_pack                  : marks -> list `tok_of_row` / inverse map `row_of_token`; W[c, d, j] of every bank ->
 //                                      one kz = 1 bank of sum(kz*ch) "product channels" (MFMA tile image) and Wprod^T rows
+//      (1-3 are the prepare stage, prod_prepare: with the id range check in launch 1 for _prepare_ids, and as two launches on
+//      a list state that stays zero for _prepare_ids_kept; 2-3 are build_list, which the list backward runs as well)
 //   4. conv_store_kernel             : T = table[tok_of_row] @ Wprod on the f32 MFMA pipe (the fused gather + MFMA kernel
 //                                      of the dense path, run over the token list as one long document, store epilogue)
 //   5. gather_pool                   : per 32-position wave-tile, sum the kz rows of T, running max / first argmax
 //   then pool_finalize as for the dense path.
 // Backward (rbr_textcnn_bwd_dtable_prod_ex): zero_g_rows, build_g (G[token][(tap, channel)] += g, d(gate) from T),
 //   g_times_w (dtable[token, :] = G[token, :] @ Wprod^T as a sparse row product; absent tokens' rows zeroed).
+// Host side: ProdChannels is the product channel map, ProdLayout / ProdState the workspace (offsets / typed pointers), and each
+// kernel argument block has one maker (make_bwd_args, make_pack_job, ptr_array).
 #include "rbr_common.h"
 #include "textcnn_b16.h"
 
@@ -161,121 +165,102 @@ __device__ __forceinline__ void pack_blocks(const PackJob& J, int nb_compact, co
     }
 }
 
-// Launch 3: blocks [0, nb_compact) turn the marks into the token list (row_of_token[v] = dense row or -1,
-// tok_of_row / row_mask describe the pseudo-document, *counter = rows); the remaining blocks write the product weight
-// image of the forward GEMM and the row-major Wprod^T the backward's sparse product reads.
+// The compaction role of the last launch, block blockIdx.x < nb_compact: the marks become the token list (row_of_token[v] =
+// dense row or -1, tok_of_row / row_mask describe the pseudo-document, *counter = rows).
+// KEPT (see KeptState): in addition every block counts ALL marks, so that it knows the list's length and can write its 256 bytes
+// of the row mask outright (1 below the count, 0 above: the mask needs no clearing), block 0 publishes the slab count and clears
+// the counters the GEMM pulls from, and the block that arrives LAST at the ticket clears the marks and re-arms the ticket.  No
+// fence: every block has consumed its mark values (they are in LDS behind a barrier) before its ticket atomic is issued, and the
+// clearing becomes visible at the kernel boundary -- the reasoning of head_rng_ticket.
+template <bool KEPT> using Marks = std::conditional_t<KEPT, unsigned char*, const unsigned char* __restrict__>;
+template <bool KEPT>
+__device__ __forceinline__ void compact_block(int nb_compact, int V, int cap, Marks<KEPT> used, int* __restrict__ row_of_token,
+                                              long long* __restrict__ tok_of_row, unsigned char* __restrict__ row_mask,
+                                              int* __restrict__ counter, float* __restrict__ zero_row, int pitch, const KeptState& KS) {
+    if (blockIdx.x == 0)      // the all-zero row of T that masked / out-of-document taps read
+        for (int k = threadIdx.x; k < pitch; k += 256) zero_row[k] = 0.f;
+    // dense row of token v = number of marked tokens below v: rows come out in token order, the same list for the
+    // same batch on every run (no atomics).  A block first counts the marks below its 256 tokens (<= V ints, L2).
+    __shared__ int s_cnt[4], s_wave[4];
+    __shared__ int s_all[4], s_last;                               // KEPT only
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int below = blockIdx.x * 256;
+    int c = 0, call = 0;
+    const int4* u4 = reinterpret_cast<const int4*>(used);          // 16 marks (bytes of value 0 / 1) per load
+    for (int q = threadIdx.x; q < (KEPT ? KS.used_words : below / 16); q += 256) {
+        const int4 m = u4[q];
+        const int n = __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w);
+        if constexpr (KEPT) call += n;
+        if (!KEPT || q < below / 16) c += n;
+    }
+    c = wave_sum(c);
+    if constexpr (KEPT) call = wave_sum(call);
+    const int v = below + threadIdx.x;
+    const int u = (v < V) ? used[v] : 0;
+    const unsigned long long b = __ballot(u);
+    if (lane == 0) {
+        s_cnt[wave] = c; s_wave[wave] = __popcll(b);
+        if constexpr (KEPT) s_all[wave] = call;
+    }
+    __syncthreads();
+    if constexpr (KEPT)
+        if (threadIdx.x == 0) s_last = atomicAdd(KS.ticket, 1) == nb_compact - 1;
+    int base = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    for (int k = 0; k < wave; ++k) base += s_wave[k];
+    if (v < V) {
+        int row = -1;
+        if (u) {
+            row = base + __popcll(b & ((1ull << lane) - 1));
+            if (row >= cap) row = -1;      // cannot happen: cap >= distinct
+            else { tok_of_row[row] = v; if constexpr (!KEPT) row_mask[row] = 1; }
+        }
+        row_of_token[v] = row;
+    }
+    if constexpr (!KEPT) {
+        if ((int)blockIdx.x == nb_compact - 1 && threadIdx.x == 0)
+            *counter = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]) + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    } else {
+        const int total = (s_all[0] + s_all[1]) + (s_all[2] + s_all[3]);
+        if (v < KS.mask_bytes) row_mask[v] = v < min(total, cap) ? 1 : 0;
+        if ((int)blockIdx.x == nb_compact - 1 && threadIdx.x == 0) *counter = total;
+        if (blockIdx.x == 0) {
+            if (threadIdx.x == 0) { KS.doc_counters[0] = *KS.slabs; *KS.slabs = 0; }
+            else if (threadIdx.x < kSchedCounters) KS.doc_counters[threadIdx.x] = 0;
+            if (threadIdx.x >= 1 && threadIdx.x < kKeptTicket) KS.gemm_counters[threadIdx.x] = 0;
+        }
+        __syncthreads();
+        if (s_last) {          // workgroup-uniform
+            int4* w4 = reinterpret_cast<int4*>(used);
+            for (int q = threadIdx.x; q < KS.used_words; q += 256) w4[q] = make_int4(0, 0, 0, 0);
+            if (threadIdx.x == 0) *KS.ticket = 0;
+        }
+    }
+}
+
+// Launch 3 of the self-initialising chains: blocks [0, nb_compact) the compaction, the remaining blocks the pack role.
 __device__ __forceinline__ void compact_pack_kernel(const PackJob& J, int nb_compact, int V, int cap,
                                                            const unsigned char* __restrict__ used, int* __restrict__ row_of_token,
                                                            long long* __restrict__ tok_of_row, unsigned char* __restrict__ row_mask,
                                                            int* __restrict__ counter, float* __restrict__ zero_row, int pitch,
                                                            const PtrArray& W, float* __restrict__ packed, float* __restrict__ WT,
                                                            const B16Pack& JB, unsigned char* __restrict__ bimg) {
-    if ((int)blockIdx.x < nb_compact) {
-        if (blockIdx.x == 0)      // the all-zero row of T that masked / out-of-document taps read
-            for (int k = threadIdx.x; k < pitch; k += 256) zero_row[k] = 0.f;
-        // dense row of token v = number of marked tokens below v: rows come out in token order, the same list for the
-        // same batch on every run (no atomics).  A block first counts the marks below its 256 tokens (<= V ints, L2).
-        __shared__ int s_cnt[4], s_wave[4];
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int below = blockIdx.x * 256;
-        int c = 0;
-        const int4* u4 = reinterpret_cast<const int4*>(used);          // 16 marks (bytes of value 0 / 1) per load
-        for (int q = threadIdx.x; q < below / 16; q += 256) {
-            const int4 m = u4[q];
-            c += __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w);
-        }
-        c = wave_sum(c);
-        const int v = below + threadIdx.x;
-        const int u = (v < V) ? used[v] : 0;
-        const unsigned long long b = __ballot(u);
-        if (lane == 0) { s_cnt[wave] = c; s_wave[wave] = __popcll(b); }
-        __syncthreads();
-        int base = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-        for (int k = 0; k < wave; ++k) base += s_wave[k];
-        if (v < V) {
-            int row = -1;
-            if (u) {
-                row = base + __popcll(b & ((1ull << lane) - 1));
-                if (row < cap) { tok_of_row[row] = v; row_mask[row] = 1; } else row = -1;   // cannot happen: cap >= distinct
-            }
-            row_of_token[v] = row;
-        }
-        if ((int)blockIdx.x == nb_compact - 1 && threadIdx.x == 0)
-            *counter = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]) + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-        return;
-    }
-    pack_blocks(J, nb_compact, W, packed, WT, JB, bimg);
+    if ((int)blockIdx.x < nb_compact)
+        compact_block<false>(nb_compact, V, cap, used, row_of_token, tok_of_row, row_mask, counter, zero_row, pitch, KeptState{});
+    else
+        pack_blocks(J, nb_compact, W, packed, WT, JB, bimg);
 }
 
-// The compaction of the kept form (see KeptState), block blockIdx.x < nb_compact.
-__device__ __forceinline__ void compact_kept_block(int nb_compact, int V, int cap, unsigned char* used, int* __restrict__ row_of_token,
-                                                   long long* __restrict__ tok_of_row, unsigned char* __restrict__ row_mask,
-                                                   int* __restrict__ counter, float* __restrict__ zero_row, int pitch,
-                                                   const KeptState& KS) {
-    // Rows, list and count exactly as compact_pack_kernel's; in addition every block counts ALL marks, so that
-    // it knows the list's length and can write its 256 bytes of the row mask outright (1 below the count, 0 above: the mask
-    // needs no clearing), block 0 publishes the slab count and clears the counters the GEMM pulls from, and the block that
-    // arrives LAST at the ticket clears the marks and re-arms the ticket.  No fence: every block has consumed its mark values
-    // (they are in LDS behind a barrier) before its ticket atomic is issued, and the clearing becomes visible at the kernel
-    // boundary -- the reasoning of head_rng_ticket.
-    if (blockIdx.x == 0)
-        for (int k = threadIdx.x; k < pitch; k += 256) zero_row[k] = 0.f;
-    __shared__ int s_cnt[4], s_all[4], s_wave[4], s_last;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int below = blockIdx.x * 256;
-    int c = 0, call = 0;
-    const int4* u4 = reinterpret_cast<const int4*>(used);
-    for (int q = threadIdx.x; q < KS.used_words; q += 256) {
-        const int4 m = u4[q];
-        const int n = __popc(m.x) + __popc(m.y) + __popc(m.z) + __popc(m.w);
-        call += n;
-        if (q < below / 16) c += n;
-    }
-    c = wave_sum(c);
-    call = wave_sum(call);
-    const int v = below + threadIdx.x;
-    const int u = (v < V) ? used[v] : 0;
-    const unsigned long long b = __ballot(u);
-    if (lane == 0) { s_cnt[wave] = c; s_all[wave] = call; s_wave[wave] = __popcll(b); }
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = atomicAdd(KS.ticket, 1) == nb_compact - 1;
-    int base = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-    for (int k = 0; k < wave; ++k) base += s_wave[k];
-    const int total = (s_all[0] + s_all[1]) + (s_all[2] + s_all[3]);
-    if (v < V) {
-        int row = -1;
-        if (u) {
-            row = base + __popcll(b & ((1ull << lane) - 1));
-            if (row < cap) tok_of_row[row] = v; else row = -1;
-        }
-        row_of_token[v] = row;
-    }
-    if (v < KS.mask_bytes) row_mask[v] = v < min(total, cap) ? 1 : 0;
-    if ((int)blockIdx.x == nb_compact - 1 && threadIdx.x == 0) *counter = total;
-    if (blockIdx.x == 0) {
-        if (threadIdx.x == 0) { KS.doc_counters[0] = *KS.slabs; *KS.slabs = 0; }
-        else if (threadIdx.x < kSchedCounters) KS.doc_counters[threadIdx.x] = 0;
-        if (threadIdx.x >= 1 && threadIdx.x < kKeptTicket) KS.gemm_counters[threadIdx.x] = 0;
-    }
-    __syncthreads();
-    if (s_last) {          // workgroup-uniform
-        int4* w4 = reinterpret_cast<int4*>(used);
-        for (int q = threadIdx.x; q < KS.used_words; q += 256) w4[q] = make_int4(0, 0, 0, 0);
-        if (threadIdx.x == 0) *KS.ticket = 0;
-    }
-}
-
+// ... and launch 2 of the kept chain
 __global__ __launch_bounds__(256) void compact_pack_kept_kernel(const PackJob J, int nb_compact, int V, int cap, unsigned char* used,
                                                                 int* __restrict__ row_of_token, long long* __restrict__ tok_of_row,
                                                                 unsigned char* __restrict__ row_mask, int* __restrict__ counter,
                                                                 float* __restrict__ zero_row, int pitch, const PtrArray W,
                                                                 float* __restrict__ packed, float* __restrict__ WT, const B16Pack JB,
                                                                 unsigned char* __restrict__ bimg, const KeptState KS) {
-    if ((int)blockIdx.x < nb_compact) {
-        compact_kept_block(nb_compact, V, cap, used, row_of_token, tok_of_row, row_mask, counter, zero_row, pitch, KS);
-        return;
-    }
-    pack_blocks(J, nb_compact, W, packed, WT, JB, bimg);
+    if ((int)blockIdx.x < nb_compact)
+        compact_block<true>(nb_compact, V, cap, used, row_of_token, tok_of_row, row_mask, counter, zero_row, pitch, KS);
+    else
+        pack_blocks(J, nb_compact, W, packed, WT, JB, bimg);
 }
 
 // ---------------------------------------------------------------------------------- gather + pool
@@ -1274,10 +1259,32 @@ using namespace rbr;
 
 namespace {
 
+// The product channel map, stated once: bank w of the conv becomes kz[w] * ch[w] product channels, channel (w, j, cl) =
+// poff[w] + j * ch[w] + cl, banks in the descriptor's order.  Only for a descriptor that passed desc_valid().
+struct ProdChannels {
+    int n_widths, cp_real;           // cp_real: product channels before any padding
+    int kz[RBR_MAX_WIDTHS], ch[RBR_MAX_WIDTHS], poff[RBR_MAX_WIDTHS];
+    int KG() const { return (cp_real + 3) / 4 * 4; }                                       // columns of a row of G (float4 rows)
+    int KGW() const { return ((KG() / 4 + kWavesPerWG - 1) / kWavesPerWG) * 4; }           // columns per wave of the sparse products
+};
+
+ProdChannels prod_channels(const rbr_textcnn_desc* d) {
+    ProdChannels c{};
+    c.n_widths = d->n_widths;
+    for (int w = 0; w < d->n_widths; ++w) {
+        c.kz[w] = d->kz[w]; c.ch[w] = d->ch[w];
+        c.poff[w] = c.cp_real; c.cp_real += d->kz[w] * d->ch[w];
+    }
+    return c;
+}
+
 struct ProdLayout {      // byte offsets inside the workspace
     size_t used, row_of_token, tok_of_row, row_mask, counter, sched, packed, wt, bimg, a16, table_T, total;
-    int cap, Cp, tiles_p;
-    rbr_textcnn_desc dp;
+    size_t used_bytes, mask_bytes;   // the token marks and the row mask as laid out (whole 256-byte blocks)
+    int cap;
+    ProdChannels ch;
+    rbr_textcnn_desc dp;             // the token pseudo-document: one document of `cap` tokens, one kz = 1 bank of Cp channels
+    ConvPlan tp;                     // ... and its plan in store mode (group 0's plan describes every group: one launch)
 };
 
 int g_conv_mode = -1;     // -1: unset -> RBR_CONV_MODE env ("dense" | "product") or auto; 0 auto, 1 dense, 2 product
@@ -1288,13 +1295,18 @@ bool prod_applicable(const rbr_textcnn_desc* d) {
     if (mode && !strcmp(mode, "dense")) return false;
     if (!desc_valid(d)) return false;                      // nothing below may index d->kz / d->ch of an unchecked descriptor
     const long n_pos = (long)d->n_docs * d->L;
-    long Cp = 0;
-    for (int w = 0; w < d->n_widths; ++w) Cp += (long)d->kz[w] * d->ch[w];
+    const int Cp = prod_channels(d).cp_real;
     if (Cp > 30000) return false;                          // slot ids are 16-bit
-    if ((Cp + kTile - 1) / kTile > (long)kMaxGroups * kProdGroupTiles) return false;
+    if ((Cp + kTile - 1) / kTile > kMaxGroups * kProdGroupTiles) return false;
     if (mode && !strcmp(mode, "product")) return true;
     // auto: worth it when the vocabulary bounds the distinct tokens well below the position count
     return (long)d->V * 5 <= n_pos * 2 && n_pos >= 4096;
+}
+
+// RBR_DTABLE_MODE=scatter: no table gradient through a token list, the window scatter everywhere
+bool dtable_scatter_forced() {
+    static const char* env = getenv("RBR_DTABLE_MODE");
+    return env && !strcmp(env, "scatter");
 }
 
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1302,27 +1314,28 @@ size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 bool prod_layout(const rbr_textcnn_desc* d, ProdLayout& Lo) {
     const long n_pos = (long)d->n_docs * d->L;
     Lo.cap = (int)std::min<long>(d->V, n_pos);
-    long Cp = 0;
-    for (int w = 0; w < d->n_widths; ++w) Cp += (long)d->kz[w] * d->ch[w];
+    Lo.ch = prod_channels(d);
+    const int cp_real = Lo.ch.cp_real;
     // zero-weight padding channels make all work-item groups identical: 8 tiles each (750 -> 768 = 3 x 8 tiles at cfg2:
     // 167 row blocks x 3 groups = 501 items for 512 resident workgroups), fewer when the whole bank is smaller
-    const int group_tiles = (int)std::min<long>(kProdGroupTiles, (Cp + kTile - 1) / kTile);
+    const int group_tiles = std::min(kProdGroupTiles, (cp_real + kTile - 1) / kTile);
     // the bf16-plane GEMM works on items of 128 product channels
     const int kGroupSlots = prod_b16_applicable(d) ? 128 : group_tiles * kTile;
-    Cp = ((Cp + kGroupSlots - 1) / kGroupSlots) * kGroupSlots;
-    Lo.Cp = (int)Cp;
-    Lo.tiles_p = (int)(Cp / kTile);
     memset(&Lo.dp, 0, sizeof(Lo.dp));
     Lo.dp.n_docs = 1; Lo.dp.L = Lo.cap; Lo.dp.D = d->D; Lo.dp.V = d->V;
-    Lo.dp.n_widths = 1; Lo.dp.kz[0] = 1; Lo.dp.ch[0] = Lo.Cp;
+    Lo.dp.n_widths = 1; Lo.dp.kz[0] = 1; Lo.dp.ch[0] = ((cp_real + kGroupSlots - 1) / kGroupSlots) * kGroupSlots;
     Lo.dp.pad_mode = RBR_PAD_SAME; Lo.dp.act = RBR_ACT_RELU; Lo.dp.padding_idx = -1;
     ConvPlan plans[kMaxGroups];
     if (!build_plans(&Lo.dp, plans, kProdGroupTiles)) return false;
-    const ConvPlan& p = plans[0];
+    Lo.tp = plans[0];
+    Lo.tp.store_rows = 1;
+    const ConvPlan& p = Lo.tp;
     size_t o = 0;
     // [used | row_mask] are contiguous and re-zeroed every call together with the counters of `sched`
-    Lo.used = o;         o += align256((size_t)d->V);                    // one byte per token id
-    Lo.row_mask = o;     o += align256((size_t)Lo.cap);
+    Lo.used_bytes = align256((size_t)d->V);                              // one byte per token id
+    Lo.mask_bytes = align256((size_t)Lo.cap);
+    Lo.used = o;         o += Lo.used_bytes;
+    Lo.row_mask = o;     o += Lo.mask_bytes;
     Lo.row_of_token = o; o += align256((size_t)d->V * sizeof(int));
     Lo.tok_of_row = o;   o += align256((size_t)Lo.cap * sizeof(long long));
     // flags | list (unused: the token list needs no scan) | counters.  counters[0] doubles as the distinct-token count:
@@ -1330,14 +1343,12 @@ bool prod_layout(const rbr_textcnn_desc* d, ProdLayout& Lo) {
     Lo.sched = o;        o += align256((2 * (size_t)p.total_wt + kSchedCounters) * sizeof(int));
     Lo.counter = Lo.sched + 2 * (size_t)p.total_wt * sizeof(int);
     Lo.packed = o;       o += align256((size_t)p.nchunks * p.tiles_total * kTile * p.DC * sizeof(float));
-    long cp_real = 0;
-    for (int w = 0; w < d->n_widths; ++w) cp_real += (long)d->kz[w] * d->ch[w];
     Lo.wt = o;           o += align256((size_t)cp_real * d->D * sizeof(float));
-    Lo.bimg = o;         o += prod_b16_applicable(d) ? align256(prod_b16_image_bytes(d, (int)cp_real)) : 0;
+    Lo.bimg = o;         o += prod_b16_applicable(d) ? align256(prod_b16_image_bytes(d, cp_real)) : 0;
     Lo.a16 = o;          o += align256(prod_b16_rows_bytes(d, Lo.cap));        // bf16 storage: compact bf16 copy of the listed rows
     // (bf16 storage: T's elements are 2 bytes; the space is reserved for f32 either way -- the layout must not depend on more
-    // run-time state than it does today)
-    Lo.table_T = o;      o += align256((((size_t)Lo.cap + 1) * p.nslots_total + 4) * sizeof(float));   // + one float4 of slack: quads read whole
+    // run-time state than it does today; + one float4 of slack: quads are read whole)
+    Lo.table_T = o;      o += align256((((size_t)Lo.cap + 1) * p.nslots_total + 4) * sizeof(float));
     Lo.total = o;
     return true;
 }
@@ -1357,59 +1368,192 @@ int forced_conv_mode() {
 }
 }  // namespace rbr
 
-extern "C" size_t rbr_textcnn_fwd_ws_bytes(const rbr_textcnn_desc* d) {
-    ConvPlan plans[kMaxGroups];
-    if (!build_plans(d, plans)) return 0;
-    if (!prod_applicable(d)) return 0;
-    ProdLayout Lo;
-    if (!prod_layout(d, Lo)) return 0;
-    return Lo.total;
-}
-
 namespace {
 
 struct ProdBwdLayout {
     size_t G, bimg_t, total;         // bimg_t: weight planes of the row GEMM (prod_b16_rows_applicable shapes), else unused
-    int KG, KGW, cp_real;
     bool rows_gemm;
 };
 
+// dynamic LDS of the sparse products: per wave KGW (offset, value) pairs, then [4][D] partial rows
+size_t sparse_product_lds(const ProdChannels& c, int D) {
+    return (size_t)c.KGW() * 8 * kWavesPerWG + (size_t)kWavesPerWG * D * sizeof(float);
+}
+
 bool prod_bwd_layout(const rbr_textcnn_desc* d, const ProdLayout& Lo, ProdBwdLayout& B) {
     if (d->D % 4 != 0) return false;                        // float4 rows; other widths keep the window scatter
-    long cp = 0;
-    for (int w = 0; w < d->n_widths; ++w) cp += (long)d->kz[w] * d->ch[w];
-    B.cp_real = (int)cp;
-    B.KG = (int)((cp + 3) / 4 * 4);
-    B.KGW = ((B.KG / 4 + kWavesPerWG - 1) / kWavesPerWG) * 4;      // columns per wave of the sparse product
-    if ((size_t)B.KGW * 8 * kWavesPerWG + (size_t)kWavesPerWG * d->D * 4 > 64 * 1024) return false;   // lists + partial rows in LDS
+    if (sparse_product_lds(Lo.ch, d->D) > 64 * 1024) return false;
+    const int KG = Lo.ch.KG();
     size_t o = 0;
-    B.G = o;  o += align256((size_t)Lo.cap * B.KG * sizeof(float));
+    B.G = o;  o += align256((size_t)Lo.cap * KG * sizeof(float));
     B.rows_gemm = prod_b16_rows_applicable(d);
-    B.bimg_t = o;  o += B.rows_gemm ? align256(prod_b16_rows_image_bytes(B.KG, d->D)) : 0;
+    B.bimg_t = o;  o += B.rows_gemm ? align256(prod_b16_rows_image_bytes(KG, d->D)) : 0;
     B.total = o;
     return true;
 }
 
+// What every size query opens with: a descriptor that plans (`plans`), that the token-product path serves (kQueryProduct),
+// the workspace layout and (kQueryBwd) the backward's.
+enum { kQueryProduct = 1, kQueryBwd = 2 };
+bool query_layouts(const rbr_textcnn_desc* d, int what, ConvPlan* plans, ProdLayout& Lo, ProdBwdLayout& B) {
+    if (!build_plans(d, plans)) return false;
+    if ((what & kQueryProduct) && !prod_applicable(d)) return false;
+    return prod_layout(d, Lo) && (!(what & kQueryBwd) || prod_bwd_layout(d, Lo, B));
+}
+
 }  // namespace
+
+extern "C" size_t rbr_textcnn_fwd_ws_bytes(const rbr_textcnn_desc* d) {
+    ConvPlan plans[kMaxGroups];
+    ProdLayout Lo; ProdBwdLayout B;
+    return query_layouts(d, kQueryProduct, plans, Lo, B) ? Lo.total : 0;
+}
 
 extern "C" size_t rbr_textcnn_bwd_prod_ws_bytes(const rbr_textcnn_desc* d) {
     ConvPlan plans[kMaxGroups];
-    if (!build_plans(d, plans)) return 0;
-    if (!prod_applicable(d)) return 0;
-    static const char* env = getenv("RBR_DTABLE_MODE");
-    if (env && !strcmp(env, "scatter")) return 0;
-    ProdLayout Lo;
-    ProdBwdLayout B;
-    if (!prod_layout(d, Lo) || !prod_bwd_layout(d, Lo, B)) return 0;
-    return B.total;
+    ProdLayout Lo; ProdBwdLayout B;
+    return query_layouts(d, kQueryProduct | kQueryBwd, plans, Lo, B) && !dtable_scatter_forced() ? B.total : 0;
+}
+
+namespace {
+
+struct ProdState {       // a workspace laid out by prod_layout as typed pointers (the one place that casts its offsets), and
+    ProdLayout Lo;       // everything else the stages derive from (d, ws) alone
+    ProdArgs A;
+    char* base;
+    unsigned char *used, *row_mask, *bimg;
+    int *row_of_token, *counter, *sched_p;
+    long long* tok_of_row;
+    float *packed_p, *WT, *T;
+    void* a16;
+    float* zero_row;     // the all-zero row of T that masked / out-of-document taps read: row `cap`
+    int zero_len;        // ... in floats (bf16 storage: T's rows are half as long)
+};
+
+// list_only: the workspace of rbr_textcnn_bwd_dtable_list -- any shape the layout exists for, and everything but T: it ends
+// with ONE row where T starts, the zero row (always f32; nothing reads T there).
+int prod_state(const rbr_textcnn_desc* d, void* ws, ProdState& S, bool list_only = false) {
+    if (ws == nullptr) { set_error("null workspace"); return RBR_ERR_BAD_ARG; }
+    if (!list_only && !prod_applicable(d)) { set_error("token-product path does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
+    if (!prod_layout(d, S.Lo)) return RBR_ERR_BAD_ARG;
+    const ProdLayout& Lo = S.Lo;
+    S.base = static_cast<char*>(ws);
+    S.used = reinterpret_cast<unsigned char*>(S.base + Lo.used);
+    S.row_of_token = reinterpret_cast<int*>(S.base + Lo.row_of_token);
+    S.tok_of_row = reinterpret_cast<long long*>(S.base + Lo.tok_of_row);
+    S.row_mask = reinterpret_cast<unsigned char*>(S.base + Lo.row_mask);
+    S.counter = reinterpret_cast<int*>(S.base + Lo.counter);
+    S.sched_p = reinterpret_cast<int*>(S.base + Lo.sched);
+    S.packed_p = reinterpret_cast<float*>(S.base + Lo.packed);
+    S.WT = reinterpret_cast<float*>(S.base + Lo.wt);
+    S.bimg = reinterpret_cast<unsigned char*>(S.base + Lo.bimg);
+    S.a16 = S.base + Lo.a16;
+    S.T = reinterpret_cast<float*>(S.base + Lo.table_T);
+    const int pitch = Lo.tp.nslots_total;
+    S.zero_len = (!list_only && prod_t_bf16(d)) ? pitch / 2 : pitch;
+    S.zero_row = list_only ? S.T : S.T + (size_t)Lo.cap * S.zero_len;
+    ProdArgs A{};
+    A.n_docs = d->n_docs; A.L = d->L; A.V = d->V; A.cap = Lo.cap; A.zrow = Lo.cap; A.pitch = pitch;
+    A.cp_real = Lo.ch.cp_real;      // product channels follow the bank order of the ORIGINAL problem (bank w, tap j, channel cl)
+    for (int w = 0; w < d->n_widths; ++w) {      // rank_off: as build_plans orders the channel slots
+        A.poff[w] = Lo.ch.poff[w];
+        int r = 0;
+        for (int v = 0; v < d->n_widths; ++v)
+            if (d->kz[v] < d->kz[w] || (d->kz[v] == d->kz[w] && v < w)) r += d->ch[v];
+        A.rank_off[w] = r;
+    }
+    S.A = A;
+    return 0;
+}
+
+// ---- one maker per kernel argument block
+// ProdBwdArgs.  Optional, zero for the kernels that do not read them: cap (rows of the list / of the rebuild), t_pitch (gated
+// convs: d(gate) reads T), kArgsTaps (padding_idx, pad_mode: the kernels that place taps), kArgsGate (gate_split).
+enum { kArgsTaps = 1, kArgsGate = 2 };
+ProdBwdArgs make_bwd_args(const rbr_textcnn_desc* d, const ConvPlan& p, const ProdChannels& c, int cap, int t_pitch = 0, int opt = 0) {
+    ProdBwdArgs A{};
+    A.n_docs = d->n_docs; A.L = d->L; A.C = p.C; A.KF = p.KF; A.KG = c.KG(); A.D = d->D; A.cap = cap; A.act = d->act;
+    A.t_pitch = t_pitch;
+    if (opt & kArgsTaps) { A.padding_idx = d->padding_idx; A.pad_mode = d->pad_mode; }
+    if (opt & kArgsGate) A.gate_split = RBR_CONV_GATE_SPLIT_OF(d->flags);
+    A.n_widths = c.n_widths;
+    for (int w = 0; w < c.n_widths; ++w) { A.kz[w] = c.kz[w]; A.ch[w] = c.ch[w]; A.ch_off[w] = p.ch_off[w]; A.poff[w] = c.poff[w]; }
+    return A;
+}
+
+// PackJob; token_plan: the plan of the token pseudo-document whose tile image the forward GEMM reads (none: Wprod^T only)
+PackJob make_pack_job(const rbr_textcnn_desc* d, const ProdChannels& c, const ConvPlan* token_plan) {
+    PackJob J{};
+    if (token_plan) J.P = *token_plan;
+    J.n_widths = c.n_widths; J.D = d->D; J.cp_real = c.cp_real;
+    for (int w = 0; w < c.n_widths; ++w) { J.kz[w] = c.kz[w]; J.ch[w] = c.ch[w]; J.poff[w] = c.poff[w]; }
+    return J;
+}
+
+template <class Array, class P> Array ptr_array(P const* W, int n) {      // PtrArray / MutPtrArray of the banks' tensors
+    Array a{};
+    for (int w = 0; w < n; ++w) a.p[w] = W[w];
+    return a;
 }
 
 // phases of dtable_through_list: build G | multiply it out | ... adding to dtable instead of overwriting it | ... into compact
 // rows + sq_part (kGtwRows) | G's rows are already zero (the forward's gather_pool launch cleared them: no zero_g_rows launch)
 enum { kGBuild = 1, kGProduct = 2, kGAccumulate = 4, kGRows = 8, kGZeroed = 16 };
-static int dtable_through_list(const rbr_textcnn_desc* d, const ConvPlan* plans, const int64_t* ids, const uint8_t* mask, const float* gate,
-                               const float* feat, const int32_t* argmax, const float* d_feat, void* fwd_ws, void* bwd_ws,
-                               float* dtable, float* dgate, hipStream_t st, int phases = kGBuild | kGProduct, float* sq_part = nullptr);
+
+// G over the token list in `S` (a forward or a list-only workspace), then dtable = G @ Wprod^T; shared by the token-product
+// backward (the forward's list) and by the dense formulation's backward (a list built for the purpose,
+// rbr_textcnn_bwd_dtable_list)
+int dtable_through_list(const rbr_textcnn_desc* d, const ConvPlan* plans, const ProdState& S, void* bwd_ws, const int64_t* ids,
+                        const uint8_t* mask, const float* gate, const float* feat, const int32_t* argmax, const float* d_feat,
+                        float* dtable, float* dgate, hipStream_t st, int phases = kGBuild | kGProduct, float* sq_part = nullptr) {
+    PairSolo solo;        // zero G -> build G -> G @ Wprod^T: a producer / consumer chain over G (rbr_launch.h)
+    const ProdLayout& Lo = S.Lo;
+    ProdBwdLayout B;
+    if (!prod_bwd_layout(d, Lo, B)) return RBR_ERR_BAD_ARG;
+    const int KG = Lo.ch.KG(), KGW = Lo.ch.KGW();
+    float* G = reinterpret_cast<float*>(static_cast<char*>(bwd_ws) + B.G);
+    unsigned char* bimg_t = static_cast<unsigned char*>(bwd_ws) + B.bimg_t;
+    // (WT: Wprod^T, written by the forward's stage 1; T: the product table, still intact)
+    const ProdBwdArgs A = make_bwd_args(d, plans[0], Lo.ch, Lo.cap, Lo.tp.nslots_total, kArgsTaps | kArgsGate);
+    // kGBuild alone (RBR_G_BUILD) always builds G: its caller multiplies it out later (a second call with RBR_G_PRODUCT)
+    const bool want_g = dtable != nullptr || !(phases & kGProduct);
+    if (phases & kGBuild) {
+        const bool zero_g = want_g && !(phases & kGZeroed);
+        if (zero_g || dgate != nullptr || B.rows_gemm) {      // dgate is zeroed here: the caller hands it over uninitialised
+            // row-GEMM shapes: the same launch writes the bf16 planes of Wprod^T the product phase multiplies G by
+            const long n_img = B.rows_gemm ? prod_b16_rows_image_items(KG, d->D) : 0;
+            const int nb_zero = 2048, nb_img = (int)std::min<long>((n_img + 255) / 256, 1024);
+            const long n_dgate = dgate != nullptr ? (long)d->n_docs * d->L * (A.gate_split ? 2 : 1) : 0L;
+            if (int e_ = rbr::launch<zero_g_rows_kernel, 256>(dim3(nb_zero + nb_img), dim3(256), 0, st, "textcnn zero_g_rows launch",
+                                                              S.counter, Lo.cap, KG / 4, zero_g ? reinterpret_cast<f32x4*>(G) : nullptr,
+                                                              dgate, n_dgate, nb_zero, S.WT, Lo.ch.cp_real, d->D, n_img, bimg_t))
+                return e_;
+        }
+        const long n_items = (long)d->n_docs * A.C * A.KF;
+        if (int e_ = rbr::launch<build_g_kernel, 256>(dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st, "textcnn build_g launch",
+                                                      A, reinterpret_cast<const long long*>(ids), mask, gate, S.row_of_token, S.T, feat,
+                                                      argmax, d_feat, want_g ? G : nullptr, dgate, prod_t_bf16(d) ? 1 : 0))
+            return e_;
+    }
+    if (dtable == nullptr || !(phases & kGProduct)) return 0;
+    const size_t lds = sparse_product_lds(Lo.ch, d->D);
+    const dim3 grid((unsigned)std::min(Lo.cap, kGtwMaxBlocks)), block(256);
+    const char* what = "textcnn g_times_w launch";
+    if (phases & kGRows) {
+        if (sq_part == nullptr) { set_error("compact row gradient needs sq_part"); return RBR_ERR_BAD_ARG; }
+        if (B.rows_gemm)          // many short documents: G is dense enough for the bf16-plane GEMM (textcnn_prod_b16.hip)
+            return prod_b16_rows_gemm(KG, d->D, Lo.cap, S.counter, G, bimg_t, dtable, sq_part, prod_precision_of(d) == RBR_PROD_BF16, st);
+        return rbr::launch<g_times_w_kernel<kGtwRows>, 256>(grid, block, lds, st, what, A, KGW, S.counter, G, S.WT, S.tok_of_row,
+                                                            S.row_of_token, d->V, dtable, sq_part);
+    }
+    if (phases & kGAccumulate)
+        return rbr::launch<g_times_w_kernel<kGtwAccumulate>, 256>(grid, block, lds, st, what, A, KGW, S.counter, G, S.WT, S.tok_of_row,
+                                                                  S.row_of_token, d->V, dtable, (float*)nullptr);
+    return rbr::launch<g_times_w_kernel<kGtwDense>, 256>(grid, block, lds, st, what, A, KGW, S.counter, G, S.WT, S.tok_of_row,
+                                                         S.row_of_token, d->V, dtable, (float*)nullptr);
+}
+
+}  // namespace
 
 // Every form of the token-product table gradient behind one entry:
 //   RBR_G_BUILD | RBR_G_PRODUCT   the phases to run -- in one call, or as two for callers that put work between them or beside
@@ -1430,11 +1574,15 @@ extern "C" int rbr_textcnn_bwd_dtable_prod_ex(const rbr_textcnn_desc* d, const i
     if (!fwd_ws || !bwd_ws) { set_error("null workspace"); return RBR_ERR_BAD_ARG; }
     if ((flags & RBR_G_BUILD) && (!ids || !feat || !argmax || !d_feat)) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
     if ((flags & RBR_G_PRODUCT) && !dtable) { set_error("null dtable"); return RBR_ERR_BAD_ARG; }
-    if ((flags & RBR_G_ROWS) && ((flags & RBR_G_ACCUMULATE) || !sq_part)) { set_error("RBR_G_ROWS needs sq_part and excludes RBR_G_ACCUMULATE"); return RBR_ERR_BAD_ARG; }
-    if (!prod_applicable(d)) { set_error("token-product path does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
+    if ((flags & RBR_G_ROWS) && ((flags & RBR_G_ACCUMULATE) || !sq_part)) {
+        set_error("RBR_G_ROWS needs sq_part and excludes RBR_G_ACCUMULATE");
+        return RBR_ERR_BAD_ARG;
+    }
+    ProdState S;
+    if (int e = prod_state(d, fwd_ws, S)) return e;
     static_assert(RBR_G_BUILD == kGBuild && RBR_G_PRODUCT == kGProduct && RBR_G_ACCUMULATE == kGAccumulate && RBR_G_ROWS == kGRows &&
                   RBR_G_ZEROED == kGZeroed, "public flags = internal phases");
-    return dtable_through_list(d, plans, ids, mask, gate, feat, argmax, d_feat, fwd_ws, bwd_ws, dtable, dgate, (hipStream_t)stream,
+    return dtable_through_list(d, plans, S, bwd_ws, ids, mask, gate, feat, argmax, d_feat, dtable, dgate, (hipStream_t)stream,
                                flags & (kGBuild | kGProduct | kGAccumulate | kGRows | kGZeroed), sq_part);
 }
 
@@ -1450,129 +1598,75 @@ extern "C" size_t rbr_textcnn_row_grad_partials(const rbr_textcnn_desc* d) {
 // device count of listed rows, tok_of_row [cap]; cap = rows the compact gradient must have room for.
 extern "C" int rbr_textcnn_token_list(const rbr_textcnn_desc* d, void* fwd_ws, const int32_t** row_of_token, const int32_t** n_rows,
                                       const int64_t** tok_of_row, int32_t* cap) {
-    ProdLayout Lo;
-    if (!fwd_ws || !prod_applicable(d) || !prod_layout(d, Lo)) { set_error("no token list for this shape"); return RBR_ERR_UNSUPPORTED; }
-    char* base = static_cast<char*>(fwd_ws);
-    if (row_of_token) *row_of_token = reinterpret_cast<const int32_t*>(base + Lo.row_of_token);
-    if (n_rows) *n_rows = reinterpret_cast<const int32_t*>(base + Lo.counter);
-    if (tok_of_row) *tok_of_row = reinterpret_cast<const int64_t*>(base + Lo.tok_of_row);
-    if (cap) *cap = Lo.cap;
-    return 0;
-}
-
-// G over the token list in `fwd_ws` (ProdLayout), then dtable = G @ Wprod^T; shared by the token-product backward (the
-// forward's list) and by the dense formulation's backward (a list built for the purpose, rbr_textcnn_bwd_dtable_list)
-static int dtable_through_list(const rbr_textcnn_desc* d, const ConvPlan* plans, const int64_t* ids, const uint8_t* mask, const float* gate,
-                               const float* feat, const int32_t* argmax, const float* d_feat, void* fwd_ws, void* bwd_ws,
-                               float* dtable, float* dgate, hipStream_t st, int phases, float* sq_part) {
-    PairSolo solo;        // zero G -> build G -> G @ Wprod^T: a producer / consumer chain over G (rbr_launch.h)
-    ProdLayout Lo;
-    ProdBwdLayout B;
-    if (!prod_layout(d, Lo) || !prod_bwd_layout(d, Lo, B)) return RBR_ERR_BAD_ARG;
-    char* fbase = static_cast<char*>(fwd_ws);
-    const int* row_of_token = reinterpret_cast<const int*>(fbase + Lo.row_of_token);
-    const long long* tok_of_row = reinterpret_cast<const long long*>(fbase + Lo.tok_of_row);
-    const int* counter = reinterpret_cast<const int*>(fbase + Lo.counter);
-    const float* WT = reinterpret_cast<const float*>(fbase + Lo.wt);     // Wprod^T, written by the forward's stage 1
-    const float* T = reinterpret_cast<const float*>(fbase + Lo.table_T);  // product table, still intact
-    float* G = reinterpret_cast<float*>(static_cast<char*>(bwd_ws) + B.G);
-
-    ProdBwdArgs A{};
-    A.n_docs = d->n_docs; A.L = d->L; A.C = plans[0].C; A.KF = plans[0].KF; A.KG = B.KG; A.D = d->D; A.cap = Lo.cap;
-    A.padding_idx = d->padding_idx; A.pad_mode = d->pad_mode; A.act = d->act; A.n_widths = d->n_widths;
-    A.gate_split = RBR_CONV_GATE_SPLIT_OF(d->flags);
-    {
-        ConvPlan pp[kMaxGroups];
-        if (!build_plans(&Lo.dp, pp, kProdGroupTiles)) return RBR_ERR_BAD_ARG;
-        A.t_pitch = pp[0].nslots_total;
-    }
-    int cp_real = 0;
-    for (int w = 0; w < d->n_widths; ++w) {
-        A.kz[w] = d->kz[w]; A.ch[w] = d->ch[w]; A.ch_off[w] = plans[0].ch_off[w];
-        A.poff[w] = cp_real; cp_real += d->kz[w] * d->ch[w];
-    }
-    // kGBuild alone (RBR_G_BUILD) always builds G: its caller multiplies it out later (a second call with RBR_G_PRODUCT)
-    const bool want_g = dtable != nullptr || !(phases & kGProduct);
-    if (phases & kGBuild) {
-        if ((want_g && !(phases & kGZeroed)) || dgate != nullptr || B.rows_gemm) {      // dgate is zeroed here: the caller hands it over uninitialised
-            // row-GEMM shapes: the same launch writes the bf16 planes of Wprod^T the product phase multiplies G by
-            const long n_img = B.rows_gemm ? prod_b16_rows_image_items(B.KG, d->D) : 0;
-            const int nb_zero = 2048, nb_img = (int)std::min<long>((n_img + 255) / 256, 1024);
-            if (int e_ = rbr::launch<zero_g_rows_kernel, 256>(dim3(nb_zero + nb_img), dim3(256), 0, st, "textcnn zero_g_rows launch", counter, Lo.cap, B.KG / 4, (want_g && !(phases & kGZeroed)) ? reinterpret_cast<f32x4*>(G) : nullptr, dgate, dgate != nullptr ? (long)d->n_docs * d->L * (RBR_CONV_GATE_SPLIT_OF(d->flags) ? 2 : 1) : 0L, nb_zero, WT, cp_real, d->D, n_img, reinterpret_cast<unsigned char*>(static_cast<char*>(bwd_ws) + B.bimg_t))) return e_;
-        }
-        const long n_items = (long)d->n_docs * A.C * A.KF;
-        if (int e_ = rbr::launch<build_g_kernel, 256>(dim3((unsigned)((n_items + 255) / 256)), dim3(256), 0, st, "textcnn build_g launch", A, reinterpret_cast<const long long*>(ids), mask, gate, row_of_token, T, feat, argmax, d_feat, want_g ? G : nullptr, dgate, prod_t_bf16(d) ? 1 : 0)) return e_;
-    }
-    if (dtable == nullptr || !(phases & kGProduct)) return 0;
-    const size_t lds = (size_t)B.KGW * 8 * kWavesPerWG + (size_t)kWavesPerWG * d->D * sizeof(float);
-    const dim3 grid((unsigned)std::min(Lo.cap, kGtwMaxBlocks));
-    if (phases & kGRows) {
-        if (sq_part == nullptr) { set_error("compact row gradient needs sq_part"); return RBR_ERR_BAD_ARG; }
-        if (B.rows_gemm)          // many short documents: G is dense enough for the bf16-plane GEMM (textcnn_prod_b16.hip)
-            return prod_b16_rows_gemm(B.KG, d->D, Lo.cap, counter, G, static_cast<char*>(bwd_ws) + B.bimg_t, dtable, sq_part,
-                                      prod_precision_of(d) == RBR_PROD_BF16, st);
-        if (int e_ = rbr::launch<g_times_w_kernel<kGtwRows>, 256>(grid, dim3(256), lds, st, "textcnn g_times_w launch", A, B.KGW, counter, G, WT, tok_of_row, row_of_token, d->V, dtable, sq_part)) return e_;
-    } else if (phases & kGAccumulate) {
-        if (int e_ = rbr::launch<g_times_w_kernel<kGtwAccumulate>, 256>(grid, dim3(256), lds, st, "textcnn g_times_w launch", A, B.KGW, counter, G, WT, tok_of_row, row_of_token, d->V, dtable, (float*)nullptr)) return e_;
-    } else {
-        if (int e_ = rbr::launch<g_times_w_kernel<kGtwDense>, 256>(grid, dim3(256), lds, st, "textcnn g_times_w launch", A, B.KGW, counter, G, WT, tok_of_row, row_of_token, d->V, dtable, (float*)nullptr)) return e_;
-    }
+    ProdState S;
+    if (!fwd_ws || prod_state(d, fwd_ws, S)) { set_error("no token list for this shape"); return RBR_ERR_UNSUPPORTED; }
+    if (row_of_token) *row_of_token = S.row_of_token;
+    if (n_rows) *n_rows = S.counter;
+    if (tok_of_row) *tok_of_row = reinterpret_cast<const int64_t*>(S.tok_of_row);
+    if (cap) *cap = S.Lo.cap;
     return 0;
 }
 
 namespace {
 
-struct ProdState {       // everything the three forward stages share, derived from (d, ws) alone
-    ProdLayout Lo;
-    ConvPlan pp[kMaxGroups];
-    ProdArgs A;
-    unsigned char* used;
-    int *row_of_token, *counter, *sched_p;
-    long long* tok_of_row;
-    unsigned char* row_mask;
-    float *packed_p, *WT, *T;
-    char* base;
-};
+// The list state every self-initialising chain clears first: token marks + row mask (contiguous), the counters of the token
+// list and (forward) the counters of the documents' work list.
+ZeroRegions list_state_regions(const ProdState& S, int* doc_counters) {
+    return ZeroRegions{{reinterpret_cast<int*>(S.used), S.counter, doc_counters},
+                       {(long)((S.Lo.used_bytes + S.Lo.mask_bytes) / sizeof(int)), kSchedCounters, doc_counters ? kSchedCounters : 0}};
+}
 
-int prod_state(const rbr_textcnn_desc* d, void* ws, ProdState& S) {
-    if (ws == nullptr) { set_error("null workspace"); return RBR_ERR_BAD_ARG; }
-    if (!prod_applicable(d)) { set_error("token-product path does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
-    if (!prod_layout(d, S.Lo)) return RBR_ERR_BAD_ARG;
-    const ProdLayout& Lo = S.Lo;
-    S.base = static_cast<char*>(ws);
-    S.used = reinterpret_cast<unsigned char*>(S.base + Lo.used);
-    S.row_of_token = reinterpret_cast<int*>(S.base + Lo.row_of_token);
-    S.tok_of_row = reinterpret_cast<long long*>(S.base + Lo.tok_of_row);
-    S.row_mask = reinterpret_cast<unsigned char*>(S.base + Lo.row_mask);
-    S.counter = reinterpret_cast<int*>(S.base + Lo.counter);
-    S.sched_p = reinterpret_cast<int*>(S.base + Lo.sched);
-    S.packed_p = reinterpret_cast<float*>(S.base + Lo.packed);
-    S.WT = reinterpret_cast<float*>(S.base + Lo.wt);
-    S.T = reinterpret_cast<float*>(S.base + Lo.table_T);
-    if (!build_plans(&S.Lo.dp, S.pp, kProdGroupTiles)) return RBR_ERR_BAD_ARG;
-    S.pp[0].store_rows = 1;      // group 0's plan describes every group; the kernel folds them into one launch
-    ProdArgs A{};
-    A.n_docs = d->n_docs; A.L = d->L; A.V = d->V; A.cap = Lo.cap; A.zrow = Lo.cap; A.pitch = S.pp[0].nslots_total;
-    int o = 0;    // product channels follow the bank order of the ORIGINAL problem (bank w, tap j, channel cl)
-    for (int w = 0; w < d->n_widths; ++w) { A.poff[w] = o; o += d->kz[w] * d->ch[w]; }
-    A.cp_real = o;
-    for (int w = 0; w < d->n_widths; ++w) {      // as build_plans orders the channel slots
-        int r = 0;
-        for (int v = 0; v < d->n_widths; ++v)
-            if (d->kz[v] < d->kz[w] || (d->kz[v] == d->kz[w] && v < w)) r += d->ch[v];
-        A.rank_off[w] = r;
-    }
-    S.A = A;
+// The last launch of every chain: marks -> token list (kept: the form of KeptState, a direct launch that never pairs), and the
+// pack role.  fwd_images: the weight image of the forward GEMM (the f32 tile image; for the bf16-plane GEMM its weight planes in
+// MFMA-fragment order instead) beside Wprod^T.
+int launch_compact_pack(const rbr_textcnn_desc* d, const ProdState& S, const float* const* W, bool fwd_images, const KeptState* kept,
+                        hipStream_t st) {
+    const ConvPlan& tp = S.Lo.tp;
+    const bool b16 = fwd_images && prod_b16_applicable(d);
+    const PackJob J = make_pack_job(d, S.Lo.ch, &tp);
+    const PtrArray wp = ptr_array<PtrArray>(W, d->n_widths);
+    const B16Pack JB = b16 ? prod_b16_pack_job(d) : B16Pack{};
+    float* packed = (fwd_images && !b16) ? S.packed_p : nullptr;
+    unsigned char* bimg = b16 ? S.bimg : nullptr;
+    long n_pack = (long)S.Lo.ch.cp_real * d->D;
+    if (b16) n_pack += (long)JB.ngroups * JB.nchunks * 4 * 64;
+    else if (fwd_images) n_pack += (long)tp.nchunks * tp.tiles_total * kTile * tp.DC;
+    const int nb_compact = (d->V + 255) / 256, nb_pack = (int)std::min<long>((n_pack + 255) / 256, 2048);
+    const dim3 grid(nb_compact + nb_pack), block(256);
+    if (kept == nullptr)
+        return rbr::launch<compact_pack_kernel, 256>(grid, block, 0, st, "textcnn compact_pack launch", J, nb_compact, d->V, S.Lo.cap,
+                                                     S.used, S.row_of_token, S.tok_of_row, S.row_mask, S.counter, S.zero_row,
+                                                     S.zero_len, wp, packed, S.WT, JB, bimg);
+    hipLaunchKernelGGL(compact_pack_kept_kernel, grid, block, 0, st, J, nb_compact, d->V, S.Lo.cap, S.used, S.row_of_token, S.tok_of_row,
+                       S.row_mask, S.counter, S.zero_row, S.zero_len, wp, packed, S.WT, JB, bimg, *kept);
+    RBR_CHECK_LAUNCH("textcnn compact_pack_kept launch");
     return 0;
+}
+
+// The two launches that follow the clearing of the list state: mark the tokens that occur (+ the slab scan of the real documents
+// `plan` into their work list `sched`) | marks -> token list, and the pack role.  sched == nullptr is the list backward's form:
+// no documents to scan, no forward GEMM to feed (Wprod^T alone).
+int build_list(const rbr_textcnn_desc* d, const ConvPlan& plan, const ProdState& S, const int64_t* ids, const uint8_t* mask,
+               const float* const* W, int* sched, hipStream_t st) {
+    const long n_tok = (long)d->n_docs * d->L;
+    const int nb_scan = sched ? (plan.total_wt + 255) / 256 : 0;
+    const int nb_mark = (int)std::min<long>((n_tok + 255) / 256, 2048);
+    if (int e = rbr::launch<mark_scan_kernel, 256>(dim3(nb_scan + nb_mark), dim3(256), 0, st, "textcnn mark_scan launch", plan, nb_scan,
+                                                   n_tok, reinterpret_cast<const long long*>(ids), mask, sched, S.used))
+        return e;
+    return launch_compact_pack(d, S, W, sched != nullptr, nullptr, st);
 }
 
 }  // namespace
 
-// Stage 1: work list of the real documents (tail of `pidx`), distinct-token list of the batch, product weight
-// images.  Three launches: zero the state | mark + scan | compact + pack.  kept (needs id_sets): the two launches of the form
-// that finds the list state zero and leaves it zero (KeptState) -- check + mark + scan | compact + pack.
-// (The weight images stay in the second launch.  Moving them into the first was NOT measured: at cfg2 the first launch is 6.4 us
-// and the second 9.9 us, of which the compaction alone was 8.2 us before)
+// Stage 1: work list of the real documents (tail of `pidx`), distinct-token list of the batch, product weight images.  Three
+// chains on the caller's stream:
+//   plain (id_sets == nullptr)   zero the list state | mark + scan | compact + pack
+//   ids                          id range check + zero the list state (prep_kernel) | mark + scan | compact + pack
+//   kept (needs id_sets)         check + mark + scan | compact + pack: the form that finds the list state zero and leaves it
+//                                zero (KeptState)
+// (The weight images stay in the last launch.  Moving them into the first was NOT measured: at cfg2 the kept chain's first launch
+// is 6.4 us and the second 9.9 us, of which the compaction alone was 8.2 us before)
 static int prod_prepare(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* const* W, int32_t* pidx,
                         void* ws, void* stream, const IdSets* id_sets, int64_t* err, bool kept = false) {
     ConvPlan plans[kMaxGroups];
@@ -1581,69 +1675,57 @@ static int prod_prepare(const rbr_textcnn_desc* d, const int64_t* ids, const uin
     ProdState S;
     if (int e = prod_state(d, ws, S)) return e;
     hipStream_t st = (hipStream_t)stream;
-    int* sched = pidx + (size_t)plans[0].total_wt * plans[0].nslots_total;
-    // token marks, row mask and both work-list counter blocks are re-initialised every call: graph-replay safe
-    ZeroRegions zr{{reinterpret_cast<int*>(S.base + S.Lo.used), S.sched_p + 2 * (size_t)S.pp[0].total_wt,
-                    sched + 2 * (size_t)plans[0].total_wt},
-                   {(long)((S.Lo.row_of_token - S.Lo.used) / sizeof(int)), kSchedCounters, kSchedCounters}};
-    const long n_tok = (long)d->n_docs * d->L;
-    const int nb_scan = (plans[0].total_wt + 255) / 256;
-    const int nb_mark = (int)std::min<long>((n_tok + 255) / 256, 2048);
+    const ConvPlan& plan = plans[0];
+    int* sched = pidx + (size_t)plan.total_wt * plan.nslots_total;      // the documents' work list: flags | list | counters
+    int* doc_counters = sched + 2 * (size_t)plan.total_wt;
+    long long* err_rec = reinterpret_cast<long long*>(err);
     if (kept) {
-        if (mask == nullptr && plans[0].pad_runs >= 0) {
+        if (mask == nullptr && plan.pad_runs >= 0) {
             set_error("prod_prepare_ids_kept: an un-masked conv with RBR_CONV_PAD_RUNS scans the clean ids (use prod_prepare_ids)");
             return RBR_ERR_UNSUPPORTED;
         }
+        const long n_tok = (long)d->n_docs * d->L;
         const long long rest = id_sets->first[id_sets->count] - n_tok;
+        const int nb_scan = (plan.total_wt + 255) / 256;
+        const int nb_mark = (int)std::min<long>((n_tok + 255) / 256, 2048);
         const int nb_rest = (int)std::min<long long>((rest + 255) / 256, 2048);
-        hipLaunchKernelGGL(mark_scan_ids_kernel, dim3(nb_scan + nb_mark + nb_rest), dim3(256), 0, st, plans[0], nb_scan, nb_mark, n_tok,
-                           *id_sets, reinterpret_cast<long long*>(err), mask, sched, S.counter + kKeptSlabs, S.used, d->V);
+        hipLaunchKernelGGL(mark_scan_ids_kernel, dim3(nb_scan + nb_mark + nb_rest), dim3(256), 0, st, plan, nb_scan, nb_mark, n_tok,
+                           *id_sets, err_rec, mask, sched, S.counter + kKeptSlabs, S.used, d->V);
         RBR_CHECK_LAUNCH("textcnn mark_scan_ids launch");
-    } else if (id_sets != nullptr) {
+        const KeptState KS{S.counter + kKeptTicket, S.counter + kKeptSlabs, doc_counters, S.counter,
+                           (int)(S.Lo.used_bytes / 16), (int)S.Lo.mask_bytes};
+        return launch_compact_pack(d, S, W, true, &KS, st);
+    }
+    // token marks, row mask and both work-list counter blocks are re-initialised every call: graph-replay safe
+    const ZeroRegions zr = list_state_regions(S, doc_counters);
+    if (id_sets != nullptr) {
         const long long total = id_sets->first[id_sets->count];
         const int nb_ids = (int)std::min<long long>((total + 255) / 256, 2048);
-        const long nz = zr.n[0] + zr.n[1] + zr.n[2];
-        const int nb_zero = (int)std::min<long>((nz + 255) / 256, 256);
-        hipLaunchKernelGGL(prep_kernel, dim3(nb_ids + nb_zero), dim3(256), 0, st, *id_sets, reinterpret_cast<long long*>(err), zr, nb_ids);
+        const int nb_zero = (int)std::min<long>((zr.n[0] + zr.n[1] + zr.n[2] + 255) / 256, 256);
+        hipLaunchKernelGGL(prep_kernel, dim3(nb_ids + nb_zero), dim3(256), 0, st, *id_sets, err_rec, zr, nb_ids);
         RBR_CHECK_LAUNCH("textcnn prep launch");
     } else if (int e = zero_regions(zr, st)) {
         return e;
     }
-    if (!kept)
-        if (int e_ = rbr::launch<mark_scan_kernel, 256>(dim3(nb_scan + nb_mark), dim3(256), 0, st, "textcnn mark_scan launch", plans[0], nb_scan, n_tok, reinterpret_cast<const long long*>(ids), mask, sched, S.used)) return e_;
-    PackJob J{};
-    J.P = S.pp[0]; J.n_widths = d->n_widths; J.D = d->D; J.cp_real = S.A.cp_real;
-    for (int w = 0; w < d->n_widths; ++w) { J.kz[w] = d->kz[w]; J.ch[w] = d->ch[w]; J.poff[w] = S.A.poff[w]; }
-    PtrArray wp{};
-    for (int w = 0; w < d->n_widths; ++w) wp.p[w] = W[w];
-    const int nb_compact = (d->V + 255) / 256;
-    const bool b16 = prod_b16_applicable(d);
-    B16Pack JB{};
-    if (b16) JB = prod_b16_pack_job(d);
-    const long n_pack = (b16 ? (long)JB.ngroups * JB.nchunks * 4 * 64 : (long)S.pp[0].nchunks * S.pp[0].tiles_total * kTile * S.pp[0].DC) +
-                        (long)S.A.cp_real * d->D;
-    const int nb_pack = (int)std::min<long>((n_pack + 255) / 256, 2048);
-    // (bf16-plane GEMM: the weight planes in MFMA-fragment order instead of the f32 tile image)
-    if (kept) {
-        const bool tb16 = prod_t_bf16(d);
-        float* zero_row = tb16 ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(S.T) + (size_t)S.Lo.cap * S.A.pitch)
-                               : S.T + (size_t)S.Lo.cap * S.A.pitch;
-        const KeptState KS{S.counter + kKeptTicket, S.counter + kKeptSlabs, sched + 2 * (size_t)plans[0].total_wt, S.counter,
-                           (int)(align256((size_t)d->V) / 16), (int)align256((size_t)S.Lo.cap)};
-        hipLaunchKernelGGL(compact_pack_kept_kernel, dim3(nb_compact + nb_pack), dim3(256), 0, st, J, nb_compact, d->V, S.Lo.cap, S.used,
-                           S.row_of_token, S.tok_of_row, S.row_mask, S.counter, zero_row, tb16 ? S.A.pitch / 2 : S.A.pitch, wp,
-                           b16 ? nullptr : S.packed_p, S.WT, JB, b16 ? reinterpret_cast<unsigned char*>(S.base + S.Lo.bimg) : nullptr, KS);
-        RBR_CHECK_LAUNCH("textcnn compact_pack_kept launch");
-        return 0;
-    }
-    if (int e_ = rbr::launch<compact_pack_kernel, 256>(dim3(nb_compact + nb_pack), dim3(256), 0, st, "textcnn compact_pack launch", J, nb_compact, d->V, S.Lo.cap, S.used, S.row_of_token, S.tok_of_row, S.row_mask, S.counter, prod_t_bf16(d) ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(S.T) + (size_t)S.Lo.cap * S.A.pitch)
-                                      : S.T + (size_t)S.Lo.cap * S.A.pitch, prod_t_bf16(d) ? S.A.pitch / 2 : S.A.pitch, wp, b16 ? nullptr : S.packed_p, S.WT, JB, b16 ? reinterpret_cast<unsigned char*>(S.base + S.Lo.bimg) : nullptr)) return e_;
-    return 0;
+    return build_list(d, plan, S, ids, mask, W, sched, st);
 }
 
 extern "C" int rbr_textcnn_prod_prepare(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask,
                                         const float* const* W, int32_t* pidx, void* ws, void* stream) {
     return prod_prepare(d, ids, mask, W, pidx, ws, stream, nullptr, nullptr);
+}
+
+// What both _ids entries ask of their id sets: valid ones (-> S), and the conv's token ids `ids` are the clean copy of the
+// first set or of the first two, adjacent ones (the stacked towers), d->n_docs * d->L ids in all.  *n_token_sets: 1 or 2.
+static int token_id_sets(const char* who, const rbr_textcnn_desc* d, int32_t n_sets, const rbr_id_set* sets, const int64_t* ids,
+                         IdSets& S, int* n_token_sets) {
+    if (int e = fill_id_sets(n_sets, sets, S)) return e;
+    const long long n_tok = (long long)d->n_docs * d->L;
+    const bool one = sets[0].out == ids && sets[0].n == n_tok;
+    const bool two = n_sets >= 2 && sets[0].out == ids && sets[1].out == sets[0].out + sets[0].n && sets[0].n + sets[1].n == n_tok;
+    if (!one && !two) { set_error("%s: `ids` is not the clean copy of the first id set(s)", who); return RBR_ERR_BAD_ARG; }
+    *n_token_sets = one ? 1 : 2;
+    return 0;
 }
 
 // rbr_textcnn_prod_prepare with the model's id range check (rbr_sanitize_ids) folded into its first launch: `sets` are the raw
@@ -1654,11 +1736,8 @@ extern "C" int rbr_textcnn_prod_prepare_ids(const rbr_textcnn_desc* d, int32_t n
                                             void* stream) {
     if (!err) { set_error("null err"); return RBR_ERR_BAD_ARG; }
     IdSets S;
-    if (int e = fill_id_sets(n_sets, sets, S)) return e;
-    const long long n_tok = (long long)d->n_docs * d->L;
-    const bool one = sets[0].out == ids && sets[0].n == n_tok;
-    const bool two = n_sets >= 2 && sets[0].out == ids && sets[1].out == sets[0].out + sets[0].n && sets[0].n + sets[1].n == n_tok;
-    if (!one && !two) { set_error("prod_prepare_ids: `ids` is not the clean copy of the first id set(s)"); return RBR_ERR_BAD_ARG; }
+    int n_token_sets;
+    if (int e = token_id_sets("prod_prepare_ids", d, n_sets, sets, ids, S, &n_token_sets)) return e;
     return prod_prepare(d, ids, mask, W, pidx, ws, stream, &S, err);
 }
 
@@ -1670,12 +1749,9 @@ extern "C" int rbr_textcnn_prod_prepare_ids_kept(const rbr_textcnn_desc* d, int3
     if (!err) { set_error("null err"); return RBR_ERR_BAD_ARG; }
     if (pair_region_open()) { set_error("prod_prepare_ids_kept: not inside a pair region"); return RBR_ERR_UNSUPPORTED; }
     IdSets S;
-    if (int e = fill_id_sets(n_sets, sets, S)) return e;
-    const long long n_tok = (long long)d->n_docs * d->L;
-    const bool one = sets[0].out == ids && sets[0].n == n_tok;
-    const bool two = n_sets >= 2 && sets[0].out == ids && sets[1].out == sets[0].out + sets[0].n && sets[0].n + sets[1].n == n_tok;
-    if (!one && !two) { set_error("prod_prepare_ids_kept: `ids` is not the clean copy of the first id set(s)"); return RBR_ERR_BAD_ARG; }
-    for (int s = 0; s < (one ? 1 : 2); ++s)      // a clean token id indexes the marks: it must lie inside the table
+    int n_token_sets;
+    if (int e = token_id_sets("prod_prepare_ids_kept", d, n_sets, sets, ids, S, &n_token_sets)) return e;
+    for (int s = 0; s < n_token_sets; ++s)       // a clean token id indexes the marks: it must lie inside the table
         if (S.limit[s] > d->V || S.replace[s] < 0 || S.replace[s] >= d->V) {
             set_error("prod_prepare_ids_kept: token set %d has limit %lld / replacement %lld outside the table of %d rows", s,
                       S.limit[s], S.replace[s], d->V);
@@ -1689,33 +1765,27 @@ extern "C" int rbr_textcnn_prod_list_state(const rbr_textcnn_desc* d, int64_t of
     if (!prod_applicable(d)) { set_error("token-product path does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
     ProdLayout Lo;
     if (!prod_layout(d, Lo)) return RBR_ERR_BAD_ARG;
-    off[0] = (int64_t)Lo.used; off[1] = (int64_t)align256((size_t)d->V);
-    off[2] = (int64_t)Lo.row_mask; off[3] = (int64_t)align256((size_t)Lo.cap);
+    off[0] = (int64_t)Lo.used; off[1] = (int64_t)Lo.used_bytes;
+    off[2] = (int64_t)Lo.row_mask; off[3] = (int64_t)Lo.mask_bytes;
     off[4] = (int64_t)(Lo.counter + kKeptTicket * sizeof(int)); off[5] = (int64_t)((kKeptSlabs - kKeptTicket + 1) * sizeof(int));
     return 0;
 }
 
 // ---- dense formulation's table gradient through a token list built for the purpose (no product table T: un-gated convs)
+// Its workspace: [the forward's layout up to T and ONE row of T, the zero row (prod_state's list_only view) | the backward's]
 namespace {
 constexpr size_t kListMaxG = (size_t)256 << 20;      // the list's worst-case G (min(V, positions) rows) must stay below this
-bool list_bwd_layout(const rbr_textcnn_desc* d, ProdLayout& Lo, ProdBwdLayout& B, size_t& list_bytes) {
-    if (!prod_layout(d, Lo) || !prod_bwd_layout(d, Lo, B)) return false;
-    if (B.total > kListMaxG) return false;
-    ConvPlan pp[kMaxGroups];
-    if (!build_plans(&Lo.dp, pp, kProdGroupTiles)) return false;
-    list_bytes = Lo.table_T + align256((size_t)pp[0].nslots_total * sizeof(float));      // everything but T: one (zero) row of it
-    return true;
+size_t list_part_bytes(const ProdLayout& Lo, const ProdBwdLayout& B) {      // 0: G would be too large
+    return B.total > kListMaxG ? 0 : Lo.table_T + align256((size_t)Lo.tp.nslots_total * sizeof(float));
 }
 }  // namespace
 
 extern "C" size_t rbr_textcnn_bwd_dtable_list_ws_bytes(const rbr_textcnn_desc* d) {
     ConvPlan plans[kMaxGroups];
-    if (!build_plans(d, plans)) return 0;
-    static const char* env = getenv("RBR_DTABLE_MODE");
-    if (env && !strcmp(env, "scatter")) return 0;
-    ProdLayout Lo; ProdBwdLayout B; size_t list_bytes;
-    if (!list_bwd_layout(d, Lo, B, list_bytes)) return 0;
-    return align256(list_bytes) + B.total;
+    ProdLayout Lo; ProdBwdLayout B;
+    if (!query_layouts(d, kQueryBwd, plans, Lo, B) || dtable_scatter_forced()) return 0;
+    const size_t list_bytes = list_part_bytes(Lo, B);
+    return list_bytes ? list_bytes + B.total : 0;
 }
 
 extern "C" int rbr_textcnn_bwd_dtable_list(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* const* W,
@@ -1724,30 +1794,15 @@ extern "C" int rbr_textcnn_bwd_dtable_list(const rbr_textcnn_desc* d, const int6
     ConvPlan plans[kMaxGroups];
     if (!build_plans(d, plans)) return RBR_ERR_BAD_ARG;
     if (!ids || !W || !feat || !argmax || !d_feat || !ws || !dtable) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    ProdLayout Lo; ProdBwdLayout B; size_t list_bytes;
-    if (!list_bwd_layout(d, Lo, B, list_bytes)) { set_error("token-list table gradient does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
+    ProdState S;
+    ProdBwdLayout B;
+    size_t list_bytes = 0;
+    if (prod_state(d, ws, S, true) == 0 && prod_bwd_layout(d, S.Lo, B)) list_bytes = list_part_bytes(S.Lo, B);
+    if (!list_bytes) { set_error("token-list table gradient does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
     hipStream_t st = (hipStream_t)stream;
-    char* base = static_cast<char*>(ws);
-    ConvPlan pp[kMaxGroups];
-    if (!build_plans(&Lo.dp, pp, kProdGroupTiles)) return RBR_ERR_BAD_ARG;
-    int* sched_p = reinterpret_cast<int*>(base + Lo.sched);
-    // list state: token marks, row mask, counters
-    ZeroRegions zr{{reinterpret_cast<int*>(base + Lo.used), sched_p + 2 * (size_t)pp[0].total_wt, nullptr},
-                   {(long)((Lo.row_of_token - Lo.used) / sizeof(int)), kSchedCounters, 0}};
-    if (int e = zero_regions(zr, st)) return e;
-    const long n_tok = (long)d->n_docs * d->L;
-    if (int e_ = rbr::launch<mark_scan_kernel, 256>(dim3((unsigned)std::min<long>((n_tok + 255) / 256, 2048)), dim3(256), 0, st, "textcnn mark launch", plans[0], 0, n_tok, reinterpret_cast<const long long*>(ids), mask, (int*)nullptr, reinterpret_cast<unsigned char*>(base + Lo.used))) return e_;
-    PackJob J{};
-    J.P = pp[0]; J.n_widths = d->n_widths; J.D = d->D;
-    int o = 0;
-    for (int w = 0; w < d->n_widths; ++w) { J.kz[w] = d->kz[w]; J.ch[w] = d->ch[w]; J.poff[w] = o; o += d->kz[w] * d->ch[w]; }
-    J.cp_real = o;
-    PtrArray wp{};
-    for (int w = 0; w < d->n_widths; ++w) wp.p[w] = W[w];
-    const int nb_compact = (d->V + 255) / 256;
-    const int nb_pack = (int)std::min<long>(((long)J.cp_real * d->D + 255) / 256, 2048);
-    if (int e_ = rbr::launch<compact_pack_kernel, 256>(dim3(nb_compact + nb_pack), dim3(256), 0, st, "textcnn compact launch", J, nb_compact, d->V, Lo.cap, reinterpret_cast<unsigned char*>(base + Lo.used), reinterpret_cast<int*>(base + Lo.row_of_token), reinterpret_cast<long long*>(base + Lo.tok_of_row), reinterpret_cast<unsigned char*>(base + Lo.row_mask), reinterpret_cast<int*>(base + Lo.counter), reinterpret_cast<float*>(base + Lo.table_T), pp[0].nslots_total, wp, (float*)nullptr, reinterpret_cast<float*>(base + Lo.wt), B16Pack{}, (unsigned char*)nullptr)) return e_;
-    return dtable_through_list(d, plans, ids, mask, nullptr, feat, argmax, d_feat, base, base + align256(list_bytes), dtable, nullptr, st);
+    if (int e = zero_regions(list_state_regions(S, nullptr), st)) return e;
+    if (int e = build_list(d, plans[0], S, ids, mask, W, nullptr, st)) return e;
+    return dtable_through_list(d, plans, S, S.base + list_bytes, ids, mask, nullptr, feat, argmax, d_feat, dtable, nullptr, st);
 }
 
 // Stage 2 (one kernel): T = table[tok_of_row] @ Wprod on the f32 MFMA pipe.
@@ -1757,9 +1812,8 @@ extern "C" int rbr_textcnn_prod_table(const rbr_textcnn_desc* d, const float* ta
     ProdState S;
     if (int e = prod_state(d, ws, S)) return e;
     if (prod_b16_applicable(d))
-        return prod_b16_gemm(d, S.A.cp_real, S.Lo.cap, S.A.pitch, S.counter, S.tok_of_row, table, S.base + S.Lo.bimg, S.T,
-                             S.base + S.Lo.a16, (hipStream_t)stream);
-    return run_conv_groups(S.pp, 1, S.tok_of_row, S.row_mask, nullptr, table, S.packed_p, S.T, nullptr, S.sched_p, (hipStream_t)stream);
+        return prod_b16_gemm(d, S.A.cp_real, S.Lo.cap, S.A.pitch, S.counter, S.tok_of_row, table, S.bimg, S.T, S.a16, (hipStream_t)stream);
+    return run_conv_groups(&S.Lo.tp, 1, S.tok_of_row, S.row_mask, nullptr, table, S.packed_p, S.T, nullptr, S.sched_p, (hipStream_t)stream);
 }
 
 // Stage 3 (one kernel): per active wave-tile of the real documents (work list in the tail of `pidx`, built by stage 1),
@@ -1775,28 +1829,27 @@ extern "C" int rbr_textcnn_prod_pool(const rbr_textcnn_desc* d, const int64_t* i
     if (int e = prod_state(d, ws, S)) return e;
     hipStream_t st = (hipStream_t)stream;
     const int* sched = pidx + (size_t)plans[0].total_wt * plans[0].nslots_total;      // filled by rbr_textcnn_prod_prepare
-    const int max_items = (plans[0].total_wt + kWavesPerWG - 1) / kWavesPerWG;
+    const dim3 grid((plans[0].total_wt + kWavesPerWG - 1) / kWavesPerWG), block(256);
+    const long long* tok = reinterpret_cast<const long long*>(ids);
+    const char* what = "textcnn gather_pool launch";
     if (prod_t_bf16(d))
-        { if (int e_ = rbr::launch<gather_pool_kernel<true>, 256>(dim3(max_items), dim3(256), 0, st, "textcnn gather_pool launch", plans[0], S.A, reinterpret_cast<const long long*>(ids), mask, gate, S.row_of_token, static_cast<const void*>(S.T), sched, pval, pidx)) return e_; }
-    else
-        if (int e_ = rbr::launch<gather_pool_kernel<false>, 256>(dim3(max_items), dim3(256), 0, st, "textcnn gather_pool launch", plans[0], S.A, reinterpret_cast<const long long*>(ids), mask, gate, S.row_of_token, static_cast<const void*>(S.T), sched, pval, pidx)) return e_;
-    return 0;
+        return rbr::launch<gather_pool_kernel<true>, 256>(grid, block, 0, st, what, plans[0], S.A, tok, mask, gate, S.row_of_token,
+                                                          static_cast<const void*>(S.T), sched, pval, pidx);
+    return rbr::launch<gather_pool_kernel<false>, 256>(grid, block, 0, st, what, plans[0], S.A, tok, mask, gate, S.row_of_token,
+                                                       static_cast<const void*>(S.T), sched, pval, pidx);
 }
 
 // ---- conv weight / bias gradient from G (see dw_from_g_kernel): after rbr_textcnn_bwd_dtable_prod_ex built G in `bwd_ws`
 static bool dw_from_g_applicable(const rbr_textcnn_desc* d) {
     // the shapes the document-centric dW kernel serves (textcnn_bwd.hip): many short documents
-    long cp = 0;
-    for (int w = 0; w < d->n_widths; ++w) cp += (long)d->kz[w] * d->ch[w];
-    return prod_applicable(d) && d->D % 4 == 0 && d->L <= 128 && d->n_docs >= 512 && cp <= 2048;
+    return prod_applicable(d) && d->D % 4 == 0 && d->L <= 128 && d->n_docs >= 512 && prod_channels(d).cp_real <= 2048;
 }
 
 extern "C" size_t rbr_textcnn_bwd_dw_from_g_ws_floats(const rbr_textcnn_desc* d) {
     ConvPlan plans[kMaxGroups];
-    if (!build_plans(d, plans) || !dw_from_g_applicable(d)) return 0;
     ProdLayout Lo; ProdBwdLayout B;
-    if (!prod_layout(d, Lo) || !prod_bwd_layout(d, Lo, B)) return 0;
-    return (size_t)kDwgSplit * B.KG * d->D + (size_t)kDbChunks * plans[0].C;
+    if (!query_layouts(d, kQueryProduct | kQueryBwd, plans, Lo, B) || !dw_from_g_applicable(d)) return 0;
+    return (size_t)kDwgSplit * Lo.ch.KG() * d->D + (size_t)kDbChunks * plans[0].C;
 }
 
 extern "C" int rbr_textcnn_bwd_dw_from_g(const rbr_textcnn_desc* d, const float* table, const float* feat, const float* d_feat,
@@ -1805,74 +1858,62 @@ extern "C" int rbr_textcnn_bwd_dw_from_g(const rbr_textcnn_desc* d, const float*
     if (!build_plans(d, plans)) return RBR_ERR_BAD_ARG;
     if (!dw_from_g_applicable(d)) { set_error("dW-from-G does not apply to this shape"); return RBR_ERR_UNSUPPORTED; }
     if (!table || !feat || !d_feat || !fwd_ws || !bwd_ws || !dW || !dbias || !ws) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    ProdLayout Lo; ProdBwdLayout B;
-    if (!prod_layout(d, Lo) || !prod_bwd_layout(d, Lo, B)) return RBR_ERR_BAD_ARG;
+    ProdState S;
+    ProdBwdLayout B;
+    if (prod_state(d, fwd_ws, S) || !prod_bwd_layout(d, S.Lo, B)) return RBR_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
-    char* fbase = static_cast<char*>(fwd_ws);
-    const long long* tok_of_row = reinterpret_cast<const long long*>(fbase + Lo.tok_of_row);
-    const int* counter = reinterpret_cast<const int*>(fbase + Lo.counter);
+    const int KG = S.Lo.ch.KG(), cp_real = S.Lo.ch.cp_real, cap = S.Lo.cap, D = d->D;
     const float* G = reinterpret_cast<const float*>(static_cast<char*>(bwd_ws) + B.G);
-    ProdBwdArgs A{};
-    A.n_docs = d->n_docs; A.L = d->L; A.C = plans[0].C; A.KF = plans[0].KF; A.KG = B.KG; A.D = d->D; A.cap = Lo.cap;
-    A.act = d->act; A.n_widths = d->n_widths;
-    int cp_real = 0;
-    for (int w = 0; w < d->n_widths; ++w) {
-        A.kz[w] = d->kz[w]; A.ch[w] = d->ch[w]; A.ch_off[w] = plans[0].ch_off[w];
-        A.poff[w] = cp_real; cp_real += d->kz[w] * d->ch[w];
-    }
+    const ProdBwdArgs A = make_bwd_args(d, plans[0], S.Lo.ch, cap);
     float* part = ws;
-    float* part_b = ws + (size_t)kDwgSplit * B.KG * d->D;
+    float* part_b = ws + (size_t)kDwgSplit * KG * D;
     static const bool f32_form = getenv("RBR_DW_FROM_G_F32") != nullptr && atoi(getenv("RBR_DW_FROM_G_F32")) != 0;
     // z slices beyond the K splits: one workgroup per (channel block, document chunk) of the bias gradient's partial sums
-    const int tile_wgs = ((B.KG + 63) / 64) * ((d->D + 63) / 64);
+    const int tile_wgs = ((KG + 63) / 64) * ((D + 63) / 64);
     const int db_slices = (((A.C + 255) / 256) * kDbChunks + tile_wgs - 1) / tile_wgs;
+    const dim3 tiles((KG + 63) / 64, (D + 63) / 64, kDwgSplit), tiles_db((KG + 63) / 64, (D + 63) / 64, kDwgSplit + db_slices);
     if (f32_form)
-        hipLaunchKernelGGL(dw_from_g_kernel, dim3((B.KG + 63) / 64, (d->D + 63) / 64, kDwgSplit), dim3(256), 0, st, B.KG, d->D, Lo.cap,
-                           counter, G, tok_of_row, table, part);
+        hipLaunchKernelGGL(dw_from_g_kernel, tiles, dim3(256), 0, st, KG, D, cap, S.counter, G, S.tok_of_row, table, part);
     else      // (the bias gradient's partials in the same launch: one z slice more)
         if (prod_precision_of(d) == RBR_PROD_BF16)      // the bf16 class: one plane product of operands rounded to bf16
-            hipLaunchKernelGGL(dw_from_g_b16_kernel<1>, dim3((B.KG + 63) / 64, (d->D + 63) / 64, kDwgSplit + db_slices), dim3(256), 0, st, B.KG, d->D, Lo.cap,
-                               counter, G, tok_of_row, table, part, d->n_docs, A.C, d->act, feat, d_feat, part_b);
+            hipLaunchKernelGGL(dw_from_g_b16_kernel<1>, tiles_db, dim3(256), 0, st, KG, D, cap, S.counter, G, S.tok_of_row, table, part,
+                               d->n_docs, A.C, d->act, feat, d_feat, part_b);
         else
-            hipLaunchKernelGGL(dw_from_g_b16_kernel<3>, dim3((B.KG + 63) / 64, (d->D + 63) / 64, kDwgSplit + db_slices), dim3(256), 0, st, B.KG, d->D, Lo.cap,
-                               counter, G, tok_of_row, table, part, d->n_docs, A.C, d->act, feat, d_feat, part_b);
+            hipLaunchKernelGGL(dw_from_g_b16_kernel<3>, tiles_db, dim3(256), 0, st, KG, D, cap, S.counter, G, S.tok_of_row, table, part,
+                               d->n_docs, A.C, d->act, feat, d_feat, part_b);
     RBR_CHECK_LAUNCH("textcnn dw_from_g launch");
     if (f32_form) {
         hipLaunchKernelGGL(dbias_partial_kernel, dim3((A.C + 255) / 256, kDbChunks), dim3(256), 0, st, d->n_docs, A.C, d->act, feat, d_feat,
                            part_b);
         RBR_CHECK_LAUNCH("textcnn dbias partial launch");
     }
-    MutPtrArray dWp{}, dbp{};
-    for (int w = 0; w < d->n_widths; ++w) { dWp.p[w] = dW[w]; dbp.p[w] = dbias[w]; }
-    const long total = (long)cp_real * d->D + A.C;
+    const long total = (long)cp_real * D + A.C;
     hipLaunchKernelGGL(dw_from_g_reduce_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, st, A, cp_real,
-                       part, part_b, dWp, dbp);
+                       part, part_b, ptr_array<MutPtrArray>(dW, d->n_widths), ptr_array<MutPtrArray>(dbias, d->n_widths));
     RBR_CHECK_LAUNCH("textcnn dw_from_g reduce launch");
     return 0;
 }
 
 // ---- data-parallel tap exchange (see taps_kernel): taps of one rank, and the averaged table gradient from all ranks' taps
 namespace {
-bool taps_args(const rbr_textcnn_desc* d, ProdBwdArgs& A, int& cp_real, int& KG) {
+bool taps_args(const rbr_textcnn_desc* d, ProdBwdArgs& A, ProdChannels& c) {      // (A.cap: the rebuild sets its rows)
     ConvPlan plans[kMaxGroups];
     if (!build_plans(d, plans)) return false;
-    memset(&A, 0, sizeof(A));
-    A.n_docs = d->n_docs; A.L = d->L; A.C = plans[0].C; A.KF = plans[0].KF; A.D = d->D;
-    A.padding_idx = d->padding_idx; A.pad_mode = d->pad_mode; A.act = d->act; A.n_widths = d->n_widths;
-    cp_real = 0;
-    for (int w = 0; w < d->n_widths; ++w) {
-        A.kz[w] = d->kz[w]; A.ch[w] = d->ch[w]; A.ch_off[w] = plans[0].ch_off[w];
-        A.poff[w] = cp_real; cp_real += d->kz[w] * d->ch[w];
-    }
-    KG = (cp_real + 3) / 4 * 4;
-    A.KG = KG;
+    c = prod_channels(d);
+    A = make_bwd_args(d, plans[0], c, 0, 0, kArgsTaps);
     return true;
 }
-struct TapsLayout { size_t keys_in, keys, pay_in, pay, start1, end, hot_count, hot_list, split_arrived, split_rows, WT, blk_cnt, temp, total; size_t temp_bytes; int KGW, max_split; };
-bool taps_layout(const rbr_textcnn_desc* d, int n_sets, long n_items, int cp_real, int KG, TapsLayout& T) {
+// dynamic LDS of taps_rows_kernel: a row of 64-bit fixed-point cells in front of the sparse product's lists and partial rows
+size_t taps_rows_lds(const ProdChannels& c, int D) { return (size_t)c.KG() * 8 + sparse_product_lds(c, D); }
+struct TapsLayout {
+    size_t keys_in, keys, pay_in, pay, start1, end, hot_count, hot_list, split_arrived, split_rows, WT, blk_cnt, temp, total;
+    size_t temp_bytes;
+    int max_split;
+};
+bool taps_layout(const rbr_textcnn_desc* d, int n_sets, long n_items, const ProdChannels& c, TapsLayout& T) {
     if (d->D % 4 != 0 || n_sets <= 0) return false;
-    T.KGW = ((KG / 4 + kWavesPerWG - 1) / kWavesPerWG) * 4;
-    if ((size_t)KG * 8 + (size_t)T.KGW * 8 * kWavesPerWG + (size_t)kWavesPerWG * d->D * 4 > 64 * 1024) return false;
+    if (taps_rows_lds(c, d->D) > 64 * 1024) return false;
+    const int KG = c.KG(), cp_real = c.cp_real;
     const size_t total = (size_t)n_items * n_sets;
     if (total >= (size_t)1 << 31) return false;
     T.temp_bytes = 0;
@@ -1887,8 +1928,8 @@ bool taps_layout(const rbr_textcnn_desc* d, int n_sets, long n_items, int cp_rea
     T.end = o;     o += align256((size_t)d->V * sizeof(int));
     T.hot_count = o; o += 256;
     T.max_split = (int)(total / kTapsSplit) + 1;                 // tokens with more than kTapsSplit taps
-    T.hot_list = o; o += align256(((size_t)d->V + 2 * (size_t)T.max_split) * sizeof(int4));     // parts: at most cnt / kTapsSplit + 1 per token
-    T.split_arrived = o; o += align256((size_t)T.max_split * 2 * sizeof(int));                  // contiguous with split_rows: zeroed together
+    T.hot_list = o; o += align256(((size_t)d->V + 2 * (size_t)T.max_split) * sizeof(int4));     // parts: <= cnt / kTapsSplit + 1 per token
+    T.split_arrived = o; o += align256((size_t)T.max_split * 2 * sizeof(int));                  // contiguous with split_rows: zeroed as one
     T.split_rows = o; o += align256((size_t)T.max_split * KG * sizeof(unsigned long long));
     T.WT = o;      o += align256((size_t)cp_real * d->D * sizeof(float));
     T.blk_cnt = o; o += align256((size_t)(kOwnChunks + 64) * sizeof(int));      // owner partition: chunk counts, then the overflow flag
@@ -1899,15 +1940,15 @@ bool taps_layout(const rbr_textcnn_desc* d, int n_sets, long n_items, int cp_rea
 }  // namespace
 
 extern "C" size_t rbr_textcnn_taps_count(const rbr_textcnn_desc* d) {
-    ProdBwdArgs A; int cp, KG;
-    if (!taps_args(d, A, cp, KG)) return 0;
+    ProdBwdArgs A; ProdChannels c;
+    if (!taps_args(d, A, c)) return 0;
     return (size_t)A.n_docs * A.C * A.KF;
 }
 
 extern "C" int rbr_textcnn_bwd_taps(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* feat,
                                     const int32_t* argmax, const float* d_feat, int32_t* tok, float* val, void* stream) {
-    ProdBwdArgs A; int cp, KG;
-    if (!taps_args(d, A, cp, KG)) return RBR_ERR_BAD_ARG;
+    ProdBwdArgs A; ProdChannels c;
+    if (!taps_args(d, A, c)) return RBR_ERR_BAD_ARG;
     if (!ids || !feat || !argmax || !d_feat || !tok || !val) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
     const long n = (long)A.n_docs * A.C * A.KF;
     hipLaunchKernelGGL(taps_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A,
@@ -1917,8 +1958,8 @@ extern "C" int rbr_textcnn_bwd_taps(const rbr_textcnn_desc* d, const int64_t* id
 }
 
 extern "C" size_t rbr_textcnn_dtable_from_taps_ws_bytes(const rbr_textcnn_desc* d, int32_t n_sets) {
-    ProdBwdArgs A; int cp, KG; TapsLayout T;
-    if (!taps_args(d, A, cp, KG) || !taps_layout(d, n_sets, (long)A.n_docs * A.C * A.KF, cp, KG, T)) return 0;
+    ProdBwdArgs A; ProdChannels c; TapsLayout T;
+    if (!taps_args(d, A, c) || !taps_layout(d, n_sets, (long)A.n_docs * A.C * A.KF, c, T)) return 0;
     return T.total;
 }
 
@@ -1927,13 +1968,16 @@ namespace {
 // out [ceil(V / n_sets), D] (row t / n_sets), `overflow` set when the rank's taps exceed the bound the sort is sized for.
 int taps_rebuild(const rbr_textcnn_desc* d, int n_sets, int own_rank, const int32_t* tok, const float* val, const float* const* W,
                  void* ws, float* out, int32_t* overflow, hipStream_t st) {
-    ProdBwdArgs A; int cp_real, KG; TapsLayout T;
-    if (!taps_args(d, A, cp_real, KG)) return RBR_ERR_BAD_ARG;
+    ProdBwdArgs A; ProdChannels c; TapsLayout T;
+    if (!taps_args(d, A, c)) return RBR_ERR_BAD_ARG;
     const long n_items = (long)A.n_docs * A.C * A.KF;
-    if (!taps_layout(d, n_sets, n_items, cp_real, KG, T)) { set_error("tap exchange does not support this shape"); return RBR_ERR_UNSUPPORTED; }
+    if (!taps_layout(d, n_sets, n_items, c, T)) { set_error("tap exchange does not support this shape"); return RBR_ERR_UNSUPPORTED; }
     if (!tok || !val || !W || !ws || !out) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
     const bool own = own_rank >= 0;
-    if (own && (own_rank >= n_sets || !overflow)) { set_error("taps owner rebuild: rank %d of %d, overflow flag %p", own_rank, n_sets, (void*)overflow); return RBR_ERR_BAD_ARG; }
+    if (own && (own_rank >= n_sets || !overflow)) {
+        set_error("taps owner rebuild: rank %d of %d, overflow flag %p", own_rank, n_sets, (void*)overflow);
+        return RBR_ERR_BAD_ARG;
+    }
     char* base = static_cast<char*>(ws);
     int* keys_in = reinterpret_cast<int*>(base + T.keys_in);
     int* keys = reinterpret_cast<int*>(base + T.keys);
@@ -1954,8 +1998,8 @@ int taps_rebuild(const rbr_textcnn_desc* d, int n_sets, int own_rank, const int3
                            blk_cnt, keys_in, pay_in, overflow);
         RBR_CHECK_LAUNCH("textcnn taps owner keys launch");
     } else {
-        hipLaunchKernelGGL(taps_keys_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st, A, n_items, n_sets,
-                           d->V, tok, val, keys_in, pay_in);
+        hipLaunchKernelGGL(taps_keys_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 8192)), dim3(256), 0, st, A, n_items,
+                           n_sets, d->V, tok, val, keys_in, pay_in);
         RBR_CHECK_LAUNCH("textcnn taps keys launch");
     }
     int bits = 1;
@@ -1976,18 +2020,13 @@ int taps_rebuild(const rbr_textcnn_desc* d, int n_sets, int own_rank, const int3
     hipLaunchKernelGGL(taps_bounds_kernel, dim3((unsigned)std::min<long>((n_sort + 255) / 256, 8192)), dim3(256), 0, st, n_sort, Vloc, keys,
                        start1, end);
     RBR_CHECK_LAUNCH("textcnn taps bounds launch");
-    PackJob J{};
-    J.n_widths = d->n_widths; J.D = d->D; J.cp_real = cp_real;
-    for (int w = 0; w < d->n_widths; ++w) { J.kz[w] = d->kz[w]; J.ch[w] = d->ch[w]; J.poff[w] = A.poff[w]; }
-    PtrArray wp{};
-    for (int w = 0; w < d->n_widths; ++w) wp.p[w] = W[w];
-    hipLaunchKernelGGL(taps_wt_kernel, dim3((unsigned)std::min<long>(((long)cp_real * d->D + 255) / 256, 1024)), dim3(256), 0, st, J, wp, WT,
-                       Vloc, start1, end, hot_count, hot_list);
+    hipLaunchKernelGGL(taps_wt_kernel, dim3((unsigned)std::min<long>(((long)c.cp_real * d->D + 255) / 256, 1024)), dim3(256), 0, st,
+                       make_pack_job(d, c, nullptr), ptr_array<PtrArray>(W, d->n_widths), WT, Vloc, start1, end, hot_count, hot_list);
     RBR_CHECK_LAUNCH("textcnn taps weights launch");
-    const size_t lds = (size_t)KG * 8 + (size_t)T.KGW * 8 * kWavesPerWG + (size_t)kWavesPerWG * d->D * sizeof(float);
+    const size_t lds = taps_rows_lds(c, d->D);
     const int n_row_wgs = std::min(Vloc, 8192), n_cold_wgs = (Vloc + kWavesPerWG - 1) / kWavesPerWG;
-    hipLaunchKernelGGL(taps_rows_kernel, dim3((unsigned)(n_row_wgs + n_cold_wgs)), dim3(256), lds, st, A, T.KGW, Vloc, hot_count, hot_list,
-                       start1, end, pay, 1.f / (kTapScale * (float)n_sets), WT, out, split_rows, split_arrived, n_row_wgs);
+    hipLaunchKernelGGL(taps_rows_kernel, dim3((unsigned)(n_row_wgs + n_cold_wgs)), dim3(256), lds, st, A, c.KGW(), Vloc, hot_count,
+                       hot_list, start1, end, pay, 1.f / (kTapScale * (float)n_sets), WT, out, split_rows, split_arrived, n_row_wgs);
     RBR_CHECK_LAUNCH("textcnn taps rows launch");
     return 0;
 }

@@ -47,6 +47,90 @@ def test_plan_queries_and_error_reporting_without_gpu():
         _lib.check(-1, "demo")
 
 
+# name -> make_desc arguments (n_docs, L, D, V, kz, ch, pad_mode, act, padding_idx, flags) of test_token_product_plan_queries_are_pinned
+def _plan_query_shapes(_lib):
+    same, relu = _lib.PAD_SAME, _lib.ACT_RELU
+    return {
+        "prepare_small": (2, 33, 8, 257, [3, 5], [5, 6], same, relu, 0, 0),                  # the shape of the prepare tests
+        "v_above_positions": (5, 64, 8, 1000, [3, 5], [5, 6], same, relu, 0, 0),             # cap = the position count
+        "datt_like": (48, 160, 100, 900, [1, 2, 3, 4], [56, 24, 24, 24], _lib.PAD_VALID, _lib.ACT_TANH, 0, _lib.conv_gate_split(1)),
+        "short_docs": (600, 40, 32, 700, [3], [20], same, relu, 0, 0),                        # n_docs >= 512, L <= 128: dW from G
+        "d_not_x4": (600, 40, 6, 700, [3], [20], same, relu, 0, 0),                           # D % 4 != 0: no list backward
+        "cfg2": (512, 512, 300, 50002, [3, 5, 7], [50, 50, 50], same, relu, 0, 0),            # the auto mode's real case
+    }
+
+
+# (shape, rbr_set_conv_mode, product precision) -> (fwd_ws_bytes, bwd_prod_ws_bytes, bwd_dtable_list_ws_bytes, bwd_dw_from_g_ws_floats,
+# row_grad_partials, taps_count, dtable_from_taps_ws_bytes for 1 and for 4 sets, taps_owner_rows for 4 sets, the return code of
+# prod_list_state and its six numbers), recorded from the library before the host code of textcnn_prod.hip was restated.
+_PLAN_QUERIES = {
+    ('prepare_small', 0, 'f32'): (0, 0, 23040, 0, 0, 110, 21504, 29184, 65, -2, None),
+    ('prepare_small', 0, None): (0, 0, 40704, 0, 0, 110, 21504, 29184, 65, -2, None),
+    ('prepare_small', 1, 'f32'): (0, 0, 23040, 0, 0, 110, 21504, 29184, 65, -2, None),
+    ('prepare_small', 1, None): (0, 0, 40704, 0, 0, 110, 21504, 29184, 65, -2, None),
+    ('prepare_small', 2, 'f32'): (27392, 12800, 23040, 0, 66, 110, 21504, 29184, 65, 0, (0, 512, 512, 256, 3088, 8)),
+    ('prepare_small', 2, None): (61952, 12800, 40704, 0, 66, 110, 21504, 29184, 65, 0, (0, 512, 512, 256, 3088, 8)),
+    ('v_above_positions', 0, 'f32'): (0, 0, 77056, 0, 0, 275, 43008, 62720, 250, -2, None),
+    ('v_above_positions', 0, None): (0, 0, 94720, 0, 0, 275, 43008, 62720, 250, -2, None),
+    ('v_above_positions', 1, 'f32'): (0, 0, 77056, 0, 0, 275, 43008, 62720, 250, -2, None),
+    ('v_above_positions', 1, None): (0, 0, 94720, 0, 0, 275, 43008, 62720, 250, -2, None),
+    ('v_above_positions', 2, 'f32'): (97792, 61440, 77056, 0, 320, 275, 43008, 62720, 250, 0, (0, 1024, 1024, 512, 8520, 8)),
+    ('v_above_positions', 2, None): (197376, 61440, 94720, 0, 320, 275, 43008, 62720, 250, 0, (0, 1024, 1024, 512, 8520, 8)),
+    ('datt_like', 0, 'f32'): (2181120, 979200, 1316864, 0, 900, 24576, 745728, 2554880, 225, 0, (0, 1024, 1024, 1024, 13792, 8)),
+    ('datt_like', 0, None): (1924608, 979200, 1521152, 0, 900, 24576, 745728, 2554880, 225, 0, (0, 1024, 1024, 1024, 13792, 8)),
+    ('datt_like', 1, 'f32'): (0, 0, 1316864, 0, 0, 24576, 745728, 2554880, 225, -2, None),
+    ('datt_like', 1, None): (0, 0, 1521152, 0, 0, 24576, 745728, 2554880, 225, -2, None),
+    ('datt_like', 2, 'f32'): (2181120, 979200, 1316864, 0, 900, 24576, 745728, 2554880, 225, 0, (0, 1024, 1024, 1024, 13792, 8)),
+    ('datt_like', 2, None): (1924608, 979200, 1521152, 0, 900, 24576, 745728, 2554880, 225, 0, (0, 1024, 1024, 1024, 13792, 8)),
+    ('short_docs', 0, 'f32'): (208128, 217344, 246016, 66560, 8, 36000, 902656, 3508736, 175, 0, (0, 768, 768, 768, 10408, 8)),
+    ('short_docs', 0, None): (422400, 217344, 281088, 66560, 8, 36000, 902656, 3508736, 175, 0, (0, 768, 768, 768, 10408, 8)),
+    ('short_docs', 1, 'f32'): (0, 0, 246016, 0, 0, 36000, 902656, 3508736, 175, -2, None),
+    ('short_docs', 1, None): (0, 0, 281088, 0, 0, 36000, 902656, 3508736, 175, -2, None),
+    ('short_docs', 2, 'f32'): (208128, 217344, 246016, 66560, 8, 36000, 902656, 3508736, 175, 0, (0, 768, 768, 768, 10408, 8)),
+    ('short_docs', 2, None): (422400, 217344, 281088, 66560, 8, 36000, 902656, 3508736, 175, 0, (0, 768, 768, 768, 10408, 8)),
+    ('d_not_x4', 0, 'f32'): (196864, 0, 0, 0, 700, 36000, 0, 0, 175, 0, (0, 768, 768, 768, 10408, 8)),
+    ('d_not_x4', 0, None): (196864, 0, 0, 0, 700, 36000, 0, 0, 175, 0, (0, 768, 768, 768, 10408, 8)),
+    ('d_not_x4', 1, 'f32'): (0, 0, 0, 0, 0, 36000, 0, 0, 175, -2, None),
+    ('d_not_x4', 1, None): (0, 0, 0, 0, 0, 36000, 0, 0, 175, -2, None),
+    ('d_not_x4', 2, 'f32'): (196864, 0, 0, 0, 700, 36000, 0, 0, 175, 0, (0, 768, 768, 768, 10408, 8)),
+    ('d_not_x4', 2, None): (196864, 0, 0, 0, 700, 36000, 0, 0, 175, 0, (0, 768, 768, 768, 10408, 8)),
+    ('cfg2', 0, 'f32'): (156144640, 150406144, 152944384, 0, 8192, 537600, 15811584, 56904704, 12501, 0, (0, 50176, 50176, 50176, 713424, 8)),
+    ('cfg2', 0, None): (157545472, 150406144, 154345216, 0, 8192, 537600, 15811584, 56904704, 12501, 0, (0, 50176, 50176, 50176, 713424, 8)),
+    ('cfg2', 1, 'f32'): (0, 0, 152944384, 0, 0, 537600, 15811584, 56904704, 12501, -2, None),
+    ('cfg2', 1, None): (0, 0, 154345216, 0, 0, 537600, 15811584, 56904704, 12501, -2, None),
+    ('cfg2', 2, 'f32'): (156144640, 150406144, 152944384, 0, 8192, 537600, 15811584, 56904704, 12501, 0, (0, 50176, 50176, 50176, 713424, 8)),
+    ('cfg2', 2, None): (157545472, 150406144, 154345216, 0, 8192, 537600, 15811584, 56904704, 12501, 0, (0, 50176, 50176, 50176, 713424, 8)),
+}
+
+
+def test_token_product_plan_queries_are_pinned():
+    """Every size / layout query the token-product host code answers, over a small grid of descriptors, conv modes and product
+    precisions: the workspaces of callers are sized by these, so a restatement of the host code must not move one byte."""
+    from review_based_recommender_amd import _lib
+    L = _lib.lib()
+    shapes = _plan_query_shapes(_lib)
+    got = {}
+    try:
+        for (name, mode, prec) in _PLAN_QUERIES:
+            L.rbr_set_conv_mode(mode)
+            L.rbr_set_prod_precision(-1 if prec is None else _lib.PROD_PRECISIONS[prec])
+            d = _lib.make_desc(*shapes[name])
+            r = C.byref(d)
+            off = (C.c_int64 * 6)(*([-1] * 6))
+            rc = L.rbr_textcnn_prod_list_state(r, off)
+            got[(name, mode, prec)] = (
+                L.rbr_textcnn_fwd_ws_bytes(r), L.rbr_textcnn_bwd_prod_ws_bytes(r), L.rbr_textcnn_bwd_dtable_list_ws_bytes(r),
+                L.rbr_textcnn_bwd_dw_from_g_ws_floats(r), L.rbr_textcnn_row_grad_partials(r), L.rbr_textcnn_taps_count(r),
+                L.rbr_textcnn_dtable_from_taps_ws_bytes(r, 1), L.rbr_textcnn_dtable_from_taps_ws_bytes(r, 4),
+                L.rbr_textcnn_taps_owner_rows(r, 4), rc, tuple(off) if rc == 0 else None)
+    finally:
+        L.rbr_set_conv_mode(0)
+        L.rbr_set_prod_precision(-1)
+    wrong = {k: (v, _PLAN_QUERIES[k]) for k, v in got.items() if v != _PLAN_QUERIES[k]}
+    assert not wrong, wrong
+    assert len(got) == 6 * 3 * 2
+
+
 def test_product_refuses_cpu_tensors():
     from review_based_recommender_amd import functional as RF
     cfg = synth.DEEPCONN_CFGS["tiny"]

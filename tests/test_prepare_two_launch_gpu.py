@@ -5,7 +5,10 @@ Equal as integers: row_of_token, tok_of_row[:count], count, the row mask, the cl
 list as a sorted set with its count; equal bits: pooled features and argmax of the forward that follows.
 
 Shapes: V = 257 and 1000 (no multiple of 256 or 16), n_docs x L = 2 x 33 (66 tokens: fewer than one block, a partial second
-slab) and 5 x 64 (320: more than one block).  The three-launch reference runs on a workspace filled with 0xAB bytes."""
+slab) and 5 x 64 (320: more than one block).  The three-launch reference runs on a workspace filled with 0xAB bytes.
+
+The plain chain (rbr_textcnn_prod_prepare: no id sets; its mark and compaction launches are the list backward's too) is compared
+with the three-launch ids chain in the same way, on the clean ids that chain produced."""
 import ctypes as C
 import functools
 import os
@@ -66,10 +69,12 @@ def _params(V):
     return table, ws, bs
 
 
-def _forward(V, ids_raw, mask, kept, prod_ws=None, static=None):
+def _forward(V, ids_raw, mask, kept, prod_ws=None, static=None, clean_from=None):
     """prepare -> table -> pool -> finalize through functional's stage sequence; everything the comparison reads, as host
     tensors.  kept: a workspace from functional's kept workspaces (or `prod_ws`, a tensor carrying one) and the two-launch
-    stage; else a 0xAB-filled workspace and the three-launch stage.  static: (raw, extra, mask) device buffers to use."""
+    stage; else a 0xAB-filled workspace and the three-launch stage.  static: (raw, extra, mask) device buffers to use.
+    clean_from: the clean ids of an earlier call -- the PLAIN chain (rbr_textcnn_prod_prepare: no id sets, no range check)
+    runs on them, on a 0xAB-filled workspace."""
     from review_based_recommender_amd import _lib, functional as RF
     L_ = _lib.lib()
     dev = torch.device(DEV)
@@ -98,7 +103,11 @@ def _forward(V, ids_raw, mask, kept, prod_ws=None, static=None):
         rec.prod_ws.fill_(0xAB)
         rec.pidx.fill_(-5)
     st = _lib.current_stream()
-    RF._prod_forward(desc, rec, table, ids, mask8, None, ws, st, id_sets=(2, arr, err.data_ptr()))
+    if clean_from is not None:
+        assert not kept
+        ids = clean_from[:raw.numel()].view(n_docs, L)
+    id_sets = None if clean_from is not None else (2, arr, err.data_ptr())
+    RF._prod_forward(desc, rec, table, ids, mask8, None, ws, st, id_sets=id_sets)
     RF._pool_finalize(desc, rec, bs, st)
     out = _Rec()
     out.rec, out.desc, out.clean, out.err = rec, desc, clean, err
@@ -174,6 +183,26 @@ def test_two_launches_equal_three(V, n_docs, L, case):
     else:
         assert int(rn["err"][0]) == 3
     assert int(rn["row_mask"].sum()) == rn["count"] and int(rn["row_mask"][:rn["count"]].sum()) == rn["count"]
+
+
+@pytest.mark.parametrize("case", ("distinct", "one_token", "all_masked", "no_mask"))
+@pytest.mark.parametrize("V,n_docs,L", SHAPES)
+def test_plain_chain_equals_ids_chain(V, n_docs, L, case):
+    """The plain chain (rbr_textcnn_prod_prepare, no id sets: zero | mark + scan | compact + pack -- the launches it shares with
+    the list backward) on the clean ids that the three-launch ids chain produced, both on 0xAB-filled workspaces: the same list,
+    work list and forward, integer for integer.  `clean` and `err` are not compared: the plain chain produces neither."""
+    ids, mask = _case(case, V, n_docs, L)
+    ref = _forward(V, ids, mask, kept=False)
+    torch.cuda.synchronize()
+    plain = _forward(V, ids, mask, kept=False, clean_from=ref.clean)
+    torch.cuda.synchronize()
+    rr, _ = _read(ref, V)
+    rp, _ = _read(plain, V)
+    assert torch.equal(rr["clean"][:n_docs * L], ids.view(-1)), "the case's ids are clean: the chains saw the same tokens"
+    for r in (rr, rp):
+        del r["clean"], r["err"]
+    _equal(rp, rr, case)
+    assert rp["count"] == {"distinct": min(n_docs * L, V), "one_token": 1, "all_masked": 0}.get(case, rp["count"])
 
 
 @pytest.mark.parametrize("V,n_docs,L", SHAPES)
