@@ -588,6 +588,11 @@ int rbr_datt_global_gate_bwd(int32_t B, int32_t L, int32_t E, const int64_t* ids
  * are not read and may be NULL). */
 size_t rbr_datt_token_rows_ws_bytes(int32_t B, int32_t L, int32_t V);
 int rbr_datt_token_rows(int32_t B, int32_t L, int32_t V, const int64_t* ids, void* rows, void* stream);
+/* Where rbr_datt_token_rows left the maps inside `rows` (the layout is private; the twin of rbr_textcnn_token_list): device
+ * addresses of row_of_token [V] (dense row or -1), of the count of rows and of tok_of_row [cap]; cap = min(V, B * L).  Any
+ * out-pointer may be NULL. */
+int rbr_datt_token_rows_maps(int32_t B, int32_t L, int32_t V, const void* rows, const int32_t** row_of_token,
+                             const int32_t** n_rows, const int32_t** tok_of_row, int32_t* cap);
 size_t rbr_datt_global_gate_bwd_rows_ws_floats(int32_t B, int32_t L, int32_t E, int32_t V);
 int rbr_datt_global_gate_bwd_rows(int32_t B, int32_t L, int32_t E, int32_t V, const int64_t* ids, const float* table,
                                   const float* w, const float* gate, const float* dgate, int32_t pad_idx, float* dw,

@@ -209,6 +209,7 @@ SIGNATURES = {
                                            c_f32p, c_f32p, c_f32p, c_stream]),
     "rbr_datt_token_rows_ws_bytes": (C.c_size_t, [i32, i32, i32]),
     "rbr_datt_token_rows": (C.c_int, [i32, i32, i32, c_i64p, C.c_void_p, c_stream]),
+    "rbr_datt_token_rows_maps": (C.c_int, [i32, i32, i32, C.c_void_p, _PP, _PP, _PP, C.POINTER(i32)]),
     "rbr_datt_global_gate_bwd_rows_ws_floats": (C.c_size_t, [i32, i32, i32, i32]),
     "rbr_datt_global_gate_bwd_rows": (C.c_int, [i32, i32, i32, i32, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, i32, c_f32p,
                                                 c_f32p, c_f32p, c_f32p, C.c_void_p, i32, c_stream]),

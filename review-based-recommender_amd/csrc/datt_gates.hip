@@ -428,14 +428,12 @@ __device__ __forceinline__ void gp_mark_kernel(long n, const long long* __restri
 // gp_count_kernel leaves the used tokens of every 256 vocabulary entries, gp_compact_kernel's workgroup adds up those before it:
 // nblk^2 / 2 reads of L2-resident ints over the grid (nblk = V / 256: 20 k reads at the 50 k vocabularies of the configs, 8 M at
 // V = 1 M -- a vocabulary of that size wants a scan of the block counts first).  The last workgroup writes the row counter.
+// The ranking inside a block is block_rank_256 (rbr_wave.h), shared with the conv's compact_block (textcnn_prod.hip).
 __device__ __forceinline__ void gp_count_kernel(int V, const int* __restrict__ used, int* __restrict__ blk_count) {
     __shared__ int s_n[4];
     const int v = blockIdx.x * 256 + threadIdx.x;
-    const int u = (v < V) ? used[v] : 0;
-    const unsigned long long b = __ballot(u);
-    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = __popcll(b);
-    __syncthreads();
-    if (threadIdx.x == 0) blk_count[blockIdx.x] = s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    const BlockRank r = block_rank_256((v < V) ? used[v] : 0, s_n);
+    if (threadIdx.x == 0) blk_count[blockIdx.x] = r.total;
 }
 
 __device__ __forceinline__ void gp_compact_kernel(int V, int cap, const int* __restrict__ used, const int* __restrict__ blk_count,
@@ -443,26 +441,23 @@ __device__ __forceinline__ void gp_compact_kernel(int V, int cap, const int* __r
                                                          int* __restrict__ counter) {
     __shared__ int s_red[256];
     __shared__ int s_n[4];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int v = blockIdx.x * 256 + tid;
     const int u = (v < V) ? used[v] : 0;
-    const unsigned long long b = __ballot(u);
     int part = 0;
     for (int k = tid; k < (int)blockIdx.x; k += 256) part += blk_count[k];
     s_red[tid] = part;
-    if (lane == 0) s_n[wave] = __popcll(b);
-    __syncthreads();
+    const BlockRank r = block_rank_256(u, s_n);      // its barrier publishes s_red too
     for (int o = 128; o > 0; o >>= 1) {
         if (tid < o) s_red[tid] += s_red[tid + o];
         __syncthreads();
     }
-    int base = s_red[0];
-    for (int w2 = 0; w2 < wave; ++w2) base += s_n[w2];
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) *counter = s_red[0] + s_n[0] + s_n[1] + s_n[2] + s_n[3];
+    const int base = s_red[0];                                          // used tokens below the block
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) *counter = base + r.total;
     if (v < V) {
         int row = -1;
-        if (u) {
-            row = base + __popcll(b & ((1ull << lane) - 1));
+        if (r.rank >= 0) {
+            row = base + r.rank;
             if (row < cap) tok_of_row[row] = v; else row = -1;
         }
         row_of_token[v] = row;
@@ -743,22 +738,42 @@ __device__ __forceinline__ void gp_dw_final_kernel(int cap, int n_out, const int
 
 using namespace rbr;
 
-static bool gate_args_ok(int B, int L, int E, int win) {
+// ---------------------------------------------------------------------------------- host side
+// The openings the entry points share -- shape check, null check, window limit -- and the launch geometry, stated once.
+namespace {
+
+bool gate_args_ok(int B, int L, int E, int win) {
     if (B <= 0 || L <= 0 || E <= 0 || win <= 0) { set_error("bad gate shape B=%d L=%d E=%d win=%d", B, L, E, win); return false; }
     return true;
 }
+template <class... P> int refuse_null(const P*... p) {
+    if (((p != nullptr) && ...)) return 0;
+    set_error("null pointer");
+    return RBR_ERR_BAD_ARG;
+}
+int refuse_wide_window(int win) {      // the dense local gate keeps kMaxKF taps in registers per pass and a halo of kMaxKF in LDS
+    if (win <= 2 * kMaxKF + 1) return 0;
+    set_error("local attention window %d exceeds the supported %d", win, 2 * kMaxKF + 1);
+    return RBR_ERR_UNSUPPORTED;
+}
+const long long* ids64(const int64_t* ids) { return reinterpret_cast<const long long*>(ids); }
+// grid of a grid-stride kernel over n items: ceil(n / 256) workgroups, at most `most`
+dim3 grid256(long n, long most) { return dim3((unsigned)std::min<long>((n + 255) / 256, most)); }
+int n_windows(int L) { return (L + kGWin - 1) / kGWin; }      // windows per document of gate_bwd_dx_kernel
+
+}  // namespace
 
 extern "C" int rbr_datt_local_gate_fwd(int32_t B, int32_t L, int32_t E, int32_t win, const int64_t* ids, const float* table,
                                        const float* w, const float* b0, float* gate, void* stream) {
     if (!gate_args_ok(B, L, E, win)) return RBR_ERR_BAD_ARG;
     if (win % 2 == 0) { set_error("local attention window must be odd, got %d", win); return RBR_ERR_BAD_ARG; }
-    if (!ids || !table || !w || !b0 || !gate) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    if (win > 2 * kMaxKF + 1) { set_error("local attention window %d exceeds the supported %d", win, 2 * kMaxKF + 1); return RBR_ERR_UNSUPPORTED; }
+    if (int e = refuse_null(ids, table, w, b0, gate)) return e;
+    if (int e = refuse_wide_window(win)) return e;
     const size_t smem = (size_t)(kGTile + win - 1) * E * sizeof(float);
     if (smem > 120 * 1024) { set_error("embedding dim %d too large for the local-gate LDS tile", E); return RBR_ERR_UNSUPPORTED; }
     const int ntile = (L + kGTile - 1) / kGTile;
     hipLaunchKernelGGL(local_gate_fwd_kernel, dim3((unsigned)(B * ntile)), dim3(256), smem, (hipStream_t)stream, B, L, E, win,
-                       ntile, reinterpret_cast<const long long*>(ids), table, w, b0, gate);
+                       ntile, ids64(ids), table, w, b0, gate);
     RBR_CHECK_LAUNCH("datt local gate fwd launch");
     return 0;
 }
@@ -766,9 +781,9 @@ extern "C" int rbr_datt_local_gate_fwd(int32_t B, int32_t L, int32_t E, int32_t 
 extern "C" int rbr_datt_global_gate_fwd(int32_t B, int32_t L, int32_t E, const int64_t* ids, const float* table,
                                         const float* w, const float* b0, float* gate, void* stream) {
     if (!gate_args_ok(B, L, E, 1)) return RBR_ERR_BAD_ARG;
-    if (!ids || !table || !w || !b0 || !gate) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    if (int e_ = rbr::launch<global_gate_fwd_kernel, 256>(dim3(B), dim3(256), 0, (hipStream_t)stream, "datt global gate fwd launch", B, L, E, reinterpret_cast<const long long*>(ids), table, w, b0, gate)) return e_;
-    return 0;
+    if (int e = refuse_null(ids, table, w, b0, gate)) return e;
+    return launch<global_gate_fwd_kernel, 256>(dim3(B), dim3(256), 0, (hipStream_t)stream, "datt global gate fwd launch",
+                                               B, L, E, ids64(ids), table, w, b0, gate);
 }
 
 extern "C" size_t rbr_datt_gate_bwd_ws_floats(int32_t B, int32_t L, int32_t E, int32_t win, int32_t is_global) {
@@ -780,172 +795,95 @@ extern "C" int rbr_datt_local_gate_bwd(int32_t B, int32_t L, int32_t E, int32_t 
                                        const float* w, const float* gate, const float* dgate, int32_t pad_idx, float* dw,
                                        float* db0, float* dtable, float* ws, void* stream) {
     if (!gate_args_ok(B, L, E, win)) return RBR_ERR_BAD_ARG;
-    if (!ids || !table || !w || !gate || !dgate || !dw || !db0 || !ws) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
+    if (int e = refuse_null(ids, table, w, gate, dgate, dw, db0, ws)) return e;
     if ((size_t)L * sizeof(float) > 60 * 1024) { set_error("doc_len %d too large for the LDS strip", L); return RBR_ERR_UNSUPPORTED; }
-    if (win > 2 * kMaxKF + 1) { set_error("local attention window %d exceeds the supported %d", win, 2 * kMaxKF + 1); return RBR_ERR_UNSUPPORTED; }
+    if (int e = refuse_wide_window(win)) return e;
     hipStream_t st = (hipStream_t)stream;
-    const long long* ids64 = reinterpret_cast<const long long*>(ids);
     const size_t smem_dw = (size_t)(L + 2 * ((win - 1) / 2) + std::max(kGTile * E, 2 * kMaxKF * 128)) * sizeof(float);
     if (smem_dw > 140 * 1024) { set_error("doc_len %d x emb %d too large for the local-gate LDS tiles", L, E); return RBR_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(local_gate_bwd_dw_kernel, dim3(B), dim3(256), smem_dw, st, B, L, E, win, ids64, table, gate, dgate, ws);
+    hipLaunchKernelGGL(local_gate_bwd_dw_kernel, dim3(B), dim3(256), smem_dw, st, B, L, E, win, ids64(ids), table, gate, dgate, ws);
     RBR_CHECK_LAUNCH("datt local gate bwd dw launch");
     hipLaunchKernelGGL(local_gate_bwd_reduce_kernel, dim3((unsigned)((win * E + 1 + 31) / 32)), dim3(256), 0, st, B, E, win,
                        ws, dw, db0);
     RBR_CHECK_LAUNCH("datt local gate bwd reduce launch");
-    if (dtable != nullptr) {
-        const int nwin = (L + kGWin - 1) / kGWin;
-        if (int e_ = rbr::launch<gate_bwd_dx_kernel, 256>(dim3((unsigned)(B * nwin)), dim3(256), (size_t)kGWin * win * sizeof(float), st, "datt local gate bwd dx launch", B, L, E, win, 0, nwin, ids64, w, (const float*)nullptr, gate, dgate, (const float*)nullptr, pad_idx, dtable, (const int*)nullptr, (float*)nullptr, 0L)) return e_;
-    }
-    return 0;
+    if (dtable == nullptr) return 0;
+    const int nwin = n_windows(L);
+    return launch<gate_bwd_dx_kernel, 256>(dim3((unsigned)(B * nwin)), dim3(256), (size_t)kGWin * win * sizeof(float), st,
+                                           "datt local gate bwd dx launch", B, L, E, win, 0, nwin, ids64(ids), w, nullptr, gate, dgate,
+                                           nullptr, pad_idx, dtable, nullptr, nullptr, 0L);
 }
+
+// ---- global gate backward: the two phases both forms share (dpre at the front of `ws`, wT behind it)
+namespace {
+int global_gate_bwd_weights(int B, int L, int E, const long long* ids, const float* table, const float* gate, const float* dgate,
+                            float* dpre, float* dw, float* db0, hipStream_t st) {
+    if (int e = launch<global_gate_bwd_dpre_kernel, 256>(dim3(B), dim3(256), 0, st, "datt global gate bwd dpre launch",
+                                                         B, L, gate, dgate, dpre)) return e;
+    return launch<global_gate_bwd_dw_kernel, 256>(dim3(L + 1), dim3(256), 0, st, "datt global gate bwd dw launch",
+                                                  B, L, E, ids, table, dpre, dw, db0);
+}
+int global_gate_transpose(int E, int L, const float* w, float* wT, hipStream_t st) {
+    return launch<transpose_w_kernel, 256>(grid256((long)E * L, 2048), dim3(256), 0, st, "datt global gate transpose launch", E, L, w, wT);
+}
+}  // namespace
 
 extern "C" int rbr_datt_global_gate_bwd(int32_t B, int32_t L, int32_t E, const int64_t* ids, const float* table,
                                         const float* w, const float* gate, const float* dgate, int32_t pad_idx, float* dw,
                                         float* db0, float* dtable, float* ws, void* stream) {
     if (!gate_args_ok(B, L, E, 1)) return RBR_ERR_BAD_ARG;
-    if (!ids || !table || !w || !gate || !dgate || !dw || !db0 || !ws) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
+    if (int e = refuse_null(ids, table, w, gate, dgate, dw, db0, ws)) return e;
     hipStream_t st = (hipStream_t)stream;
-    const long long* ids64 = reinterpret_cast<const long long*>(ids);
-    if (int e_ = rbr::launch<global_gate_bwd_dpre_kernel, 256>(dim3(B), dim3(256), 0, st, "datt global gate bwd dpre launch", B, L, gate, dgate, ws)) return e_;
-    if (int e_ = rbr::launch<global_gate_bwd_dw_kernel, 256>(dim3(L + 1), dim3(256), 0, st, "datt global gate bwd dw launch", B, L, E, ids64, table, ws, dw, db0)) return e_;
-    if (dtable != nullptr) {
-        float* wT = ws + B;
-        if (int e_ = rbr::launch<transpose_w_kernel, 256>(dim3((unsigned)std::min<long>(((long)E * L + 255) / 256, 2048)), dim3(256), 0, st, "datt global gate transpose launch", E, L, w, wT)) return e_;
-        const int nwin = (L + kGWin - 1) / kGWin;
-        if (int e_ = rbr::launch<gate_bwd_dx_kernel, 256>(dim3((unsigned)(B * nwin)), dim3(256), 0, st, "datt global gate bwd dx launch", B, L, E, 1, 1, nwin, ids64, w, (const float*)wT, gate, dgate, (const float*)ws, pad_idx, dtable, (const int*)nullptr, (float*)nullptr, 0L)) return e_;
-    }
-    return 0;
+    float *dpre = ws, *wT = ws + B;
+    if (int e = global_gate_bwd_weights(B, L, E, ids64(ids), table, gate, dgate, dpre, dw, db0, st)) return e;
+    if (dtable == nullptr) return 0;
+    if (int e = global_gate_transpose(E, L, w, wT, st)) return e;
+    const int nwin = n_windows(L);
+    return launch<gate_bwd_dx_kernel, 256>(dim3((unsigned)(B * nwin)), dim3(256), 0, st, "datt global gate bwd dx launch",
+                                           B, L, E, 1, 1, nwin, ids64(ids), w, wT, gate, dgate, dpre, pad_idx, dtable,
+                                           nullptr, nullptr, 0L);
 }
 
-// ---- token-product local gate (same results as rbr_datt_local_gate_fwd / _bwd; `ws` must survive from forward to backward)
+// ---- distinct-token row maps of a document batch: row_of_token [V] (dense row or -1), tok_of_row [cap],
+// the row counter; rows numbered in vocabulary order.  One layout and one build for the tower's shared maps (rbr_datt_token_rows:
+// the whole `rows` buffer) and for a token-product gate's private ones (the same block at the front of its `ws`).
 namespace {
-struct GateProdLayout { size_t used, counter, row_of_token, tok_of_row, S, c, part, blk, total; int cap, n_chunks; };
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-bool gate_prod_layout(int B, int L, int E, int win, int V, GateProdLayout& G) {
-    if (B <= 0 || L <= 0 || E <= 0 || V <= 0 || win <= 0 || win > kGateWP || win % 2 == 0) return false;
-    const long n_pos = (long)B * L;
-    G.cap = (int)std::min<long>(V, n_pos);
-    G.n_chunks = (G.cap + kGpRows - 1) / kGpRows;
-    size_t o = 0;
-    G.used = o;         o += al256((size_t)V * sizeof(int));
-    G.counter = o;      o += 256;                                   // contiguous with `used`: zeroed together
-    G.row_of_token = o; o += al256((size_t)V * sizeof(int));
-    G.tok_of_row = o;   o += al256((size_t)G.cap * sizeof(int));
-    G.S = o;            o += al256((size_t)G.cap * kGateWP * sizeof(float));
-    G.c = o;            o += al256((size_t)G.cap * kGateWP * sizeof(float) * kGateCopies);
-    G.part = o;         o += al256((size_t)G.n_chunks * ((size_t)win * E + 1) * sizeof(float));
-    G.blk = o;          o += al256((((size_t)V + 255) / 256) * sizeof(int));        // used tokens per 256 vocabulary entries
-    G.total = o;
-    return true;
-}
-}  // namespace
 
-// ---- distinct-token rows of a document batch, shared by the gates of one tower (layout: counter | used | row_of_token | tok_of_row | block counts)
-namespace {
-struct TokenRowsLayout { size_t counter, used, row_of_token, tok_of_row, blk, total; int cap; };
+struct TokenRowsLayout { size_t counter, used, row_of_token, tok_of_row, blk, total; int cap; };      // byte offsets
 bool token_rows_layout(int B, int L, int V, TokenRowsLayout& T) {
     if (B <= 0 || L <= 0 || V <= 0) return false;
     T.cap = (int)std::min<long>(V, (long)B * L);
     size_t o = 0;
     T.counter = o;      o += 256;
-    T.used = o;         o += al256((size_t)V * sizeof(int));      // contiguous with the counter: zeroed together
-    T.row_of_token = o; o += al256((size_t)V * sizeof(int));
-    T.tok_of_row = o;   o += al256((size_t)T.cap * sizeof(int));
-    T.blk = o;          o += al256((((size_t)V + 255) / 256) * sizeof(int));        // used tokens per 256 vocabulary entries
+    T.used = o;         o += align256((size_t)V * sizeof(int));      // contiguous with the counter: zeroed together
+    T.row_of_token = o; o += align256((size_t)V * sizeof(int));
+    T.tok_of_row = o;   o += align256((size_t)T.cap * sizeof(int));
+    T.blk = o;          o += align256((((size_t)V + 255) / 256) * sizeof(int));        // used tokens per 256 vocabulary entries
     T.total = o;
     return true;
 }
-}  // namespace
 
-
-namespace {
-struct GateRowMaps { const int *counter, *row_of_token, *tok_of_row; };
-// the distinct-token maps a token-product gate call works on: the tower's shared ones (`rows`) or the private ones in its ws
-bool gate_row_maps(int B, int L, int V, const GateProdLayout& G, const char* ws_base, const void* rows, GateRowMaps& M) {
-    if (rows == nullptr) {
-        M.counter = reinterpret_cast<const int*>(ws_base + G.counter);
-        M.row_of_token = reinterpret_cast<const int*>(ws_base + G.row_of_token);
-        M.tok_of_row = reinterpret_cast<const int*>(ws_base + G.tok_of_row);
-        return true;
-    }
+// The maps as typed pointers: the one place that casts the layout's offsets.  `base` is const for the consumers, which only read.
+struct TokenRows { int *counter, *used, *row_of_token, *tok_of_row, *blk; int cap; };
+bool token_rows(int B, int L, int V, const void* base, TokenRows& R) {
     TokenRowsLayout T;
-    if (!token_rows_layout(B, L, V, T) || T.cap != G.cap) { set_error("token rows do not fit the gate shape"); return false; }
-    const char* r = static_cast<const char*>(rows);
-    M.counter = reinterpret_cast<const int*>(r + T.counter);
-    M.row_of_token = reinterpret_cast<const int*>(r + T.row_of_token);
-    M.tok_of_row = reinterpret_cast<const int*>(r + T.tok_of_row);
+    if (!token_rows_layout(B, L, V, T)) return false;
+    char* p = static_cast<char*>(const_cast<void*>(base));
+    auto at = [p](size_t o) { return reinterpret_cast<int*>(p + o); };
+    R = TokenRows{at(T.counter), at(T.used), at(T.row_of_token), at(T.tok_of_row), at(T.blk), T.cap};
     return true;
 }
+
+// zero (counter | used) -> mark -> count per 256 vocabulary entries -> compact
+int build_token_rows(const TokenRows& R, const long long* ids, long n_pos, int V, hipStream_t st) {
+    const dim3 vocab_blocks((V + 255) / 256);
+    if (int e = zero_words(R.counter, (size_t)(R.row_of_token - R.counter) * sizeof(int), st)) return e;
+    if (int e = launch<gp_mark_kernel, 256>(grid256(n_pos, 2048), dim3(256), 0, st, "token rows mark launch", n_pos, ids, R.used)) return e;
+    if (int e = launch<gp_count_kernel, 256>(vocab_blocks, dim3(256), 0, st, "token rows count launch", V, R.used, R.blk)) return e;
+    return launch<gp_compact_kernel, 256>(vocab_blocks, dim3(256), 0, st, "token rows compact launch",
+                                          V, R.cap, R.used, R.blk, R.row_of_token, R.tok_of_row, R.counter);
+}
+
 }  // namespace
-
-extern "C" size_t rbr_datt_local_gate_prod_ws_bytes(int32_t B, int32_t L, int32_t E, int32_t win, int32_t V) {
-    GateProdLayout G;
-    if (!gate_prod_layout(B, L, E, win, V, G)) return 0;
-    // worth it when the vocabulary bounds the distinct tokens well below the position count (as rbr_textcnn_fwd_ws_bytes)
-    const int mode = forced_conv_mode();
-    if (mode == 1) return 0;
-    if (mode != 2 && ((long)V * 5 > (long)B * L * 2 || (long)B * L < 4096)) return 0;
-    return G.total;
-}
-
-extern "C" int rbr_datt_local_gate_fwd_prod(int32_t B, int32_t L, int32_t E, int32_t win, int32_t V, const int64_t* ids,
-                                            const float* table, const float* w, const float* b0, float* gate, void* ws,
-                                            const void* rows, void* stream) {
-    GateProdLayout G;
-    if (!gate_prod_layout(B, L, E, win, V, G)) { set_error("bad local gate shape B=%d L=%d E=%d win=%d V=%d", B, L, E, win, V); return RBR_ERR_BAD_ARG; }
-    if (!ids || !table || !w || !b0 || !gate || !ws) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    char* base = static_cast<char*>(ws);
-    int* used = reinterpret_cast<int*>(base + G.used);
-    float* S = reinterpret_cast<float*>(base + G.S);
-    const long long* ids64 = reinterpret_cast<const long long*>(ids);
-    const long n_pos = (long)B * L;
-    GateRowMaps M;
-    if (!gate_row_maps(B, L, V, G, base, rows, M)) return RBR_ERR_BAD_ARG;
-    const int *counter = M.counter, *row_of_token = M.row_of_token, *tok_of_row = M.tok_of_row;
-    if (rows == nullptr) {               // the tower's shared maps (rbr_datt_token_rows) were not handed in: build private ones
-        if (int e = zero_words(used, G.row_of_token - G.used, st)) return e;
-        if (int e_ = rbr::launch<gp_mark_kernel, 256>(dim3((unsigned)std::min<long>((n_pos + 255) / 256, 2048)), dim3(256), 0, st, "datt gate mark launch", n_pos, ids64, used)) return e_;
-        if (int e_ = rbr::launch<gp_count_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "datt gate count launch", V, (const int*)used, reinterpret_cast<int*>(base + G.blk))) return e_;
-        if (int e_ = rbr::launch<gp_compact_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "datt gate compact launch", V, G.cap, (const int*)used, (const int*)reinterpret_cast<int*>(base + G.blk), reinterpret_cast<int*>(base + G.row_of_token), reinterpret_cast<int*>(base + G.tok_of_row), reinterpret_cast<int*>(base + G.counter))) return e_;
-    }
-    if (int e_ = rbr::launch<gp_taps_kernel, 256>(dim3((unsigned)std::min((G.cap + 15) / 16, 4096)), dim3(256), 0, st, "datt gate taps launch", E, win, G.cap, counter, tok_of_row, table, w, S)) return e_;
-    if (int e_ = rbr::launch<gp_gate_kernel, 256>(dim3((unsigned)std::min<long>((n_pos + 255) / 256, 8192)), dim3(256), 0, st, "datt gate gather launch", B, L, win, ids64, row_of_token, S, b0, gate)) return e_;
-    return 0;
-}
-
-extern "C" int rbr_datt_local_gate_bwd_prod(int32_t B, int32_t L, int32_t E, int32_t win, int32_t V, const int64_t* ids,
-                                            const float* table, const float* w, const float* gate, const float* dgate,
-                                            int32_t pad_idx, float* dw, float* db0, float* dtable, void* ws, const void* rows,
-                                            int32_t accumulate, void* stream) {
-    GateProdLayout G;
-    if (!gate_prod_layout(B, L, E, win, V, G)) { set_error("bad local gate shape B=%d L=%d E=%d win=%d V=%d", B, L, E, win, V); return RBR_ERR_BAD_ARG; }
-    if (!ids || !table || !w || !gate || !dgate || !dw || !db0 || !ws) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    char* base = static_cast<char*>(ws);
-    GateRowMaps M;
-    if (!gate_row_maps(B, L, V, G, base, rows, M)) return RBR_ERR_BAD_ARG;
-    const int *counter = M.counter, *row_of_token = M.row_of_token, *tok_of_row = M.tok_of_row;
-    float* c = reinterpret_cast<float*>(base + G.c);
-    float* part = reinterpret_cast<float*>(base + G.part);
-    const long long* ids64 = reinterpret_cast<const long long*>(ids);
-    if (int e = zero_words(c, (size_t)G.cap * kGateWP * sizeof(float) * kGateCopies, st)) return e;
-    const int nwin = (L + kGWin - 1) / kGWin;
-    if (int e_ = rbr::launch<gate_bwd_dx_kernel, 256>(dim3((unsigned)(B * nwin)), dim3(256), 0, st, "datt gate tap-sum launch", B, L, E, win, 0, nwin, ids64, w, (const float*)nullptr, gate, dgate, (const float*)nullptr, pad_idx, (float*)nullptr, row_of_token, c, (long)G.cap * kGateWP)) return e_;
-    if (int e_ = rbr::launch<gp_csum_kernel, 256>(dim3((unsigned)std::min((G.cap * kGateWP + 255) / 256, 2048)), dim3(256), 0, st, "datt gate tap-sum fold launch", G.cap, counter, c)) return e_;
-    const int n_out = win * E + 1;
-    if (int e_ = rbr::launch<gp_dw_partial_kernel, 256>(dim3(G.n_chunks), dim3(256), 0, st, "datt gate dw partial launch", E, win, G.cap, counter, tok_of_row, table, c, part)) return e_;
-    if (int e_ = rbr::launch<gp_dw_final_kernel, 256>(dim3((n_out + 3) / 4), dim3(256), 0, st, "datt gate dw final launch", G.cap, n_out, counter, part, dw, db0)) return e_;
-    if (dtable != nullptr) {
-        const long n = (long)V * E;
-        if (accumulate) {
-            if (int e_ = rbr::launch<gp_dtable_rows_kernel, 256>(dim3((unsigned)std::min<long>(((long)G.cap * E + 255) / 256, 8192)), dim3(256), 0, st, "gp_dtable_rows_kernel launch", E, win, G.cap, pad_idx, counter, tok_of_row, c, w, dtable)) return e_;
-        } else {
-            if (int e_ = rbr::launch<gp_dtable_kernel, 256>(dim3((unsigned)std::min<long>((n + 255) / 256, 8192)), dim3(256), 0, st, "datt gate dtable launch", V, E, win, pad_idx, row_of_token, c, w, dtable, 0)) return e_;
-        }
-    }
-    return 0;
-}
 
 extern "C" size_t rbr_datt_token_rows_ws_bytes(int32_t B, int32_t L, int32_t V) {
     TokenRowsLayout T;
@@ -953,60 +891,173 @@ extern "C" size_t rbr_datt_token_rows_ws_bytes(int32_t B, int32_t L, int32_t V) 
 }
 
 extern "C" int rbr_datt_token_rows(int32_t B, int32_t L, int32_t V, const int64_t* ids, void* rows, void* stream) {
-    TokenRowsLayout T;
-    if (!token_rows_layout(B, L, V, T)) { set_error("bad token-rows shape B=%d L=%d V=%d", B, L, V); return RBR_ERR_BAD_ARG; }
-    if (!ids || !rows) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
-    hipStream_t st = (hipStream_t)stream;
-    char* base = static_cast<char*>(rows);
-    int* counter = reinterpret_cast<int*>(base + T.counter);
-    int* used = reinterpret_cast<int*>(base + T.used);
-    if (int e = zero_words(counter, T.row_of_token - T.counter, st)) return e;
-    const long n_pos = (long)B * L;
-    if (int e_ = rbr::launch<gp_mark_kernel, 256>(dim3((unsigned)std::min<long>((n_pos + 255) / 256, 2048)), dim3(256), 0, st, "token rows mark launch", n_pos, reinterpret_cast<const long long*>(ids), used)) return e_;
-    if (int e_ = rbr::launch<gp_count_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "token rows count launch", V, (const int*)used, reinterpret_cast<int*>(base + T.blk))) return e_;
-    if (int e_ = rbr::launch<gp_compact_kernel, 256>(dim3((V + 255) / 256), dim3(256), 0, st, "token rows compact launch", V, T.cap, (const int*)used, (const int*)reinterpret_cast<int*>(base + T.blk), reinterpret_cast<int*>(base + T.row_of_token), reinterpret_cast<int*>(base + T.tok_of_row), counter)) return e_;
+    TokenRows R;
+    if (!rbr_datt_token_rows_ws_bytes(B, L, V)) { set_error("bad token-rows shape B=%d L=%d V=%d", B, L, V); return RBR_ERR_BAD_ARG; }
+    if (int e = refuse_null(ids, rows)) return e;
+    token_rows(B, L, V, rows, R);
+    return build_token_rows(R, ids64(ids), (long)B * L, V, (hipStream_t)stream);
+}
+
+// Where rbr_datt_token_rows left the maps inside `rows` (the layout is private): the twin of rbr_textcnn_token_list
+extern "C" int rbr_datt_token_rows_maps(int32_t B, int32_t L, int32_t V, const void* rows, const int32_t** row_of_token,
+                                        const int32_t** n_rows, const int32_t** tok_of_row, int32_t* cap) {
+    TokenRows R;
+    if (!rows || !token_rows(B, L, V, rows, R)) { set_error("no token rows for B=%d L=%d V=%d", B, L, V); return RBR_ERR_BAD_ARG; }
+    if (row_of_token) *row_of_token = R.row_of_token;
+    if (n_rows) *n_rows = R.counter;
+    if (tok_of_row) *tok_of_row = R.tok_of_row;
+    if (cap) *cap = R.cap;
     return 0;
 }
+
+// ---- token-product local gate (same results as rbr_datt_local_gate_fwd / _bwd; `ws` must survive from forward to backward)
+// ws = a token-rows block (the private maps; unused when the tower's shared ones are handed in) | S | c | part
+namespace {
+
+struct GateProdLayout { TokenRowsLayout rows; size_t S, c, part, total; int cap, n_chunks; };
+bool gate_prod_layout(int B, int L, int E, int win, int V, GateProdLayout& G) {
+    if (E <= 0 || win <= 0 || win > kGateWP || win % 2 == 0 || !token_rows_layout(B, L, V, G.rows)) return false;
+    G.cap = G.rows.cap;
+    G.n_chunks = (G.cap + kGpRows - 1) / kGpRows;
+    size_t o = G.rows.total;
+    G.S = o;            o += align256((size_t)G.cap * kGateWP * sizeof(float));
+    G.c = o;            o += align256((size_t)G.cap * kGateWP * sizeof(float) * kGateCopies);
+    G.part = o;         o += align256((size_t)G.n_chunks * ((size_t)win * E + 1) * sizeof(float));
+    G.total = o;
+    return true;
+}
+
+// What a token-product gate call works on: its row maps -- the tower's shared ones (`rows`) or the private ones at the front of
+// `ws` -- and its own regions, typed.
+struct GateProd {
+    TokenRows R;
+    float *S, *c, *part;      // tap products [cap][kGateWP], tap sums [kGateCopies][cap][kGateWP], dw partials [n_chunks][win * E + 1]
+    int cap, n_chunks;
+};
+int gate_prod(int B, int L, int E, int win, int V, void* ws, const void* rows, GateProd& P) {
+    GateProdLayout G;
+    if (!gate_prod_layout(B, L, E, win, V, G)) {
+        set_error("bad local gate shape B=%d L=%d E=%d win=%d V=%d", B, L, E, win, V);
+        return RBR_ERR_BAD_ARG;
+    }
+    if (int e = refuse_null(ws)) return e;
+    token_rows(B, L, V, rows ? rows : ws, P.R);
+    char* p = static_cast<char*>(ws);
+    auto at = [p](size_t o) { return reinterpret_cast<float*>(p + o); };
+    P.S = at(G.S); P.c = at(G.c); P.part = at(G.part);
+    P.cap = G.cap; P.n_chunks = G.n_chunks;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" size_t rbr_datt_local_gate_prod_ws_bytes(int32_t B, int32_t L, int32_t E, int32_t win, int32_t V) {
+    GateProdLayout G;
+    if (!gate_prod_layout(B, L, E, win, V, G)) return 0;
+    const int mode = forced_conv_mode();
+    if (mode == 1 || (mode != 2 && !token_rows_pay(V, (long)B * L))) return 0;
+    return G.total;
+}
+
+extern "C" int rbr_datt_local_gate_fwd_prod(int32_t B, int32_t L, int32_t E, int32_t win, int32_t V, const int64_t* ids,
+                                            const float* table, const float* w, const float* b0, float* gate, void* ws,
+                                            const void* rows, void* stream) {
+    GateProd P;
+    if (int e = gate_prod(B, L, E, win, V, ws, rows, P)) return e;
+    if (int e = refuse_null(ids, table, w, b0, gate)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const long n_pos = (long)B * L;
+    // the tower's shared maps (rbr_datt_token_rows) were not handed in: build private ones
+    if (rows == nullptr)
+        if (int e = build_token_rows(P.R, ids64(ids), n_pos, V, st)) return e;
+    if (int e = launch<gp_taps_kernel, 256>(dim3((unsigned)std::min((P.cap + 15) / 16, 4096)), dim3(256), 0, st, "datt gate taps launch",
+                                            E, win, P.cap, P.R.counter, P.R.tok_of_row, table, w, P.S)) return e;
+    return launch<gp_gate_kernel, 256>(grid256(n_pos, 8192), dim3(256), 0, st, "datt gate gather launch",
+                                       B, L, win, ids64(ids), P.R.row_of_token, P.S, b0, gate);
+}
+
+extern "C" int rbr_datt_local_gate_bwd_prod(int32_t B, int32_t L, int32_t E, int32_t win, int32_t V, const int64_t* ids,
+                                            const float* table, const float* w, const float* gate, const float* dgate,
+                                            int32_t pad_idx, float* dw, float* db0, float* dtable, void* ws, const void* rows,
+                                            int32_t accumulate, void* stream) {
+    GateProd P;
+    if (int e = gate_prod(B, L, E, win, V, ws, rows, P)) return e;
+    if (int e = refuse_null(ids, table, w, gate, dgate, dw, db0)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const TokenRows& R = P.R;
+    const long c_stride = (long)P.cap * kGateWP;       // one copy of the tap-sum table
+    if (int e = zero_words(P.c, (size_t)c_stride * sizeof(float) * kGateCopies, st)) return e;
+    const int nwin = n_windows(L);
+    if (int e = launch<gate_bwd_dx_kernel, 256>(dim3((unsigned)(B * nwin)), dim3(256), 0, st, "datt gate tap-sum launch",
+                                                B, L, E, win, 0, nwin, ids64(ids), w, nullptr, gate, dgate, nullptr, pad_idx,
+                                                nullptr, R.row_of_token, P.c, c_stride)) return e;
+    if (int e = launch<gp_csum_kernel, 256>(grid256(c_stride, 2048), dim3(256), 0, st, "datt gate tap-sum fold launch",
+                                            P.cap, R.counter, P.c)) return e;
+    const int n_out = win * E + 1;
+    if (int e = launch<gp_dw_partial_kernel, 256>(dim3(P.n_chunks), dim3(256), 0, st, "datt gate dw partial launch",
+                                                  E, win, P.cap, R.counter, R.tok_of_row, table, P.c, P.part)) return e;
+    if (int e = launch<gp_dw_final_kernel, 256>(dim3((n_out + 3) / 4), dim3(256), 0, st, "datt gate dw final launch",
+                                                P.cap, n_out, R.counter, P.part, dw, db0)) return e;
+    if (dtable == nullptr) return 0;
+    if (accumulate)
+        return launch<gp_dtable_rows_kernel, 256>(grid256((long)P.cap * E, 8192), dim3(256), 0, st, "gp_dtable_rows_kernel launch",
+                                                  E, win, P.cap, pad_idx, R.counter, R.tok_of_row, P.c, w, dtable);
+    return launch<gp_dtable_kernel, 256>(grid256((long)V * E, 8192), dim3(256), 0, st, "datt gate dtable launch",
+                                         V, E, win, pad_idx, R.row_of_token, P.c, w, dtable, 0);
+}
+
+// ---- global gate backward over the tower's row maps
+// ws = dpre [B] | wT [E * L] | A [cap * L] (16-byte aligned) | dense count (4 ints) | dense list [V]
+namespace {
+struct GlobalRowsWs { float *dpre, *wT, *A; f32x4g* A4; int *dense_count, *dense_list; };
+GlobalRowsWs global_rows_ws(int B, int L, int E, int cap, float* ws) {
+    GlobalRowsWs W;
+    W.dpre = ws;
+    W.wT = ws + B;
+    W.A = W.wT + (((size_t)E * L + 3) & ~(size_t)3);             // 16-byte aligned behind wT when ws is
+    if ((reinterpret_cast<uintptr_t>(W.A) & 15) != 0) W.A += 4 - ((reinterpret_cast<uintptr_t>(W.A) & 15) >> 2);
+    W.A4 = reinterpret_cast<f32x4g*>(W.A);
+    W.dense_count = reinterpret_cast<int*>(W.A + (size_t)cap * L);
+    W.dense_list = W.dense_count + 4;
+    return W;
+}
+}  // namespace
 
 extern "C" size_t rbr_datt_global_gate_bwd_rows_ws_floats(int32_t B, int32_t L, int32_t E, int32_t V) {
     TokenRowsLayout T;
     if (!token_rows_layout(B, L, V, T) || E <= 0 || E > kGgChunks * 64 || L % 4 != 0) return 0;   // 0: use rbr_datt_global_gate_bwd
-    return (size_t)B + (size_t)E * L + 8 + (size_t)T.cap * L + 4 + (size_t)V;       // dpre | wT | A | dense count + list
+    return (size_t)B + (size_t)E * L + 8 + (size_t)T.cap * L + 4 + (size_t)V;
 }
 
 extern "C" int rbr_datt_global_gate_bwd_rows(int32_t B, int32_t L, int32_t E, int32_t V, const int64_t* ids, const float* table,
                                              const float* w, const float* gate, const float* dgate, int32_t pad_idx, float* dw,
                                              float* db0, float* dtable, float* ws, const void* rows, int32_t accumulate, void* stream) {
-    TokenRowsLayout T;
-    if (!gate_args_ok(B, L, E, 1) || !token_rows_layout(B, L, V, T)) return RBR_ERR_BAD_ARG;
-    if (E > kGgChunks * 64 || L % 4 != 0) { set_error("global gate over token rows needs E <= %d and L %% 4 == 0 (E=%d L=%d)", kGgChunks * 64, E, L); return RBR_ERR_UNSUPPORTED; }
+    if (!gate_args_ok(B, L, E, 1) || !rbr_datt_token_rows_ws_bytes(B, L, V)) return RBR_ERR_BAD_ARG;
+    if (E > kGgChunks * 64 || L % 4 != 0) {
+        set_error("global gate over token rows needs E <= %d and L %% 4 == 0 (E=%d L=%d)", kGgChunks * 64, E, L);
+        return RBR_ERR_UNSUPPORTED;
+    }
     // accumulate & 2: the table-gradient phase alone -- dpre is in `ws` already (an earlier call with dtable == NULL on the same
     // workspace did the weight phase); a caller that puts the two phases of its towers on different streams (functional._DattTowers)
     const bool rows_only = (accumulate & 2) != 0;
     accumulate &= 1;
-    if (!ids || !w || !ws || !rows || (!rows_only && (!table || !gate || !dgate || !dw || !db0)) || (rows_only && !dtable)) { set_error("null pointer"); return RBR_ERR_BAD_ARG; }
+    if (int e = refuse_null(ids, w, ws, rows)) return e;
+    if (int e = rows_only ? refuse_null(dtable) : refuse_null(table, gate, dgate, dw, db0)) return e;
     hipStream_t st = (hipStream_t)stream;
-    const long long* ids64 = reinterpret_cast<const long long*>(ids);
-    const char* base = static_cast<const char*>(rows);
-    const int* counter = reinterpret_cast<const int*>(base + T.counter);
-    const int* row_of_token = reinterpret_cast<const int*>(base + T.row_of_token);
-    if (!rows_only) {
-        if (int e_ = rbr::launch<global_gate_bwd_dpre_kernel, 256>(dim3(B), dim3(256), 0, st, "datt global gate bwd dpre launch", B, L, gate, dgate, ws)) return e_;
-        if (int e_ = rbr::launch<global_gate_bwd_dw_kernel, 256>(dim3(L + 1), dim3(256), 0, st, "datt global gate bwd dw launch", B, L, E, ids64, table, ws, dw, db0)) return e_;
-    }
-    if (dtable != nullptr) {
-        float* wT = ws + B;
-        float* A = wT + (((size_t)E * L + 3) & ~(size_t)3);             // 16-byte aligned behind wT when ws is
-        if ((reinterpret_cast<uintptr_t>(A) & 15) != 0) A += 4 - ((reinterpret_cast<uintptr_t>(A) & 15) >> 2);
-        if (int e_ = rbr::launch<transpose_w_kernel, 256>(dim3((unsigned)std::min<long>(((long)E * L + 255) / 256, 2048)), dim3(256), 0, st, "datt global gate transpose launch", E, L, w, wT)) return e_;
-        int* dense_count = reinterpret_cast<int*>(A + (size_t)T.cap * L);
-        int* dense_list = dense_count + 4;
-        PairSolo solo;        // zero A -> scatter into A -> rows from A: a chain over the 160 MB occurrence matrix (rbr_launch.h)
-        if (int e_ = rbr::launch<gg_zero_kernel, 256>(dim3((unsigned)std::min<long>(((long)T.cap * L / 4 + 255) / 256, 8192)), dim3(256), 0, st, "datt global gate occurrence zero launch", T.cap, L, counter, reinterpret_cast<f32x4g*>(A), dense_count)) return e_;
-        const long n_pos = (long)B * L;
-        if (int e_ = rbr::launch<gg_scatter_kernel, 256>(dim3((unsigned)std::min<long>((n_pos + 255) / 256, 8192)), dim3(256), 0, st, "datt global gate occurrence scatter launch", B, L, pad_idx, ids64, row_of_token, (const float*)ws, A)) return e_;
-        if (int e_ = rbr::launch<gg_rows_kernel, 256>(dim3((unsigned)((V + 3) / 4)), dim3(256), 0, st, "datt global gate rows launch", V, L, E, pad_idx, row_of_token, (const float*)A, (const float*)wT, dtable, dense_count, dense_list, accumulate)) return e_;
-        if (int e_ = rbr::launch<gg_dense_rows_kernel, 1024>(dim3((unsigned)std::min(V, 512)), dim3(1024), 0, st, "datt global gate dense rows launch", L, E, row_of_token, (const float*)A, (const float*)wT, dtable, (const int*)dense_count, (const int*)dense_list, accumulate)) return e_;
-    }
-    return 0;
+    TokenRows R;
+    token_rows(B, L, V, rows, R);
+    const GlobalRowsWs W = global_rows_ws(B, L, E, R.cap, ws);
+    if (!rows_only)
+        if (int e = global_gate_bwd_weights(B, L, E, ids64(ids), table, gate, dgate, W.dpre, dw, db0, st)) return e;
+    if (dtable == nullptr) return 0;
+    if (int e = global_gate_transpose(E, L, w, W.wT, st)) return e;
+    PairSolo solo;        // zero A -> scatter into A -> rows from A: a chain over the 160 MB occurrence matrix (rbr_launch.h)
+    if (int e = launch<gg_zero_kernel, 256>(grid256((long)R.cap * L / 4, 8192), dim3(256), 0, st, "datt global gate occurrence zero launch",
+                                            R.cap, L, R.counter, W.A4, W.dense_count)) return e;
+    if (int e = launch<gg_scatter_kernel, 256>(grid256((long)B * L, 8192), dim3(256), 0, st, "datt global gate occurrence scatter launch",
+                                               B, L, pad_idx, ids64(ids), R.row_of_token, W.dpre, W.A)) return e;
+    if (int e = launch<gg_rows_kernel, 256>(dim3((unsigned)((V + 3) / 4)), dim3(256), 0, st, "datt global gate rows launch",
+                                            V, L, E, pad_idx, R.row_of_token, W.A, W.wT, dtable, W.dense_count, W.dense_list, accumulate)) return e;
+    return launch<gg_dense_rows_kernel, 1024>(dim3((unsigned)std::min(V, 512)), dim3(1024), 0, st, "datt global gate dense rows launch",
+                                              L, E, R.row_of_token, W.A, W.wT, dtable, W.dense_count, W.dense_list, accumulate);
 }

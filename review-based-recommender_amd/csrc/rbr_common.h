@@ -87,6 +87,11 @@ int run_token_product(const rbr_textcnn_desc* d, const long long* ids, const uns
                       const float* table, const float* const* W, float* pval, int* pidx, void* ws, hipStream_t st);
 // 0 auto, 1 dense forced, 2 token-product forced (rbr_set_conv_mode / RBR_CONV_MODE)
 int forced_conv_mode();
+// auto mode: the distinct-token row maps of a batch pay -- the token-product conv, the token-product local gate -- when the
+// vocabulary bounds the distinct tokens well below the position count
+inline bool token_rows_pay(long V, long n_pos) { return V * 5 <= n_pos * 2 && n_pos >= 4096; }
+// workspace regions start on 256-byte boundaries
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // bf16-plane form of the token-product GEMM (textcnn_prod_b16.hip): RBR_PROD_* in force, whether it serves `d`, the
 // bytes of its weight-plane image, the pack launch and the GEMM launch (T pitch must be >= 128 * prod_b16_groups)
 int prod_precision();

@@ -5,6 +5,20 @@
 // partner 1 last -- and the kernels whose results are tested for bit-reproducibility rely on exactly that order.
 // wave_incl_scan: inclusive prefix sum over the 64 lanes (__shfl_up ladder); lane 63 holds the total.
 // The cross-wave step of a block reduction stays with its kernel: the sites add their four wave sums in different orders.
+//
+// block_rank_256: the in-block ranking of the distinct-token row maps, for a workgroup of 256 threads (4 waves), every thread
+// of which makes the call.  Users: gp_count_kernel, gp_compact_kernel (datt_gates.hip), compact_block<KEPT> (textcnn_prod.hip).
+// Contract -- u = the thread's mark (non-zero: marked), s_n = the caller's own __shared__ int[4]:
+//   inside   ballot of the marks, s_n[w] = marked threads of wave w (written by lane 0), ONE barrier, then the prefix over the
+//            earlier waves.  After the call s_n holds the four wave counts for every thread.
+//   returns  rank  = marked threads of the workgroup below this one (-1 for an unmarked thread): with `base` marked tokens below
+//                    the block, the thread's row is base + rank, rows ascending with the thread index;
+//            total = marked threads of the workgroup.
+//   barriers the one inside also publishes whatever the caller wrote to LDS before the call -- that is how each caller's
+//            partial sums of `base` reach all its threads without a barrier of their own.  None behind: a caller that writes
+//            s_n (or calls again) afterwards puts its own barrier in front.
+// `base` itself stays with the caller (block counts of an earlier launch in the gates, popcounts of byte marks in the conv), and
+// so does whoever writes the row counter.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,6 +46,18 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
         if (lane >= o) v += up;
     }
     return v;
+}
+
+struct BlockRank { int rank, total; };
+__device__ __forceinline__ BlockRank block_rank_256(int u, int* s_n) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long b = __ballot(u);
+    if (lane == 0) s_n[wave] = __popcll(b);
+    __syncthreads();
+    int below = 0;
+    for (int k = 0; k < wave; ++k) below += s_n[k];
+    const int rank = u ? below + (int)__popcll(b & ((1ull << lane) - 1)) : -1;
+    return {rank, s_n[0] + s_n[1] + s_n[2] + s_n[3]};
 }
 
 }  // namespace rbr

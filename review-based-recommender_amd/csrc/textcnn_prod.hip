@@ -197,28 +197,25 @@ __device__ __forceinline__ void compact_block(int nb_compact, int V, int cap, Ma
     if constexpr (KEPT) call = wave_sum(call);
     const int v = below + threadIdx.x;
     const int u = (v < V) ? used[v] : 0;
-    const unsigned long long b = __ballot(u);
     if (lane == 0) {
-        s_cnt[wave] = c; s_wave[wave] = __popcll(b);
+        s_cnt[wave] = c;
         if constexpr (KEPT) s_all[wave] = call;
     }
-    __syncthreads();
+    const BlockRank r = block_rank_256(u, s_wave);      // rbr_wave.h; its barrier publishes s_cnt / s_all too
     if constexpr (KEPT)
         if (threadIdx.x == 0) s_last = atomicAdd(KS.ticket, 1) == nb_compact - 1;
-    int base = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-    for (int k = 0; k < wave; ++k) base += s_wave[k];
+    const int base = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);      // marks below the block
     if (v < V) {
         int row = -1;
-        if (u) {
-            row = base + __popcll(b & ((1ull << lane) - 1));
+        if (r.rank >= 0) {
+            row = base + r.rank;
             if (row >= cap) row = -1;      // cannot happen: cap >= distinct
             else { tok_of_row[row] = v; if constexpr (!KEPT) row_mask[row] = 1; }
         }
         row_of_token[v] = row;
     }
     if constexpr (!KEPT) {
-        if ((int)blockIdx.x == nb_compact - 1 && threadIdx.x == 0)
-            *counter = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]) + s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        if ((int)blockIdx.x == nb_compact - 1 && threadIdx.x == 0) *counter = base + r.total;
     } else {
         const int total = (s_all[0] + s_all[1]) + (s_all[2] + s_all[3]);
         if (v < KS.mask_bytes) row_mask[v] = v < min(total, cap) ? 1 : 0;
@@ -1290,17 +1287,14 @@ struct ProdLayout {      // byte offsets inside the workspace
 int g_conv_mode = -1;     // -1: unset -> RBR_CONV_MODE env ("dense" | "product") or auto; 0 auto, 1 dense, 2 product
 
 bool prod_applicable(const rbr_textcnn_desc* d) {
-    static const char* env = getenv("RBR_CONV_MODE");
-    const char* mode = g_conv_mode == 1 ? "dense" : g_conv_mode == 2 ? "product" : g_conv_mode == 0 ? nullptr : env;
-    if (mode && !strcmp(mode, "dense")) return false;
+    const int mode = forced_conv_mode();
+    if (mode == 1) return false;
     if (!desc_valid(d)) return false;                      // nothing below may index d->kz / d->ch of an unchecked descriptor
     const long n_pos = (long)d->n_docs * d->L;
     const int Cp = prod_channels(d).cp_real;
     if (Cp > 30000) return false;                          // slot ids are 16-bit
     if ((Cp + kTile - 1) / kTile > kMaxGroups * kProdGroupTiles) return false;
-    if (mode && !strcmp(mode, "product")) return true;
-    // auto: worth it when the vocabulary bounds the distinct tokens well below the position count
-    return (long)d->V * 5 <= n_pos * 2 && n_pos >= 4096;
+    return mode == 2 || token_rows_pay(d->V, n_pos);
 }
 
 // RBR_DTABLE_MODE=scatter: no table gradient through a token list, the window scatter everywhere
@@ -1308,8 +1302,6 @@ bool dtable_scatter_forced() {
     static const char* env = getenv("RBR_DTABLE_MODE");
     return env && !strcmp(env, "scatter");
 }
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 bool prod_layout(const rbr_textcnn_desc* d, ProdLayout& Lo) {
     const long n_pos = (long)d->n_docs * d->L;

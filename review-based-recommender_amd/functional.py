@@ -2165,8 +2165,9 @@ def _region_or_timed():
 
 
 def _token_rows_pay(V: int, B: int, L: int) -> bool:
-    """The distinct-token rows of a tower's [B, L] documents pay: enough positions per vocabulary entry (the same rule as the
-    token-product conv), and RBR_DATT_ROWS=0 does not switch them off."""
+    """The distinct-token rows of a tower's [B, L] documents pay: enough positions per vocabulary entry, and RBR_DATT_ROWS=0
+    does not switch them off.  The rule is token_rows_pay() of csrc/rbr_common.h (the token-product conv and local gate); this
+    is its copy for rbr_datt_token_rows, whose workspace query answers for every shape."""
     return not (V * 5 > B * L * 2 or B * L < 4096 or os.environ.get("RBR_DATT_ROWS", "1") == "0")
 
 

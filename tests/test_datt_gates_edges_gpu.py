@@ -411,7 +411,105 @@ def test_local_gate_prod_shared_rows_bit_equal_private(shape, accumulate):
     assert torch.equal(got_s["dw"], got_p["dw"]) and torch.equal(got_s["db0"], got_p["db0"])
 
 
-# ------------------------------------------------------------------------------------------------------------------ 5. refusals
+# -------------------------------------------------------------------------------------------------- 5. the row maps themselves
+def _uniform(lo=0, hi=None):
+    return lambda B, L, V, g: torch.randint(lo, V if hi is None else hi, (B, L), generator=g)
+
+
+# name: (B, L, V, ids(B, L, V, generator)) -- the edges of the ranking: block_rank_256 (rbr_wave.h) in gp_count_kernel and
+# gp_compact_kernel, one workgroup per 256 vocabulary entries
+ROW_MAP_CASES = {
+    "one token, one position": (1, 1, 1, lambda B, L, V, g: torch.zeros(B, L, dtype=I64)),
+    "V 255": (2, 40, 255, _uniform()),                       # one block, not full
+    "V 256": (2, 40, 256, _uniform()),                       # one block, exactly full
+    "V 257": (2, 40, 257, _uniform()),                       # one token into a second block
+    "only token 256": (2, 40, 257, lambda B, L, V, g: torch.full((B, L), 256, dtype=I64)),      # the last block holds the only mark
+    "empty leading blocks": (2, 64, 1000, _uniform(600, 1000)),                                 # base from zero block counts
+    "one row": (4, 100, 300, lambda B, L, V, g: torch.full((B, L), 7, dtype=I64)),
+    "cap full": (1, 70, 5000, lambda B, L, V, g: torch.randperm(V, generator=g)[:B * L].view(B, L)),      # cap = B * L < V
+    "all waves full": (4, 64, 64, lambda B, L, V, g: torch.stack([torch.randperm(V, generator=g) for _ in range(B)])),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _row_maps(name):
+    """The ids of a case (host), and what rbr_datt_token_rows built for them, read through rbr_datt_token_rows_maps: n_rows,
+    row_of_token [V], tok_of_row [cap] (all of it, not only the listed rows) and cap, as numpy arrays."""
+    import ctypes as C
+    from review_based_recommender_amd import _lib
+    B, L, V, make = ROW_MAP_CASES[name]
+    ids = make(B, L, V, torch.Generator().manual_seed(zlib.crc32(name.encode())))
+    assert ids.shape == (B, L) and ids.dtype == I64 and 0 <= int(ids.min()) and int(ids.max()) < V
+    rows = _token_rows(ids.to(DEV), V)
+    torch.cuda.synchronize()
+    rot, n, tor, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+    assert _lib.lib().rbr_datt_token_rows_maps(B, L, V, rows.data_ptr(), C.byref(rot), C.byref(n), C.byref(tor), C.byref(cap)) == 0
+
+    def view(ptr, count):
+        o = ptr.value - rows.data_ptr()
+        assert 0 <= o and o + 4 * count <= rows.numel()
+        return rows[o:o + 4 * count].view(torch.int32).cpu().numpy()
+
+    return ids, int(view(n, 1)[0]), view(rot, V), view(tor, cap.value), cap.value
+
+
+@pytest.mark.parametrize("name", list(ROW_MAP_CASES))
+def test_token_rows_maps_exact(name):
+    """rbr_datt_token_rows against numpy: with u = np.unique(ids), n_rows == len(u), tok_of_row[:n_rows] == u, row_of_token[u] ==
+    arange(len(u)) and -1 at every other vocabulary entry.  Integers, no tolerance, no element left out."""
+    B, L, V, _ = ROW_MAP_CASES[name]
+    ids, n_rows, row_of_token, tok_of_row, cap = _row_maps(name)
+    u = np.unique(ids.numpy())
+    assert cap == min(V, B * L)
+    assert n_rows == len(u)
+    assert np.array_equal(tok_of_row[:n_rows], u)
+    want = np.full(V, -1, dtype=np.int32)
+    want[u] = np.arange(len(u), dtype=np.int32)
+    assert np.array_equal(row_of_token, want)
+
+
+@pytest.mark.parametrize("name", ["V 257", "empty leading blocks", "cap full"])
+def test_conv_token_list_equals_gate_row_maps(name):
+    """The token-product conv's list (compact_block<false> of textcnn_prod.hip: byte marks, the self-initialising prepare stage
+    rbr_textcnn_prod_prepare on a 0xAB-filled workspace) on the same unmasked ids, a one-bank conv with the product form forced:
+    the same n_rows, the same row_of_token, and tok_of_row (int64 there) equal to the gates' after the cast to int32.  The kept
+    chain (compact_block<true>) is tied to this one by test_prepare_two_launch_gpu.py."""
+    import ctypes as C
+    from review_based_recommender_amd import _lib, functional as RF
+    from review_based_recommender_amd._lib import dev_ptr, ptr_array
+    L_ = _lib.lib()
+    B, L, V, _ = ROW_MAP_CASES[name]
+    ids, n_rows, row_of_token, tok_of_row, cap = _row_maps(name)
+    table = torch.zeros(V, 8, device=DEV)
+    ws = [torch.zeros(5, 8, 3, device=DEV)]
+    L_.rbr_set_conv_mode(2)
+    try:
+        desc = RF._conv_desc(table, B, L, ws, RF.PAD_SAME, RF.ACT_RELU, 0)
+        rec = RF._conv_fwd_buffers(type("Rec", (), {})(), desc, torch.device(DEV))
+        assert rec.prod_ws is not None
+        rec.prod_ws.fill_(0xAB)
+        ids_dev = ids.to(DEV)
+        rc = L_.rbr_textcnn_prod_prepare(C.byref(desc), dev_ptr(ids_dev, I64, "ids"), None, ptr_array(ws, F32, "w"),
+                                         dev_ptr(rec.pidx, torch.int32, "pidx"), rec.prod_ws.data_ptr(), _lib.current_stream())
+        assert rc == 0, L_.rbr_last_error()
+        torch.cuda.synchronize()
+        rot, n, tor, ccap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        assert L_.rbr_textcnn_token_list(C.byref(desc), rec.prod_ws.data_ptr(), C.byref(rot), C.byref(n), C.byref(tor), C.byref(ccap)) == 0
+    finally:
+        L_.rbr_set_conv_mode(0)
+
+    def view(ptr, nbytes, dtype):
+        o = ptr.value - rec.prod_ws.data_ptr()
+        return rec.prod_ws[o:o + nbytes].view(dtype).cpu().numpy()
+
+    assert ccap.value == cap
+    assert int(view(n, 4, torch.int32)[0]) == n_rows
+    assert np.array_equal(view(rot, 4 * V, torch.int32), row_of_token)
+    conv_tok = view(tor, 8 * cap, torch.int64)[:n_rows]
+    assert np.array_equal(conv_tok.astype(np.int32), tok_of_row[:n_rows]) and int(conv_tok.max()) < V
+
+
+# ------------------------------------------------------------------------------------------------------------------ 6. refusals
 REFUSALS = {
     # name: ((B, L, E, kw, V), is_global, what the RuntimeError and -- for the C entry points -- rbr_last_error() must name)
     "even win": ((2, 10, 4, 4, 9), False, ("window must be odd", "got 4")),
