@@ -289,7 +289,19 @@ int rbr_textcnn_bwd_dw_from_g(const rbr_textcnn_desc* d, const float* table, con
  *                                    sorted by token, each token's row is accumulated in LDS in 64-bit fixed point (2^-40
  *                                    units, integer atomics: independent of the order, so replicas stay bit-identical) and
  *                                    multiplied by Wprod^T.  W: HOST array of the conv weights;
- *                                    ws: rbr_textcnn_dtable_from_taps_ws_bytes(d, n_sets) bytes (0: unsupported, D % 4 != 0). */
+ *                                    ws: rbr_textcnn_dtable_from_taps_ws_bytes(d, n_sets) bytes (0: unsupported, D % 4 != 0).
+ *                                    Value domain.  A token with at most 16 taps is summed in f32 in array order: no fixed
+ *                                    point, and a tap of any value (non-finite ones included) is carried through into its row
+ *                                    as f32 arithmetic carries it.  A token with more than 16 taps takes the fixed-point path:
+ *                                      - every tap is rounded to a multiple of 2^-40, so its share of the mean is resolved to
+ *                                        2^-41 / n_sets (half a unit; 4.5e-13 at n_sets = 1) -- gradients much smaller than that
+ *                                        lose their low bits there;
+ *                                      - a tap with |val| > 8e6, or a NaN / inf one, makes the token's whole row NaN (as a dense
+ *                                        all-reduce would propagate it) and touches no other row;
+ *                                      - a cell -- the taps of one token in one product column (bank, tap j, channel) -- whose
+ *                                        exact sum leaves +-2^23 (8.4e6) is OUTSIDE the domain: the 64-bit sum wraps and the row
+ *                                        is silently wrong.  Nothing checks it: two taps below the per-tap limit can do it, and
+ *                                        an exact check would put an overflow test on every integer atomic of the hot loop. */
 size_t rbr_textcnn_taps_count(const rbr_textcnn_desc* d);
 int rbr_textcnn_bwd_taps(const rbr_textcnn_desc* d, const int64_t* ids, const uint8_t* mask, const float* feat,
                          const int32_t* argmax, const float* d_feat, int32_t* tok, float* val, void* stream);
