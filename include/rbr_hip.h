@@ -711,6 +711,36 @@ int rbr_review_gather(int32_t B, int32_t R, int32_t T, const int64_t* u_ids, con
                       int32_t leave_one_out, int64_t pad_token, int64_t replace_id, int64_t* revs_out, uint8_t* word_masks_out,
                       uint8_t* rev_masks_out, int64_t* rids_out, int64_t* ids_out, int64_t* err, void* stream);
 
+/* ---- id-fed TRAIN batch of the review split with review sampling: the reference's sample_train_review
+ *      (trainer/train_simple_siamese.py:346-368 -- each time a training example is fetched, a fresh uniform random subset of
+ *      u_rv_num / i_rv_num of its non-empty reviews, in shuffled order, padded with empty reviews) inside the gather launch.
+ *      Arguments and outputs are those of rbr_review_gather, with: a pool of P slots to draw from, R <= P <= 63 -- the tables
+ *      are [N, P+1, T] / [N, P+1] int32; the reviews kept per side, n_user / n_item in [1, R]; seed; state (2 x uint64 in device
+ *      memory, [call number, ticket], the convention of rbr_sample_negatives); and slots_out int32 [2B, R] (or NULL): the table
+ *      slot each output slot was copied from, -1 for an empty one.
+ *      THE DRAW (integers only; a host restatement gives the same outputs).  Output row r in [0, 2B) of side s (0: r < B) has
+ *      own id a -- checked and replaced as in rbr_review_gather -- and counterpart c, the other side's id of the pair as given
+ *      (unchecked); call = state[0].
+ *        1. d = the first j in [0, P) with rids[a][j] == c when leave_one_out = 1 and 0 < c < rows of the other side; else d = P.
+ *        2. candidate q in [0, P) reads table slot src(q) = q + (q >= d): rbr_review_gather's rule with P in place of R.
+ *        3. live(q): review src(q) has a token != pad_token (the reference's np.nonzero(np.sum(revs, axis=1))).
+ *        4. key(q) = word (e & 3) of Philox4x32-10 with counter (e >> 2, call) and key seed, e = r * 64 + q -- the generator of
+ *           rbr_sample_negatives.
+ *        5. the m live candidates ordered by (key ascending, q ascending); k_s = min(n_s, m); output slot k < k_s is the k-th of
+ *           them: its tokens, word mask, review mask 1, its rid, slots_out = src(q).
+ *        6. output slots k_s <= k < R are empty reviews: pad_token in every position, masks 0, rid 0, slots_out = -1.
+ *      Every subset of k_s live candidates in every order is equally likely up to the tie-break by q between equal 32-bit keys, a
+ *      bias of order 2^-32 that is left as it is.  Liveness is read from the tokens at launch (the row's (P + 1) * T tokens).
+ *      Every workgroup reads state[0] first and, behind a workgroup barrier, one thread of it takes the ticket; the last one
+ *      resets the ticket and stores state[0] + 1: a launch recorded into a graph draws a new set on every replay.
+ *      One launch, one wave per output row, no sync, no allocation, static shapes: graph-capturable.  B <= 2^30.        ---- */
+int rbr_review_sample_gather(int32_t B, int32_t R, int32_t T, int32_t P, const int64_t* u_ids, const int64_t* i_ids,
+                             const int32_t* user_revs, const int32_t* user_rids, int32_t U, const int32_t* item_revs,
+                             const int32_t* item_rids, int32_t I, int32_t leave_one_out, int32_t n_user, int32_t n_item,
+                             int64_t pad_token, int64_t replace_id, uint64_t seed, uint64_t* state, int64_t* revs_out,
+                             uint8_t* word_masks_out, uint8_t* rev_masks_out, int64_t* rids_out, int64_t* ids_out,
+                             int32_t* slots_out, int64_t* err, void* stream);
+
 /* ---- negatives for a pairwise objective, in front of either id feed: for each of the B observed pairs (u_ids[b], i_ids[b]),
  *      n_neg >= 1 items of [item_lo, I) that are neither i_ids[b] nor in the user's seen row, with replacement across j.
  *      seen_off int64 [U + 1] / seen_item int32 [seen_nnz]: the CSR rbr_pair_score_topk takes for its exclusion (sorted within a

@@ -389,25 +389,37 @@ class DeviceReviewCache:
     from meta, and id 0, are all-pad rows.  Tokens were range-checked against the vocabulary and rids against the other side's
     id count once, here, so a gathered batch needs no per-step check.  `.user` / `.item` / `.user_rids` / `.item_rids` are the
     first R slots -- the valid rule, what recommend.Recommender encodes.  With device "cpu" the same methods run a plain torch
-    restatement of the kernel (host tests, cross-checks)."""
+    restatement of the kernel (host tests, cross-checks).
+
+    pool = P (rv_num <= P <= 63; None: today's object, nothing more is resident): the review SAMPLER's tables
+    (`user_pool_table` / `user_pool_rid_table` and the item side's) hold P + 1 slots per id, so sampled_feed() draws a train
+    example's reviews from the id's first P reviews instead of its first rv_num.  Everything above keeps its meaning and its
+    bytes: the plain tables, gather and feed read the first R + 1 slots only."""
 
     PAD = 0
     ORDER = {"narre": ("revs", "word_masks", "ids", "rids"), "simple_siamese": ("revs", "word_masks", "rev_masks", "ids")}
+    MAX_POOL = 63        # one lane of a wave per table slot (csrc/review_sample.hip)
 
-    def __init__(self, ds, device):
+    def __init__(self, ds, device, pool=None):
         self.device = torch.device(device)
         self.rv_num, self.rv_len = int(ds.rv_num), int(ds.rv_len)
         R = self.rv_num
+        if pool is not None and (isinstance(pool, bool) or not isinstance(pool, int) or not R <= pool <= self.MAX_POOL):
+            raise ValueError(f"pool must be an integer in [rv_num = {R}, {self.MAX_POOL}], got {pool!r}")
+        self.pool = R if pool is None else pool
         tabs = {}
         for side, revs, rids, n, n_other in (("user", ds.user_reviews, ds.user_rids, ds.user_num, ds.item_num),
                                              ("item", ds.item_reviews, ds.item_rids, ds.item_num, ds.user_num)):
-            tab, rid = _review_tables(revs, rids, n, R + 1, self.rv_len)
+            tab, rid = _review_tables(revs, rids, n, self.pool + 1, self.rv_len)
             _check_range(tab, ds.vocab_size, f"meta.pkl {side}_reviews tokens")
             _check_range(rid, n_other, f"meta.pkl {side}_rids")
             tab[0] = self.PAD                   # id 0 is the padding id: the row a bad id is replaced by
             rid[0] = 0
-            tabs[side] = (tab.to(torch.int32).to(self.device), rid.to(torch.int32).to(self.device))
-        (self.user_table, self.user_rid_table), (self.item_table, self.item_rid_table) = tabs["user"], tabs["item"]
+            wide = (tab.to(torch.int32).to(self.device), rid.to(torch.int32).to(self.device))
+            # the plain gather takes contiguous [N, R + 1, ..] tables: with a wider pool, its own copies of the leading slots
+            tabs[side] = wide + (wide if self.pool == R else (wide[0][:, :R + 1].contiguous(), wide[1][:, :R + 1].contiguous()))
+        (self.user_pool_table, self.user_pool_rid_table, self.user_table, self.user_rid_table) = tabs["user"]
+        (self.item_pool_table, self.item_pool_rid_table, self.item_table, self.item_rid_table) = tabs["item"]
         self.user, self.item = self.user_table[:, :R], self.item_table[:, :R]
         self.user_rids = self.user_rid_table[:, :R].to(torch.int64)
         self.item_rids = self.item_rid_table[:, :R].to(torch.int64)
@@ -453,6 +465,84 @@ class DeviceReviewCache:
         the trainer take for `cache`.  leave_one_out=True rebuilds train examples, False valid / test examples."""
         return ReviewFeed(self, kind, leave_one_out)
 
+    def sampled_feed(self, kind: str, n_user=None, n_item=None, seed: int = 0) -> "SampledReviewFeed":
+        """The TRAIN feed of model `kind` with review sampling (the reference's sample_train_review, u_rv_num = n_user, i_rv_num =
+        n_item; None: rv_num): every gather keeps a fresh uniform random subset of each row's non-empty candidate reviews -- the
+        id's first `pool` reviews less the pair's own -- in random order, in rv_num slots with an empty tail."""
+        return SampledReviewFeed(self, kind, n_user, n_item, seed)
+
+    def sample_gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, n_user: int, n_item: int, seed: int, state: torch.Tensor,
+                      revs=None, word_masks=None, rev_masks=True, rids=True, ids=True, slots=None):
+        """functional.review_sample_gather over the pool tables, leave-one-out (stacked outputs, user rows first, plus the slots);
+        on the cpu, the host restatement of the draw, which advances state[0] itself."""
+        u_ids, i_ids = u_ids.to(self.device, non_blocking=True), i_ids.to(self.device, non_blocking=True)
+        if self.device.type == "cuda":
+            from . import functional as RF
+            return RF.review_sample_gather(u_ids, i_ids, self.user_pool_table, self.user_pool_rid_table, self.item_pool_table,
+                                           self.item_pool_rid_table, self.rv_num, n_user, n_item, state=state, seed=seed,
+                                           leave_one_out=True, pad_token=self.PAD, replace_id=0, revs=revs, word_masks=word_masks,
+                                           rev_masks=rev_masks, rids=rids, ids=ids, slots=slots)
+        got = self._sample_gather_host(u_ids, i_ids, n_user, n_item, seed, int(state[0]))
+        state[0] += 1
+        outs = []
+        for n, (val, dst) in enumerate(zip(got, (revs, word_masks, rev_masks, rids, ids, slots))):
+            if torch.is_tensor(dst):
+                outs.append(dst.copy_(val))
+            else:
+                outs.append(val if dst is True or (dst is None and n < 2) else None)
+        return tuple(outs)
+
+    def _sample_gather_host(self, u_ids, i_ids, n_user: int, n_item: int, seed: int, call: int):
+        """THE DRAW of include/rbr_hip.h (rbr_review_sample_gather) in numpy, for call number `call`."""
+        import numpy as np
+        R, P, T, B = self.rv_num, self.pool, self.rv_len, u_ids.shape[0]
+        u, i = u_ids.numpy().astype(np.int64), i_ids.numpy().astype(np.int64)
+        q = np.arange(P, dtype=np.int64)
+        k = np.arange(R, dtype=np.int64)
+        outs = []
+        for side, (own, other, tab, rid, n_other, keep) in enumerate(
+                ((u, i, self.user_pool_table, self.user_pool_rid_table, self.item_pool_table.shape[0], n_user),
+                 (i, u, self.item_pool_table, self.item_pool_rid_table, self.user_pool_table.shape[0], n_item))):
+            _check_range(own, tab.shape[0], "ids of a gathered batch")
+            rr = rid.numpy()[own].astype(np.int64)                                  # [B, P + 1]
+            rv = tab.numpy()[own].astype(np.int64)                                  # [B, P + 1, T]
+            hit = (rr[:, :P] == other[:, None]) & ((other > 0) & (other < n_other))[:, None]
+            d = np.where(hit.any(1), hit.argmax(1), P)                              # the FIRST match, else P
+            src = q[None, :] + (q[None, :] >= d[:, None])                           # [B, P]
+            live = np.take_along_axis((rv != self.PAD).any(-1), src, 1)
+            e = ((np.arange(B, dtype=np.uint64) + np.uint64(side * B))[:, None] * np.uint64(64) + q[None, :].astype(np.uint64))
+            words = np.stack(_philox4x32_10(e >> np.uint64(2), call, seed))         # [4, B, P]
+            key = np.take_along_axis(words, (e & np.uint64(3)).astype(np.int64)[None], 0)[0]
+            # live candidates first, by (key, q): a dead one sorts behind every 32-bit key
+            order = np.argsort(np.where(live, key, np.uint64(1) << np.uint64(32)) * np.uint64(64) + q[None, :].astype(np.uint64), 1)
+            filled = k[None, :] < np.minimum(keep, live.sum(1))[:, None]            # [B, R]
+            slot = np.where(filled, np.take_along_axis(src, order[:, :R], 1), -1)
+            at = np.maximum(slot, 0)
+            revs = np.where(filled[:, :, None], np.take_along_axis(rv, at[:, :, None], 1), self.PAD)
+            rids = np.where(filled, np.take_along_axis(rr, at, 1), 0)
+            outs.append((revs, rids, slot))
+        revs2 = torch.from_numpy(np.concatenate([o[0] for o in outs]))
+        rids2 = torch.from_numpy(np.concatenate([o[1] for o in outs]))
+        slots2 = torch.from_numpy(np.concatenate([o[2] for o in outs]).astype(np.int32))
+        wm = revs2 != self.PAD
+        return revs2, wm, wm.any(-1), rids2, torch.cat([u_ids, i_ids]), slots2
+
+
+def _philox4x32_10(quad, call: int, seed: int):
+    """The four words of the Philox4x32-10 block with counter (quad, call) under key `seed` (csrc/rbr_rng.h): quad a uint64 numpy
+    array, words as uint64 arrays below 2^32."""
+    import numpy as np
+    lo, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    c0, c1 = quad & lo, quad >> s32
+    c2 = np.full_like(quad, call & 0xFFFFFFFF)
+    c3 = np.full_like(quad, (call >> 32) & 0xFFFFFFFF)
+    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
+        c0, c1, c2, c3 = (p1 >> s32) ^ c1 ^ np.uint64(k0), p1 & lo, (p0 >> s32) ^ c3 ^ np.uint64(k1), p0 & lo
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return c0, c1, c2, c3
+
 
 class ReviewFeed:
     """One model's view of a DeviceReviewCache under one rule: empty_inputs / gather / inputs with DeviceDocCache's meaning, in
@@ -478,6 +568,11 @@ class ReviewFeed:
     def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None):
         """The pairs' batch, stacked ({name: [2B, ...]} in the model's order).  `out`: the model's eight arguments to write into
         instead, each (user, item) pair adjacent in one allocation -- the input views of a recorded step."""
+        got = self.cache.gather(u_ids, i_ids, self.leave_one_out, **self._outputs(out))
+        return dict(zip(("revs", "word_masks", "rev_masks", "rids", "ids"), got))
+
+    def _outputs(self, out):
+        """The cache's output arguments for `out`: the model's own outputs (allocated, or the stacked views of `out`), no others."""
         if out is None:
             kw = {k: True for k in self.order if k not in ("revs", "word_masks")}
         else:
@@ -486,14 +581,49 @@ class ReviewFeed:
             kw = {k: _adjacent(out[2 * n], out[2 * n + 1]) for n, k in enumerate(self.order)}
         for k in ("rev_masks", "rids", "ids"):
             kw.setdefault(k, None)
-        got = self.cache.gather(u_ids, i_ids, self.leave_one_out, **kw)
-        return dict(zip(("revs", "word_masks", "rev_masks", "rids", "ids"), got))
+        return kw
 
     def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
         """The model's arguments for the pairs -- views of one gather."""
         B = u_ids.shape[0]
         got = self.gather(u_ids, i_ids)
         return tuple(half for k in self.order for half in (got[k][:B], got[k][B:]))
+
+
+class SampledReviewFeed(ReviewFeed):
+    """ReviewFeed under the train rule with the reference's review sampling (trainer/train_simple_siamese.py:346-368,
+    sample_train_review): every gather keeps n_user / n_item (the reference's u_rv_num / i_rv_num; None: rv_num) of each row's
+    non-empty candidate reviews, a fresh uniform random subset in random order, and pads to rv_num slots with empty reviews.  The
+    candidates are the id's first cache.pool reviews less the pair's own, so with pool > rv_num reviews that truncation drops
+    reach training.  Shapes, dtypes and protocol are ReviewFeed's: models, recorded input blocks and wrappers (NegativeFeed,
+    InBatchFeed) take it unchanged, and a recorded gather draws anew on every replay.
+
+    `state`: int64 [2] on the feed's device, [call number, ticket] (csrc/rbr_rng.h); the launch advances the call number, on the
+    cpu the host restatement does.  reseed(seed, call) restarts the sequence: (seed, call) fixes a draw exactly
+    (include/rbr_hip.h, rbr_review_sample_gather).  `slots` of the last gather's dict: None unless asked for (gather(slots=True))."""
+
+    def __init__(self, cache: DeviceReviewCache, kind: str, n_user=None, n_item=None, seed: int = 0):
+        super().__init__(cache, kind, True)
+        R = cache.rv_num
+        self.n_user, self.n_item = (R if n is None else n for n in (n_user, n_item))
+        for name, n in (("n_user", self.n_user), ("n_item", self.n_item)):
+            if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= R:
+                raise ValueError(f"{name} must be an integer in [1, rv_num = {R}], got {n!r}")
+        self.seed = int(seed)
+        self.state = torch.zeros(2, dtype=torch.int64, device=self.device)
+
+    def reseed(self, seed: int, call: int = 0) -> None:
+        """The next draw is call number `call` under `seed` (no host synchronisation: one small copy on the current stream).
+        A recorded step holds the seed it was recorded with: reseed it with that seed, to move the call number only."""
+        self.seed = int(seed)
+        self.state.copy_(torch.tensor([int(call), 0], dtype=torch.int64), non_blocking=True)
+
+    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None, slots=None):
+        """ReviewFeed.gather with the draw of the feed's next call number; `slots`: True / an int32 [2B, R] tensor for the table
+        slot behind every output slot (-1: empty)."""
+        got = self.cache.sample_gather(u_ids, i_ids, self.n_user, self.n_item, self.seed, self.state, slots=slots,
+                                       **self._outputs(out))
+        return dict(zip(("revs", "word_masks", "rev_masks", "rids", "ids", "slots"), got))
 
 
 class NegativeFeed:

@@ -255,6 +255,60 @@ def review_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_revs: torch.Ten
     return revs, word_masks, rev_masks, rids, ids
 
 
+def review_sample_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_revs: torch.Tensor, user_rids: torch.Tensor,
+                         item_revs: torch.Tensor, item_rids: torch.Tensor, R: int, n_user: int, n_item: int, *, state, seed: int = 0,
+                         leave_one_out: bool = True, pad_token: int = 0, replace_id: int = 0, revs: Optional[torch.Tensor] = None,
+                         word_masks: Optional[torch.Tensor] = None, rev_masks=True, rids=True, ids=True, slots=None):
+    """The id-fed TRAIN batch of the review split with review sampling (rbr_review_sample_gather, one launch): review_gather's
+    outputs with R slots per row, of which the leading min(n_side, live) hold a fresh uniform random subset of the row's live
+    candidate reviews in random order and the rest are empty reviews -- the reference's sample_train_review
+    (trainer/train_simple_siamese.py:346-368).  Tables: user_revs [U, P+1, T] / user_rids [U, P+1], item_revs [I, P+1, T] /
+    item_rids [I, P+1], int32, R <= P <= 63: the candidates are the P slots that review_gather's rule with P in place of R gives;
+    a candidate is live when its review holds a token != pad_token.  The draw is stated in include/rbr_hip.h.
+
+    `state`: int64 [2] on the device, [call number, 0]; the launch advances the call number itself, so two calls (or two replays
+    of a recorded call) draw different sets, and (seed, call number) fixes a set exactly.
+    Returns (revs2, word_masks2, rev_masks2, rids2, ids2, slots2): the first five as review_gather's (`revs` / `word_masks`:
+    tensors to write into or None to allocate; `rev_masks` / `rids` / `ids`: a tensor, True to allocate, None / False to leave out);
+    slots2 int32 [2B, R] -- the table slot each output slot was copied from, -1 for an empty one -- under the same convention
+    (default: left out).  No autograd, no sync: graph-capturable."""
+    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
+        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+    if user_revs.dim() != 3 or item_revs.dim() != 3 or user_revs.shape[1:] != item_revs.shape[1:] or user_revs.shape[1] < 2:
+        raise RuntimeError(f"review tables must be [U, P+1, T] / [I, P+1, T], got {tuple(user_revs.shape)} / {tuple(item_revs.shape)}")
+    B, P, T, R = u_ids.shape[0], user_revs.shape[1] - 1, user_revs.shape[2], int(R)
+    if user_rids.shape != (user_revs.shape[0], P + 1) or item_rids.shape != (item_revs.shape[0], P + 1):
+        raise RuntimeError(f"rid tables must be [U, {P + 1}] / [I, {P + 1}], got {tuple(user_rids.shape)} / {tuple(item_rids.shape)}")
+    if state.shape != (2,) or state.dtype != I64:
+        raise RuntimeError(f"state must be int64 [2], got {state.dtype} {tuple(state.shape)}")
+    if R < 1:
+        raise RuntimeError(f"R must be >= 1, got {R}")
+    dev = u_ids.device
+    if revs is None:
+        revs = torch.empty(2 * B, R, T, dtype=I64, device=dev)
+    if word_masks is None:
+        word_masks = torch.empty(2 * B, R, T, dtype=torch.bool, device=dev)
+    rev_masks = torch.empty(2 * B, R, dtype=torch.bool, device=dev) if rev_masks is True else (None if rev_masks is False else rev_masks)
+    rids = torch.empty(2 * B, R, dtype=I64, device=dev) if rids is True else (None if rids is False else rids)
+    ids = torch.empty(2 * B, dtype=I64, device=dev) if ids is True else (None if ids is False else ids)
+    slots = torch.empty(2 * B, R, dtype=I32, device=dev) if slots is True else (None if slots is False else slots)
+    for name, t, shape, dtype in (("revs", revs, (2 * B, R, T), I64), ("word_masks", word_masks, (2 * B, R, T), torch.bool),
+                                  ("rev_masks", rev_masks, (2 * B, R), torch.bool), ("rids", rids, (2 * B, R), I64),
+                                  ("ids", ids, (2 * B,), I64), ("slots", slots, (2 * B, R), I32)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}, got {t.dtype} {list(t.shape)}")
+    if B == 0:
+        return revs, word_masks, rev_masks, rids, ids, slots
+    _call(None, _lib.lib().rbr_review_sample_gather, B, R, T, P, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),
+          dev_ptr(user_revs, I32, "user_revs"), dev_ptr(user_rids, I32, "user_rids"), user_revs.shape[0],
+          dev_ptr(item_revs, I32, "item_revs"), dev_ptr(item_rids, I32, "item_rids"), item_revs.shape[0],
+          int(bool(leave_one_out)), int(n_user), int(n_item), int(pad_token), int(replace_id), int(seed) & 0xFFFFFFFFFFFFFFFF,
+          dev_ptr(state, I64, "state"), dev_ptr(revs, I64, "revs"), dev_ptr(word_masks.view(U8), U8, "word_masks"),
+          dev_ptr(None if rev_masks is None else rev_masks.view(U8), U8, "rev_masks"), dev_ptr(rids, I64, "rids"),
+          dev_ptr(ids, I64, "ids"), dev_ptr(slots, I32, "slots"), _id_err(dev).data_ptr(), current_stream())
+    return revs, word_masks, rev_masks, rids, ids, slots
+
+
 def set_tap_sink(sink, table: Optional[torch.Tensor] = None) -> None:
     """Installs `sink` for the word table it exchanges (sink.table); set_tap_sink(None, table) removes that table's sink,
     set_tap_sink(None) removes all of them."""

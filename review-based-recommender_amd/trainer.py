@@ -1,6 +1,6 @@
 """Trainer-equivalent entry point: the behaviour of the reference's
 trainer/train_{deepconn_pp,narre,dual_att}.py on top of the HIP modules (plus `--model simple_siamese` on the review
-split: plain Adam, none of train_simple_siamese.py's SparseAdam / scheduler / review sampling).
+split: plain Adam, none of train_simple_siamese.py's SparseAdam / scheduler; its review sampling is `sample_train_review`).
 
     python -m review_based_recommender_amd.trainer --model deepconn --config cfg.json
     python -m torch.distributed.run --nproc-per-node 8 -m review_based_recommender_amd.trainer --model deepconn --config cfg.json
@@ -31,6 +31,12 @@ selection and early stopping, is unchanged;
 GPU (data.DeviceReviewCache), the loaders ship (u_id, i_id, rating) and one launch rebuilds the batch -- training examples with
 the pair's own review left out, validation examples plain (the loaders check once that every example is what that rule gives
 for its ids); eval_from_towers works on top of it;
+`sample_train_review: true` (with device_reviews, one process; `u_rv_num` / `i_rv_num` default rv_num, `review_pool` default rv_num,
+`review_sample_seed` default `seed`) is train_simple_siamese.py:346-368 inside that launch: every training batch keeps a fresh
+uniform random subset of u_rv_num / i_rv_num of each example's non-empty reviews, in random order, in rv_num slots with an empty
+tail (data.SampledReviewFeed); the subset is drawn from the id's first review_pool (<= 63) reviews less the pair's own, so a pool
+above rv_num lets reviews that truncation drops reach training.  Validation batches stay plain.  The draw is counter-based --
+fixed by (review_sample_seed, step, row) -- where the reference uses numpy's global generator;
 `loss: "bpr"` (with device_cache or device_reviews, one process; `n_neg: 1`, `neg_seed` = `seed`) trains for ranking instead of
 rating regression: every batch pair is joined by n_neg items its user has not rated in the training split, drawn on the device
 (data.NegativeFeed), and the step minimises -log sigmoid(score(u, i+) - score(u, i-)) (train_step.BprObjective); the step log line
@@ -88,7 +94,8 @@ DEFAULTS = dict(log_dir="logs", dataset="dataset", log=True, log_idx=500, verbos
                 batch_size=50, lr=0.002, max_grad_norm=5.0, patience=5, dropout=0.5, arch="CNN", use_pretrain=False,
                 num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False, eval_from_towers=False,
                 device_reviews=False, rank_metrics=[], loss="mse", n_neg=1, neg_seed=None, select_by="rmse",
-                softmax_temperature=1.0, logq_correction=False, neg_candidates=1, neg_refresh_steps=0)
+                softmax_temperature=1.0, logq_correction=False, neg_candidates=1, neg_refresh_steps=0, sample_train_review=False,
+                u_rv_num=None, i_rv_num=None, review_pool=None, review_sample_seed=None)
 
 LOSSES = ("mse", "bpr", "softmax")
 
@@ -103,6 +110,16 @@ def _rank_metric_of(select_by):
     if name in ("hr", "ndcg") and k.isdigit() and int(k) >= 1 and str(int(k)) == k:
         return name, int(k)
     raise ValueError(f"select_by must be \"rmse\", \"hr@K\", \"ndcg@K\" or \"mrr\", got {select_by!r}")
+
+
+def _feed_states(feed):
+    """The device-resident call numbers (`state`) of an id feed and of the feeds it wraps (`.feed`), outermost first."""
+    states = []
+    while feed is not None:
+        if hasattr(feed, "state"):
+            states.append(feed.state)
+        feed = getattr(feed, "feed", None)
+    return states
 
 
 class _ShardSampler(torch.utils.data.Sampler):
@@ -255,6 +272,19 @@ class ReviewExperiment:
             if metric is None:
                 raise ValueError("loss \"softmax\" needs a rank metric in select_by (\"hr@K\", \"ndcg@K\" or \"mrr\"): a "
                                  "ranking loss does not fit ratings, so the validation RMSE cannot select the model")
+        if bool(args.sample_train_review):
+            if not bool(args.device_reviews):
+                raise ValueError("sample_train_review needs device_reviews (--model narre or simple_siamese): the reviews are "
+                                 "drawn inside the launch that rebuilds a batch from its ids")
+            if bool(args.parallel):
+                raise ValueError("sample_train_review is not available with parallel: every process would draw the same keys "
+                                 "for its local rows")
+            for name in ("u_rv_num", "i_rv_num", "review_pool"):
+                v = getattr(args, name)
+                if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
+                    raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+            if args.review_pool is not None and args.review_pool > D.DeviceReviewCache.MAX_POOL:
+                raise ValueError(f"review_pool must be at most {D.DeviceReviewCache.MAX_POOL}, got {args.review_pool}")
         self.select_metric = None if metric is None else args.select_by
         self.best_score = -math.inf          # the best select_by metric so far (higher is better); unused with "rmse"
         self.kind, self.args, self.quirks = kind, args, reference_quirks
@@ -283,8 +313,20 @@ class ReviewExperiment:
         self.train_feed = self.eval_feed = self.cache     # what rebuilds a batch from its ids
         if args.device_reviews:
             # meta.pkl's reviews resident on this GPU; a train batch leaves each pair's own review out, a valid batch does not
-            self.cache = D.DeviceReviewCache(self.train_set, self.device)
+            R = int(self.train_set.rv_num)
+            sampling = bool(args.sample_train_review)
+            if sampling:
+                # counts and pool against the split's rv_num, before anything goes to the GPU
+                for name in ("u_rv_num", "i_rv_num"):
+                    if getattr(args, name) is not None and getattr(args, name) > R:
+                        raise ValueError(f"{name} must be in [1, rv_num = {R}], got {getattr(args, name)}")
+                if args.review_pool is not None and args.review_pool < R:
+                    raise ValueError(f"review_pool must be in [rv_num = {R}, {D.DeviceReviewCache.MAX_POOL}], got {args.review_pool}")
+            self.cache = D.DeviceReviewCache(self.train_set, self.device, pool=args.review_pool if sampling else None)
             self.train_feed, self.eval_feed = self.cache.feed(kind, True), self.cache.feed(kind, False)
+            if sampling:
+                seed = args.seed if args.review_sample_seed is None else args.review_sample_seed
+                self.train_feed = self.cache.sampled_feed(kind, args.u_rv_num, args.i_rv_num, seed=int(seed))
         self.objective = None
         if args.loss == "bpr":
             # negatives are items the user has not rated in the training split: the same CSR the validation ranks against
@@ -471,13 +513,14 @@ class ReviewExperiment:
         if a.fast_step:
             key = tuple((t.shape, t.dtype) for t in batch)
             if self._graphed is None:
-                # recording runs warm-up steps: they must not use up the negative sampler's draws either
-                calls = self.train_feed.state.clone() if hasattr(self.train_feed, "state") else None
+                # recording runs warm-up steps: they must not use up the draws of the negative sampler or the review sampler
+                states = _feed_states(self.train_feed)
+                calls = [t.clone() for t in states]
                 self._graphed = GraphedTrainStep.from_ids(self.model, self.optimizer, self.train_feed, u_ids, i_ids, ratings,
                                                           a.max_grad_norm, self.grad_sync, with_ids=with_ids,
                                                           objective=self.objective)
-                if calls is not None:
-                    self.train_feed.state.copy_(calls)
+                for t, c in zip(states, calls):
+                    t.copy_(c)
                 self._graphed_key = key
             if key == self._graphed_key:
                 loss, gnorm, _ = self._graphed((u_ids, i_ids), ratings)
