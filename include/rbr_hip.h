@@ -921,6 +921,43 @@ int rbr_clip_adam_step_rows(int32_t n_tensors, float* const* params, float* cons
 /* dense[v, :] = rows[row_of_token[v], :] for listed tokens, 0 elsewhere: the [V, D] gradient for consumers outside the fused step */
 int rbr_row_grad_to_dense(int32_t V, int32_t D, const int32_t* row_of_token, const float* rows, float* dense, void* stream);
 
+/* ---- One-layer bidirectional LSTM over N padded sequences of at most T steps with torch.nn.LSTM's arithmetic on packed
+ *      sequences, and the max over the steps that AHN takes of it: replaces Seq2SeqEncoder.forward's pack_padded_sequence ->
+ *      nn.LSTM -> pad_packed_sequence -> zero the empty rows (models/ahn/ahn_layers.py:304-314) and the torch.max(words, dim=1)
+ *      behind it (models/ahn/ahn_model.py:62-67).
+ *      Gate order i, f, g, o;  c_t = f c_{t-1} + i g,  h_t = o tanh(c_t), zero initial state.  The forward direction walks
+ *      t = 0 .. len-1, the reverse direction t = len-1 .. 0 of the same sequence.  f32 FMAs in a fixed order.
+ *        xproj [N, T, 8 Hh]  x W_ih^T + b_ih + b_hh: the forward direction's 4 Hh gate columns, then the reverse direction's
+ *                            (rbr_linear_fwd over [N * T, E] with the two W_ih stacked)
+ *        w_hh_fwd / w_hh_rev [4 Hh, Hh] each, torch layout
+ *        lengths [N] int64; a length beyond T counts as T, a negative one as 0
+ *        t_out   DEVICE int32: the batch's output length max(clamp(lengths, 1, 1000)) (ahn_layers.py:307-311) -- one scalar, or
+ *                with t_out_per_seq != 0 one value per sequence [N] (AHN encodes two sides with two output lengths in one call);
+ *                read on the device, so the pooled path needs no host synchronisation and can be recorded into a hipGraph
+ *      Outputs, either or both (NULL to skip):
+ *        out [N, T, 2 Hh]    forward half then reverse half; positions t >= len are 0; a row with len == 0 is all zeros and takes
+ *                            no gradient (the reference overwrites it in place, ahn_layers.py:312)
+ *        pooled [N, 2 Hh], argmax [N, 2 Hh] int32: the reference's max over the batch-trimmed, zero-padded output:
+ *                            pooled = max(h over t < len, and 0 when len < t_out); argmax = the step, or -1 where the zero wins
+ *                            and where len == 0
+ *      saved: rbr_lstm_seq_ws_bytes(N, T, Hh) bytes the forward fills for the backward (gate activations, cell states,
+ *             h_{t-1}, and the k-major weight copy the forward itself reads): required.
+ *      Backward: from d_out [N, T, 2 Hh] and / or d_pooled [N, 2 Hh] (routed by argmax, as rbr_textcnn_bwd routes by its argmax)
+ *             OVERWRITES d_xproj [N, T, 8 Hh] (zeros at t >= len and in empty rows) and d_w_hh_fwd / d_w_hh_rev [4 Hh, Hh].  No
+ *             float atomics: the sum of d W_hh over the positions is one MFMA product per direction whose K is split in a fixed
+ *             way and added in slice order -- the same bits on every run.  ws: rbr_lstm_seq_bwd_ws_bytes(N, T, Hh) bytes.
+ *      1 <= Hh <= 256 and T <= 1000 (the reference's clamp), else RBR_ERR_UNSUPPORTED; N * T * 8 Hh < 2^31 elements, and
+ *      d_xproj below 1 GiB for the backward's product.  N == 0 returns 0 without a launch (the backward then zero-fills the
+ *      weight gradients).                                                                                              ---- */
+size_t rbr_lstm_seq_ws_bytes(int32_t N, int32_t T, int32_t Hh);
+size_t rbr_lstm_seq_bwd_ws_bytes(int32_t N, int32_t T, int32_t Hh);
+int rbr_lstm_seq_fwd(int32_t N, int32_t T, int32_t Hh, const float* xproj, const float* w_hh_fwd, const float* w_hh_rev,
+                     const int64_t* lengths, const int32_t* t_out, int32_t t_out_per_seq, float* out, float* pooled,
+                     int32_t* argmax, void* saved, void* stream);
+int rbr_lstm_seq_bwd(int32_t N, int32_t T, int32_t Hh, const float* w_hh_fwd, const float* w_hh_rev, const int64_t* lengths,
+                     const void* saved, const float* d_out, const float* d_pooled, const int32_t* argmax, float* d_xproj,
+                     float* d_w_hh_fwd, float* d_w_hh_rev, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

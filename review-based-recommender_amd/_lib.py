@@ -248,6 +248,12 @@ SIGNATURES = {
     "rbr_hier_pool_fwd": (C.c_int, [i32, i32, i32, i32, c_i64p, c_u8p, c_f32p, i32, c_f32p, c_i32p, c_stream]),
     "rbr_hier_pool_bwd": (C.c_int, [i32, i32, i32, i32, c_i64p, c_u8p, c_i32p, c_f32p, c_f32p, i32, i32, c_f32p,
                                     c_stream]),
+    "rbr_lstm_seq_ws_bytes": (C.c_size_t, [i32, i32, i32]),
+    "rbr_lstm_seq_bwd_ws_bytes": (C.c_size_t, [i32, i32, i32]),
+    "rbr_lstm_seq_fwd": (C.c_int, [i32, i32, i32, c_f32p, c_f32p, c_f32p, c_i64p, c_i32p, i32, c_f32p, c_f32p, c_i32p, C.c_void_p,
+                                   c_stream]),
+    "rbr_lstm_seq_bwd": (C.c_int, [i32, i32, i32, c_f32p, c_f32p, c_i64p, C.c_void_p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p,
+                                   c_f32p, C.c_void_p, c_stream]),
 }
 
 _lib = None

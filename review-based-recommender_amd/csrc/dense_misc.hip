@@ -297,6 +297,14 @@ static int launch_gemm(int M, int N, int K, const float* A, long sam, long sak, 
     return 0;
 }
 
+// The same product for the other translation units (lstm_seq.hip: the recurrent weight gradient), without an epilogue.
+// part: gemm_strided_ws_floats(M, N, K) floats of split-K scratch (0: the product is not split, part may be NULL).
+size_t gemm_strided_ws_floats(int M, int N, int K) { return gemm_split_floats(M, N, K); }
+int gemm_strided(int M, int N, int K, const float* A, long sam, long sak, const float* B, long sbn, long sbk, float* C, long ldc,
+                 float* part, hipStream_t st) {
+    return launch_gemm(M, N, K, A, sam, sak, B, sbn, sbk, C, ldc, Epi{nullptr, nullptr, 0}, st, part);
+}
+
 // dyeff = dy * mul * (y > 0 when relu);  y is the layer OUTPUT (post relu, post mul)
 __global__ __launch_bounds__(256) void act_bwd_kernel(long n, const float* __restrict__ dy, const float* __restrict__ y,
                                                       const float* __restrict__ mul, int relu, float* __restrict__ out) {

@@ -128,6 +128,13 @@ inline int zero_words(void* p, size_t bytes, hipStream_t st) {
     return zero_regions(r, st);
 }
 
+// C[M,N] = sum_k A(m,k) B(n,k) with element strides A(m,k) = A[m*sam + k*sak], B(n,k) = B[n*sbn + k*sbk] on the f32 MFMA GEMM of
+// dense_misc.hip; K split over workgroups in a fixed way and added in slice order (`part`: gemm_strided_ws_floats floats, or
+// NULL when that is 0).  Operands up to 1 GiB each.
+size_t gemm_strided_ws_floats(int M, int N, int K);
+int gemm_strided(int M, int N, int K, const float* A, long sam, long sak, const float* B, long sbn, long sbk, float* C, long ldc,
+                 float* part, hipStream_t st);
+
 // Id range check (dense_misc.hip: rbr_sanitize_ids; textcnn_prod.hip: the same job inside the prepare stage's first launch).
 struct IdSets {
     const long long* in[RBR_MAX_ID_SETS];

@@ -2681,3 +2681,98 @@ def sample_hard_negatives(u_ids, i_ids, n_neg: int, n_items: int, seen=None, *, 
     if return_candidates:
         return u_out, i_out, valid, cand, cand_score
     return u_out, i_out, valid
+
+
+# --------------------------------------------------------------------------- bidirectional LSTM over padded sequences
+LSTM_MAX_LEN = 1000      # the reference clamps sequence lengths there (models/ahn/ahn_layers.py:307)
+
+
+def lstm_t_out(lengths: torch.Tensor, T: int) -> torch.Tensor:
+    """The batch's output length max(clamp(lengths, 1, 1000)) as a DEVICE int32 [1] (no host synchronisation): what
+    pad_packed_sequence trims the reference's output to (ahn_layers.py:307-311)."""
+    return lengths.clamp(1, min(int(T), LSTM_MAX_LEN)).max().to(I32).view(1)
+
+
+class _LstmSeq(torch.autograd.Function):
+    """rbr_lstm_seq_fwd / rbr_lstm_seq_bwd of rbr_hip.h: the recurrence over xproj, returning out [N, T, 2 Hh] or the fused
+    (pooled [N, 2 Hh], argmax int32 [N, 2 Hh])."""
+
+    @staticmethod
+    def forward(ctx, xproj, w_f, w_r, lengths, t_out, pool):
+        if xproj.dim() != 3 or xproj.shape[2] % 8:
+            raise RuntimeError(f"lstm_seq: xproj must be [N, T, 8 * Hh], got {tuple(xproj.shape)}")
+        N, T, H8 = xproj.shape
+        Hh = H8 // 8
+        if tuple(w_f.shape) != (4 * Hh, Hh) or tuple(w_r.shape) != (4 * Hh, Hh):
+            raise RuntimeError(f"lstm_seq: w_hh must be [{4 * Hh}, {Hh}] for both directions")
+        if lengths.dtype != I64 or lengths.numel() != N:
+            raise RuntimeError("lstm_seq: lengths must be int64 [N]")
+        L_ = _lib.lib()
+        dev = xproj.device
+        xproj, w_f, w_r, lengths = xproj.contiguous(), w_f.contiguous(), w_r.contiguous(), lengths.contiguous().view(-1)
+        per_seq = 0
+        if pool:
+            if t_out is None:
+                t_out = lstm_t_out(lengths, T)
+            t_out = t_out.contiguous().view(-1)
+            if t_out.numel() not in (1, N):
+                raise RuntimeError("lstm_seq: t_out must hold one value, or one per sequence")
+            per_seq = int(t_out.numel() == N and N > 1)
+        saved = torch.empty(L_.rbr_lstm_seq_ws_bytes(N, T, Hh), dtype=U8, device=dev)
+        out = pooled = argmax = None
+        if pool:
+            pooled = torch.empty(N, 2 * Hh, dtype=F32, device=dev)
+            argmax = torch.empty(N, 2 * Hh, dtype=I32, device=dev)
+        else:
+            out = torch.empty(N, T, 2 * Hh, dtype=F32, device=dev)
+        _call("lstm_seq_fwd", L_.rbr_lstm_seq_fwd, N, T, Hh, dev_ptr(xproj, F32, "xproj"), dev_ptr(w_f, F32, "w_hh_fwd"),
+              dev_ptr(w_r, F32, "w_hh_rev"), dev_ptr(lengths, I64, "lengths"), dev_ptr(t_out if pool else None, I32, "t_out"), per_seq,
+              dev_ptr(out, F32, "out"), dev_ptr(pooled, F32, "pooled"), dev_ptr(argmax, I32, "argmax"),
+              saved.data_ptr() if saved.numel() else None, current_stream())
+        ctx.job = (N, T, Hh, bool(pool))
+        ctx.save_for_backward(w_f, w_r, lengths, saved, *([argmax] if pool else []))
+        if pool:
+            ctx.mark_non_differentiable(argmax)
+            return pooled, argmax
+        return out
+
+    @staticmethod
+    def backward(ctx, d_a, d_argmax=None):
+        N, T, Hh, pool = ctx.job
+        w_f, w_r, lengths, saved = ctx.saved_tensors[:4]
+        argmax = ctx.saved_tensors[4] if pool else None
+        L_ = _lib.lib()
+        dev = w_f.device
+        d_a = d_a.contiguous()
+        d_xproj = torch.empty(N, T, 8 * Hh, dtype=F32, device=dev)
+        dwf, dwr = torch.empty_like(w_f), torch.empty_like(w_r)
+        ws = torch.empty(L_.rbr_lstm_seq_bwd_ws_bytes(N, T, Hh), dtype=U8, device=dev)
+        _call("lstm_seq_bwd", L_.rbr_lstm_seq_bwd, N, T, Hh, dev_ptr(w_f, F32, "w_hh_fwd"), dev_ptr(w_r, F32, "w_hh_rev"),
+              dev_ptr(lengths, I64, "lengths"), saved.data_ptr() if saved.numel() else None,
+              None if pool else dev_ptr(d_a, F32, "d_out"), dev_ptr(d_a, F32, "d_pooled") if pool else None,
+              dev_ptr(argmax, I32, "argmax"), dev_ptr(d_xproj, F32, "d_xproj"), dev_ptr(dwf, F32, "d_w_hh_fwd"),
+              dev_ptr(dwr, F32, "d_w_hh_rev"), ws.data_ptr() if ws.numel() else None, current_stream())
+        return d_xproj, dwf, dwr, None, None, None
+
+
+def lstm_seq(xproj, w_hh_fwd, w_hh_rev, lengths, *, pool: bool, t_out=None):
+    """One-layer bidirectional LSTM recurrence over N padded sequences (torch.nn.LSTM's arithmetic on packed sequences; HIP
+    forward and backward).  xproj [N, T, 8 Hh] = x W_ih^T + b_ih + b_hh of both directions (forward direction's gates first),
+    w_hh_* [4 Hh, Hh], lengths int64 [N].  pool False: out [N, T, 2 Hh] with zeros behind each sequence's end and in empty
+    rows.  pool True: (pooled [N, 2 Hh], argmax int32 [N, 2 Hh]) = the max over the steps of the output trimmed to `t_out` and
+    zero-padded (AHN's torch.max(words, dim=1)); t_out: device int32, one value or one per sequence, default
+    max(clamp(lengths, 1, 1000)) computed on the device -- no host synchronisation on this path."""
+    return _LstmSeq.apply(xproj, w_hh_fwd, w_hh_rev, lengths, t_out, bool(pool))
+
+
+def bilstm_encode(x, lstm_params, lengths, *, pool: bool, t_out=None):
+    """x [N, T, E] through a bidirectional nn.LSTM layer given by lstm_params = (weight_ih_l0, weight_hh_l0, bias_ih_l0,
+    bias_hh_l0, weight_ih_l0_reverse, weight_hh_l0_reverse, bias_ih_l0_reverse, bias_hh_l0_reverse).  The input projection of both
+    directions is ONE product over [N * T, E] on the MFMA `linear` (the two W_ih stacked, b_ih + b_hh added once), whose own
+    backward gives dW_ih, the bias gradients and dx; the recurrence is lstm_seq."""
+    w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r = lstm_params
+    N, T, E = x.shape
+    W = torch.cat([w_ih_f, w_ih_r], dim=0)
+    b = torch.cat([b_ih_f + b_hh_f, b_ih_r + b_hh_r], dim=0)
+    xproj = linear(x.reshape(N * T, E), W, b).view(N, T, W.shape[0])
+    return lstm_seq(xproj, w_hh_f, w_hh_r, lengths, pool=pool, t_out=t_out)

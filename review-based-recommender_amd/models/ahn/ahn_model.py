@@ -1,0 +1,88 @@
+"""AHN with the reference's constructor / forward signature, return values and state_dict keys (models/ahn/ahn_model.py:7-92).
+The shared BiLSTM sentence encoder -- about nine tenths of the model's arithmetic -- runs on the HIP kernels of
+csrc/lstm_seq.hip; the hierarchical co-attention behind it is the torch composition of ahn_layers.py."""
+import torch
+import torch.nn as nn
+
+from ... import functional as RF
+from .ahn_layers import (Embedding, Seq2SeqEncoder, TorchFM, UnbalancedCoAttentionAggregator,
+                         UnbalancedCoAttentionAggregatorReview, WordEmbedding)
+
+
+class AHN(nn.Module):
+    def __init__(self, embedding_dim, hidden_dim, k_factor, user_size, item_size, word_vocab_size,
+                 pretrained_word_embeddings, rnn_dropout=0., dropout=0.5, item_review_num=None, word_encoder_str="LSTM"):
+        super().__init__()
+        if word_encoder_str != "LSTM":
+            raise ValueError(f"word_encoder_str={word_encoder_str!r}: the HIP encoder covers 'LSTM'")
+        if hidden_dim % 2:
+            raise ValueError(f"hidden_dim {hidden_dim} must be even (hidden_dim // 2 units per LSTM direction)")
+        self.hidden_dim = hidden_dim
+        self.word_vocab_size, self.user_size, self.item_size = word_vocab_size, user_size, item_size
+        self.validate_ids = True      # device-side range check of every id tensor (functional.sanitize_ids), see DeepCoNNpp
+
+        self.word_embeddings = WordEmbedding(word_vocab_size, embedding_dim, pretrained_word_embeddings)
+        self.word_encoder = Seq2SeqEncoder(nn.LSTM, embedding_dim, hidden_dim // 2, dropout=rnn_dropout, bidirectional=True)
+        self.unbalanced_sentence_aggregator = UnbalancedCoAttentionAggregator(hidden_dim, hidden_dim, item_review_num)
+        self.user_review_trans_layer = nn.Sequential(nn.Linear(hidden_dim, hidden_dim), nn.ReLU())
+        self.item_review_trans_layer = nn.Sequential(nn.Linear(hidden_dim, hidden_dim), nn.ReLU())
+        self.unbalanced_review_aggregator = UnbalancedCoAttentionAggregatorReview(hidden_dim, hidden_dim)
+        self.user_embeddings = Embedding(user_size, hidden_dim)
+        self.item_embeddigns = Embedding(item_size, hidden_dim)          # the reference's spelling: a state_dict key
+        self.dropout = nn.Dropout(p=dropout)
+        self.fm = TorchFM(n=hidden_dim * 4, k=k_factor)
+
+    def encode_sentences(self, user_reviews, item_reviews, user_sent_lengths, item_sent_lenghts, drop=None):
+        """Word ids [bz, r, s, w] and sentence lengths [bz, r, s] of both sides -> (user_sents [bz, ur, us, hidden],
+        item_sents [bz, ir, is, hidden]): lookup, shared BiLSTM, max over the words (ahn_model.py:55-68).  With equal sentence
+        widths both sides go through the encoder as ONE batch; each sentence is told its own side's output length, because the
+        reference encodes the sides separately and the zero candidate of the max depends on it.  `drop`: the encoder's
+        [sentences, E] dropout multiplier drawn by the caller (user rows first) instead of a fresh one."""
+        bz, ur_num, us_num, uw_num = user_reviews.shape
+        _, ir_num, is_num, iw_num = item_reviews.shape
+        table = self.word_embeddings.weight
+        pad = self.word_embeddings.padding_idx
+        n_u, n_i = bz * ur_num * us_num, bz * ir_num * is_num
+        u_len = user_sent_lengths.reshape(n_u).to(torch.int64)
+        i_len = item_sent_lenghts.reshape(n_i).to(torch.int64)
+        t_u, t_i = RF.lstm_t_out(u_len, uw_num), RF.lstm_t_out(i_len, iw_num)
+        enc = self.word_encoder
+        if uw_num == iw_num:
+            ids = torch.cat([user_reviews.reshape(n_u, uw_num), item_reviews.reshape(n_i, iw_num)], dim=0)
+            sents = enc.encode_max(RF.embedding(table, ids, pad), torch.cat([u_len, i_len]),
+                                   t_out=torch.cat([t_u.expand(n_u), t_i.expand(n_i)]), drop=drop)
+            u_sents, i_sents = sents[:n_u], sents[n_u:]
+        else:
+            u_drop, i_drop = (None, None) if drop is None else (drop[:n_u], drop[n_u:])
+            u_sents = enc.encode_max(RF.embedding(table, user_reviews.reshape(n_u, uw_num), pad), u_len, t_out=t_u, drop=u_drop)
+            i_sents = enc.encode_max(RF.embedding(table, item_reviews.reshape(n_i, iw_num), pad), i_len, t_out=t_i, drop=i_drop)
+        return u_sents.reshape(bz, ur_num, us_num, self.hidden_dim), i_sents.reshape(bz, ir_num, is_num, self.hidden_dim)
+
+    def forward(self, user_reviews, item_reviews, user_sent_masks, item_sent_masks, user_sent_lengths, item_sent_lenghts,
+                user_review_masks, item_review_masks, user_ids, item_ids):
+        """user_reviews [bz, ur_num, us_num, uw_num] / item_reviews [bz, ir_num, is_num, iw_num] int64 word ids, sentence masks
+        and lengths [bz, r_num, s_num], review masks [bz, r_num], ids [bz] -> (out_logits [bz], user_sent_weights
+        [bz, ur_num, us_num], item_sent_weights [bz, ir_num, is_num], user_review_weights [bz, ur_num], item_review_weights
+        [bz, ir_num])."""
+        if self.validate_ids:
+            user_reviews, item_reviews, user_ids, item_ids = RF.sanitize_ids(
+                [(user_reviews, self.word_vocab_size, 0), (item_reviews, self.word_vocab_size, 0), (user_ids, self.user_size, 0),
+                 (item_ids, self.item_size, 0)])
+        user_sents, item_sents = self.encode_sentences(user_reviews, item_reviews, user_sent_lengths, item_sent_lenghts)
+        return self.aggregate(user_sents, item_sents, user_sent_masks, item_sent_masks, user_review_masks, item_review_masks,
+                              user_ids, item_ids)
+
+    def aggregate(self, user_sents, item_sents, user_sent_masks, item_sent_masks, user_review_masks, item_review_masks,
+                  user_ids, item_ids):
+        """Everything behind the sentence vectors (ahn_model.py:70-92): the torch composition, on the inputs' device."""
+        user_reviews, item_reviews, user_sent_weights, item_sent_weights, _ = self.unbalanced_sentence_aggregator(
+            user_sents, item_sents, user_sent_masks, item_sent_masks)
+        user_reviews = self.user_review_trans_layer(user_reviews)
+        item_reviews = self.item_review_trans_layer(item_reviews)
+        rv_users, rv_items, user_review_weights, item_review_weights = self.unbalanced_review_aggregator(
+            user_reviews, item_reviews, user_review_masks, item_review_masks)
+        users = torch.cat([rv_users, self.user_embeddings(user_ids)], dim=-1)
+        items = torch.cat([rv_items, self.item_embeddigns(item_ids)], dim=-1)
+        final_features = self.dropout(torch.cat([users, items], dim=-1))
+        out_logits = self.fm(final_features).view(-1)
+        return out_logits, user_sent_weights, item_sent_weights, user_review_weights, item_review_weights
