@@ -711,6 +711,22 @@ int rbr_review_gather(int32_t B, int32_t R, int32_t T, const int64_t* u_ids, con
                       int32_t leave_one_out, int64_t pad_token, int64_t replace_id, int64_t* revs_out, uint8_t* word_masks_out,
                       uint8_t* rev_masks_out, int64_t* rids_out, int64_t* ids_out, int64_t* err, void* stream);
 
+/* ---- id-fed sentence-split batch (AHN).  Replaces the reference's host collate of the sentence split (trainer/train_ahn.py:
+ *      381-419: one LongTensor copy per sentence) and the three masks and the lengths it derives on the host (:149-184) with ONE
+ *      launch over device-resident int32 tables of R + 1 slots per id: user_revs [U, R+1, S, W] / user_rids [U, R+1], item_revs
+ *      [I, R+1, S, W] / item_rids [I, R+1] -- a review is S sentences of W tokens; unused slots hold pad_token / 0.  Rows, own id,
+ *      counterpart, leave_one_out and the slot map q -> q + (q >= d) are rbr_review_gather's
+ *      (preprocess/divide_and_create_example_sent.py:262-300 is the review split's rule).
+ *      revs_out [2B, R, S, W] int64; sent_len_out [2B, R, S] int64 = the number of tokens != pad_token of the sentence, wherever
+ *      they stand; sent_mask_out [2B, R, S] = (sent_len_out > 0); rev_mask_out [2B, R] = any sentence of the review is non-empty;
+ *      rids_out [2B, R] int64 (or NULL); ids_out [2B] = the checked ids (or NULL).  Bad own ids, replace_id and err: as in
+ *      rbr_review_gather.  No sync, no allocation, no float arithmetic, static shapes: graph-capturable.                ---- */
+int rbr_sentence_gather(int32_t B, int32_t R, int32_t S, int32_t W, const int64_t* u_ids, const int64_t* i_ids,
+                        const int32_t* user_revs, const int32_t* user_rids, int32_t U, const int32_t* item_revs,
+                        const int32_t* item_rids, int32_t I, int32_t leave_one_out, int64_t pad_token, int64_t replace_id,
+                        int64_t* revs_out, int64_t* sent_len_out, uint8_t* sent_mask_out, uint8_t* rev_mask_out,
+                        int64_t* rids_out, int64_t* ids_out, int64_t* err, void* stream);
+
 /* ---- id-fed TRAIN batch of the review split with review sampling: the reference's sample_train_review
  *      (trainer/train_simple_siamese.py:346-368 -- each time a training example is fetched, a fresh uniform random subset of
  *      u_rv_num / i_rv_num of its non-empty reviews, in shuffled order, padded with empty reviews) inside the gather launch.

@@ -231,6 +231,8 @@ SIGNATURES = {
                                  c_i64p, c_stream]),
     "rbr_review_gather": (C.c_int, [i32, i32, i32, c_i64p, c_i64p, c_i32p, c_i32p, i32, c_i32p, c_i32p, i32, i32, C.c_int64, C.c_int64,
                                     c_i64p, c_u8p, c_u8p, c_i64p, c_i64p, c_i64p, c_stream]),
+    "rbr_sentence_gather": (C.c_int, [i32, i32, i32, i32, c_i64p, c_i64p, c_i32p, c_i32p, i32, c_i32p, c_i32p, i32, i32, C.c_int64,
+                                      C.c_int64, c_i64p, c_i64p, c_u8p, c_u8p, c_i64p, c_i64p, c_i64p, c_stream]),
     "rbr_review_sample_gather": (C.c_int, [i32, i32, i32, i32, c_i64p, c_i64p, c_i32p, c_i32p, i32, c_i32p, c_i32p, i32, i32, i32, i32,
                                            C.c_int64, C.c_int64, C.c_uint64, C.c_void_p, c_i64p, c_u8p, c_u8p, c_i64p, c_i64p, c_i32p,
                                            c_i64p, c_stream]),

@@ -3,6 +3,7 @@
 // wave_sum / wave_max: xor butterfly over groups of WIDTH consecutive lanes (WIDTH a power of two <= 64, the group aligned to
 // WIDTH): every lane of the group ends with the group's result.  The order of the additions is fixed -- partner WIDTH/2 first,
 // partner 1 last -- and the kernels whose results are tested for bit-reproducibility rely on exactly that order.
+// wave_sum_n: wave_sum for a group width that is a kernel argument (sentence_feed.hip).
 // wave_incl_scan: inclusive prefix sum over the 64 lanes (__shfl_up ladder); lane 63 holds the total.
 // The cross-wave step of a block reduction stays with its kernel: the sites add their four wave sums in different orders.
 //
@@ -29,6 +30,14 @@ template <int WIDTH = 64, typename T>      // T: float, int or long
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
     for (int o = WIDTH / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// wave_sum with a group width known only at run time (a power of two <= 64, the same for the whole wave): the same butterfly in
+// the same order.  Every lane of the wave makes the call.
+template <typename T>
+__device__ __forceinline__ T wave_sum_n(T v, int width) {
+    for (int o = width >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
 

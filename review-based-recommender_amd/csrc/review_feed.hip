@@ -46,14 +46,7 @@ __global__ __launch_bounds__(256) void review_gather_kernel(const ReviewGather P
             int side;
             const long long a = feed_row_id(P.F, r, side, q == 0 && lane_g == 0, err);
             const int* rid_row = P.rids[side] + a * (P.R + 1);
-            int d = P.R;
-            if (P.loo) {
-                const long long c = P.F.ids[side ^ 1][r - side * P.F.B];
-                if (c > 0 && c < P.F.rows[side ^ 1]) {      // rid 0 is the pad, id 0 the padding id: neither ever matches
-                    for (int j = P.R - 1; j >= 0; --j)      // no early exit: the R loads are independent of each other
-                        d = (long long)rid_row[j] == c ? j : d;
-                }
-            }
+            const int d = feed_dropped_slot(P.F, rid_row, r, side, P.R, P.loo);
             const int src = q + (q >= d ? 1 : 0);
             const int* s = P.revs[side] + (a * (P.R + 1) + src) * P.T;
             long long* o = P.revs_out + v * P.T;

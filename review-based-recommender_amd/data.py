@@ -5,6 +5,8 @@ Format (written by the reference's preprocess/divide_and_create_example_{doc,wor
       doc split  : user_docs, item_docs (id -> [doc_len] token ids), doc_len     (train_deepconn_pp.py:254-262)
       review split: rv_num, rv_len, user_reviews, item_reviews (id -> [rv_num][rv_len]),
                     user_rids, item_rids (id -> [rv_num] counterpart ids)          (train_narre.py:254-266)
+      sentence split: rv_num, sent_num, word_num, user_reviews, item_reviews (id -> reviews, each [sent_num][word_num]),
+                    user_rids, item_rids                                           (train_ahn.py:329-338)
   <data_dir>/{train,valid,test}_exmaples.pkl   (sic)  list of examples
       doc split  : [u_id, i_id, rating, u_doc, i_doc]                              (train_deepconn_pp.py:276)
       review split: 7-tuples (valid/test) or 8-tuples (train; the last field is dropped)  (train_narre.py:273-279)
@@ -186,17 +188,49 @@ def _first_slots(lists, idx: int, n: int, pad):
     return row + [pad] * (n - len(row))
 
 
+def _review_shape(ds):
+    """The shape of one review of the split `ds` was read from: (rv_len,) tokens on the review split, (sent_num, word_num) -- sentences
+    of words -- on the sentence split."""
+    return (int(ds.sent_num), int(ds.word_num)) if hasattr(ds, "sent_num") else (int(ds.rv_len),)
+
+
+def _fit(x, shape):
+    """The nested list `x` truncated / zero-padded to `shape` on every axis (a list of lists)."""
+    n = shape[0]
+    if len(shape) == 1:
+        x = list(x[:n])
+        return x + [0] * (n - len(x))
+    rows = [_fit(r, shape[1:]) for r in list(x)[:n]]
+    return rows + [_fit((), shape[1:]) for _ in range(n - len(rows))]
+
+
+def _fill(dst, x) -> None:
+    """The ragged nested list `x` into the zeroed numpy array `dst`, left-aligned on every axis.  A rectangular (sub)list is one
+    array assignment; only where the list is ragged does the copy descend a level."""
+    import numpy as np
+    try:
+        a = np.asarray(x, dtype=np.int64)
+    except (ValueError, TypeError):          # ragged below this level
+        a = None
+    if a is not None and a.ndim == dst.ndim:
+        dst[tuple(slice(0, n) for n in a.shape)] = a
+    elif a is None or a.size:
+        for j, sub in enumerate(x):
+            _fill(dst[j], sub)
+
+
 def review_example_from_meta(ds, u_id: int, i_id: int, leave_one_out: bool):
-    """Fields 3..6 (u_revs, i_revs, u_rids, i_rids) of the review-split example of the pair, from meta's per-id lists alone.
-    leave_one_out (the train split, preprocess/divide_and_create_example_word.py:263-285): the id's review of the pair's
-    counterpart -- the first one in its rid list -- is removed before the list is truncated / padded to rv_num; removing one
-    slot and keeping rv_num reads the first rv_num + 1 entries only, and a match at or beyond slot rv_num changes nothing.
+    """Fields 3..6 (u_revs, i_revs, u_rids, i_rids) of the example of the pair, from meta's per-id lists alone -- on the review
+    split and, with a review of sent_num x word_num tokens, on the sentence split (_review_shape).
+    leave_one_out (the train split, preprocess/divide_and_create_example_word.py:263-285, ..._sent.py:262-300): the id's review of
+    the pair's counterpart -- the first one in its rid list -- is removed before the list is truncated / padded to rv_num; removing
+    one slot and keeping rv_num reads the first rv_num + 1 entries only, and a match at or beyond slot rv_num changes nothing.
     Without leave_one_out (valid / test, :306-323), or without such a review, the first rv_num slots as they are."""
-    R, T = ds.rv_num, ds.rv_len
-    zero = [0] * T
+    R, shape = ds.rv_num, _review_shape(ds)
+    zero = _fit((), shape)
     out = []
     for revs, rids, own, other in ((ds.user_reviews, ds.user_rids, u_id, i_id), (ds.item_reviews, ds.item_rids, i_id, u_id)):
-        rv = [list(r[:T]) + [0] * (T - len(r)) for r in _first_slots(revs, own, R + 1, zero)]
+        rv = [_fit(r, shape) for r in _first_slots(revs, own, R + 1, zero)]
         rd = [int(x) for x in _first_slots(rids, own, R + 1, 0)]
         d = R
         if leave_one_out and other > 0 and other in rd[:R]:
@@ -274,11 +308,133 @@ class ReviewDataset(torch.utils.data.Dataset):
                 torch.LongTensor(u_rids), torch.LongTensor(i_rids), torch.FloatTensor(ratings))
 
 
-def _review_tables(reviews, rids, n: int, slots: int, T: int):
+class SentenceDataset(torch.utils.data.Dataset):
+    """sentence split (AHN; written by preprocess/divide_and_create_example_sent.py, read by trainer/train_ahn.py:319-358): meta.pkl
+    holds rv_num, sent_num, word_num and the per-id lists user_reviews / item_reviews (id -> reviews, each a list of sentences of
+    word ids) and user_rids / item_rids; examples are (u_id, i_id, rating, u_revs, i_revs, u_rids, i_rids[, extra]).
+
+    feed="examples" (the reference's): a batch carries its reviews -- collate_fn returns train_ahn.py:381-419's 7-tuple, zero-padded
+    to [B, rv_num, sent_num, word_num] from lists that may hold fewer reviews, fewer sentences or shorter sentences.  Anything
+    LONGER than that shape is refused at load time (the reference's collate would fail on its first such batch).
+    feed="ids": a batch is (u_ids int64, i_ids int64, ratings f32) and the reviews are rebuilt on the device from meta.pkl's per-id
+    lists (DeviceSentenceCache) under ReviewDataset's precondition, checked once at load time: every example, padded, IS what
+    review_example_from_meta gives for its ids."""
+
+    FEEDS = ("examples", "ids")
+    FIELDS = ("u_revs", "i_revs", "u_rids", "i_rids")
+
+    def __init__(self, data_dir: str, set_name: str, feed: str = "examples"):
+        if feed not in self.FEEDS:
+            raise ValueError(f"feed must be one of {self.FEEDS}, got {feed!r}")
+        meta = load_pickle(os.path.join(data_dir, "meta.pkl"))
+        self.user_num, self.item_num = meta["user_num"], meta["item_num"]
+        self.rv_num, self.sent_num, self.word_num = int(meta["rv_num"]), int(meta["sent_num"]), int(meta["word_num"])
+        self.vocab_size = vocab_size_of(meta["indexlizer"])
+        self.user_reviews, self.item_reviews = meta["user_reviews"], meta["item_reviews"]
+        self.user_rids, self.item_rids = meta["user_rids"], meta["item_rids"]
+        self.examples = load_pickle(os.path.join(data_dir, f"{set_name}_exmaples.pkl"))
+        self.set_name = set_name
+        self.feed = feed
+        self.check_example_shapes()
+        self.validate_ranges()
+        if feed == "ids":
+            self.check_examples_match_meta()
+
+    def check_example_shapes(self) -> None:
+        """No example holds more than rv_num reviews (or rids), a review more than sent_num sentences, a sentence more than
+        word_num words: the padded batch has no room for them."""
+        R, S, W = self.rv_num, self.sent_num, self.word_num
+        for k, e in enumerate(self.examples):
+            for name, field in zip(self.FIELDS, e[3:7]):
+                if len(field) > R:
+                    raise ValueError(f"{self.set_name} example {k}: its {name} holds {len(field)} entries, more than rv_num = {R}")
+                if name.endswith("rids"):
+                    continue
+                for j, review in enumerate(field):
+                    if len(review) > S:
+                        raise ValueError(f"{self.set_name} example {k}: review {j} of its {name} has {len(review)} sentences, "
+                                         f"more than sent_num = {S}")
+                    longest = max(map(len, review), default=0)
+                    if longest > W:
+                        raise ValueError(f"{self.set_name} example {k}: review {j} of its {name} has a sentence of {longest} "
+                                         f"words, more than word_num = {W}")
+
+    def validate_ranges(self) -> None:
+        """As ReviewDataset.validate_ranges; the ragged reviews are walked example by example."""
+        import itertools
+
+        import numpy as np
+        flat = itertools.chain.from_iterable
+        _check_range([e[0] for e in self.examples], self.user_num, "user ids")
+        _check_range([e[1] for e in self.examples], self.item_num, "item ids")
+        for f, limit, what in ((3, self.vocab_size, "user review tokens"), (4, self.vocab_size, "item review tokens")):
+            lo, hi = 0, -1
+            for e in self.examples:
+                t = np.fromiter(flat(flat(e[f])), dtype=np.int64)
+                if t.size:
+                    lo, hi = min(lo, int(t.min())), max(hi, int(t.max()))
+            _check_range([lo, max(hi, 0)], limit, what)
+        _check_range([x for e in self.examples for x in e[5]], self.item_num, "user-side counterpart (item) ids")
+        _check_range([x for e in self.examples for x in e[6]], self.user_num, "item-side counterpart (user) ids")
+
+    def padded(self, e):
+        """Fields 3..6 of example `e` as zero-padded numpy arrays: ([R, S, W], [R, S, W], [R], [R]) int64."""
+        import numpy as np
+        R, S, W = self.rv_num, self.sent_num, self.word_num
+        out = (np.zeros((R, S, W), np.int64), np.zeros((R, S, W), np.int64), np.zeros(R, np.int64), np.zeros(R, np.int64))
+        for dst, x in zip(out, e[3:7]):
+            _fill(dst, x)
+        return out
+
+    def check_examples_match_meta(self) -> None:
+        """The id feed's precondition: fields 3..6 of example k, padded to [R][S][W], are review_example_from_meta of its ids --
+        leave-one-out for the train split, plain otherwise."""
+        import numpy as np
+        loo = self.set_name == "train"
+        for k, e in enumerate(self.examples):
+            want = review_example_from_meta(self, int(e[0]), int(e[1]), loo)
+            for name, got, ref in zip(self.FIELDS, self.padded(e), want):
+                if not np.array_equal(got, np.asarray(ref, dtype=np.int64)):
+                    rule = "with the pair's own review left out" if loo else "truncated / padded to rv_num"
+                    raise ValueError(f"{self.set_name} example {k}: its {name} is not meta.pkl's list of id "
+                                     f"{int(e[0]) if name[0] == 'u' else int(e[1])} {rule}, so the id feed would train on other "
+                                     "reviews than the example's (use feed='examples')")
+
+    def __len__(self):
+        return len(self.examples)
+
+    def __getitem__(self, i):
+        if self.feed == "ids":
+            return self.examples[i][:3]
+        return self.examples[i][:7]     # train examples carry an 8th field (the popped review) that the trainer drops
+
+    def collate_fn(self, batch):
+        """train_ahn.py:381-419: (u_revs [B, R, S, W] int64, i_revs, u_ids, i_ids, u_rids [B, R], i_rids, ratings f32), filled with
+        numpy -- one array assignment per rectangular block -- instead of one tensor per sentence; the id feed's batch is
+        DocDataset.id_collate_fn's."""
+        if self.feed == "ids":
+            return DocDataset.id_collate_fn(batch)
+        import numpy as np
+        B, R, S, W = len(batch), self.rv_num, self.sent_num, self.word_num
+        revs = np.zeros((2, B, R, S, W), np.int64)
+        rids = np.zeros((2, B, R), np.int64)
+        for b, e in enumerate(batch):
+            _fill(revs[0, b], e[3])
+            _fill(revs[1, b], e[4])
+            _fill(rids[0, b], e[5])
+            _fill(rids[1, b], e[6])
+        revs, rids = torch.from_numpy(revs), torch.from_numpy(rids)
+        return (revs[0], revs[1], torch.LongTensor([e[0] for e in batch]), torch.LongTensor([e[1] for e in batch]),
+                rids[0], rids[1], torch.FloatTensor([e[2] for e in batch]))
+
+
+def _review_tables(reviews, rids, n: int, slots: int, T):
     """meta's per-id review lists -- ragged: an id has as many reviews as it wrote, and absent ids have none -- as rectangular
-    tables of `slots` reviews per id: (int64 [n, slots, T], int64 [n, slots]) on the host, zero-padded (pad token / rid 0)."""
+    tables of `slots` reviews per id: (int64 [n, slots, *T], int64 [n, slots]) on the host, zero-padded (pad token / rid 0).
+    T: the shape of one review -- its token count, or (sent_num, word_num) on the sentence split."""
     import numpy as np
-    tab = np.zeros((n, slots, T), dtype=np.int64)
+    shape = (T,) if isinstance(T, int) else tuple(T)
+    tab = np.zeros((n, slots) + shape, dtype=np.int64)
     rid = np.zeros((n, slots), dtype=np.int64)
     for i in range(n):
         rv = _first_slots(reviews, i, slots, None)
@@ -288,13 +444,41 @@ def _review_tables(reviews, rids, n: int, slots: int, T: int):
             raise ValueError(f"id {i} has {k} reviews but {sum(r is not None for r in rd)} counterpart ids in meta.pkl")
         if k:
             rid[i, :k] = rd[:k]
-            if all(len(r) == T for r in rv[:k]):
-                tab[i, :k] = rv[:k]
-            else:                                    # reviews of another length: truncated / zero-padded one by one
-                for j in range(k):
-                    r = list(rv[j])[:T]
-                    tab[i, j, :len(r)] = r
+            try:
+                block = np.asarray(rv[:k], dtype=np.int64)
+            except (ValueError, TypeError):          # ragged reviews
+                block = None
+            if block is not None and block.shape == (k,) + shape:
+                tab[i, :k] = block
+            else:                                    # reviews of another shape: truncated / zero-padded one by one
+                tab[i, :k] = [_fit(r, shape) for r in rv[:k]]
     return torch.from_numpy(tab), torch.from_numpy(rid)
+
+
+def _slots_torch(own, other, tab, rid, n_other: int, leave_one_out: bool):
+    """The id feeds' rule on the host, one side: for own ids [B] with counterparts `other`, over the tables tab [N, R+1, ...] /
+    rid [N, R+1], d = the FIRST j < R with rid[own][j] == other (leave_one_out and 0 < other < n_other; else R) and output slot q
+    reads table slot q + (q >= d).  Returns (reviews [B, R, ...] int64, rids [B, R] int64)."""
+    R = rid.shape[1] - 1
+    _check_range(own, tab.shape[0], "ids of a gathered batch")
+    q = torch.arange(R)
+    rr = rid.index_select(0, own).to(torch.int64)                                   # [B, R + 1]
+    hit = (rr[:, :R] == other[:, None]) & ((other > 0) & (other < n_other))[:, None] & bool(leave_one_out)
+    d = torch.where(hit.any(1), hit.to(torch.int64).argmax(1), torch.full_like(own, R))
+    src = q[None, :] + (q[None, :] >= d[:, None]).to(torch.int64)
+    rows = tab.index_select(0, own).to(torch.int64)
+    idx = src.view(*src.shape, *([1] * (rows.dim() - 2))).expand(-1, -1, *rows.shape[2:])
+    return rows.gather(1, idx), rr.gather(1, src)
+
+
+def sentence_masks(revs: torch.Tensor, pad: int = 0):
+    """trainer/train_ahn.py:149-184 for word ids revs [.., R, S, W], on the tensor's device: (sentence lengths [.., R, S] int64 --
+    the number of tokens != pad, get_sent_lengths counts and does not look for a prefix --, sentence masks [.., R, S] bool,
+    review masks [.., R] bool).  The reference's masks are `token sum != 0`; token ids are non-negative, so that is `length > 0`
+    and `any sentence non-empty`."""
+    lens = (revs != pad).sum(-1)
+    sent_masks = lens > 0
+    return lens, sent_masks, sent_masks.any(-1)
 
 
 class DeviceDocCache:
@@ -444,19 +628,9 @@ class DeviceReviewCache:
         return tuple(outs)
 
     def _gather_torch(self, u_ids, i_ids, leave_one_out: bool):
-        R, T = self.rv_num, self.rv_len
-        q = torch.arange(R)
-        revs, rids = [], []
-        for own, other, tab, rid, n_other in ((u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table.shape[0]),
-                                              (i_ids, u_ids, self.item_table, self.item_rid_table, self.user_table.shape[0])):
-            _check_range(own, tab.shape[0], "ids of a gathered batch")
-            rr = rid.index_select(0, own).to(torch.int64)                                   # [B, R + 1]
-            hit = (rr[:, :R] == other[:, None]) & ((other > 0) & (other < n_other))[:, None] & bool(leave_one_out)
-            d = torch.where(hit.any(1), hit.to(torch.int64).argmax(1), torch.full_like(own, R))      # the FIRST match, else R
-            src = q[None, :] + (q[None, :] >= d[:, None]).to(torch.int64)
-            revs.append(tab.index_select(0, own).to(torch.int64).gather(1, src[:, :, None].expand(-1, -1, T)))
-            rids.append(rr.gather(1, src))
-        revs2, rids2 = torch.cat(revs), torch.cat(rids)
+        u = _slots_torch(u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table.shape[0], leave_one_out)
+        i = _slots_torch(i_ids, u_ids, self.item_table, self.item_rid_table, self.user_table.shape[0], leave_one_out)
+        revs2, rids2 = torch.cat([u[0], i[0]]), torch.cat([u[1], i[1]])
         wm = revs2 != self.PAD
         return revs2, wm, wm.any(-1), rids2, torch.cat([u_ids, i_ids])
 
@@ -624,6 +798,86 @@ class SampledReviewFeed(ReviewFeed):
         got = self.cache.sample_gather(u_ids, i_ids, self.n_user, self.n_item, self.seed, self.state, slots=slots,
                                        **self._outputs(out))
         return dict(zip(("revs", "word_masks", "rev_masks", "rids", "ids", "slots"), got))
+
+
+class DeviceSentenceCache:
+    """The sentence split's DeviceReviewCache (AHN): meta.pkl's reviews resident on the device as int32 tables [N, R+1, S, W] with
+    their counterpart ids [N, R+1] per side, so that a batch -- train (leave-one-out) or valid -- is rebuilt from (u_ids, i_ids) by
+    one launch (functional.sentence_gather), sentence lengths and masks included.  Ids absent from meta, and id 0, are all-pad rows;
+    tokens were range-checked against the vocabulary and rids against the other side's id count once, here.  With device "cpu"
+    the same methods run a plain torch restatement of the kernel (host tests, cross-checks)."""
+
+    PAD = 0
+    NAMES = ("revs", "sent_lens", "sent_masks", "rev_masks", "rids", "ids")
+
+    def __init__(self, ds, device):
+        self.device = torch.device(device)
+        self.rv_num, self.sent_num, self.word_num = int(ds.rv_num), int(ds.sent_num), int(ds.word_num)
+        tabs = {}
+        for side, revs, rids, n, n_other in (("user", ds.user_reviews, ds.user_rids, ds.user_num, ds.item_num),
+                                             ("item", ds.item_reviews, ds.item_rids, ds.item_num, ds.user_num)):
+            tab, rid = _review_tables(revs, rids, n, self.rv_num + 1, (self.sent_num, self.word_num))
+            _check_range(tab, ds.vocab_size, f"meta.pkl {side}_reviews tokens")
+            _check_range(rid, n_other, f"meta.pkl {side}_rids")
+            tab[0] = self.PAD                   # id 0 is the padding id: the row a bad id is replaced by
+            rid[0] = 0
+            tabs[side] = (tab.to(torch.int32).to(self.device), rid.to(torch.int32).to(self.device))
+        (self.user_table, self.user_rid_table), (self.item_table, self.item_rid_table) = tabs["user"], tabs["item"]
+
+    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, leave_one_out: bool, rids=True, ids=True, **out):
+        """functional.sentence_gather over the tables: (revs, sent_lens, sent_masks, rev_masks, rids, ids), stacked, user rows first
+        (`out`: its output tensors by name); on the cpu, its torch restatement, which raises the IndexError of an id outside its
+        table at once."""
+        u_ids, i_ids = u_ids.to(self.device, non_blocking=True), i_ids.to(self.device, non_blocking=True)
+        if self.device.type == "cuda":
+            from . import functional as RF
+            return RF.sentence_gather(u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table, self.item_rid_table,
+                                      leave_one_out, self.PAD, 0, rids=rids, ids=ids, **out)
+        got = dict(zip(self.NAMES, self._gather_torch(u_ids, i_ids, leave_one_out)))
+        out.update(rids=rids, ids=ids)
+        res = []
+        for name in self.NAMES:
+            dst = out.get(name)
+            if torch.is_tensor(dst):
+                res.append(dst.copy_(got[name]))
+            else:                               # the first four: None allocates; rids / ids: True allocates, None / False omits
+                res.append(None if name in ("rids", "ids") and dst is not True else got[name])
+        return tuple(res)
+
+    def _gather_torch(self, u_ids, i_ids, leave_one_out: bool):
+        u = _slots_torch(u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table.shape[0], leave_one_out)
+        i = _slots_torch(i_ids, u_ids, self.item_table, self.item_rid_table, self.user_table.shape[0], leave_one_out)
+        revs2 = torch.cat([u[0], i[0]])
+        return (revs2, *sentence_masks(revs2, self.PAD), torch.cat([u[1], i[1]]), torch.cat([u_ids, i_ids]))
+
+    def feed(self, leave_one_out: bool) -> "SentenceFeed":
+        """AHN's id feed under one rule: leave_one_out=True rebuilds train examples, False valid / test examples."""
+        return SentenceFeed(self, leave_one_out)
+
+
+class SentenceFeed:
+    """AHN's view of a DeviceSentenceCache under one rule: the model's ten forward arguments (models/ahn/ahn_model.py) --
+    (u_revs, i_revs, u_sent_masks, i_sent_masks, u_sent_lens, i_sent_lens, u_rev_masks, i_rev_masks, u_ids, i_ids)."""
+
+    ORDER = ("revs", "sent_masks", "sent_lens", "rev_masks", "ids")
+
+    def __init__(self, cache: DeviceSentenceCache, leave_one_out: bool):
+        self.cache, self.leave_one_out = cache, bool(leave_one_out)
+        self.device = cache.device
+
+    def empty_inputs(self, B: int, with_ids: bool = True):
+        """Zeroed tensors of inputs()' shapes and dtypes for B pairs."""
+        c, dev = self.cache, self.device
+        R, S, W = c.rv_num, c.sent_num, c.word_num
+        like = {"revs": ((B, R, S, W), torch.int64), "sent_masks": ((B, R, S), torch.bool), "sent_lens": ((B, R, S), torch.int64),
+                "rev_masks": ((B, R), torch.bool), "ids": ((B,), torch.int64)}
+        return tuple(torch.zeros(like[k][0], dtype=like[k][1], device=dev) for k in self.ORDER for _ in range(2))
+
+    def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
+        """The model's arguments for the pairs -- views of one gather.  `with_ids` is DeviceDocCache's parameter: AHN takes its ids."""
+        B = u_ids.shape[0]
+        got = dict(zip(self.cache.NAMES, self.cache.gather(u_ids, i_ids, self.leave_one_out, rids=False)))
+        return tuple(half for k in self.ORDER for half in (got[k][:B], got[k][B:]))
 
 
 class NegativeFeed:

@@ -255,6 +255,55 @@ def review_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_revs: torch.Ten
     return revs, word_masks, rev_masks, rids, ids
 
 
+def sentence_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_revs: torch.Tensor, user_rids: torch.Tensor,
+                    item_revs: torch.Tensor, item_rids: torch.Tensor, leave_one_out: bool, pad_token: int = 0, replace_id: int = 0,
+                    revs: Optional[torch.Tensor] = None, sent_lens: Optional[torch.Tensor] = None,
+                    sent_masks: Optional[torch.Tensor] = None, rev_masks: Optional[torch.Tensor] = None, rids=True, ids=True):
+    """The id-fed sentence-split batch (rbr_sentence_gather, one launch): returns (revs2 [2B, R, S, W] int64, sent_lens2 [2B, R, S]
+    int64, sent_masks2 [2B, R, S] bool, rev_masks2 [2B, R] bool, rids2 [2B, R] int64 or None, ids2 [2B] int64 or None), user rows
+    first -- the halves are what SentenceDataset.collate_fn builds from the examples of the same pairs, with the lengths and masks
+    of data.sentence_masks.  Tables: user_revs [U, R+1, S, W] / user_rids [U, R+1], item_revs [I, R+1, S, W] / item_rids [I, R+1],
+    int32 (data.DeviceSentenceCache).  leave_one_out, bad ids and replace_id: as in review_gather.
+
+    `revs` / `sent_lens` / `sent_masks` / `rev_masks`: stacked tensors to write into, or None to allocate; `rids` / `ids`: a stacked
+    tensor, True to allocate, None / False to leave out.  No autograd, no sync: graph-capturable."""
+    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
+        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+    if user_revs.dim() != 4 or item_revs.dim() != 4 or user_revs.shape[1:] != item_revs.shape[1:] or user_revs.shape[1] < 2:
+        raise RuntimeError(f"review tables must be [U, R+1, S, W] / [I, R+1, S, W], got {tuple(user_revs.shape)} / "
+                           f"{tuple(item_revs.shape)}")
+    B, R, S, W = u_ids.shape[0], user_revs.shape[1] - 1, user_revs.shape[2], user_revs.shape[3]
+    if user_rids.shape != (user_revs.shape[0], R + 1) or item_rids.shape != (item_revs.shape[0], R + 1):
+        raise RuntimeError(f"rid tables must be [U, {R + 1}] / [I, {R + 1}], got {tuple(user_rids.shape)} / {tuple(item_rids.shape)}")
+    dev = u_ids.device
+    if revs is None:
+        revs = torch.empty(2 * B, R, S, W, dtype=I64, device=dev)
+    if sent_lens is None:
+        sent_lens = torch.empty(2 * B, R, S, dtype=I64, device=dev)
+    if sent_masks is None:
+        sent_masks = torch.empty(2 * B, R, S, dtype=torch.bool, device=dev)
+    if rev_masks is None:
+        rev_masks = torch.empty(2 * B, R, dtype=torch.bool, device=dev)
+    rids = torch.empty(2 * B, R, dtype=I64, device=dev) if rids is True else (None if rids is False else rids)
+    ids = torch.empty(2 * B, dtype=I64, device=dev) if ids is True else (None if ids is False else ids)
+    for name, t, shape, dtype in (("revs", revs, (2 * B, R, S, W), I64), ("sent_lens", sent_lens, (2 * B, R, S), I64),
+                                  ("sent_masks", sent_masks, (2 * B, R, S), torch.bool),
+                                  ("rev_masks", rev_masks, (2 * B, R), torch.bool), ("rids", rids, (2 * B, R), I64),
+                                  ("ids", ids, (2 * B,), I64)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}, got {t.dtype} {list(t.shape)}")
+    if B == 0:
+        return revs, sent_lens, sent_masks, rev_masks, rids, ids
+    _call(None, _lib.lib().rbr_sentence_gather, B, R, S, W, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),
+          dev_ptr(user_revs, I32, "user_revs"), dev_ptr(user_rids, I32, "user_rids"), user_revs.shape[0],
+          dev_ptr(item_revs, I32, "item_revs"), dev_ptr(item_rids, I32, "item_rids"), item_revs.shape[0],
+          int(bool(leave_one_out)), int(pad_token), int(replace_id), dev_ptr(revs, I64, "revs"),
+          dev_ptr(sent_lens, I64, "sent_lens"), dev_ptr(sent_masks.view(U8), U8, "sent_masks"),
+          dev_ptr(rev_masks.view(U8), U8, "rev_masks"), dev_ptr(rids, I64, "rids"), dev_ptr(ids, I64, "ids"),
+          _id_err(dev).data_ptr(), current_stream())
+    return revs, sent_lens, sent_masks, rev_masks, rids, ids
+
+
 def review_sample_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_revs: torch.Tensor, user_rids: torch.Tensor,
                          item_revs: torch.Tensor, item_rids: torch.Tensor, R: int, n_user: int, n_item: int, *, state, seed: int = 0,
                          leave_one_out: bool = True, pad_token: int = 0, replace_id: int = 0, revs: Optional[torch.Tensor] = None,

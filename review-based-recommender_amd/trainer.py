@@ -56,6 +56,12 @@ The tables are a snapshot: encoded once before the first training step and taken
 next epoch, and with `neg_refresh_steps: N` (default 0 = never) also re-encoded every N updates within an epoch; the feed keeps its
 own copies (data.NegativeFeed.set_tables), so a recorded step stays valid across refreshes.  A small M is advised: the arg-max of
 many candidates is often an item the user would rate well but has not rated in the training split.  The log format is unchanged.
+`--model ahn` trains AHN (trainer/train_ahn.py) on the sentence split (data.SentenceDataset): the loader's 7-tuple goes to the device,
+where the sentence lengths and the sentence / review masks of train_ahn.py:149-184 are derived from the tokens (data.sentence_masks);
+`device_reviews: true` keeps meta.pkl's reviews on the GPU (data.DeviceSentenceCache) and one launch rebuilds a batch -- reviews,
+lengths and masks -- from (u_id, i_id), leave-one-out for training, plain for validation; `fast_step` selects HipClipAdam but AHN's step
+and eval forward run eagerly (no hipGraph is recorded, and one log line says so); device_cache, eval_from_towers, rank_metrics, a
+`loss` other than "mse", sample_train_review and parallel are refused: AHN's sides attend to each other, so it has no per-id towers.
 """
 from __future__ import annotations
 
@@ -190,6 +196,12 @@ def make_model(kind: str, a: Args, ds, quirks: bool = False):
                                  review_dropout=getattr(a, "review_dropout", 0.0),
                                  use_ui_bias=getattr(a, "use_ui_bias", True),
                                  latent_transform=getattr(a, "latent_transform", False))
+        if kind == "ahn":
+            # trainer/train_ahn.py:129-134 (keys of models/ahn/default_ahn.json)
+            from .models.ahn.ahn_model import AHN
+            return AHN(a.embedding_dim, a.hidden_dim, a.k_factor, user_size=ds.user_num, item_size=ds.item_num,
+                       word_vocab_size=ds.vocab_size, pretrained_word_embeddings=None, rnn_dropout=a.rnn_dropout,
+                       dropout=a.dropout, item_review_num=ds.rv_num)
         from .models.dual_att.dual_att import DualAtt
         return DualAtt(vocab_size=ds.vocab_size, doc_len=ds.doc_len, l_window_size=a.l_window_size,
                        l_out_size=a.l_out_size, g_out_size=a.g_out_size, emb_size=a.emb_size,
@@ -198,7 +210,7 @@ def make_model(kind: str, a: Args, ds, quirks: bool = False):
 
 
 class ReviewExperiment:
-    KINDS = ("deepconn", "narre", "dual_att", "simple_siamese")
+    KINDS = ("deepconn", "narre", "dual_att", "simple_siamese", "ahn")
 
     def __init__(self, kind: str, args: Args, reference_quirks: bool = False, uid: str | None = None):
         if kind not in self.KINDS:
@@ -209,14 +221,28 @@ class ReviewExperiment:
         if getattr(args, "use_pretrain", False):
             raise RuntimeError("use_pretrain needs gensim + a word2vec file (train_deepconn_pp.py:105-119): pass "
                                "pretrained rows through the model's `pretrained_embeddings` argument instead")
+        if kind == "ahn":
+            # AHN's two sides attend to each other from the sentences up: there is no per-id tower whose
+            # latent row could be cached, ranked from or scored against a sampled negative
+            no_towers = "AHN's sides attend to each other, so it has no per-id towers"
+            refused = (("device_cache", bool(args.device_cache), "the sentence split's id feed is device_reviews"),
+                       ("eval_from_towers", bool(args.eval_from_towers), no_towers + " to validate from"),
+                       ("rank_metrics", bool(args.rank_metrics), no_towers + " to rank a catalogue from"),
+                       ("loss", args.loss != "mse", f"only \"mse\" is, got {args.loss!r}; the ranking losses score their negatives "
+                        "from per-id towers, and " + no_towers),
+                       ("sample_train_review", bool(args.sample_train_review), "review sampling is not built for the sentence split"),
+                       ("parallel", bool(args.parallel), "data-parallel AHN is not built"))
+            for key, on, why in refused:
+                if on:
+                    raise ValueError(f"{key} is not available with --model ahn: {why}")
         if bool(args.device_cache) and kind not in ("deepconn", "dual_att"):
             # the review split's training examples are not per-id data: the reference drops the target pair's own review from
             # the user's and the item's lists before truncating (preprocess/divide_and_create_example_word.py:263-285)
             raise ValueError(f"device_cache is valid for --model deepconn and dual_att, not {kind}: the review split's examples "
                              "are not per-id documents (its id feed is device_reviews)")
-        if bool(args.device_reviews) and kind not in ("narre", "simple_siamese"):
-            raise ValueError(f"device_reviews is valid for --model narre and simple_siamese, not {kind}: the doc split's id feed "
-                             "is device_cache")
+        if bool(args.device_reviews) and kind not in ("narre", "simple_siamese", "ahn"):
+            raise ValueError(f"device_reviews is valid for --model narre, simple_siamese and ahn, not {kind}: the doc split's id "
+                             "feed is device_cache")
         if bool(args.eval_from_towers) and not (bool(args.device_cache) or bool(args.device_reviews)):
             raise ValueError("eval_from_towers needs device_cache (--model deepconn or dual_att) or device_reviews (narre or "
                              "simple_siamese): validation then scores each pair from latent tables encoded once per epoch from "
@@ -301,8 +327,8 @@ class ReviewExperiment:
         self.patience = 0
         self.grad_sync = None
 
-        review_split = kind in ("narre", "simple_siamese")
-        cls = D.ReviewDataset if review_split else D.DocDataset
+        review_split = kind in ("narre", "simple_siamese", "ahn")
+        cls = D.SentenceDataset if kind == "ahn" else D.ReviewDataset if review_split else D.DocDataset
         kw = {} if review_split else {"with_ids": kind == "deepconn"}
         if args.device_cache or args.device_reviews:
             kw["feed"] = "ids"
@@ -311,7 +337,11 @@ class ReviewExperiment:
         # device_cache: meta.pkl's documents resident on this GPU (train and valid share meta.pkl, so one cache serves both)
         self.cache = D.DeviceDocCache(self.train_set, self.device) if args.device_cache else None
         self.train_feed = self.eval_feed = self.cache     # what rebuilds a batch from its ids
-        if args.device_reviews:
+        if args.device_reviews and kind == "ahn":
+            # the sentence split's reviews resident on this GPU: the same two rules, lengths and masks made by the same launch
+            self.cache = D.DeviceSentenceCache(self.train_set, self.device)
+            self.train_feed, self.eval_feed = self.cache.feed(True), self.cache.feed(False)
+        elif args.device_reviews:
             # meta.pkl's reviews resident on this GPU; a train batch leaves each pair's own review out, a valid batch does not
             R = int(self.train_set.rv_num)
             sampling = bool(args.sample_train_review)
@@ -356,6 +386,7 @@ class ReviewExperiment:
         # device-side check (one launch) is not needed on top
         self.model.validate_ids = False
         self.step_losses = [] if args.record_steps else None      # per-step training loss (device scalars), for tests
+        self.step_gnorms = [] if args.record_steps else None      # and the gradient norm in front of the clip
         self.parallel = self.world > 1 and bool(args.parallel)
         (self.train_loader, self.valid_loader, self.train_sampler, self.valid_sampler,
          self.rank_batch) = make_loaders(self.train_set, self.valid_set, args, self.rank, self.world if self.parallel else 1)
@@ -364,6 +395,9 @@ class ReviewExperiment:
         self.optimizer = make_optimizer(self.model, lr=args.lr, hip_clip_adam=bool(args.fast_step))
         self._graphed = None
         self._graphed_key = None
+        # fast_step records the step and the eval forward as hipGraphs -- not for AHN, whose recorded step is not built: it keeps
+        # HipClipAdam and runs eagerly
+        self._record = bool(args.fast_step) and kind != "ahn"
         self.loss_func = nn.MSELoss()
         if self.parallel:
             from .distributed import GradAllReduce, broadcast_parameters, init_process_group_from_env
@@ -372,6 +406,9 @@ class ReviewExperiment:
             self.grad_sync = GradAllReduce(self.model)
         self.print_args()
         self.print_model_stats()
+        if bool(args.fast_step) and not self._record:
+            self.print_write_to_log("fast_step: HipClipAdam only; the AHN step and eval forward are not recorded as hipGraphs "
+                                    "(they run eagerly)")
 
     # ------------------------------------------------------------------ bookkeeping (experiment.py:64-123)
     def _make_dir(self):
@@ -426,6 +463,12 @@ class ReviewExperiment:
             # review masks mark the reviews that hold any token (simple_siamese/utils.py:94-106)
             u_revs, i_revs, u_wm, i_wm, u_ids, i_ids = batch[:6]
             return (u_revs, i_revs, u_wm, i_wm, u_wm.any(-1), i_wm.any(-1), u_ids, i_ids), batch[-1]
+        if self.kind == "ahn":
+            # sentence-split batch (u_revs, i_revs, ids x2, review ids x2, ratings) -> AHN's ten arguments: the sentence lengths
+            # and the masks are derived here, on the device, from the tokens (train_ahn.py:197-202 does it on the host)
+            u_revs, i_revs, u_ids, i_ids = batch[:4]
+            (u_len, u_sm, u_rm), (i_len, i_sm, i_rm) = D.sentence_masks(u_revs), D.sentence_masks(i_revs)
+            return (u_revs, i_revs, u_sm, i_sm, u_len, i_len, u_rm, i_rm, u_ids, i_ids), batch[-1]
         return tuple(batch[:-1]), batch[-1]
 
     # ------------------------------------------------------------------ loops (train_deepconn_pp.py:143-232)
@@ -457,6 +500,7 @@ class ReviewExperiment:
             self.updates += 1
             if self.step_losses is not None:
                 self.step_losses.append(loss.detach().clone())
+                self.step_gnorms.append(gnorm.detach().clone())
             loss_sum += loss
             sq_err += loss * ratings.size(0)
             steps += 1
@@ -479,7 +523,7 @@ class ReviewExperiment:
         the step's input block (GraphedTrainStep.stage) and the step is replayed -- no intermediate device tensors, no
         device-to-device copies.  None: not applicable (first batch, ragged batch, a model whose inputs are derived on the
         device), the caller takes the _to_device + _step route."""
-        if not self.args.fast_step or self._graphed is None or (self.kind == "simple_siamese" and self.cache is None):
+        if not self._record or self._graphed is None or (self.kind == "simple_siamese" and self.cache is None):
             return None
         key = tuple((t.shape, t.dtype) for t in batch)
         if key != self._graphed_key:
@@ -492,7 +536,7 @@ class ReviewExperiment:
         """One optimisation step; with `fast_step` the step recorded for this batch shape is replayed (a ragged last
         batch, or a batch of another shape, runs eagerly)."""
         a = self.args
-        if a.fast_step:
+        if self._record:
             key = tuple((t.shape, t.dtype) for t in inputs) + ((ratings.shape, ratings.dtype),)
             if self._graphed is None:
                 self._graphed = GraphedTrainStep(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync)
@@ -510,7 +554,7 @@ class ReviewExperiment:
         a = self.args
         u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
         with_ids = self.kind != "dual_att"
-        if a.fast_step:
+        if self._record:
             key = tuple((t.shape, t.dtype) for t in batch)
             if self._graphed is None:
                 # recording runs warm-up steps: they must not use up the draws of the negative sampler or the review sampler
@@ -534,7 +578,7 @@ class ReviewExperiment:
         """device_cache / device_reviews: the eval forward of an id batch -- gather + forward replayed from a hipGraph for the
         loader's regular batch shape with `fast_step`, eager otherwise."""
         with_ids = self.kind != "dual_att"
-        if self.args.fast_step:
+        if self._record:
             g = getattr(self, "_graphed_eval", None)
             if g is None:
                 try:
@@ -551,7 +595,7 @@ class ReviewExperiment:
         """The eval forward: replayed from a hipGraph for the loader's regular batch shape (recorded at first use; the
         parameters are read in place, so training steps in between need no re-recording), eager for any other shape
         (the ragged last batch) and when graphs are off."""
-        if self.args.fast_step and inputs and inputs[0].is_cuda:
+        if self._record and inputs and inputs[0].is_cuda:
             g = getattr(self, "_graphed_eval", None)
             if g is None:
                 try:

@@ -1,0 +1,293 @@
+"""The id-fed sentence split (AHN) on the GPU: rbr_sentence_gather against the examples' own collate plus the reference's length
+and mask rules and against the cache's CPU restatement, and trainer.py --model ahn -- loader-fed, `device_reviews`, `fast_step`."""
+import contextlib
+import io
+import json
+import math
+import os
+import types
+
+import pytest
+import torch
+
+import make_sentence_dataset
+from test_sentence_feed_host import ref_review_mask, ref_sent_lengths, ref_sent_mask
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda", 0)
+NAMES = ("revs", "sent_lens", "sent_masks", "rev_masks", "rids", "ids")
+
+
+def _rel(a, b):
+    return abs(float(a) - float(b)) / abs(float(b))
+
+
+def _collate(examples, R, S, W):
+    """SentenceDataset.collate_fn of the examples and train_ahn.py's rules on its tokens, as a dict of stacked tensors (user rows
+    first) plus the id vectors and the ratings."""
+    from review_based_recommender_amd import data as D
+    ns = types.SimpleNamespace(feed="examples", rv_num=R, sent_num=S, word_num=W)
+    b = D.SentenceDataset.collate_fn(ns, [e[:7] for e in examples])
+    revs = torch.cat([b[0], b[1]])
+    return dict(revs=revs, sent_lens=ref_sent_lengths(revs), sent_masks=ref_sent_mask(revs), rev_masks=ref_review_mask(revs),
+                rids=torch.cat([b[4], b[5]]), ids=torch.cat([b[2], b[3]]), u_ids=b[2], i_ids=b[3], ratings=b[6])
+
+
+_SPLITS = {}
+
+
+def _split(R, S, W, n_train, seed=0):
+    """(cache on the GPU, cache on the cpu, train examples, valid examples), built once per shape and left unchanged."""
+    from review_based_recommender_amd import data as D
+    key = (R, S, W, n_train, seed)
+    if key not in _SPLITS:
+        meta, train, valid = make_sentence_dataset.random_split(7, 7, 40, R, S, W, n_train, 48, seed)
+        ds = types.SimpleNamespace(**meta)
+        _SPLITS[key] = (D.DeviceSentenceCache(ds, DEV), D.DeviceSentenceCache(ds, "cpu"), train, valid)
+    return _SPLITS[key]
+
+
+def _gather(cache, u, i, loo, **kw):
+    from review_based_recommender_amd import functional as RF
+    return RF.sentence_gather(u.to(DEV), i.to(DEV), cache.user_table, cache.user_rid_table, cache.item_table, cache.item_rid_table,
+                              loo, **kw)
+
+
+# ------------------------------------------------------------------------------------------------ 1. the kernel
+# (B, R, S, W, train interactions).  (1,1,1,1): one lane; (3,1,3,3): one word per unit; (3,4,2,8): four words per unit; (5,4,3,6);
+# (7,3,10,20): the default review shape, 3 reviews of 10 sentences on a workgroup's 32 groups; (40,4,3,4): one lane per sentence, 85
+# reviews per workgroup, four workgroups and a tail of 65 reviews whose last wave is partly idle; (4,2,2,260) and (9,2,1,70): a
+# sentence wider than one 64-lane group on either path (a lane takes a second unit); (2,2,70,4): a review's sentences on two waves;
+# (2,2,5,260) and (3,2,9,33): 64 lanes per sentence leave a workgroup 4 groups, fewer than a review has sentences -- one review per
+# tile, in 2 / 3 passes, on either path
+SHAPES = [(1, 1, 1, 1, 30), (3, 1, 3, 3, 30), (3, 4, 2, 8, 30), (5, 4, 3, 6, 30), (7, 3, 10, 20, 30), (40, 4, 3, 4, 60),
+          (4, 2, 2, 260, 30), (9, 2, 1, 70, 30), (2, 2, 70, 4, 30), (2, 2, 5, 260, 30), (3, 2, 9, 33, 30)]
+
+
+def _rules_are_exercised(cpu, train, R):
+    """The split exercises the rule: dropped slots inside and beyond the R that the kernel scans."""
+    d = set()
+    for e in train:
+        row = cpu.user_rid_table[e[0], :R].tolist()
+        d.add(row.index(e[1]) if e[1] in row else R)
+    assert {0, R - 1, R} <= d, d
+
+
+@pytest.mark.parametrize("B,R,S,W,n_train", SHAPES)
+@pytest.mark.parametrize("loo", [True, False])
+def test_sentence_gather_is_bit_equal_to_the_collate_and_the_reference_rules(B, R, S, W, n_train, loo):
+    """Every batch of B consecutive examples of the split (train under leave-one-out, valid without), all six outputs."""
+    from review_based_recommender_amd import functional as RF
+    cache, cpu, train, valid = _split(R, S, W, n_train)
+    examples = train if loo else valid
+    if loo:
+        _rules_are_exercised(cpu, train, R)
+    RF.check_id_errors(DEV)
+    for s in range(0, len(examples) - B + 1, B):
+        want = _collate(examples[s:s + B], R, S, W)
+        got = _gather(cache, want["u_ids"], want["i_ids"], loo)
+        torch.cuda.synchronize()
+        ref = cpu.gather(want["u_ids"], want["i_ids"], loo)
+        for name, g, r in zip(NAMES, got, ref):
+            assert g.dtype == want[name].dtype and g.shape == want[name].shape, name
+            assert torch.equal(g.cpu(), want[name]), (name, s)
+            assert r.dtype == g.dtype and torch.equal(g.cpu(), r), (name, s)
+    RF.check_id_errors(DEV)                                                   # no id was out of range
+    # train pairs under the valid rule (and the reverse) have no examples: the cpu restatement is the cross-check there
+    other = _collate((valid if loo else train)[:B], R, S, W)
+    got = _gather(cache, other["u_ids"], other["i_ids"], loo)
+    ref = cpu.gather(other["u_ids"], other["i_ids"], loo)
+    for name, g, r in zip(NAMES, got, ref):
+        assert torch.equal(g.cpu(), r), name
+
+
+@pytest.mark.parametrize("loo", [True, False])
+def test_sentence_gather_from_misaligned_tables_and_into_misaligned_views(loo):
+    """W % 4 == 0 with a table (or the output) 4 (8) bytes off a 16-byte boundary: the one-word path runs and gives the same bits;
+    nothing is written outside the views; rids / ids can be left out."""
+    from review_based_recommender_amd import functional as RF
+    B, R, S, W = 3, 4, 2, 8
+    cache, _, train, valid = _split(R, S, W, 30)
+    want = _collate((train if loo else valid)[:B], R, S, W)
+    u, i = want["u_ids"].to(DEV), want["i_ids"].to(DEV)
+    for side in ("user", "item"):
+        tab = cache.user_table if side == "user" else cache.item_table
+        buf = torch.empty(tab.numel() + 1, dtype=torch.int32, device=DEV)
+        off = buf[1:].view(tab.shape).copy_(tab)
+        assert tab.data_ptr() % 16 == 0 and off.data_ptr() % 16 == 4
+        tabs = (off, cache.user_rid_table, cache.item_table, cache.item_rid_table) if side == "user" else \
+            (cache.user_table, cache.user_rid_table, off, cache.item_rid_table)
+        got = RF.sentence_gather(u, i, *tabs, loo)
+        torch.cuda.synchronize()
+        for name, g in zip(NAMES, got):
+            assert g.dtype == want[name].dtype and g.shape == want[name].shape and torch.equal(g.cpu(), want[name]), (side, name)
+    n = 2 * B * R * S * W
+    rbuf = torch.full((n + 2,), -7, dtype=torch.int64, device=DEV)
+    lbuf = torch.full((2 * B * R * S + 2,), -7, dtype=torch.int64, device=DEV)
+    mbuf = torch.full((2 * B * R * S + 2,), 0xAB, dtype=torch.uint8, device=DEV)
+    kbuf = torch.full((2 * B * R + 2,), 0xAB, dtype=torch.uint8, device=DEV)
+    revs, lens = rbuf[1:n + 1].view(2 * B, R, S, W), lbuf[1:-1].view(2 * B, R, S)
+    sm, rm = mbuf[1:-1].view(torch.bool).view(2 * B, R, S), kbuf[1:-1].view(torch.bool).view(2 * B, R)
+    assert revs.data_ptr() % 16 == 8
+    got = _gather(cache, u, i, loo, revs=revs, sent_lens=lens, sent_masks=sm, rev_masks=rm, rids=False, ids=None)
+    torch.cuda.synchronize()
+    assert got[0].data_ptr() == revs.data_ptr() and got[2].data_ptr() == sm.data_ptr() and got[4:] == (None, None)
+    for name, g in zip(NAMES[:4], got):
+        assert torch.equal(g.cpu(), want[name]), name
+    for b, fill in ((rbuf, -7), (lbuf, -7), (mbuf, 0xAB), (kbuf, 0xAB)):
+        assert b[0].item() == fill and b[-1].item() == fill
+
+
+@pytest.mark.parametrize("B,R,S,W,n_train", [(3, 1, 3, 3, 30), (3, 4, 2, 8, 30), (7, 3, 10, 20, 30)])
+@pytest.mark.parametrize("loo", [True, False])
+def test_ids_outside_their_table_read_row_zero_and_are_reported_once(B, R, S, W, n_train, loo):
+    from review_based_recommender_amd import functional as RF
+    cache, cpu, train, _ = _split(R, S, W, n_train)
+    want = _collate(train[:B], R, S, W)
+    u, i = want["u_ids"], want["i_ids"]
+    RF.check_id_errors(DEV)
+    bad_u, bad_i = u.clone(), i.clone()
+    bad_u[0] = cache.user_table.shape[0]
+    bad_i[-1] = -3
+    got = _gather(cache, bad_u, bad_i, loo)
+    torch.cuda.synchronize()
+    ok_u, ok_i = bad_u.clone(), bad_i.clone()
+    ok_u[0] = 0
+    ok_i[-1] = 0
+    ref = cpu.gather(ok_u, ok_i, loo)
+    # a replaced id is the padding id, which never matches: its partner keeps all its reviews
+    for name, g, r in zip(NAMES, got, ref):
+        assert g.dtype == r.dtype and g.shape == r.shape and torch.equal(g.cpu(), r), name
+    for row in (0, 2 * B - 1):
+        assert not got[0][row].any() and not got[1][row].any() and not got[2][row].any() and not got[3][row].any()
+        assert int(got[5][row]) == 0
+    assert int(RF._id_err(DEV).cpu()[0]) == 2
+    with pytest.raises(IndexError):
+        RF.check_id_errors(DEV)
+    RF.check_id_errors(DEV)
+    with pytest.raises(IndexError):
+        cpu.gather(bad_u, bad_i, loo)
+    # a clean call afterwards is clean
+    got = _gather(cache, u, i, loo)
+    torch.cuda.synchronize()
+    for name, g, r in zip(NAMES, got, cpu.gather(u, i, loo)):
+        assert torch.equal(g.cpu(), r), name
+    RF.check_id_errors(DEV)
+
+
+def test_sentence_gather_refuses_bad_arguments():
+    from review_based_recommender_amd import functional as RF
+    cache, _, train, _ = _split(4, 2, 8, 30)
+    want = _collate(train[:3], 4, 2, 8)
+    u, i = want["u_ids"].to(DEV), want["i_ids"].to(DEV)
+    with pytest.raises(RuntimeError):
+        _gather(cache, want["u_ids"], want["i_ids"][:2], True)
+    with pytest.raises(RuntimeError):
+        _gather(cache, want["u_ids"], want["i_ids"], True, revs=torch.empty(6, 4, 2, 7, dtype=torch.int64, device=DEV))
+    with pytest.raises(RuntimeError):
+        _gather(cache, want["u_ids"], want["i_ids"], True, sent_lens=torch.empty(6, 4, 2, dtype=torch.int32, device=DEV))
+    with pytest.raises(RuntimeError, match="replace_id"):
+        RF.sentence_gather(u, i, cache.user_table, cache.user_rid_table, cache.item_table, cache.item_rid_table, True, 0, 7)
+
+
+# ------------------------------------------------------------------------------------------------ 2. trainer
+def _cfg(tmp_path, data_dir, tag, **extra):
+    cfg = {"data_dir": data_dir, "dataset": "synthetic", "log_dir": str(tmp_path / "logs"), "log": True, "log_idx": 2,
+           "model_name": "ahn", "parallel": False, "hidden_dim": 12, "embedding_dim": 12, "k_factor": 4, "dropout": 0.0,
+           "rnn_dropout": 0.0, "use_pretrain": False, "epochs": 2, "batch_size": 16, "lr": 0.002, "max_grad_norm": 5.0, "patience": 5,
+           "fast_step": False, "shuffle": False, "record_steps": True}
+    cfg.update(extra)
+    path = tmp_path / f"ahn_{tag}.json"
+    path.write_text(json.dumps(cfg))
+    return str(path)
+
+
+def _run(tmp_path, data_dir, tag, epochs, **extra):
+    from review_based_recommender_amd.trainer import ReviewExperiment, parse_args
+    torch.manual_seed(0)
+    exp = ReviewExperiment("ahn", parse_args(_cfg(tmp_path, data_dir, tag, epochs=epochs, **extra)), uid=tag)
+    init = {k: v.detach().clone() for k, v in exp.model.state_dict().items()}
+    rmse = []
+    for e in range(epochs):
+        exp.train_one_epoch(e)
+        exp.valid_one_epoch()
+        rmse.append(exp.last_valid_rmse)
+    torch.cuda.synchronize()
+    with open(exp.log_path) as f:
+        log = f.read()
+    return types.SimpleNamespace(exp=exp, init=init, losses=[float(x) for x in exp.step_losses],
+                                 gnorms=[float(x) for x in exp.step_gnorms], rmse=rmse, log=log)
+
+
+@pytest.fixture(scope="module")
+def runs(tmp_path_factory):
+    """The tiny split (43 train / 20 valid pairs: ragged last batches of 11 and 4) trained for two epochs, example-fed and id-fed."""
+    tmp = tmp_path_factory.mktemp("ahn_trainer")
+    data_dir = str(tmp / "data")
+    info = make_sentence_dataset.write_sentence_split(data_dir)
+    return types.SimpleNamespace(tmp=tmp, data_dir=data_dir, info=info, loader=_run(tmp, data_dir, "loader", 2),
+                                 ids=_run(tmp, data_dir, "ids", 2, device_reviews=True))
+
+
+def test_trainer_device_reviews_follows_the_example_fed_trainer(runs):
+    from review_based_recommender_amd import data as D
+    e, i = runs.loader, runs.ids
+    assert e.exp.cache is None and e.exp.train_set.feed == "examples" and isinstance(e.exp.train_set, D.SentenceDataset)
+    assert isinstance(i.exp.cache, D.DeviceSentenceCache) and i.exp.train_set.feed == i.exp.valid_set.feed == "ids"
+    assert i.exp.train_feed.leave_one_out and not i.exp.eval_feed.leave_one_out
+    assert runs.info["n_train"] == 43 and len(e.losses) == len(i.losses) == len(e.gnorms) == len(i.gnorms) == 2 * 3
+    for k in range(6):
+        print(f"ahn step {k}: id-fed loss {i.losses[k]!r} gnorm {i.gnorms[k]!r}, example-fed {e.losses[k]!r} {e.gnorms[k]!r}")
+    for k in range(6):
+        assert _rel(i.losses[k], e.losses[k]) <= 1e-5, (k, i.losses[k], e.losses[k])
+        assert _rel(i.gnorms[k], e.gnorms[k]) <= 1e-5, (k, i.gnorms[k], e.gnorms[k])
+    for a, b in zip(i.rmse, e.rmse):
+        print(f"ahn: id-fed valid rmse {a!r}, example-fed {b!r}")
+        assert math.isfinite(a) and abs(a - b) <= 2e-4, (a, b)
+    assert i.exp.valid_count == e.exp.valid_count == 20
+
+
+def test_trainer_ahn_loader_fed_logs_and_checkpoints(runs):
+    from review_based_recommender_amd.trainer import make_model
+    r = runs.loader
+    assert r.log.count("valid loss: ") == 2 and "valid rmse: " in r.log and "best rmse: " in r.log
+    assert r.log.count(", step: 2/3, loss: ") == 2                                 # log_idx 2: one step line per epoch of 3 steps
+    assert all(math.isfinite(x) for x in r.losses + r.gnorms + r.rmse)
+    ck = torch.load(os.path.join(r.exp.out_dir, "best_model.pt"), map_location="cpu")
+    assert set(ck) == {"model", "optimizer", "updates", "args"} and 3 <= ck["updates"] <= 6
+    with contextlib.redirect_stdout(io.StringIO()):
+        fresh = make_model("ahn", r.exp.args, r.exp.train_set)
+    assert type(fresh).__name__ == "AHN"
+    fresh.load_state_dict(ck["model"], strict=True)
+    assert "item_embeddigns.embedding.weight" in ck["model"]
+
+
+def test_first_step_loss_is_the_hand_written_loops(runs):
+    """train_ahn.py:194-217 by hand on the first batch: collate, the reference's masks and lengths made on the host, forward, MSE."""
+    from review_based_recommender_amd.trainer import make_model
+    r = runs.loader
+    ds = r.exp.train_set
+    with contextlib.redirect_stdout(io.StringIO()):
+        model = make_model("ahn", r.exp.args, ds)
+    model.load_state_dict(r.init)
+    model.to(DEV).train()
+    u_text, i_text, u_id, i_id, _, _, label = ds.collate_fn([ds[k] for k in range(16)])
+    args = (u_text, i_text, ref_sent_mask(u_text), ref_sent_mask(i_text), ref_sent_lengths(u_text), ref_sent_lengths(i_text),
+            ref_review_mask(u_text), ref_review_mask(i_text), u_id, i_id)
+    y_pred = model(*[t.to(DEV) for t in args])[0]
+    loss = float(torch.nn.MSELoss()(y_pred, label.to(DEV)))
+    print(f"ahn first step: trainer {r.losses[0]!r}, by hand {loss!r}")
+    assert _rel(r.losses[0], loss) <= 1e-5
+
+
+@pytest.mark.parametrize("on", [False, True])
+def test_fast_step_runs_ahn_eagerly_with_hip_clip_adam(runs, on):
+    from review_based_recommender_amd.train_step import HipClipAdam
+    r = _run(runs.tmp, runs.data_dir, f"fast{int(on)}", 1, fast_step=True, device_reviews=on)
+    assert isinstance(r.exp.optimizer, HipClipAdam)
+    assert r.exp._graphed is None and not getattr(r.exp, "_graphed_eval", None)          # nothing was captured
+    assert r.log.count("not recorded as hipGraphs") == 1 and "valid loss: " in r.log and len(r.losses) == 3
+    base = runs.ids if on else runs.loader
+    print(f"ahn fast_step (device_reviews {on}): first loss {r.losses[0]!r}, without fast_step {base.losses[0]!r}")
+    assert _rel(r.losses[0], base.losses[0]) <= 1e-5
+    assert math.isfinite(r.rmse[0])
