@@ -974,6 +974,64 @@ int rbr_lstm_seq_bwd(int32_t N, int32_t T, int32_t Hh, const float* w_hh_fwd, co
                      const void* saved, const float* d_out, const float* d_pooled, const int32_t* argmax, float* d_xproj,
                      float* d_w_hh_fwd, float* d_w_hh_rev, void* ws, void* stream);
 
+/* ---- AHN's pair-dependent tail from cached per-id sentence tables (csrc/ahn_pair.hip).  AHN's co-attention is asymmetric
+ *      (models/ahn/ahn_layers.py:562-660): the item side is pooled by GatedAttention alone, only the user side looks at the pair.
+ *      With F = hidden_dim, NU = Ru * Su user sentences and NJ = Ri * Si item sentences the per-id state is
+ *        user row u: X [NU, F] sentence vectors, Xt [NU, F] = X @ Wt^T (user_review_trans_layer's weight, no bias), sent_mask
+ *                    [NU] / rev_mask [Ru] bytes, fm [K + 2] = (e_u V[F:2F], sum_k (e_u^2 V[F:2F]^2)_k, e_u . lin_w[F:2F])
+ *        item row i: Ks [NJ, F] = (a * Y) @ Ws^T (a: the item's all-sentence weights, Ws the sentence aggregator's bilinear
+ *                    weight), Kr [Ri, F] = r' @ Wr^T (r' the transformed item reviews), fm [K + 2] = the same three terms of
+ *                    q (rows 2F:3F) and e_i (rows 3F:4F) added up
+ *        head      : bt [F] user_review_trans_layer's bias, VzT [K, F] = V[0:F]^T, vz2 [F] = sum_k V[f, k]^2, lz [F] =
+ *                    lin_w[0:F], lin_b [1]
+ *      and the score of a pair, in eval mode, is
+ *        s[n] = max_j X[n] . Ks[j] over ALL NJ rows;  w[r, :] = softmax_s(mask ? s : -1e8);  p[r] = relu(sum_s w[r, s] Xt[r, s] + bt)
+ *        t[r] = max_j p[r] . Kr[j];  v = softmax_r(mask ? t : -1e8);  z = sum_r v[r] p[r]
+ *        score = 0.5 (sum_k (z VzT[k] + fm_u[k] + fm_i[k])^2 - z^2 . vz2 - fm_u[K] - fm_i[K]) + z . lz + fm_u[K+1] + fm_i[K+1] + lin_b
+ *      (Xt moves the trans layer's product in front of the weighted sum: a reassociation of the module composition, not its
+ *      bits).  The first maximum runs on v_mfma_f32_32x32x2_f32 with F streamed through LDS; the score matrix is never stored.
+ *      ONE launch on `stream`, no workspace, no host synchronisation, no float atomics, a fixed summation order: a pair has the
+ *      same bits in both entries, wherever it stands in the launch, on every run.
+ *      pair_score_ids  : P pairs (1 .. 2^31 - 1) of row indices u_rows / i_rows [P], int32 or int64 (index_bits 32 / 64), into the
+ *        two tables.  out [P]; w_out [P, NU] / v_out [P, Ru] (each may be NULL): the user's sentence and review weights.  An
+ *        index outside its table is never read: row 0 stands in and err (the int64[4] record of rbr_sanitize_ids, set 0 =
+ *        u_rows, 1 = i_rows; may be NULL) is updated.
+ *      pair_score_dense: out [Nu, I]: user rows u_rows [Nu] (NULL: rows 0 .. Nu-1 of the table, Nu <= user->rows) against every
+ *        item row.  Workgroups that follow each other share a user.  Nu * ceil(I / 4) < 2^31.
+ *      Caps (RBR_ERR_BAD_ARG beyond, with the text in rbr_last_error()): Ru <= 64, Su <= 64, Ru * Su <= 128, Ri * Si <= 128,
+ *      F <= 2048, (Ru + 1) * F <= 9216, K <= 64; all sizes >= 1.  AHN's default (10 x 10 sentences per side, F = 300, K = 10) is
+ *      inside.  Nothing is assumed of the pointers beyond 4-byte alignment (16-byte aligned tables with F % 4 == 0 load wider). ---- */
+typedef struct rbr_ahn_shape {
+    int32_t Ru, Su, Ri, Si, F, K;
+} rbr_ahn_shape;
+typedef struct rbr_ahn_user_state {
+    const float* X;
+    const float* Xt;
+    const uint8_t* sent_mask;
+    const uint8_t* rev_mask;
+    const float* fm;
+    int32_t rows;
+} rbr_ahn_user_state;
+typedef struct rbr_ahn_item_state {
+    const float* Ks;
+    const float* Kr;
+    const float* fm;
+    int32_t rows;
+} rbr_ahn_item_state;
+typedef struct rbr_ahn_head {
+    const float* bt;
+    const float* VzT;
+    const float* vz2;
+    const float* lz;
+    const float* lin_b;
+} rbr_ahn_head;
+int rbr_ahn_pair_score_ids(const rbr_ahn_shape* shape, const rbr_ahn_user_state* user, const rbr_ahn_item_state* item,
+                           const rbr_ahn_head* head, int64_t P, const void* u_rows, const void* i_rows, int32_t index_bits,
+                           float* out, float* w_out, float* v_out, int64_t* err, void* stream);
+int rbr_ahn_pair_score_dense(const rbr_ahn_shape* shape, const rbr_ahn_user_state* user, const rbr_ahn_item_state* item,
+                             const rbr_ahn_head* head, int32_t Nu, const void* u_rows, int32_t index_bits, float* out,
+                             int64_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,22 @@ class AttnGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dW_rv", "dW_id", "dh", "db1", "db2", "debd")]
 
 
+class AhnShape(C.Structure):          # rbr_ahn_shape
+    _fields_ = [(n, C.c_int32) for n in ("Ru", "Su", "Ri", "Si", "F", "K")]
+
+
+class AhnUserState(C.Structure):      # rbr_ahn_user_state
+    _fields_ = [(n, C.c_void_p) for n in ("X", "Xt", "sent_mask", "rev_mask", "fm")] + [("rows", C.c_int32)]
+
+
+class AhnItemState(C.Structure):      # rbr_ahn_item_state
+    _fields_ = [(n, C.c_void_p) for n in ("Ks", "Kr", "fm")] + [("rows", C.c_int32)]
+
+
+class AhnHead(C.Structure):           # rbr_ahn_head
+    _fields_ = [(n, C.c_void_p) for n in ("bt", "VzT", "vz2", "lz", "lin_b")]
+
+
 _PP = C.POINTER(C.c_void_p)
 _DESC = C.POINTER(TextCNNDesc)
 i32 = C.c_int32
@@ -245,6 +261,10 @@ SIGNATURES = {
     "rbr_pair_score_rank_ws_bytes": (C.c_size_t, [i32, i32, i32]),
     "rbr_pair_score_rank": (C.c_int, [i32, i32, i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64p, c_i64p, c_i32p,
                                       C.c_int64, c_i64p, i32, c_i32p, c_i32p, c_i64p, C.c_void_p, c_stream]),
+    "rbr_ahn_pair_score_ids": (C.c_int, [C.POINTER(AhnShape), C.POINTER(AhnUserState), C.POINTER(AhnItemState), C.POINTER(AhnHead),
+                                         C.c_int64, C.c_void_p, C.c_void_p, i32, c_f32p, c_f32p, c_f32p, c_i64p, c_stream]),
+    "rbr_ahn_pair_score_dense": (C.c_int, [C.POINTER(AhnShape), C.POINTER(AhnUserState), C.POINTER(AhnItemState), C.POINTER(AhnHead),
+                                           i32, C.c_void_p, i32, c_f32p, c_i64p, c_stream]),
     "rbr_embedding_fwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, c_f32p, c_stream]),
     "rbr_embedding_bwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, i32, c_f32p, c_stream]),
     "rbr_hier_pool_fwd": (C.c_int, [i32, i32, i32, i32, c_i64p, c_u8p, c_f32p, i32, c_f32p, c_i32p, c_stream]),

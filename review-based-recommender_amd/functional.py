@@ -5,7 +5,7 @@ import contextlib
 import ctypes as C
 import os
 import weakref
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -2730,6 +2730,119 @@ def sample_hard_negatives(u_ids, i_ids, n_neg: int, n_items: int, seen=None, *, 
     if return_candidates:
         return u_out, i_out, valid, cand, cand_score
     return u_out, i_out, valid
+
+
+# --------------------------------------------------------------------------- AHN: the pair tail over cached sentence tables
+class AhnUserState(NamedTuple):
+    """Per-user rows of AHN's sentence tables (AHN.encode_users; rbr_ahn_user_state): everything of a user the pair tail reads."""
+    X: torch.Tensor             # [U, Ru * Su, F] the encoder's sentence vectors
+    Xt: torch.Tensor            # [U, Ru * Su, F] X @ Wt^T, user_review_trans_layer's product moved in front of the weighted sum
+    sent_masks: torch.Tensor    # [U, Ru, Su] bool
+    rev_masks: torch.Tensor     # [U, Ru] bool
+    fm: torch.Tensor            # [U, K + 2] the id embedding's part of the FM
+
+
+class AhnItemState(NamedTuple):
+    """Per-item rows (AHN.encode_items; rbr_ahn_item_state), and the item's own two weight arrays, which no pair changes."""
+    Ks: torch.Tensor            # [I, Ri * Si, F] (all-sentence weights * sentence vectors) @ Ws^T
+    Kr: torch.Tensor            # [I, Ri, F] transformed reviews @ Wr^T
+    fm: torch.Tensor            # [I, K + 2] the pooled item's and the id embedding's part of the FM
+    item_sent_weights: torch.Tensor      # [I, Ri, Si]
+    item_review_weights: torch.Tensor    # [I, Ri]
+
+
+class AhnPairHead(NamedTuple):
+    """The parameters the pair tail reads (AHN.pair_head; rbr_ahn_head)."""
+    bt: torch.Tensor            # [F]
+    VzT: torch.Tensor           # [K, F]
+    vz2: torch.Tensor           # [F]
+    lz: torch.Tensor            # [F]
+    lin_b: torch.Tensor         # [1]
+
+
+def _ahn_operands(user_state, item_state, head):
+    """The four argument structs of the rbr_ahn_pair_score_* entries, the tensors they point into (kept alive by the caller) and
+    the shape (Ru, Su, Ri, Si, F, K)."""
+    us = [t.detach().contiguous() for t in user_state]
+    its = [t.detach().contiguous() for t in item_state[:3]]
+    hd = [t.detach().contiguous().view(-1) if k != 1 else t.detach().contiguous() for k, t in enumerate(head)]
+    X, Xt, sm, rm, ufm = us
+    Ks, Kr, ifm = its
+    for t, name in ((X, "user_state.X"), (Xt, "user_state.Xt"), (ufm, "user_state.fm"), (Ks, "item_state.Ks"), (Kr, "item_state.Kr"),
+                    (ifm, "item_state.fm"), *zip(hd, ("head.bt", "head.VzT", "head.vz2", "head.lz", "head.lin_b"))):
+        dev_ptr(t, F32, name)               # device gate first: a CPU tensor is refused before anything else is looked at
+    if X.dim() != 3 or sm.dim() != 3 or Ks.dim() != 3 or Kr.dim() != 3 or item_state[3].dim() != 3:
+        raise RuntimeError("AHN states must be X [U, Ru*Su, F], sent_masks [U, Ru, Su], Ks [I, Ri*Si, F], Kr [I, Ri, F], "
+                           "item_sent_weights [I, Ri, Si]")
+    U, NU, F_ = X.shape
+    _, Ru, Su = sm.shape
+    I, NJ, _ = Ks.shape
+    Ri, Si = item_state[3].shape[1:]
+    K = ufm.shape[1] - 2
+    want = {"Xt": (Xt, (U, NU, F_)), "sent_masks": (sm, (U, Ru, Su)), "rev_masks": (rm, (U, Ru)), "user fm": (ufm, (U, K + 2)),
+            "Ks": (Ks, (I, NJ, F_)), "Kr": (Kr, (I, Ri, F_)), "item fm": (ifm, (I, K + 2)), "bt": (hd[0], (F_,)), "VzT": (hd[1], (K, F_)),
+            "vz2": (hd[2], (F_,)), "lz": (hd[3], (F_,)), "lin_b": (hd[4], (1,))}
+    for name, (t, shape) in want.items():
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"AHN pair score: {name} must be {shape}, got {tuple(t.shape)}")
+    if NU != Ru * Su or NJ != Ri * Si or K < 1:
+        raise RuntimeError(f"AHN pair score: {NU} user / {NJ} item sentence rows do not match {Ru} x {Su} / {Ri} x {Si}, or K = {K} < 1")
+    sm8, rm8 = _mask_u8(sm), _mask_u8(rm)
+    keep = (us, its, hd, sm8, rm8)
+    shape = _lib.AhnShape(Ru, Su, Ri, Si, F_, K)
+    c_user = _lib.AhnUserState(X.data_ptr(), Xt.data_ptr(), dev_ptr(sm8, U8, "sent_masks"), dev_ptr(rm8, U8, "rev_masks"),
+                               ufm.data_ptr(), U)
+    c_item = _lib.AhnItemState(Ks.data_ptr(), Kr.data_ptr(), ifm.data_ptr(), I)
+    c_head = _lib.AhnHead(*(t.data_ptr() for t in hd))
+    return shape, c_user, c_item, c_head, keep
+
+
+def _ahn_rows(rows, name):
+    rows = rows.contiguous()
+    if rows.dim() != 1 or rows.dtype not in (I32, I64):
+        raise RuntimeError(f"{name} must be a 1-D int32 or int64 tensor, got {rows.dtype} {tuple(rows.shape)}")
+    return rows, dev_ptr(rows, rows.dtype, name), 64 if rows.dtype == I64 else 32
+
+
+def ahn_pair_score(user_state, item_state, head, u_rows, i_rows, *, weights=False):
+    """AHN's eval-mode scores [P] of the pairs (u_rows[p], i_rows[p]) -- row indices, int32 or int64, into the state tables of
+    AHN.encode_users / encode_items -- in ONE launch (rbr_ahn_pair_score_ids): the encoder is not run, the tables are.  With
+    weights=True: (scores, user_sent_weights [P, Ru, Su], user_review_weights [P, Ru]); the item's two weight arrays are per id
+    (item_state.item_sent_weights / item_review_weights).  No autograd, no host synchronisation.  A row outside its table scores as
+    row 0 and is recorded like sanitize_ids() records it (check_id_errors)."""
+    shape, c_user, c_item, c_head, keep = _ahn_operands(user_state, item_state, head)
+    dev = keep[0][0].device
+    u_rows, pu, bits = _ahn_rows(u_rows, "u_rows")
+    i_rows, pi, bits_i = _ahn_rows(i_rows, "i_rows")
+    if u_rows.shape != i_rows.shape or bits != bits_i:
+        raise RuntimeError(f"u_rows / i_rows must be [P] each of one dtype, got {tuple(u_rows.shape)} {u_rows.dtype} / "
+                           f"{tuple(i_rows.shape)} {i_rows.dtype}")
+    P = u_rows.shape[0]
+    out = torch.empty(P, dtype=F32, device=dev)
+    w = torch.empty(P, shape.Ru, shape.Su, dtype=F32, device=dev) if weights else None
+    v = torch.empty(P, shape.Ru, dtype=F32, device=dev) if weights else None
+    if P:
+        _call("ahn_pair_score_ids", _lib.lib().rbr_ahn_pair_score_ids, C.byref(shape), C.byref(c_user), C.byref(c_item), C.byref(c_head),
+              P, pu, pi, bits, dev_ptr(out, F32, "out"), dev_ptr(w, F32, "w"), dev_ptr(v, F32, "v"), _id_err(dev).data_ptr(),
+              current_stream())
+    return (out, w, v) if weights else out
+
+
+def ahn_pair_score_dense(user_state, item_state, head, u_rows=None):
+    """AHN's eval-mode scores [len(u_rows), I] of the user rows u_rows (None: every row of user_state) against every item row
+    (rbr_ahn_pair_score_dense): the same arithmetic, bit for bit, as ahn_pair_score.  No autograd, no host synchronisation."""
+    shape, c_user, c_item, c_head, keep = _ahn_operands(user_state, item_state, head)
+    dev = keep[0][0].device
+    if u_rows is None:
+        Nu, pu, bits = c_user.rows, None, 64
+    else:
+        u_rows, pu, bits = _ahn_rows(u_rows, "u_rows")
+        Nu = u_rows.shape[0]
+    out = torch.empty(Nu, c_item.rows, dtype=F32, device=dev)
+    if out.numel():
+        _call("ahn_pair_score_dense", _lib.lib().rbr_ahn_pair_score_dense, C.byref(shape), C.byref(c_user), C.byref(c_item),
+              C.byref(c_head), Nu, pu, bits, dev_ptr(out, F32, "out"), _id_err(dev).data_ptr(), current_stream())
+    return out
 
 
 # --------------------------------------------------------------------------- bidirectional LSTM over padded sequences

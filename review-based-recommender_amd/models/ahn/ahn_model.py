@@ -72,6 +72,75 @@ class AHN(nn.Module):
         return self.aggregate(user_sents, item_sents, user_sent_masks, item_sent_masks, user_review_masks, item_review_masks,
                               user_ids, item_ids)
 
+    # ------------------------------------------------------------------ per-id sentence tables (recommend.AhnRecommender)
+    # The co-attention is asymmetric: the item side is pooled by GatedAttention alone, only the user side looks at the pair, and
+    # the encoder -- nine tenths of the arithmetic -- depends on the id only.  encode_users / encode_items cut the eval-mode
+    # forward at that line; functional.ahn_pair_score (csrc/ahn_pair.hip) is the rest.  A cached sentence vector needs a FIXED
+    # t_out (the zero candidate of the max over the words depends on the batch's longest sentence): the caller
+    # passes, per side, one device int32 -- AhnRecommender takes the longest clamped sentence of the whole table -- and a table
+    # score equals forward() on a batch whose longest sentence per side is that value.
+    def _encode_side(self, reviews, sent_lens, t_out):
+        n, r_num, s_num, w_num = reviews.shape
+        rows = RF.embedding(self.word_embeddings.weight, reviews.reshape(n * r_num * s_num, w_num), self.word_embeddings.padding_idx)
+        return self.word_encoder.encode_max(rows, sent_lens.reshape(-1).to(torch.int64), t_out=t_out).view(n, r_num, s_num, self.hidden_dim)
+
+    def _fm_blocks(self):
+        """fm.V and fm.lin.weight cut into the four blocks of final_features = [z, e_u, q, e_i]."""
+        F_ = self.hidden_dim
+        V, lw = self.fm.V.detach(), self.fm.lin.weight.detach().view(-1)
+        return [V[b * F_:(b + 1) * F_] for b in range(4)], [lw[b * F_:(b + 1) * F_] for b in range(4)]
+
+    @staticmethod
+    def _fm_partial(x, V, lw):
+        """[n, K + 2] of the rows x [n, F]: x V, sum_k (x^2 V^2)_k, x . lw -- a block's share of TorchFM.forward."""
+        return torch.cat([x @ V, ((x * x) @ (V * V)).sum(1, keepdim=True), (x @ lw).unsqueeze(1)], dim=1)
+
+    def user_state(self, user_sents, sent_masks, rev_masks, ids) -> "RF.AhnUserState":
+        """encode_users behind the encoder: sentence vectors [n, Ru, Su, F] -> the state rows."""
+        n, r_num, s_num, F_ = user_sents.shape
+        with RF.eval_mode(self):
+            X = user_sents.detach().reshape(n * r_num * s_num, F_).contiguous()
+            Xt = RF.linear(X, self.user_review_trans_layer[0].weight.detach())
+            Vb, lb = self._fm_blocks()
+            fm = self._fm_partial(self.user_embeddings(ids), Vb[1], lb[1])
+        return RF.AhnUserState(X.view(n, r_num * s_num, F_), Xt.view(n, r_num * s_num, F_), sent_masks.bool(), rev_masks.bool(), fm)
+
+    def item_state(self, item_sents, sent_masks, rev_masks, ids) -> "RF.AhnItemState":
+        """encode_items behind the encoder: sentence vectors [n, Ri, Si, F] -> the state rows, from the existing modules."""
+        n, r_num, s_num, F_ = item_sents.shape
+        sa, ra = self.unbalanced_sentence_aggregator, self.unbalanced_review_aggregator
+        with RF.eval_mode(self):
+            Y = item_sents.detach().reshape(n * r_num, s_num, F_)
+            r, sent_w, all_w = sa.item_aggregator(Y, sent_masks.reshape(n * r_num, s_num).bool())
+            Ks = RF.linear((all_w.reshape(n * r_num * s_num, 1) * Y.reshape(n * r_num * s_num, F_)).contiguous(), sa.bilinear.weight.detach())
+            r = self.item_review_trans_layer(r)
+            q, rev_w = ra.item_aggregator(r, rev_masks.bool())
+            Kr = RF.linear(r.reshape(n * r_num, F_).contiguous(), ra.bilinear.weight.detach())
+            Vb, lb = self._fm_blocks()
+            fm = self._fm_partial(q, Vb[2], lb[2]) + self._fm_partial(self.item_embeddigns(ids), Vb[3], lb[3])
+        return RF.AhnItemState(Ks.view(n, r_num * s_num, F_), Kr.view(n, r_num, F_), fm, sent_w, rev_w)
+
+    def encode_users(self, reviews, sent_masks, sent_lens, rev_masks, ids, t_out) -> "RF.AhnUserState":
+        """Word ids [n, Ru, Su, W], sentence masks / lengths [n, Ru, Su], review masks [n, Ru], user ids [n] and the side's fixed
+        output length t_out (device int32 [1], functional.lstm_t_out) -> the per-user state of the pair tail; eval semantics."""
+        with RF.eval_mode(self):
+            sents = self._encode_side(reviews, sent_lens, t_out)
+        return self.user_state(sents, sent_masks, rev_masks, ids)
+
+    def encode_items(self, reviews, sent_masks, sent_lens, rev_masks, ids, t_out) -> "RF.AhnItemState":
+        """The item side of encode_users; the state carries item_sent_weights [n, Ri, Si] and item_review_weights [n, Ri], which
+        no pair changes."""
+        with RF.eval_mode(self):
+            sents = self._encode_side(reviews, sent_lens, t_out)
+        return self.item_state(sents, sent_masks, rev_masks, ids)
+
+    def pair_head(self) -> "RF.AhnPairHead":
+        """What the pair tail reads of the parameters: user_review_trans_layer's bias and the FM's z block (its per-id blocks are
+        in the states' fm rows).  A snapshot, like the tables."""
+        Vb, lb = self._fm_blocks()
+        return RF.AhnPairHead(self.user_review_trans_layer[0].bias.detach().clone(), Vb[0].t().contiguous(),
+                              (Vb[0] * Vb[0]).sum(1).contiguous(), lb[0].contiguous().clone(), self.fm.lin.bias.detach().clone())
+
     def aggregate(self, user_sents, item_sents, user_sent_masks, item_sent_masks, user_review_masks, item_review_masks,
                   user_ids, item_ids):
         """Everything behind the sentence vectors (ahn_model.py:70-92): the torch composition, on the inputs' device."""

@@ -21,6 +21,10 @@ readable, else token ids; NARRE: position = review slot * rv_len + position in t
 weightiest reviews as [slot, id of the review's author, attention weight, contribution] (Recommender.explain).
 With --eval-split the (user, item) pairs of that split are ranked instead (as well, when --out is given too) and one JSON line of
 rank_metrics goes to --metrics-out, or to stdout.
+
+--model ahn: AHN's towers attend to each other, so it has no latent tables -- but only the user side depends on the pair, and the
+encoder on the id alone.  `AhnRecommender` keeps per-id SENTENCE tables and scores a pair by the co-attention tail in one HIP launch
+per block (csrc/ahn_pair.hip); same flags and JSON lines, sentence split instead of the doc / review split, --explain refused.
 """
 from __future__ import annotations
 
@@ -302,11 +306,214 @@ class Recommender:
         return SeenItems(off.to(device), items.to(device)) if device is not None else SeenItems(off, items)
 
 
+# ---------------------------------------------------------------------------------------------------------------- AHN
+def exclusion_mask(exclude, u_ids: torch.Tensor, n_items: int) -> Optional[torch.Tensor]:
+    """bool [len(u_ids), n_items] of the items each row must never get, from the `exclude` argument of topk / rank: None, a
+    SeenItems (CSR over all user ids; row b takes user u_ids[b]) or a CSR pair (off int64 [len(u_ids) + 1], items int32)
+    aligned with u_ids.  Torch composition, any device, no host synchronisation; items outside [0, n_items) list nothing."""
+    if exclude is None:
+        return None
+    n, dev = u_ids.shape[0], u_ids.device
+    off, items = exclude[0].to(dev), exclude[1].to(dev, torch.int64)
+    entry_row = torch.searchsorted(off[1:].contiguous(), torch.arange(items.shape[0], device=dev), right=True)
+    if isinstance(exclude, SeenItems):
+        # several rows may name one user: one of them collects the user's entries, every row then copies its user's collector
+        n_users = off.shape[0] - 1
+        collector = torch.full((n_users + 1,), n, dtype=torch.int64, device=dev)
+        inside = (u_ids >= 0) & (u_ids < n_users)
+        slot = torch.where(inside, u_ids, torch.full_like(u_ids, n_users))
+        collector[slot] = torch.where(inside, torch.arange(n, device=dev), torch.full_like(u_ids, n))
+        entry_row = collector[entry_row.clamp_max(n_users)]
+        row_of = collector[slot]
+    else:
+        if off.shape[0] != n + 1:
+            raise ValueError(f"exclude offsets must be [{n + 1}] for {n} rows, got {tuple(off.shape)}")
+        row_of = torch.arange(n, device=dev)
+    ok = (items >= 0) & (items < n_items) & (entry_row < n)
+    mask = torch.zeros(n + 1, n_items, dtype=torch.bool, device=dev)          # row n: the sink of everything that lists nothing
+    mask[torch.where(ok, entry_row, torch.full_like(entry_row, n)), torch.where(ok, items, torch.zeros_like(items))] = True
+    mask[n] = False
+    return mask[row_of]
+
+
+def select_topk(scores: torch.Tensor, k: int, excluded: Optional[torch.Tensor] = None, item_lo: int = 1):
+    """Recommender.topk's rule over a dense score block [n, I]: (items int64 [n, k], scores [n, k]) -- the candidates are the
+    items >= item_lo that are not `excluded` (bool [n, I]) and whose score is not NaN; score descending, ties by the lower item
+    id; rows with fewer than k candidates end in item -1, score -inf.  Two stable sorts (torch composition)."""
+    if k < 1:
+        raise ValueError("k must be at least 1")
+    n, n_items = scores.shape
+    cols = torch.arange(n_items, device=scores.device).view(1, n_items)
+    cand = (cols >= item_lo) & ~torch.isnan(scores)
+    if excluded is not None:
+        cand = cand & ~excluded
+    order = torch.sort(torch.where(cand, scores, torch.full_like(scores, float("-inf"))), dim=1, descending=True, stable=True).indices
+    first = torch.sort((~torch.gather(cand, 1, order)).to(torch.int8), dim=1, stable=True).indices      # candidates first, order kept
+    order = torch.gather(order, 1, first)
+    got = torch.gather(cand, 1, order)
+    if k > n_items:                             # more asked than there are items: the rest is fill
+        order = torch.cat([order, order.new_zeros(n, k - n_items)], dim=1)
+        got = torch.cat([got, got.new_zeros(n, k - n_items)], dim=1)
+    order, got = order[:, :k], got[:, :k]
+    vals = torch.gather(scores, 1, order)
+    return (torch.where(got, order, torch.full_like(order, -1)),
+            torch.where(got, vals, torch.full_like(vals, float("-inf"))))
+
+
+def rank_in_block(scores: torch.Tensor, targets: torch.Tensor, excluded: Optional[torch.Tensor] = None, item_lo: int = 1):
+    """Recommender.rank's rule over a dense score block [B, I], row b for the pair (b, targets[b]): (rank int32 [B], n_cand int32
+    [B]).  Candidates as in select_topk, except that the target is never excluded; rank = candidates with a higher score, or the
+    same score and a lower id; rank -1: a target outside [item_lo, I) or a NaN score.  Compare and count (torch composition)."""
+    B, n_items = scores.shape
+    cols = torch.arange(n_items, device=scores.device).view(1, n_items)
+    tgt = targets.to(torch.int64).view(B, 1)
+    ranked = (tgt >= item_lo) & (tgt < n_items)
+    t_safe = torch.where(ranked, tgt, torch.zeros_like(tgt))
+    s_t = torch.gather(scores, 1, t_safe)
+    ranked = ranked & ~torch.isnan(s_t)
+    cand = (cols >= item_lo) & ~torch.isnan(scores)
+    if excluded is not None:
+        cand = cand & (~excluded | (cols == tgt))
+    beats = cand & ((scores > s_t) | ((scores == s_t) & (cols < tgt)))
+    rank = torch.where(ranked.view(B), beats.sum(1), torch.full((B,), -1, dtype=torch.int64, device=scores.device))
+    return rank.to(torch.int32), cand.sum(1).to(torch.int32)
+
+
+class AhnRecommender:
+    """Recommender's queries for AHN, over per-id SENTENCE tables instead of latent tables.
+
+    AHN's towers attend to each other, but not symmetrically (models/ahn/ahn_layers.py): the item side is pooled by
+    GatedAttention alone and only the user side depends on the pair -- through two bilinear max-similarities, two masked
+    softmaxes, one Linear + ReLU and the FM.  The BiLSTM encoder, nine tenths of the arithmetic, depends on the id only.
+    refresh() therefore runs the encoder ONCE per id (AHN.encode_users / encode_items) and keeps, per user, the sentence
+    vectors X and X @ Wt^T with the masks, and per item the pre-multiplied keys Ks, Kr and its own attention weights; a score
+    is then the pair tail alone, one HIP launch per block (functional.ahn_pair_score*, csrc/ahn_pair.hip).  In f32 that is
+    2 * Ru * Su * F * 4 bytes per user and (Ri * Si + Ri) * F * 4 per item: about 240 KB and 120 KB at the default shape.
+
+    `cache`: a data.DeviceSentenceCache of the sentence split, or pass `user` / `item` = per-id word-id tensors [N, R, S, W] on
+    the model's device (row 0 = the padding id).  The tables are read by the PLAIN rule: the first rv_num slots of an id's row, as
+    a valid or test example reads them (DeviceSentenceCache.gather(..., leave_one_out=False)); masks are data.sentence_masks.
+
+    The t_out rule: the reference's max over the words has a zero candidate that depends on the BATCH's longest sentence per
+    side, so a cached sentence vector needs one fixed output length.  refresh() takes, per side, the longest clamped sentence of
+    the whole table (functional.lstm_t_out, on the device).  A table score then equals AHN.forward on a plain-gathered batch
+    whenever that batch's longest sentence per side equals the table's.
+
+    topk / rank / evaluate have Recommender's semantics (score descending, ties by the lower item id, item 0 never recommended,
+    -1 / -inf fill, the target never excluded, rank -1 for the padding item, an id outside the table or a NaN score).  They
+    select over the dense block of score_all with a torch composition (select_topk: stable sorts; rank_in_block: compare and
+    count): the top-K and rank kernels of csrc/pair_score.hip score from latent rows internally and take no score block.
+
+    `stale` is Recommender's: torch version counters, blind to raw-pointer updates."""
+
+    def __init__(self, model, cache=None, *, user=None, item=None):
+        if type(model).__name__ != "AHN":
+            raise ValueError(f"AhnRecommender serves AHN, not {type(model).__name__} (Recommender serves {sorted(KINDS)})")
+        if cache is not None:
+            R = int(cache.rv_num)
+            user, item = cache.user_table[:, :R], cache.item_table[:, :R]
+        if user is None or item is None:
+            raise ValueError("AhnRecommender needs a DeviceSentenceCache or the per-id `user` / `item` word-id tensors [N, R, S, W]")
+        if user.dim() != 4 or item.dim() != 4:
+            raise ValueError(f"AHN reads [N, R, S, W] sentences per id, got {tuple(user.shape)} / {tuple(item.shape)}")
+        self.model, self.user, self.item = model, user, item
+        self.n_users, self.n_items = user.shape[0], item.shape[0]
+        self.item_lo = 1                     # the padding id 0 is never recommended
+        self.user_state = self.item_state = self.head = None
+        self._versions = None
+
+    # ------------------------------------------------------------------ the tables
+    def refresh(self, chunk: int = 32) -> "AhnRecommender":
+        """Encodes all users and all items, `chunk` ids (chunk * R * S sentences) at a time, into the state tables; eval
+        semantics, no autograd, the model's mode is restored.  Call it again after the parameters change."""
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        from . import data as D
+        m = self.model
+        states = []
+        with RF.eval_mode(m):
+            for docs, n, enc in ((self.user, self.n_users, m.encode_users), (self.item, self.n_items, m.encode_items)):
+                if not docs.is_cuda:
+                    raise RuntimeError(f"the per-id sentence tables must live on a HIP device (got {docs.device}); there is no CPU path")
+                t_out = RF.lstm_t_out(D.sentence_masks(docs, PAD)[0].reshape(-1), docs.shape[-1])
+                fields = None
+                for a in range(0, n, chunk):
+                    revs = docs[a:a + chunk].to(torch.int64).contiguous()
+                    lens, sent_masks, rev_masks = D.sentence_masks(revs, PAD)
+                    ids = torch.arange(a, a + revs.shape[0], dtype=torch.int64, device=revs.device)
+                    rows = enc(revs, sent_masks, lens, rev_masks, ids, t_out)
+                    if fields is None:
+                        fields = [torch.empty(n, *t.shape[1:], dtype=t.dtype, device=t.device) for t in rows]
+                    for dst, t in zip(fields, rows):
+                        dst[a:a + t.shape[0]] = t
+                states.append(type(rows)(*fields))
+            self.user_state, self.item_state = states
+            self.head = m.pair_head()
+        self._versions = [p._version for p in m.parameters()]
+        return self
+
+    stale = Recommender.stale
+    seen_from = staticmethod(Recommender.seen_from)
+
+    def _tables(self):
+        if self.user_state is None:
+            raise RuntimeError("AhnRecommender.refresh() has not been called: there are no sentence tables yet")
+        return self.user_state, self.item_state, self.head
+
+    # ------------------------------------------------------------------ the queries
+    def score(self, u_ids: torch.Tensor, i_ids: torch.Tensor) -> torch.Tensor:
+        """Predicted ratings [B] of the pairs (u_ids[b], i_ids[b]): the pair tail over the tables, one launch."""
+        us, its, head = self._tables()
+        return RF.ahn_pair_score(us, its, head, u_ids, i_ids)
+
+    def score_all(self, u_ids: torch.Tensor) -> torch.Tensor:
+        """Predicted ratings [len(u_ids), I] of the given users against every item id (column 0 is the padding id), bit for bit
+        what score() gives for each pair."""
+        us, its, head = self._tables()
+        (u_ids,) = RF.sanitize_ids([(u_ids, self.n_users, PAD)])
+        return RF.ahn_pair_score_dense(us, its, head, u_ids)
+
+    def attention(self, u_ids: torch.Tensor, i_ids: torch.Tensor):
+        """The model's four weight arrays for the pairs, without the encoder: (user_sent_weights [B, Ru, Su], item_sent_weights
+        [B, Ri, Si], user_review_weights [B, Ru], item_review_weights [B, Ri]) -- AHN.forward's outputs 1..4."""
+        us, its, head = self._tables()
+        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
+        _, w, v = RF.ahn_pair_score(us, its, head, u_ids, i_ids, weights=True)
+        return w, its.item_sent_weights.index_select(0, i_ids), v, its.item_review_weights.index_select(0, i_ids)
+
+    def topk(self, u_ids: torch.Tensor, k: int, exclude=None):
+        """Recommender.topk over score_all's block (select_topk)."""
+        scores = self.score_all(u_ids)
+        (u_ids,) = RF.sanitize_ids([(u_ids, self.n_users, PAD)])
+        return select_topk(scores, k, exclusion_mask(exclude, u_ids, self.n_items), self.item_lo)
+
+    def rank(self, u_ids: torch.Tensor, i_ids: torch.Tensor, exclude=None):
+        """Recommender.rank over score_all's block (rank_in_block): one row of I scores per pair."""
+        scores = self.score_all(u_ids)
+        (u_ids,) = RF.sanitize_ids([(u_ids, self.n_users, PAD)])
+        return rank_in_block(scores, i_ids.to(scores.device), exclusion_mask(exclude, u_ids, self.n_items), self.item_lo)
+
+    def evaluate(self, pairs, ks=(5, 10, 20), exclude=None, chunk: int = 256) -> dict:
+        """Recommender.evaluate: rank_metrics of held-out pairs, ranked `chunk` pairs (chunk x I scores) at a time."""
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        dev = self._tables()[0].X.device
+        if len(pairs) == 2 and all(torch.is_tensor(t) for t in pairs):
+            u_ids, i_ids = (t.to(dev, torch.int64) for t in pairs)
+        else:
+            u_ids = torch.tensor([int(e[0]) for e in pairs], dtype=torch.int64, device=dev)
+            i_ids = torch.tensor([int(e[1]) for e in pairs], dtype=torch.int64, device=dev)
+        parts = [self.rank(u_ids[a:a + chunk], i_ids[a:a + chunk], exclude) for a in range(0, u_ids.shape[0], chunk)]
+        rank = torch.cat([p[0] for p in parts]) if parts else torch.empty(0, dtype=torch.int32, device=dev)
+        n_cand = torch.cat([p[1] for p in parts]) if parts else torch.empty(0, dtype=torch.int32, device=dev)
+        return rank_metrics(rank, n_cand, ks)
+
+
 # ---------------------------------------------------------------------------------------------------------------- CLI
 def parse_cli(argv=None):
     ap = argparse.ArgumentParser(prog="python -m review_based_recommender_amd.recommend",
                                  description="top-K recommendations of a trained model for every user of its dataset")
-    ap.add_argument("--model", required=True, choices=sorted(KINDS.values()))
+    ap.add_argument("--model", required=True, choices=sorted(KINDS.values()) + ["ahn"])
     ap.add_argument("--config", required=True, help="the flat JSON config the model was trained with (trainer.py)")
     ap.add_argument("--checkpoint", required=True, help="best_model.pt written by the trainer")
     ap.add_argument("--k", type=int, default=10, help="items per user (1..128)")
@@ -401,15 +608,22 @@ def main(argv=None) -> int:
             setattr(cfg, key, v)
     dev = torch.device(a.device)
     review_split = a.model in ("narre", "simple_siamese")
-    ds = D.ReviewDataset(cfg.data_dir, "train") if review_split else D.DocDataset(cfg.data_dir, "train", with_ids=a.model == "deepconn")
+    if a.model == "ahn":
+        ds = D.SentenceDataset(cfg.data_dir, "train")
+    else:
+        ds = D.ReviewDataset(cfg.data_dir, "train") if review_split else D.DocDataset(cfg.data_dir, "train", with_ids=a.model == "deepconn")
     # the review split's meta holds as many reviews per id as the id wrote: DeviceReviewCache's first rv_num slots are what a
     # valid / test example reads
-    cache = D.DeviceReviewCache(ds, dev) if review_split else D.DeviceDocCache(ds, dev)
+    if a.model == "ahn":
+        cache = D.DeviceSentenceCache(ds, dev)
+    else:
+        cache = D.DeviceReviewCache(ds, dev) if review_split else D.DeviceDocCache(ds, dev)
     model = make_model(a.model, cfg, ds, a.reference_quirks)
     ck = torch.load(a.checkpoint, map_location="cpu", weights_only=False)
     model.load_state_dict(ck["model"] if "model" in ck else ck)
     model.to(dev).eval()
-    rec = Recommender(model, cache).refresh(chunk=a.chunk)
+    # AHN: sentence tables and the pair tail (AhnRecommender); a chunk of ids is chunk * R * S sentences through the encoder
+    rec = AhnRecommender(model, cache).refresh(chunk=min(a.chunk, 32)) if a.model == "ahn" else Recommender(model, cache).refresh(chunk=a.chunk)
     seen = Recommender.seen_from(ds.examples, rec.n_users, dev) if a.exclude_train else None
     words = _vocabulary(cfg.data_dir) if a.explain is not None else None
     if a.out is not None:
