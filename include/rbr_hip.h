@@ -1032,6 +1032,35 @@ int rbr_ahn_pair_score_dense(const rbr_ahn_shape* shape, const rbr_ahn_user_stat
                              const rbr_ahn_head* head, int32_t Nu, const void* u_rows, int32_t index_bits, float* out,
                              int64_t* err, void* stream);
 
+/* ---- AHN's user-side co-attention as one differentiable op for training (csrc/ahn_attend.hip): the tail above without the FM,
+ *      forward and backward.  Grouped layout: G = 1 + n_neg groups of B pairs, P = G * B; pair p = g * B + b reads USER row b
+ *      and ITEM row p (the negative sampler's layout: rows [0, B) the observed pairs, then the slabs of negatives).
+ *        inputs : X, Xt [B, NU, F], sent_mask [B, NU] / rev_mask [B, Ru] bytes, Ks [P, NJ, F], Kr [P, Ri, F], bt [F]
+ *                 (shape->K is not read)
+ *      attend_fwd: s, w, p, t, v, z as above -- the same instructions in the same order as rbr_ahn_pair_score_*, so w and v have
+ *        its bits -- written to z [P, F], w [P, NU], v [P, Ru], and, for the backward, p [P, Ru, F] and the item rows that
+ *        attained the two maxima: js [P, NU], jr [P, Ru] int32, ties to the LOWEST index.  One launch.
+ *      attend_bwd: from dz [P, F] and the forward's w, v, js, jr, p:
+ *          dv[r] = dz . p[r];  c = sum_r v[r] dv[r];  dt[r] = rev_mask[r] ? v[r] (dv[r] - c) : 0
+ *          da[r] = p[r] > 0 ? v[r] dz + dt[r] Kr[jr[r]] : 0;  dKr[j] = sum_{r: jr[r] = j} dt[r] p[r]
+ *          e[n] = da[r(n)] . Xt[n];  cs[r] = sum_s w[r, s] e[r, s];  ds[n] = sent_mask[n] ? w[n] (e[n] - cs[r]) : 0
+ *          dXt[n] = w[n] da[r(n)];  dX[n] = ds[n] Ks[js[n]];  dKs[j] = sum_{n: js[n] = j} ds[n] X[n]
+ *        dKs [P, NJ, F] and dKr [P, Ri, F] are overwritten whole (a row nobody selected is zeros); dX, dXt [B, NU, F] are the sum
+ *        over a user's G pairs, g ascending; dbt_part [B, F] is each user's sum_g sum_r da[r] -- the caller adds the B rows.
+ *        js / jr are clamped into [0, NJ) / [0, Ri) before they address anything.  One launch of B workgroups.
+ *      No float atomics, no workspace, no host synchronisation; every sum has one order fixed by the shape: the same inputs
+ *      give the same bits on every run, and a pair's dKs / dKr do not depend on its place in the launch.
+ *      Caps of BOTH entries (RBR_ERR_BAD_ARG beyond, with the text in rbr_last_error()): Ru <= 64, Su <= 64, Ru * Su <= 128,
+ *      Ri * Si <= 128, F <= 2048, (Ru + 1) * F <= 9216 (the backward keeps dz and da [Ru, F] in LDS: the forward's budget);
+ *      all sizes >= 1, G >= 1, B >= 0, G * B < 2^31.  B = 0 returns 0 without a launch. ---- */
+int rbr_ahn_pair_attend_fwd(const rbr_ahn_shape* shape, int32_t B, int32_t G, const float* X, const float* Xt,
+                            const uint8_t* sent_mask, const uint8_t* rev_mask, const float* Ks, const float* Kr, const float* bt,
+                            float* z, float* w, float* v, int32_t* js, int32_t* jr, float* p, void* stream);
+int rbr_ahn_pair_attend_bwd(const rbr_ahn_shape* shape, int32_t B, int32_t G, const float* X, const float* Xt,
+                            const uint8_t* sent_mask, const uint8_t* rev_mask, const float* Ks, const float* Kr, const float* w,
+                            const float* v, const int32_t* js, const int32_t* jr, const float* p, const float* dz, float* dX,
+                            float* dXt, float* dKs, float* dKr, float* dbt_part, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -265,6 +265,10 @@ SIGNATURES = {
                                          C.c_int64, C.c_void_p, C.c_void_p, i32, c_f32p, c_f32p, c_f32p, c_i64p, c_stream]),
     "rbr_ahn_pair_score_dense": (C.c_int, [C.POINTER(AhnShape), C.POINTER(AhnUserState), C.POINTER(AhnItemState), C.POINTER(AhnHead),
                                            i32, C.c_void_p, i32, c_f32p, c_i64p, c_stream]),
+    "rbr_ahn_pair_attend_fwd": (C.c_int, [C.POINTER(AhnShape), i32, i32, c_f32p, c_f32p, c_u8p, c_u8p, c_f32p, c_f32p, c_f32p,
+                                          c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, c_stream]),
+    "rbr_ahn_pair_attend_bwd": (C.c_int, [C.POINTER(AhnShape), i32, i32, c_f32p, c_f32p, c_u8p, c_u8p, c_f32p, c_f32p, c_f32p,
+                                          c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "rbr_embedding_fwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, c_f32p, c_stream]),
     "rbr_embedding_bwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, i32, c_f32p, c_stream]),
     "rbr_hier_pool_fwd": (C.c_int, [i32, i32, i32, i32, c_i64p, c_u8p, c_f32p, i32, c_f32p, c_i32p, c_stream]),

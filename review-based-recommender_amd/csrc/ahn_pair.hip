@@ -17,47 +17,30 @@
 //
 // Work split.  A workgroup of 4 waves owns kAhnTile consecutive pairs of the launch and walks them one after the other; in the
 // dense entry these are one user against kAhnTile neighbouring items and blockIdx runs over the items first, so the workgroups
-// that are resident together read the same user's X (L2 hits after the first).  Step 1 is a [Ri*Si, F] x [F, Ru*Su] product on
-// v_mfma_f32_32x32x2_f32 (exact f32 fma chains): F is streamed in slices of kAhnKS columns through LDS (both operands, rows
-// beyond the operand and columns beyond F zero-filled), wave w keeps the up to four 32 x 32 accumulators of user rows
-// [32 w, 32 w + 32) in registers, and the score matrix is never stored: the item's sentences are the MFMA's A rows, so a lane
-// holds 16 item sentences of ONE user sentence per tile and the row max is 16 in-lane maxima and one exchange between the wave's
-// halves.  Steps 2-5 are a few hundred kFLOP: wave reductions (rbr_wave.h) in a fixed order, p and z in the LDS the slices used.
+// that are resident together read the same user's X (L2 hits after the first).  Steps 1-4 are ahn_tail.h's (shared with the
+// training op of ahn_attend.hip): step 1 on v_mfma_f32_32x32x2_f32 with F streamed through LDS, the score matrix never stored.
+// Steps 2-5 are a few hundred kFLOP: wave reductions (rbr_wave.h) in a fixed order, p and z in the LDS the slices used.
 //
 // Rules kept: every loop in front of a barrier or shuffle has a workgroup- (wave-) uniform trip count; no atomics but the id
 // error record; every sum has one fixed order that depends on the shape alone, so a pair has the same bits in both entries,
 // in every tile position and on every run.
-#include "rbr_common.h"
-
-#include <cmath>
-#include <cstdint>
+#include "ahn_tail.h"
 
 namespace rbr {
 
-constexpr int kAhnRows = 128;                      // cap on Ru*Su and on Ri*Si: four 32-row MFMA tiles each
-constexpr int kAhnKS = 32;                         // columns of F per LDS slice
-constexpr int kAhnLd = kAhnKS + 4;                 // LDS row pitch in floats (16-byte aligned rows, 4 * odd)
-constexpr int kAhnTile = 4;                        // pairs per workgroup
-constexpr int kAhnLds = 2 * kAhnRows * kAhnLd;     // floats: the two operand slices, later p [Ru, F] and z [F]
-constexpr int kAhnSuMax = 64, kAhnRuMax = 64;      // one wave holds a review's sentences / a user's reviews in its lanes
-constexpr int kAhnFMax = 2048, kAhnKMax = 64;
-constexpr float kAhnMaskFill = -1e8f;              // the reference's fill of masked scores (utils.py:13)
+constexpr int kAhnKMax = 64;
 
-typedef float ahn_f32x16 __attribute__((ext_vector_type(16)));
-
-struct AhnPair {
-    const float *X, *Xt, *ufm;                     // user state
-    const unsigned char *usm, *urm;
-    const float *Ks, *Kr, *ifm;                    // item state
-    const float *bt, *VzT, *vz2, *lz, *lin_b;      // head
+struct AhnPair : AhnTail {
+    const float *ufm, *ifm;                        // the ids' parts of the FM
+    const float *VzT, *vz2, *lz, *lin_b;           // head
     const void *u_rows, *i_rows;                   // ids entry: P row indices each; dense entry: u_rows [Nu] or null
-    float *out, *w_out, *v_out;
+    float* out;
     long long* err;
     long long P;                                   // ids entry: pairs
     int U, I;                                      // rows of the user / item state tables
     int Nu;                                        // dense entry: user rows of the block
-    int Ru, Su, NU, NJ, Ri, F, K;                  // NU = Ru * Su, NJ = Ri * Si
-    int idx64, dense, ntiles, vec;
+    int K;
+    int idx64, dense, ntiles;
 };
 
 __device__ __forceinline__ long long ahn_row(const void* rows, long long q, int idx64) {
@@ -80,138 +63,10 @@ __device__ __forceinline__ long long ahn_checked(long long v, int rows, int set,
 __device__ __forceinline__ void ahn_pair_body(const AhnPair& A, long long u, long long i, long long q, float* __restrict__ smem,
                                               float* __restrict__ s_s, float* __restrict__ w_s, float* __restrict__ t_s,
                                               float* __restrict__ v_s, float* __restrict__ red_s) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, col = lane & 31, half = lane >> 5;
-    const int F = A.F, NU = A.NU, NJ = A.NJ, Ru = A.Ru, Su = A.Su, Ri = A.Ri, K = A.K;
-    const float* __restrict__ Xu = A.X + (size_t)u * NU * F;
-    const float* __restrict__ Ki = A.Ks + (size_t)i * NJ * F;
-    float* As = smem;                              // item sentences: the MFMA's A rows
-    float* Bs = smem + kAhnRows * kAhnLd;          // user sentences: the MFMA's B columns
-    const int nct = (NJ + 31) >> 5;                // item tiles
-    const bool mine = wave * 32 < NU;              // wave-uniform: this wave's user rows exist
-
-    // ---- 1. s[n] = max_j X[n] . Ks[j]
-    ahn_f32x16 acc[4];
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
-    for (int k0 = 0; k0 < F; k0 += kAhnKS) {
-        __syncthreads();                           // the previous slice's (the previous pair's) LDS reads are done
-        if (A.vec) {                               // F % 4 == 0, 16-byte aligned tables: 8 lanes per row
-            for (int e = tid; e < kAhnRows * (kAhnKS / 4); e += 256) {
-                const int row = e >> 3, kk = (e & 7) * 4;
-                float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-                if (k0 + kk < F) {
-                    if (row < NJ) a = *reinterpret_cast<const float4*>(Ki + (size_t)row * F + k0 + kk);
-                    if (row < NU) b = *reinterpret_cast<const float4*>(Xu + (size_t)row * F + k0 + kk);
-                }
-                *reinterpret_cast<float4*>(As + row * kAhnLd + kk) = a;
-                *reinterpret_cast<float4*>(Bs + row * kAhnLd + kk) = b;
-            }
-        } else {
-            for (int e = tid; e < kAhnRows * kAhnKS; e += 256) {
-                const int row = e >> 5, kk = e & 31;
-                const bool in = k0 + kk < F;
-                As[row * kAhnLd + kk] = (in && row < NJ) ? Ki[(size_t)row * F + k0 + kk] : 0.f;
-                Bs[row * kAhnLd + kk] = (in && row < NU) ? Xu[(size_t)row * F + k0 + kk] : 0.f;
-            }
-        }
-        __syncthreads();
-        if (mine) {
-            // lane (col, half) supplies k = 8 q + 4 half + {0, 1, 2, 3} of its row: one 16-byte LDS read per operand and 8 k
-            const int steps = (min(kAhnKS, F - k0) + 7) >> 3;
-            const float* pb = Bs + (wave * 32 + col) * kAhnLd + 4 * half;
-            const float* pa = As + col * kAhnLd + 4 * half;
-            for (int qd = 0; qd < steps; ++qd) {
-                const float4 b = *reinterpret_cast<const float4*>(pb + 8 * qd);
-#pragma unroll
-                for (int ct = 0; ct < 4; ++ct) {
-                    if (ct < nct) {
-                        const float4 a = *reinterpret_cast<const float4*>(pa + ct * 32 * kAhnLd + 8 * qd);
-                        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[ct], 0, 0, 0);
-                        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[ct], 0, 0, 0);
-                        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[ct], 0, 0, 0);
-                        acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[ct], 0, 0, 0);
-                    }
-                }
-            }
-        }
-    }
-    {   // register r of tile ct is item sentence ct * 32 + (r & 3) + 8 (r >> 2) + 4 half of user sentence wave * 32 + col
-        float mx = -INFINITY;
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int j = ct * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (j < NJ) mx = fmaxf(mx, acc[ct][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const int n = wave * 32 + col;
-        if (half == 0 && n < NU) s_s[n] = mx;
-    }
-    __syncthreads();                               // s is complete, and the slices are free: p and z take their place
-
-    // ---- 2. w[r, :] = softmax over the review's sentences, a wave per review
-    const unsigned char* __restrict__ sm = A.usm + (size_t)u * NU;
-    for (int r = wave; r < Ru; r += 4) {
-        const bool in = lane < Su;
-        const int n = r * Su + (in ? lane : 0);
-        const float x = in ? (sm[n] ? s_s[n] : kAhnMaskFill) : -INFINITY;
-        const float m = wave_max(x);
-        const float e = in ? expf(x - m) : 0.f;
-        const float w = e / wave_sum(e);
-        if (in) {
-            w_s[n] = w;
-            if (A.w_out) A.w_out[(size_t)q * NU + n] = w;
-        }
-    }
-    __syncthreads();
-
-    // ---- 3. p[r] = relu(sum_s w[r, s] X'[r, s] + bt), s ascending
-    float* p_s = smem;
-    float* z_s = smem + Ru * F;
-    const float* __restrict__ Xtu = A.Xt + (size_t)u * NU * F;
-    for (int idx = tid; idx < Ru * F; idx += 256) {
-        const int r = idx / F, f = idx - r * F;
-        float a = 0.f;
-        for (int s = 0; s < Su; ++s) a = fmaf(w_s[r * Su + s], Xtu[(size_t)(r * Su + s) * F + f], a);
-        a += A.bt[f];
-        p_s[idx] = (a < 0.f) ? 0.f : a;            // not fmaxf: it would turn NaN into 0 (torch.relu(NaN) is NaN)
-    }
-    __syncthreads();
-
-    // ---- 4. t[r] = max_j p[r] . Kr[j], a wave per review; v = softmax over the reviews; z = sum_r v[r] p[r]
-    const float* __restrict__ Kri = A.Kr + (size_t)i * Ri * F;
-    for (int r = wave; r < Ru; r += 4) {
-        float t = -INFINITY;
-        for (int j = 0; j < Ri; ++j) {
-            float d = 0.f;
-            for (int f = lane; f < F; f += 64) d = fmaf(p_s[r * F + f], Kri[(size_t)j * F + f], d);
-            t = fmaxf(t, wave_sum(d));
-        }
-        if (lane == 0) t_s[r] = t;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        const bool in = lane < Ru;
-        const int r = in ? lane : 0;
-        const float x = in ? (A.urm[(size_t)u * Ru + r] ? t_s[r] : kAhnMaskFill) : -INFINITY;
-        const float m = wave_max(x);
-        const float e = in ? expf(x - m) : 0.f;
-        const float v = e / wave_sum(e);
-        if (in) {
-            v_s[r] = v;
-            if (A.v_out) A.v_out[(size_t)q * Ru + r] = v;
-        }
-    }
-    __syncthreads();
-    for (int f = tid; f < F; f += 256) {
-        float a = 0.f;
-        for (int r = 0; r < Ru; ++r) a = fmaf(v_s[r], p_s[r * F + f], a);
-        z_s[f] = a;
-    }
-    __syncthreads();
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int F = A.F, K = A.K;
+    ahn_tail<false>(A, u, i, q, smem, s_s, w_s, t_s, v_s);            // ---- 1-4: z [F] behind p [Ru, F], behind a barrier
+    const float* z_s = smem + A.Ru * F;
 
     // ---- 5. the FM: a wave per factor, then one thread adds the K squares in factor order
     const float* __restrict__ fu = A.ufm + (size_t)u * (K + 2);
@@ -297,6 +152,7 @@ static void ahn_fill(AhnPair& A, const rbr_ahn_shape* s, const rbr_ahn_user_stat
     A.vec = (s->F % 4 == 0 && aligned(us->X) && aligned(is->Ks)) ? 1 : 0;
     A.u_rows = A.i_rows = nullptr;
     A.out = A.w_out = A.v_out = nullptr;
+    A.js_out = A.jr_out = nullptr;
     A.err = nullptr;
     A.P = 0; A.Nu = 0; A.idx64 = 1; A.dense = 0; A.ntiles = 1;
 }

@@ -2845,6 +2845,77 @@ def ahn_pair_score_dense(user_state, item_state, head, u_rows=None):
     return out
 
 
+class _AhnPairAttend(torch.autograd.Function):
+    """rbr_ahn_pair_attend_fwd / rbr_ahn_pair_attend_bwd of rbr_hip.h: (z, w, v, js, jr), all but z non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, X, Xt, sent_masks, rev_masks, Ks, Kr, bt, groups):
+        X, Xt, Ks, Kr, bt = (t.detach().contiguous() for t in (X, Xt, Ks, Kr, bt))
+        for t, name in ((X, "X"), (Xt, "Xt"), (Ks, "Ks"), (Kr, "Kr"), (bt, "bt")):
+            dev_ptr(t, F32, name)               # device gate first: a CPU tensor is refused before anything else is looked at
+        G = int(groups)
+        if X.dim() != 3 or sent_masks.dim() != 3 or Ks.dim() != 3 or Kr.dim() != 3 or G < 1:
+            raise RuntimeError("ahn_pair_attend: X [B, Ru*Su, F], sent_masks [B, Ru, Su], Ks [G*B, Ri*Si, F], Kr [G*B, Ri, F], "
+                               f"groups >= 1; got {tuple(X.shape)}, {tuple(sent_masks.shape)}, {tuple(Ks.shape)}, {tuple(Kr.shape)}, {G}")
+        B, NU, F_ = X.shape
+        _, Ru, Su = sent_masks.shape
+        P, NJ, _ = Ks.shape
+        Ri = Kr.shape[1]
+        want = {"Xt": (Xt, (B, NU, F_)), "sent_masks": (sent_masks, (B, Ru, Su)), "rev_masks": (rev_masks, (B, Ru)),
+                "Ks": (Ks, (G * B, NJ, F_)), "Kr": (Kr, (G * B, Ri, F_)), "bt": (bt, (F_,))}
+        for name, (t, shape) in want.items():
+            if tuple(t.shape) != shape:
+                raise RuntimeError(f"ahn_pair_attend: {name} must be {shape}, got {tuple(t.shape)}")
+        if NU != Ru * Su or Ri < 1 or NJ % max(Ri, 1):
+            raise RuntimeError(f"ahn_pair_attend: {NU} user / {NJ} item sentence rows do not match {Ru} x {Su} / {Ri} reviews")
+        sm8, rm8 = _mask_u8(sent_masks), _mask_u8(rev_masks)
+        dev = X.device
+        shape = _lib.AhnShape(Ru, Su, Ri, NJ // Ri, F_, 1)
+        z = torch.empty(P, F_, dtype=F32, device=dev)
+        w = torch.empty(P, Ru, Su, dtype=F32, device=dev)
+        v = torch.empty(P, Ru, dtype=F32, device=dev)
+        js = torch.empty(P, NU, dtype=I32, device=dev)
+        jr = torch.empty(P, Ru, dtype=I32, device=dev)
+        p = torch.empty(P, Ru, F_, dtype=F32, device=dev)
+        if P:
+            _call("ahn_pair_attend_fwd", _lib.lib().rbr_ahn_pair_attend_fwd, C.byref(shape), B, G, dev_ptr(X, F32, "X"),
+                  dev_ptr(Xt, F32, "Xt"), dev_ptr(sm8, U8, "sent_masks"), dev_ptr(rm8, U8, "rev_masks"), dev_ptr(Ks, F32, "Ks"),
+                  dev_ptr(Kr, F32, "Kr"), dev_ptr(bt, F32, "bt"), dev_ptr(z, F32, "z"), dev_ptr(w, F32, "w"), dev_ptr(v, F32, "v"),
+                  dev_ptr(js, I32, "js"), dev_ptr(jr, I32, "jr"), dev_ptr(p, F32, "p"), current_stream())
+        ctx.job = (shape, B, G)
+        ctx.save_for_backward(X, Xt, sm8, rm8, Ks, Kr, w, v, js, jr, p)
+        ctx.mark_non_differentiable(w, v, js, jr)
+        return z, w, v, js, jr
+
+    @staticmethod
+    def backward(ctx, dz, dw=None, dv=None, djs=None, djr=None):
+        shape, B, G = ctx.job
+        X, Xt, sm8, rm8, Ks, Kr, w, v, js, jr, p = ctx.saved_tensors
+        dz = dz.contiguous()
+        dX, dXt, dKs, dKr = torch.empty_like(X), torch.empty_like(Xt), torch.empty_like(Ks), torch.empty_like(Kr)
+        dbt_part = torch.empty(B, shape.F, dtype=F32, device=X.device)
+        if B:
+            _call("ahn_pair_attend_bwd", _lib.lib().rbr_ahn_pair_attend_bwd, C.byref(shape), B, G, dev_ptr(X, F32, "X"),
+                  dev_ptr(Xt, F32, "Xt"), dev_ptr(sm8, U8, "sent_masks"), dev_ptr(rm8, U8, "rev_masks"), dev_ptr(Ks, F32, "Ks"),
+                  dev_ptr(Kr, F32, "Kr"), dev_ptr(w, F32, "w"), dev_ptr(v, F32, "v"), dev_ptr(js, I32, "js"), dev_ptr(jr, I32, "jr"),
+                  dev_ptr(p, F32, "p"), dev_ptr(dz, F32, "dz"), dev_ptr(dX, F32, "dX"), dev_ptr(dXt, F32, "dXt"),
+                  dev_ptr(dKs, F32, "dKs"), dev_ptr(dKr, F32, "dKr"), dev_ptr(dbt_part, F32, "dbt_part"), current_stream())
+        return dX, dXt, None, None, dKs, dKr, dbt_part.sum(0), None
+
+
+def ahn_pair_attend(X, Xt, sent_masks, rev_masks, Ks, Kr, bt, *, groups: int = 1, saved: bool = False):
+    """AHN's user-side co-attention as one differentiable op (csrc/ahn_attend.hip; steps 1-4 of ahn_pair_score with a HIP
+    backward).  Grouped layout: G = `groups` = 1 + n_neg groups of B pairs; pair p = g * B + b reads USER row b of X, Xt
+    [B, Ru*Su, F] (sentence vectors and X @ Wt^T), sent_masks [B, Ru, Su], rev_masks [B, Ru] and ITEM row p of Ks [G*B, Ri*Si, F],
+    Kr [G*B, Ri, F]; bt [F] is user_review_trans_layer's bias.  Returns (z [G*B, F], user_sent_weights [G*B, Ru, Su],
+    user_review_weights [G*B, Ru]): z carries gradients to X, Xt, Ks, Kr and bt, the weights are non-differentiable and have
+    ahn_pair_score's bits.  Each max routes its gradient to the lowest-index row that attained it, where torch.max on a tie
+    picks an unspecified one.  No float atomics; the same inputs give the same bits, forward and backward, on every run.
+    saved=True also returns the routing (js int32 [G*B, Ru*Su], jr int32 [G*B, Ru]) -- for tests."""
+    z, w, v, js, jr = _AhnPairAttend.apply(X, Xt, sent_masks, rev_masks, Ks, Kr, bt, int(groups))
+    return (z, w, v, js, jr) if saved else (z, w, v)
+
+
 # --------------------------------------------------------------------------- bidirectional LSTM over padded sequences
 LSTM_MAX_LEN = 1000      # the reference clamps sequence lengths there (models/ahn/ahn_layers.py:307)
 

@@ -1,6 +1,8 @@
 """AHN with the reference's constructor / forward signature, return values and state_dict keys (models/ahn/ahn_model.py:7-92).
 The shared BiLSTM sentence encoder -- about nine tenths of the model's arithmetic -- runs on the HIP kernels of
-csrc/lstm_seq.hip; the hierarchical co-attention behind it is the torch composition of ahn_layers.py."""
+csrc/lstm_seq.hip; the hierarchical co-attention behind it is the torch composition of ahn_layers.py -- or, with `fused_tail`
+and in forward_groups (the BPR step: B users against (1 + n_neg) * B items), its user side is one HIP op, forward and backward
+(functional.ahn_pair_attend, csrc/ahn_attend.hip)."""
 import torch
 import torch.nn as nn
 
@@ -20,6 +22,7 @@ class AHN(nn.Module):
         self.hidden_dim = hidden_dim
         self.word_vocab_size, self.user_size, self.item_size = word_vocab_size, user_size, item_size
         self.validate_ids = True      # device-side range check of every id tensor (functional.sanitize_ids), see DeepCoNNpp
+        self.fused_tail = False       # opt-in: aggregate()'s user side on functional.ahn_pair_attend (csrc/ahn_attend.hip)
 
         self.word_embeddings = WordEmbedding(word_vocab_size, embedding_dim, pretrained_word_embeddings)
         self.word_encoder = Seq2SeqEncoder(nn.LSTM, embedding_dim, hidden_dim // 2, dropout=rnn_dropout, bidirectional=True)
@@ -39,10 +42,10 @@ class AHN(nn.Module):
         reference encodes the sides separately and the zero candidate of the max depends on it.  `drop`: the encoder's
         [sentences, E] dropout multiplier drawn by the caller (user rows first) instead of a fresh one."""
         bz, ur_num, us_num, uw_num = user_reviews.shape
-        _, ir_num, is_num, iw_num = item_reviews.shape
+        bz_i, ir_num, is_num, iw_num = item_reviews.shape         # forward_groups: B users against G * B items
         table = self.word_embeddings.weight
         pad = self.word_embeddings.padding_idx
-        n_u, n_i = bz * ur_num * us_num, bz * ir_num * is_num
+        n_u, n_i = bz * ur_num * us_num, bz_i * ir_num * is_num
         u_len = user_sent_lengths.reshape(n_u).to(torch.int64)
         i_len = item_sent_lenghts.reshape(n_i).to(torch.int64)
         t_u, t_i = RF.lstm_t_out(u_len, uw_num), RF.lstm_t_out(i_len, iw_num)
@@ -56,7 +59,35 @@ class AHN(nn.Module):
             u_drop, i_drop = (None, None) if drop is None else (drop[:n_u], drop[n_u:])
             u_sents = enc.encode_max(RF.embedding(table, user_reviews.reshape(n_u, uw_num), pad), u_len, t_out=t_u, drop=u_drop)
             i_sents = enc.encode_max(RF.embedding(table, item_reviews.reshape(n_i, iw_num), pad), i_len, t_out=t_i, drop=i_drop)
-        return u_sents.reshape(bz, ur_num, us_num, self.hidden_dim), i_sents.reshape(bz, ir_num, is_num, self.hidden_dim)
+        return u_sents.reshape(bz, ur_num, us_num, self.hidden_dim), i_sents.reshape(bz_i, ir_num, is_num, self.hidden_dim)
+
+    def forward_groups(self, user_reviews, item_reviews, user_sent_masks, item_sent_masks, user_sent_lengths, item_sent_lenghts,
+                       user_review_masks, item_review_masks, user_ids, item_ids, *, groups):
+        """forward()'s ten arguments for G * B rows in the negative sampler's layout (G = `groups` = 1 + n_neg: rows [0, B) the
+        observed pairs, rows [(j+1)B, (j+2)B) their j-th negatives, so row g * B + b is user b's) -> forward()'s five outputs for
+        the G * B pairs, with every user encoded ONCE: the user side -- reviews, lengths, masks -- is read from the first B rows
+        only, the item side from all G * B, and the pair-dependent tail is functional.ahn_pair_attend (one HIP launch forward,
+        one backward).  Both sides' sentences go through the encoder as one batch when the word widths agree, each side with its
+        own t_out, as in encode_sentences.
+
+        The AHN BPR rule: fed by data.NegativeFeed over a leave-one-out SentenceFeed, a user is represented -- for the observed
+        item AND for its negatives -- by the observed pair's leave-one-out reviews.  This is a definition, not what forward() on
+        the expanded batch computes: there a negative's own user rows are gathered for the pair (u, i-), which has no review
+        to leave out, i.e. the plain first rv_num reviews.  forward_groups equals forward() on the expanded batch whose user
+        rows are the first B rows repeated G times.  Everything but the encoder and the tail is the torch composition of
+        aggregate()."""
+        G = int(groups)
+        P = item_reviews.shape[0]
+        if G < 1 or P % G or user_reviews.shape[0] != P:
+            raise ValueError(f"forward_groups: {P} item rows / {user_reviews.shape[0]} user rows are not groups={groups} x B pairs")
+        B = P // G
+        if self.validate_ids:
+            user_reviews, item_reviews, user_ids, item_ids = RF.sanitize_ids(
+                [(user_reviews, self.word_vocab_size, 0), (item_reviews, self.word_vocab_size, 0), (user_ids, self.user_size, 0),
+                 (item_ids, self.item_size, 0)])
+        user_sents, item_sents = self.encode_sentences(user_reviews[:B], item_reviews, user_sent_lengths[:B], item_sent_lenghts)
+        return self._aggregate_fused(user_sents, item_sents, user_sent_masks[:B], item_sent_masks, user_review_masks[:B],
+                                     item_review_masks, user_ids, item_ids, G)
 
     def forward(self, user_reviews, item_reviews, user_sent_masks, item_sent_masks, user_sent_lengths, item_sent_lenghts,
                 user_review_masks, item_review_masks, user_ids, item_ids):
@@ -143,13 +174,48 @@ class AHN(nn.Module):
 
     def aggregate(self, user_sents, item_sents, user_sent_masks, item_sent_masks, user_review_masks, item_review_masks,
                   user_ids, item_ids):
-        """Everything behind the sentence vectors (ahn_model.py:70-92): the torch composition, on the inputs' device."""
+        """Everything behind the sentence vectors (ahn_model.py:70-92): the torch composition, on the inputs' device; with
+        `fused_tail` the user side runs on functional.ahn_pair_attend instead (_aggregate_fused at one group)."""
+        if self.fused_tail:
+            return self._aggregate_fused(user_sents, item_sents, user_sent_masks, item_sent_masks, user_review_masks,
+                                         item_review_masks, user_ids, item_ids, 1)
         user_reviews, item_reviews, user_sent_weights, item_sent_weights, _ = self.unbalanced_sentence_aggregator(
             user_sents, item_sents, user_sent_masks, item_sent_masks)
         user_reviews = self.user_review_trans_layer(user_reviews)
         item_reviews = self.item_review_trans_layer(item_reviews)
         rv_users, rv_items, user_review_weights, item_review_weights = self.unbalanced_review_aggregator(
             user_reviews, item_reviews, user_review_masks, item_review_masks)
+        users = torch.cat([rv_users, self.user_embeddings(user_ids)], dim=-1)
+        items = torch.cat([rv_items, self.item_embeddigns(item_ids)], dim=-1)
+        final_features = self.dropout(torch.cat([users, items], dim=-1))
+        out_logits = self.fm(final_features).view(-1)
+        return out_logits, user_sent_weights, item_sent_weights, user_review_weights, item_review_weights
+
+    def _aggregate_fused(self, user_sents, item_sents, user_sent_masks, item_sent_masks, user_review_masks, item_review_masks,
+                         user_ids, item_ids, groups):
+        """aggregate() for B users [B, Ru, Su, F] against groups * B items [G * B, Ri, Si, F] (pair g * B + b is user b's), with
+        the user side's co-attention on functional.ahn_pair_attend (csrc/ahn_attend.hip, forward and backward).  The op takes the
+        three products of the user side's parameters as inputs -- Xt = X Wt^T, Ks = (a * Y) Ws^T, Kr = r' Wr^T, each the
+        autograd `linear` -- which moves user_review_trans_layer's product in front of the weighted sum: a reassociation of
+        aggregate()'s arithmetic, not its bits.  The item side (GatedAttention, item_review_trans_layer), the id embeddings, the
+        dropout and the FM are aggregate()'s torch composition."""
+        sa, ra = self.unbalanced_sentence_aggregator, self.unbalanced_review_aggregator
+        n_u, ur_num, us_num, F_ = user_sents.shape
+        n_i, ir_num, is_num, _ = item_sents.shape
+        item_rows = item_sents.reshape(n_i * ir_num, is_num, F_)
+        item_reviews, item_sent_weights, item_all_sent_weights = sa.item_aggregator(
+            item_rows, item_sent_masks.reshape(n_i * ir_num, is_num))
+        Ks = RF.linear((item_all_sent_weights.reshape(n_i * ir_num * is_num, 1) * item_rows.reshape(n_i * ir_num * is_num, F_)).contiguous(),
+                       sa.bilinear.weight)
+        item_reviews = self.item_review_trans_layer(item_reviews)
+        rv_items, item_review_weights = ra.item_aggregator(item_reviews, item_review_masks)
+        Kr = RF.linear(item_reviews.reshape(n_i * ir_num, F_).contiguous(), ra.bilinear.weight)
+        trans = self.user_review_trans_layer[0]
+        X = user_sents.reshape(n_u * ur_num * us_num, F_).contiguous()
+        Xt = RF.linear(X, trans.weight)
+        rv_users, user_sent_weights, user_review_weights = RF.ahn_pair_attend(
+            X.view(n_u, ur_num * us_num, F_), Xt.view(n_u, ur_num * us_num, F_), user_sent_masks, user_review_masks,
+            Ks.view(n_i, ir_num * is_num, F_), Kr.view(n_i, ir_num, F_), trans.bias, groups=groups)
         users = torch.cat([rv_users, self.user_embeddings(user_ids)], dim=-1)
         items = torch.cat([rv_items, self.item_embeddigns(item_ids)], dim=-1)
         final_features = self.dropout(torch.cat([users, items], dim=-1))

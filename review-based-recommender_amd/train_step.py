@@ -347,6 +347,28 @@ class BprObjective:
         return RF.bpr_loss(pred, n_neg, self.feed.buffers(pred.shape[0] // (1 + n_neg))[2])
 
 
+class AhnBprObjective:
+    """BprObjective for AHN, with the forward_loss(model, batch) protocol: `batch` is the feed's expanded batch -- AHN's ten
+    arguments for (1 + n_neg) * B rows -- and the scores come from model.forward_groups(*batch, groups=1 + n_neg), which encodes
+    every user once (from the observed pair's rows: the AHN BPR rule stated there) and runs the pair-dependent tail as one HIP
+    op; the loss is functional.bpr_loss over the feed's valid flags, as in BprObjective.  The step stays eager."""
+
+    def __init__(self, feed):
+        if not hasattr(feed, "n_neg") or not hasattr(feed, "buffers"):
+            raise ValueError("AhnBprObjective takes a data.NegativeFeed (n_neg, the valid flags of its last draw)")
+        self.feed = feed
+
+    def forward_loss(self, model, batch):
+        if not hasattr(model, "forward_groups"):
+            raise ValueError(f"AhnBprObjective needs a model with forward_groups(); {type(model).__name__} has none")
+        n_neg = self.feed.n_neg
+        rows = batch[0].shape[0]
+        if rows % (1 + n_neg):
+            raise RuntimeError(f"AhnBprObjective: a batch of {rows} rows is not (1 + {n_neg}) * B pairs")
+        pred = model.forward_groups(*batch, groups=1 + n_neg)[0]
+        return pred, RF.bpr_loss(pred, n_neg, self.feed.buffers(rows // (1 + n_neg))[2])
+
+
 class InBatchSoftmaxObjective:
     """The in-batch softmax ranking objective for a step fed through `feed` (a data.InBatchFeed): the towers' latent rows of the
     B observed pairs (model.pair_latents), then functional.pair_softmax_loss over ALL B x B pairs -- every user's negatives are

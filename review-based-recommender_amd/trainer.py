@@ -62,6 +62,18 @@ where the sentence lengths and the sentence / review masks of train_ahn.py:149-1
 lengths and masks -- from (u_id, i_id), leave-one-out for training, plain for validation; `fast_step` selects HipClipAdam but AHN's step
 and eval forward run eagerly (no hipGraph is recorded, and one log line says so); device_cache, eval_from_towers, rank_metrics, a
 `loss` other than "mse", sample_train_review and parallel are refused: AHN's sides attend to each other, so it has no per-id towers.
+`ahn_tables: true` (--model ahn with device_reviews) opts into what AHN's asymmetry does allow -- the item side never looks at the
+user, so every id has SENTENCE tables (recommend.AhnRecommender; about 240 KB per user and 120 KB per item in f32 at the default
+shape: a deliberate memory opt-in, the bytes are logged once after the first refresh).  With it eval_from_towers validates from
+those tables (refresh once per pass, then one launch of the fused pair tail per batch), rank_metrics / select_by rank every
+validation pair's item from them (rank_metrics alone switches eval_from_towers on: AHN has no other way to rank), and `loss: "bpr"`
+trains through AHN.forward_groups (train_step.AhnBprObjective over data.NegativeFeed): a step encodes B users and (1 + n_neg) * B
+items instead of (1 + n_neg) * B of each, the user side's co-attention is one differentiable HIP op (functional.ahn_pair_attend),
+and a user is represented by the observed pair's leave-one-out reviews for its negatives too (the AHN BPR rule, stated at
+forward_groups).  Table scores follow the fixed-t_out rule of DESIGN.md 4.20: they can differ from the loader-fed validation where
+a batch's longest sentence is shorter than the table's.  `fused_pair_tail: true` (with ahn_tables) runs the MSE step's user-side
+co-attention on the same op (AHN.fused_tail).  Still refused for AHN, each with its reason: loss "softmax", neg_candidates > 1,
+sample_train_review, parallel, device_cache; the step stays eager.
 """
 from __future__ import annotations
 
@@ -101,7 +113,7 @@ DEFAULTS = dict(log_dir="logs", dataset="dataset", log=True, log_idx=500, verbos
                 num_workers=0, fast_step=False, shuffle=True, seed=0, record_steps=False, device_cache=False, eval_from_towers=False,
                 device_reviews=False, rank_metrics=[], loss="mse", n_neg=1, neg_seed=None, select_by="rmse",
                 softmax_temperature=1.0, logq_correction=False, neg_candidates=1, neg_refresh_steps=0, sample_train_review=False,
-                u_rv_num=None, i_rv_num=None, review_pool=None, review_sample_seed=None)
+                u_rv_num=None, i_rv_num=None, review_pool=None, review_sample_seed=None, ahn_tables=False, fused_pair_tail=False)
 
 LOSSES = ("mse", "bpr", "softmax")
 
@@ -224,17 +236,38 @@ class ReviewExperiment:
         if kind == "ahn":
             # AHN's two sides attend to each other from the sentences up: there is no per-id tower whose
             # latent row could be cached, ranked from or scored against a sampled negative
+            # `ahn_tables` opts into what the asymmetry does allow: only the user side looks at the pair,
+            # so per-id SENTENCE tables (recommend.AhnRecommender) validate and rank, and a BPR step encodes every user once
             no_towers = "AHN's sides attend to each other, so it has no per-id towers"
+            tables = bool(args.ahn_tables)
+            opt_in = "; \"ahn_tables\": true (with device_reviews) uses per-id sentence tables instead"
             refused = (("device_cache", bool(args.device_cache), "the sentence split's id feed is device_reviews"),
-                       ("eval_from_towers", bool(args.eval_from_towers), no_towers + " to validate from"),
-                       ("rank_metrics", bool(args.rank_metrics), no_towers + " to rank a catalogue from"),
-                       ("loss", args.loss != "mse", f"only \"mse\" is, got {args.loss!r}; the ranking losses score their negatives "
-                        "from per-id towers, and " + no_towers),
+                       ("eval_from_towers", bool(args.eval_from_towers) and not tables, no_towers + " to validate from" + opt_in),
+                       ("rank_metrics", bool(args.rank_metrics) and not tables, no_towers + " to rank a catalogue from" + opt_in),
+                       ("loss", args.loss != "mse" and not tables, f"only \"mse\" is, got {args.loss!r}; the ranking losses score "
+                        "their negatives from per-id towers, and " + no_towers + "; \"ahn_tables\": true (with device_reviews) "
+                        "trains \"bpr\" with every user encoded once"),
+                       ("loss", args.loss == "softmax" and tables, "the in-batch softmax scores all B x B pairs from latent rows, "
+                        "and " + no_towers + " (\"bpr\" is available with ahn_tables)"),
+                       ("neg_candidates", args.neg_candidates != 1 and tables, "the hard-negative sampler scores its candidates "
+                        "from latent tables, and " + no_towers),
                        ("sample_train_review", bool(args.sample_train_review), "review sampling is not built for the sentence split"),
                        ("parallel", bool(args.parallel), "data-parallel AHN is not built"))
             for key, on, why in refused:
                 if on:
                     raise ValueError(f"{key} is not available with --model ahn: {why}")
+            if tables and not bool(args.device_reviews):
+                raise ValueError("ahn_tables needs device_reviews: the per-id sentence tables are encoded from the reviews resident "
+                                 "on the GPU (data.DeviceSentenceCache)")
+            if bool(args.fused_pair_tail) and not tables:
+                raise ValueError("fused_pair_tail needs ahn_tables: both opt into the HIP pair tail of csrc/ahn_attend.hip")
+            if tables and args.rank_metrics:
+                # AHN ranks from the sentence tables only, so asking for ranks IS asking for the table validation: the RMSE line
+                # and the ranks then come from the same scores (the args table prints the key as it ends up)
+                args.eval_from_towers = True
+        elif bool(args.ahn_tables) or bool(args.fused_pair_tail):
+            raise ValueError(f"ahn_tables / fused_pair_tail are valid for --model ahn, not {kind}: the other models have per-id "
+                             "towers (eval_from_towers)")
         if bool(args.device_cache) and kind not in ("deepconn", "dual_att"):
             # the review split's training examples are not per-id data: the reference drops the target pair's own review from
             # the user's and the item's lists before truncating (preprocess/divide_and_create_example_word.py:263-285)
@@ -361,14 +394,18 @@ class ReviewExperiment:
         if args.loss == "bpr":
             # negatives are items the user has not rated in the training split: the same CSR the validation ranks against
             from .recommend import Recommender
-            from .train_step import BprObjective
+            from .train_step import AhnBprObjective, BprObjective
             self._seen = Recommender.seen_from(self.train_set.examples, self.train_set.user_num, self.device)
             seed = args.seed if args.neg_seed is None else args.neg_seed
-            self.train_feed = D.NegativeFeed(self.train_feed, self._seen, self.cache.item.shape[0], n_neg=args.n_neg, seed=int(seed),
+            n_items = (self.cache.item_table if kind == "ahn" else self.cache.item).shape[0]
+            self.train_feed = D.NegativeFeed(self.train_feed, self._seen, n_items, n_neg=args.n_neg, seed=int(seed),
                                              n_cand=args.neg_candidates)
-            self.objective = BprObjective(self.train_feed)
+            # AHN: every user encoded once for its 1 + n_neg items (AHN.forward_groups), not once per expanded pair
+            self.objective = AhnBprObjective(self.train_feed) if kind == "ahn" else BprObjective(self.train_feed)
         self._make_dir()
         self.build_model()
+        if kind == "ahn" and bool(args.fused_pair_tail):
+            self.model.fused_tail = True         # the MSE step's user-side co-attention on csrc/ahn_attend.hip
         if args.loss == "softmax":
             # false negatives are the items the user has rated in the training split: the CSR the validation ranks against
             from .recommend import Recommender
@@ -611,8 +648,9 @@ class ReviewExperiment:
     def _negative_towers(self):
         """The one Recommender of this experiment: the validation's latent tables, and with neg_candidates > 1 the sampler's."""
         if getattr(self, "_towers", None) is None:
-            from .recommend import Recommender
-            self._towers = Recommender(self.model, self.cache)
+            from .recommend import AhnRecommender, Recommender
+            # AHN (ahn_tables): per-id sentence tables and the fused pair tail speak the same protocol
+            self._towers = (AhnRecommender if self.kind == "ahn" else Recommender)(self.model, self.cache)
         return self._towers
 
     def _hand_tables_to_feed(self, towers):
@@ -638,6 +676,11 @@ class ReviewExperiment:
             # pair is two row gathers and the head's arithmetic instead of two document encodes (recommend.Recommender)
             towers = self._negative_towers()
             towers.refresh()
+            if self.kind == "ahn" and not getattr(self, "_table_bytes_logged", False):
+                self._table_bytes_logged = True      # ahn_tables is a memory opt-in: say once what it costs
+                nbytes = sum(t.numel() * t.element_size() for st in (towers.user_state, towers.item_state) for t in st)
+                self.print_write_to_log("ahn_tables: {:,d} bytes of per-id sentence tables ({} users, {} items)".format(
+                    nbytes, towers.n_users, towers.n_items))
             if self.args.neg_candidates > 1:
                 self._hand_tables_to_feed(towers)          # the next epoch's candidates are scored from this pass's tables
         ranks = []
