@@ -70,7 +70,8 @@ typedef struct rbr_textcnn_desc {
 #define RBR_CONV_GATE_SPLIT(k) (((k) & 0xf) << 8)
 #define RBR_CONV_GATE_SPLIT_OF(flags) (((flags) >> 8) & 0xf)
 /* Arithmetic class STAMPED into a descriptor (rbr_textcnn_desc_stamp): bits 16-17 the RBR_PROD_* precision, bit 18 bf16 storage of
- * the product table, bit 19 "stamped".  A stamped descriptor carries the class it was planned with from the forward to the
+ * the product table, bit 19 "stamped", bit 20 the six-product bf16 realisation of RBR_PROD_BF16X3 (clear: RBR_SPLIT_F16X2S where
+ * it applies; the pack launch and the GEMM of one call read the same split, as they read the same class).  A stamped descriptor carries the class it was planned with from the forward to the
  * backward: the workspace layout (weight image, bf16 row copy, element type of T) depends on it, and reading the process-wide
  * settings again in every stage let a change between a forward and its backward -- or between a graph capture and a later
  * eager call on the same workspace -- silently reinterpret T.  An unstamped descriptor (flags bit 19 clear) reads the
@@ -78,6 +79,7 @@ typedef struct rbr_textcnn_desc {
 #define RBR_CONV_CLASS_STAMPED (1 << 19)
 #define RBR_CONV_CLASS_PRECISION_OF(flags) (((flags) >> 16) & 0x3)
 #define RBR_CONV_CLASS_T_BF16 (1 << 18)
+#define RBR_CONV_CLASS_SPLIT_BF16X3 (1 << 20)
 void rbr_textcnn_desc_stamp(rbr_textcnn_desc* d);
 
 int rbr_version(void);
@@ -151,6 +153,26 @@ void rbr_set_conv_mode(int32_t mode);
 #define RBR_PROD_BF16 3
 void rbr_set_prod_precision(int32_t mode);
 int32_t rbr_get_prod_precision(void);
+/* Realisation of the RBR_PROD_BF16X3 class ("exact split on the 16-bit MFMA pipe, f32-class accuracy") on the rows-in-registers
+ * route of the forward GEMM (six or more 128-column groups and D >= 177: DeepCoNN's long documents); every other kernel and class
+ * keeps its arithmetic whatever this says.
+ *   RBR_SPLIT_F16X2S default: x * 2^s = h1 + h2, two f16 planes (22 significant bits), 3 products per f32 product on
+ *                    v_mfma_f32_32x32x16_f16: lo*hi, hi*lo, hi*hi.  s is an integer, one per token row and one per weight
+ *                    column, taken from the exponent field of the row's / column's largest magnitude so that it lands in
+ *                    [2^14, 2^15); applied with ldexp and taken back out of the f32 accumulator with ldexp, so table * 2^k with
+ *                    weights * 2^-k give the same product table bit for bit.  Neglected: the operands' truncation at 2^-22 and
+ *                    the lo*lo term, < 2^-20 |a b| per product together, below the f32 accumulation's own rounding.
+ *   RBR_SPLIT_BF16X3 the six-product bf16 kernel (the fallback and the A/B switch).
+ * Operand domain of RBR_SPLIT_F16X2S: any finite f32 row and column whose largest magnitude is a normal number.  An element more
+ * than 2^16 below its row's (column's) largest magnitude keeps an ABSOLUTE accuracy of 2^-40 of that magnitude instead of 22
+ * relative bits (its low plane lies under f16's normal range; 2^-29 where a matrix pipe flushes f16 subnormals -- gfx950 honours
+ * them).  An all-zero row or column has exponent 0.  A row or column holding inf / NaN has exponent 0 and poisons itself
+ * through its own planes, as above; the other rows and columns keep their bits.
+ * -1 restores the default (env RBR_PROD_SPLIT=f16x2s|bf16x3).  Like the precision: set between steps only. */
+#define RBR_SPLIT_F16X2S 0
+#define RBR_SPLIT_BF16X3 1
+void rbr_set_prod_split(int32_t split);
+int32_t rbr_get_prod_split(void);
 /* RBR_PROD_BF16 with bf16 STORAGE (default on; 0 = f32 streams, -1 = default / env RBR_B16_STORAGE): the byte streams of the
  * conv stage are bf16 as well -- the distinct tokens' rows are rounded once into a compact bf16 copy the GEMM reads (600-byte
  * rows by plain index, no conversion in the loop), and the product table T is stored in bf16 (the gather-add reads half the

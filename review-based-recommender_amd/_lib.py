@@ -22,6 +22,7 @@ ACT_RELU, ACT_TANH = 0, 1
 PROD_F32, PROD_BF16X3, PROD_BF16X2, PROD_BF16 = 0, 1, 2, 3     # rbr_set_prod_precision (RBR_PROD_* of rbr_hip.h)
 SCORE_FM, SCORE_DOT = 0, 1                                       # RBR_SCORE_* of rbr_hip.h (pair_score_*)
 PROD_PRECISIONS = {"f32": PROD_F32, "bf16x3": PROD_BF16X3, "bf16x2": PROD_BF16X2, "bf16": PROD_BF16}
+PROD_SPLITS = {"f16x2s": 0, "bf16x3": 1}                       # rbr_set_prod_split (RBR_SPLIT_* of rbr_hip.h)
 
 c_f32p = C.c_void_p
 c_i64p = C.c_void_p
@@ -110,6 +111,8 @@ SIGNATURES = {
     "rbr_set_conv_mode": (None, [i32]),
     "rbr_set_prod_precision": (None, [i32]),
     "rbr_get_prod_precision": (i32, []),
+    "rbr_set_prod_split": (None, [i32]),
+    "rbr_get_prod_split": (i32, []),
     "rbr_textcnn_desc_stamp": (None, [_DESC]),
     "rbr_set_b16_storage": (None, [i32]),
     "rbr_textcnn_conv_fwd": (C.c_int, [_DESC, c_i64p, c_u8p, c_f32p, c_f32p, _PP, c_f32p, c_f32p, c_i32p, C.c_void_p,

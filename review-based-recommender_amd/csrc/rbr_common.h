@@ -97,6 +97,9 @@ inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 int prod_precision();
 int prod_precision_of(const rbr_textcnn_desc* d);      // the descriptor's stamped class, else the process-wide setting
 bool prod_b16_applicable(const rbr_textcnn_desc* d);
+// the call's forward GEMM is the scaled two-plane f16 kernel (RBR_SPLIT_F16X2S on the rows-in-registers route): what the pack
+// launch and the GEMM both ask, so that the image one writes is the image the other reads
+bool prod_f16x2s_route(const rbr_textcnn_desc* d);
 int prod_b16_groups(int cp_real);
 size_t prod_b16_image_bytes(const rbr_textcnn_desc* d, int cp_real);
 struct B16Pack;

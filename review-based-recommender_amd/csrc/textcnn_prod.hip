@@ -47,14 +47,21 @@ RBR_SHARED_KERNEL_ARG(ProdArgs);
 // ---------------------------------------------------------------------------------- distinct tokens
 // Launch 2 of the forward chain: blocks [0, nb_scan) build the work list of the REAL documents (which 32-token slabs
 // hold an unmasked token), the remaining blocks mark the tokens that occur.  Independent jobs, one launch.
+// nb_wexp trailing blocks (f16x2s split only, textcnn_b16.h): the weight columns' exponents, which the pack items of the next
+// launch read.
 __device__ __forceinline__ void mark_scan_kernel(const ConvPlan& P, int nb_scan, long n_tok, const long long* __restrict__ ids,
                                                         const unsigned char* __restrict__ mask, int* __restrict__ sched,
-                                                        unsigned char* __restrict__ used) {
+                                                        unsigned char* __restrict__ used, const B16Pack& JB, const PtrArray& W,
+                                                        int* __restrict__ wexp, int nb_wexp) {
     if ((int)blockIdx.x < nb_scan) {
         tile_scan_block(P, mask, sched, blockIdx.x, ids);
         return;
     }
-    const long nb = gridDim.x - nb_scan;
+    if ((int)blockIdx.x >= (int)gridDim.x - nb_wexp) {
+        f16s_wexp_block(JB, W, wexp, (int)blockIdx.x - ((int)gridDim.x - nb_wexp));
+        return;
+    }
+    const long nb = gridDim.x - nb_wexp - nb_scan;
     for (long k = (long)(blockIdx.x - nb_scan) * 256 + threadIdx.x; k < n_tok; k += nb * 256)
         if (mask == nullptr || mask[k]) used[ids[k]] = 1;      // benign race: everyone stores 1 (one byte per token id)
 }
@@ -96,13 +103,18 @@ struct KeptState {                   // all NULL: the self-initialising chain
 // Launch A: blocks [0, nb_scan) the slab scan (counting in the workspace: `slabs`), blocks [nb_scan, nb_scan + nb_mark) check,
 // clean and mark the token ids -- the check and the mark of an id in one thread, so no mark can land outside used[] --, the rest
 // check the id sets that are not conv tokens.  The scan reads no ids: the entry refuses convs whose scan would (RBR_CONV_PAD_RUNS
-// without a mask), because the clean ids are only being written beside it.
+// without a mask), because the clean ids are only being written beside it.  nb_wexp trailing blocks: as in mark_scan_kernel.
 __global__ __launch_bounds__(256) void mark_scan_ids_kernel(const ConvPlan P, int nb_scan, int nb_mark, long n_tok, const IdSets S,
                                                             long long* __restrict__ err, const unsigned char* __restrict__ mask,
                                                             int* __restrict__ sched, int* __restrict__ slabs,
-                                                            unsigned char* __restrict__ used, int V) {
+                                                            unsigned char* __restrict__ used, int V, const B16Pack JB,
+                                                            const PtrArray W, int* __restrict__ wexp, int nb_wexp) {
     if ((int)blockIdx.x < nb_scan) {
         tile_scan_block(P, mask, sched, blockIdx.x, nullptr, slabs);
+        return;
+    }
+    if ((int)blockIdx.x >= (int)gridDim.x - nb_wexp) {
+        f16s_wexp_block(JB, W, wexp, (int)blockIdx.x - ((int)gridDim.x - nb_wexp));
         return;
     }
     if ((int)blockIdx.x < nb_scan + nb_mark) {
@@ -114,7 +126,7 @@ __global__ __launch_bounds__(256) void mark_scan_ids_kernel(const ConvPlan P, in
         return;
     }
     const long long total = S.first[S.count];
-    const long nb = gridDim.x - nb_scan - nb_mark;
+    const long nb = gridDim.x - nb_wexp - nb_scan - nb_mark;
     for (long long k = n_tok + (long long)(blockIdx.x - nb_scan - nb_mark) * 256 + threadIdx.x; k < total; k += (long long)nb * 256)
         sanitize_id(S, k, err);
 }
@@ -1608,6 +1620,18 @@ ZeroRegions list_state_regions(const ProdState& S, int* doc_counters) {
                        {(long)((S.Lo.used_bytes + S.Lo.mask_bytes) / sizeof(int)), kSchedCounters, doc_counters ? kSchedCounters : 0}};
 }
 
+// The exponent role of the launch in front of the pack launch (f16x2s split of the forward GEMM only, else no blocks): the
+// weight columns' exponents go behind the two-plane image.
+struct WexpJob { B16Pack JB; PtrArray W; int* wexp; int nb; };
+WexpJob wexp_job(const rbr_textcnn_desc* d, const ProdState& S, const float* const* W, bool fwd_images) {
+    WexpJob X{};
+    if (fwd_images && prod_b16_applicable(d)) X.JB = prod_b16_pack_job(d);
+    X.W = ptr_array<PtrArray>(W, d->n_widths);
+    X.nb = f16s_wexp_blocks(X.JB);
+    X.wexp = X.nb ? f16s_wexp(X.JB, S.bimg) : nullptr;
+    return X;
+}
+
 // The last launch of every chain: marks -> token list (kept: the form of KeptState, a direct launch that never pairs), and the
 // pack role.  fwd_images: the weight image of the forward GEMM (the f32 tile image; for the bf16-plane GEMM its weight planes in
 // MFMA-fragment order instead) beside Wprod^T.
@@ -1643,8 +1667,10 @@ int build_list(const rbr_textcnn_desc* d, const ConvPlan& plan, const ProdState&
     const long n_tok = (long)d->n_docs * d->L;
     const int nb_scan = sched ? (plan.total_wt + 255) / 256 : 0;
     const int nb_mark = (int)std::min<long>((n_tok + 255) / 256, 2048);
-    if (int e = rbr::launch<mark_scan_kernel, 256>(dim3(nb_scan + nb_mark), dim3(256), 0, st, "textcnn mark_scan launch", plan, nb_scan,
-                                                   n_tok, reinterpret_cast<const long long*>(ids), mask, sched, S.used))
+    const WexpJob X = wexp_job(d, S, W, sched != nullptr);
+    if (int e = rbr::launch<mark_scan_kernel, 256>(dim3(nb_scan + nb_mark + X.nb), dim3(256), 0, st, "textcnn mark_scan launch", plan,
+                                                   nb_scan, n_tok, reinterpret_cast<const long long*>(ids), mask, sched, S.used, X.JB,
+                                                   X.W, X.wexp, X.nb))
         return e;
     return launch_compact_pack(d, S, W, sched != nullptr, nullptr, st);
 }
@@ -1681,8 +1707,9 @@ static int prod_prepare(const rbr_textcnn_desc* d, const int64_t* ids, const uin
         const int nb_scan = (plan.total_wt + 255) / 256;
         const int nb_mark = (int)std::min<long>((n_tok + 255) / 256, 2048);
         const int nb_rest = (int)std::min<long long>((rest + 255) / 256, 2048);
-        hipLaunchKernelGGL(mark_scan_ids_kernel, dim3(nb_scan + nb_mark + nb_rest), dim3(256), 0, st, plan, nb_scan, nb_mark, n_tok,
-                           *id_sets, err_rec, mask, sched, S.counter + kKeptSlabs, S.used, d->V);
+        const WexpJob X = wexp_job(d, S, W, true);
+        hipLaunchKernelGGL(mark_scan_ids_kernel, dim3(nb_scan + nb_mark + nb_rest + X.nb), dim3(256), 0, st, plan, nb_scan, nb_mark, n_tok,
+                           *id_sets, err_rec, mask, sched, S.counter + kKeptSlabs, S.used, d->V, X.JB, X.W, X.wexp, X.nb);
         RBR_CHECK_LAUNCH("textcnn mark_scan_ids launch");
         const KeptState KS{S.counter + kKeptTicket, S.counter + kKeptSlabs, doc_counters, S.counter,
                            (int)(S.Lo.used_bytes / 16), (int)S.Lo.mask_bytes};

@@ -379,6 +379,170 @@ __device__ __forceinline__ void prod_gemm_b16d_kernel(const B16Gemm& g) {
     }
 }
 
+// ---------------------------------------------------------------------------------- two scaled f16 planes (f16x2s)
+// The rows-in-registers kernel above (NT = 8) with a second realisation of the same arithmetic class: v_mfma_f32_32x32x16_f16
+// runs at the bf16 rate and an f16 plane carries 11 significant bits, so TWO planes of x * 2^s carry 22 and the contraction is
+// 3 products per f32 product -- lo*hi, hi*lo, hi*hi, small terms first -- instead of 6; what f16 lacks in exponent range an
+// integer exponent per token row and per weight column gives back exactly (textcnn_b16.h).
+//   prologue : lane (r32, h) reads its half of the row once (the K loop re-reads lines that are then in L2), takes the integer
+//              max of the magnitudes' bits and meets the other half by one shuffle: the row's exponent.  No launch, no atomics.
+//   stage    : 2 row loads + 2 planes x 2 groups of weight fragments = kOps = 6 vector-memory instructions per wave, 16 KiB of
+//              LDS; three stages = 48 KiB (72 for the three-plane image), two workgroups per CU as before.
+//   epilogue : T = ldexp(acc, -(s_row + s_col)); the exponents of a lane's 16 output rows come from their lanes by shuffle.
+// Counted waits: every stage issues exactly kOps instructions after its barrier (clamped sources past the end), so in front of
+// stage c's barrier everything but the youngest kOps -- stage c + 1's -- has landed: s_waitcnt vmcnt(6).  The prologue's row
+// reads are issued behind the first two stages' loads and fills (which need no exponent: their latency and the prologue's are
+// one round trip, not two) and the exponent the first split needs waits for them, hence for everything older: nothing is in
+// flight when stage 0 begins, and the count holds from there.
+// Measured at cfg2, same box, alternating: 58.1 us (prod_gemm_b16d_kernel<6, 8>) -> 45.4.  Tried and
+// dropped: every fragment of a stage read into registers BEFORE the stage's fills are issued, with and without the row scaling
+// ahead of them too (the compiler drains all LDS-DMA in flight in front of any LDS read or row-register use that follows a fill
+// -- s_waitcnt vmcnt(0) in the middle of every stage, in the kernel above as well -- and with the reads first that drain moves
+// to the next stage's start): 242 / 256 registers, 46.9 / 49.3 us.  The drain is hidden by the CU's other workgroup as it is.
+constexpr int kF16dStages = 3;
+constexpr int kF16dStageBytes = 2 * kF16BBytes;                 // 16 KiB: [group][tile][plane]
+constexpr int kF16dLds = kF16dStages * kF16dStageBytes;         // 48 KiB
+constexpr int kF16dOps = 2 + 2 * 2;
+
+__device__ __forceinline__ void prod_gemm_f16d_kernel(const B16Gemm& g, const int* __restrict__ wexp) {
+    extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+    constexpr int S = kF16dStages, NG = 2, NT = 8;
+    static_assert(kF16dOps == 6, "the counted wait of a stage below is vmcnt(6)");
+    const int n = min(*g.counter, g.cap);
+    const int gpw = (g.ngroups + NG - 1) / NG;                   // workgroups per row block
+    const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
+    const int mblock = (jj / gpw) * 8 + xcd, ng = (jj - (jj / gpw) * gpw) * NG;
+    const int m0 = mblock * kB16BM;
+    if (m0 >= n) return;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int D = g.D;
+    unsigned char* const Bbuf = smem;
+    const int r32 = lane & 31, h = lane >> 5;
+    const int row = m0 + wave * 32 + r32;
+    const float* const arow = (row < n) ? g.table + g.tok_of_row[row] * (long)D + 8 * h : nullptr;
+    const int nch = g.nchunks;
+    const unsigned char* bsrc[NG];
+#pragma unroll
+    for (int q = 0; q < NG; ++q)       // a second group past the last one re-reads the last (its tiles are never stored)
+        bsrc[q] = g.bimg + ((size_t)min(ng + q, g.ngroups - 1) * nch) * kF16BBytes + (size_t)wave * 2 * kB16BFrag + lane * 16;
+    // the exponents of this lane's NT columns (a column of a group that does not exist reads the last group's: never stored)
+    // (|s| <= 141: kept two to a register until the epilogue)
+    int s_col2[NT / 2];
+#pragma unroll
+    for (int t = 0; t < NT; t += 2) {
+        const int* we = wexp + min(ng + (t >> 2), g.ngroups - 1) * kB16BN + (t & 3) * 32 + r32;
+        s_col2[t / 2] = (we[0] & 0xffff) | (we[32] << 16);
+    }
+    f32x4 ring0[S], ring1[S];                  // [slot]: floats 0..3 / 4..7 of the lane's 8 (compile-time slots only)
+    auto issue_a = [&](int c, f32x4& x0, f32x4& x1) {          // ALWAYS two loads (clamped source past the end / outside the rows)
+        const int cs = min(c, nch - 1), col = cs * kB16KC + 8 * h;
+        const float* s0 = (arow != nullptr && col + 4 <= D) ? arow + cs * kB16KC : g_b16_zero;
+        const float* s1 = (arow != nullptr && col + 8 <= D) ? arow + cs * kB16KC + 4 : g_b16_zero;
+        x0 = *reinterpret_cast<const f32x4*>(s0);
+        x1 = *reinterpret_cast<const f32x4*>(s1);
+    };
+    auto issue_b = [&](int c, int slot) {                      // ALWAYS four fills
+        const int cs = min(c, nch - 1);
+#pragma unroll
+        for (int q = 0; q < NG; ++q) {
+            unsigned char* B = Bbuf + slot * kF16dStageBytes + q * kF16BBytes + wave * 2 * kB16BFrag;
+            const unsigned char* s_ = bsrc[q] + (size_t)cs * kF16BBytes;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) b16_dma16(s_ + t * kB16BFrag, B + t * kB16BFrag);
+        }
+    };
+    // the first stages' loads and fills leave first (they need no exponent), then the row's exponent: twenty steps' loads in flight
+    // at a time (a step past the end re-reads the last one) -- one round trip at D <= 320
+#pragma unroll
+    for (int c = 0; c < S - 1; ++c) { issue_a(c, ring0[c], ring1[c]); issue_b(c, c); }
+    unsigned am = 0u;
+    for (int c0 = 0; c0 < nch; c0 += 20) {
+        f32x4 x[40];
+#pragma unroll
+        for (int i = 0; i < 20; ++i) {
+            const int cs = min(c0 + i, nch - 1), col = cs * kB16KC + 8 * h;
+            const float* s0 = (arow != nullptr && col + 4 <= D) ? arow + cs * kB16KC : g_b16_zero;
+            const float* s1 = (arow != nullptr && col + 8 <= D) ? arow + cs * kB16KC + 4 : g_b16_zero;
+            x[2 * i] = *reinterpret_cast<const f32x4*>(s0);
+            x[2 * i + 1] = *reinterpret_cast<const f32x4*>(s1);
+        }
+#pragma unroll
+        for (int i = 0; i < 40; ++i) {
+            const u32x4 b = __builtin_bit_cast(u32x4, x[i]);
+            am = max(max(am, b.x & 0x7fffffffu), max(b.y & 0x7fffffffu, max(b.z & 0x7fffffffu, b.w & 0x7fffffffu)));
+        }
+    }
+    am = max(am, (unsigned)__shfl_xor((int)am, 32));
+    const int s_row = f16s_exponent(am);
+    f32x16 acc[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+    f16x8 a_hi, a_lo;                          // planes of the stage being multiplied
+    f16x8 n_hi, n_lo;                          // ... of the next one: split between this stage's MFMAs, handed over at its end
+    auto split_rows = [&](const f32x4 x0, const f32x4 x1) {
+        unsigned h4[4], l4[4];
+        split_pair_f16(x0.x, x0.y, s_row, h4[0], l4[0]);
+        split_pair_f16(x0.z, x0.w, s_row, h4[1], l4[1]);
+        split_pair_f16(x1.x, x1.y, s_row, h4[2], l4[2]);
+        split_pair_f16(x1.z, x1.w, s_row, h4[3], l4[3]);
+        const u32x4 ah = {h4[0], h4[1], h4[2], h4[3]}, al = {l4[0], l4[1], l4[2], l4[3]};
+        n_hi = __builtin_bit_cast(f16x8, ah);
+        n_lo = __builtin_bit_cast(f16x8, al);
+    };
+    auto mma_tile = [&](const unsigned char* B, int t) {       // t: tile of the workgroup's NT (group t / 4, tile t % 4 of it)
+        const unsigned char* bf = B + (t >> 2) * kF16BBytes + ((t & 3) * 2) * kB16BFrag;
+        const f16x8 b_hi = *reinterpret_cast<const f16x8*>(bf);
+        const f16x8 b_lo = *reinterpret_cast<const f16x8*>(bf + kB16BFrag);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, acc[t], 0, 0, 0);      // small terms first
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_lo, acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, acc[t], 0, 0, 0);
+    };
+    auto stage = [&](int c, auto Sc_) {
+        constexpr int Sc = decltype(Sc_)::value;
+        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");        // stage c landed: one younger stage x kF16dOps
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const unsigned char* B = Bbuf + Sc * kF16dStageBytes + lane * 16;
+        mma_tile(B, 0);
+        issue_a(c + S - 1, ring0[(Sc + S - 1) % S], ring1[(Sc + S - 1) % S]);
+        mma_tile(B, 1);
+        issue_b(c + S - 1, (Sc + S - 1) % S);
+        split_rows(ring0[(Sc + 1) % S], ring1[(Sc + 1) % S]);
+#pragma unroll
+        for (int t = 2; t < NT; ++t) mma_tile(B, t);
+#pragma unroll
+        for (int k = 0; k < NT * 3; ++k) {                       // one MFMA, then two VALU instructions of the split
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+        }
+        a_hi = n_hi; a_lo = n_lo;
+    };
+    split_rows(ring0[0], ring1[0]);
+    a_hi = n_hi; a_lo = n_lo;
+    for (int c = 0; c < nch; c += 3) {                           // workgroup-uniform guards
+        stage(c, std::integral_constant<int, 0>{});
+        if (c + 1 < nch) stage(c + 1, std::integral_constant<int, 1>{});
+        if (c + 2 < nch) stage(c + 2, std::integral_constant<int, 2>{});
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // the surplus fills have drained before the LDS is released
+    float* out = g.T + (size_t)(m0 + wave * 32 + 4 * h) * g.pitch + ng * kB16BN + r32;
+    const int rows_left = n - (m0 + wave * 32 + 4 * h);
+    const int tiles_ok = min(NT, (g.ngroups - ng) * 4);          // the tiles of a second group that does not exist are dropped
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int dr = (r & 3) + 8 * (r >> 2);
+        const int sr = __shfl(s_row, 4 * h + dr);                // every lane takes part; row 4 h + dr of the tile is lane 4 h + dr
+        if (dr < rows_left) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                if (t < tiles_ok) out[(size_t)dr * g.pitch + t * 32] = ldexpf(acc[t][r], -(sr + ((t & 1) ? s_col2[t / 2] >> 16 : (int)(short)s_col2[t / 2])));
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------- rows stationary (short K)
 // The same GEMM for a SHORT contraction (D <= 128: D-ATT's 100-wide embeddings are 7 steps).  With so few steps the kernels
 // above spend as long filling their ring and storing their tile as multiplying: a 128 x 128 item is ~9 us of which 4.5 are the
@@ -691,6 +855,19 @@ int prod_precision_of(const rbr_textcnn_desc* d) {
 }
 bool prod_b16_applicable(const rbr_textcnn_desc* d) { return prod_precision_of(d) != RBR_PROD_F32 && d->D % 4 == 0; }
 
+// Realisation of the BF16X3 class on the rows-in-registers route: the scaled two-plane f16 split (default) or the six-product
+// bf16 kernel.  Stamped beside the class: the pack launch and the GEMM of one call read the same split.
+static int g_prod_split = -1;            // -1: RBR_PROD_SPLIT env or the default (f16x2s)
+int prod_split() {
+    if (g_prod_split >= 0) return g_prod_split;
+    static const char* env = getenv("RBR_PROD_SPLIT");
+    return (env && !strcmp(env, "bf16x3")) ? RBR_SPLIT_BF16X3 : RBR_SPLIT_F16X2S;
+}
+static bool gemm_rows_in_registers_ok() {
+    static const bool ok = getenv("RBR_GEMM_ROWS_IN_LDS") == nullptr || atoi(getenv("RBR_GEMM_ROWS_IN_LDS")) == 0;
+    return ok;
+}
+
 // bf16 STORAGE (rows copy, product table): the plain-bf16 class only; RBR_B16_STORAGE=0 keeps f32 streams (an A/B switch: same
 // arithmetic class either way, T's extra rounding stays inside the class's stated tolerances)
 static int g_b16_storage = -1;           // -1: RBR_B16_STORAGE env (default on), 0 off, 1 on
@@ -707,6 +884,17 @@ size_t prod_b16_rows_bytes(const rbr_textcnn_desc* d, int cap) {
 }
 
 int prod_b16_groups(int cp_real) { return (cp_real + kB16BN - 1) / kB16BN; }
+// six or more column groups and twelve or more K steps, f32 product table, class BF16X3: where prod_b16_gemm takes the
+// rows-in-registers kernel
+bool prod_f16x2s_route(const rbr_textcnn_desc* d) {
+    if (!prod_b16_applicable(d) || prod_precision_of(d) != RBR_PROD_BF16X3 || !gemm_rows_in_registers_ok()) return false;
+    const int split = (d->flags & RBR_CONV_CLASS_STAMPED) ? ((d->flags & RBR_CONV_CLASS_SPLIT_BF16X3) ? RBR_SPLIT_BF16X3 : RBR_SPLIT_F16X2S)
+                                                          : prod_split();
+    if (split != RBR_SPLIT_F16X2S) return false;
+    int cp = 0;
+    for (int w = 0; w < d->n_widths; ++w) cp += d->kz[w] * d->ch[w];
+    return prod_b16_groups(cp) >= 6 && (d->D + kB16KC - 1) / kB16KC >= 12;
+}
 size_t prod_b16_image_bytes(const rbr_textcnn_desc* d, int cp_real) {
     return (size_t)prod_b16_groups(cp_real) * ((d->D + kB16KC - 1) / kB16KC) * kB16BBytes;
 }
@@ -719,6 +907,7 @@ B16Pack prod_b16_pack_job(const rbr_textcnn_desc* d) {
     J.cp_real = o;
     J.ngroups = prod_b16_groups(o);
     J.nchunks = (d->D + kB16KC - 1) / kB16KC;
+    J.f16 = prod_f16x2s_route(d) ? 1 : 0;
     return J;
 }
 
@@ -906,7 +1095,7 @@ int prod_b16_gemm(const rbr_textcnn_desc* d, int cp_real, int cap, int pitch, co
     // measured to win: six or more groups (three workgroups per row block: cfg2's 167 row blocks fill the 512 workgroup slots
     // once) and a K of at least 12 steps.  NARRE cfg3 (4 groups: 314 workgroups) 36.5 us against 32.0, D-ATT's merged conv (9
     // groups but K = 100: 7 steps) 61 against 58 -- those keep the kernel above.
-    static const bool direct_ok = getenv("RBR_GEMM_ROWS_IN_LDS") == nullptr || atoi(getenv("RBR_GEMM_ROWS_IN_LDS")) == 0;
+    const bool direct_ok = gemm_rows_in_registers_ok();
     // Short contractions (D <= 128) with at least four column groups: the rows-stationary kernel (D-ATT's merged conv: 9 groups
     // x 7 steps).  RBR_GEMM_ROWS_STATIONARY=0: the ring kernel below.
     static const bool stationary_ok = getenv("RBR_GEMM_ROWS_STATIONARY") == nullptr || atoi(getenv("RBR_GEMM_ROWS_STATIONARY")) != 0;
@@ -923,6 +1112,12 @@ int prod_b16_gemm(const rbr_textcnn_desc* d, int cp_real, int cap, int pitch, co
     }
     if (direct_ok && g.ngroups >= 6 && g.nchunks >= 12) {
         const dim3 grid_d((unsigned)(mblocks * ((g.ngroups + 1) / 2)));
+        if (prod_f16x2s_route(d)) {      // two scaled f16 planes: the image and the column exponents behind it are the pack launch's
+            B16Pack J{};
+            J.ngroups = g.ngroups; J.nchunks = g.nchunks;
+            const int* wexp = f16s_wexp(J, const_cast<unsigned char*>(g.bimg));
+            return rbr::launch<prod_gemm_f16d_kernel, kB16Threads, 2>(grid_d, block, kF16dLds, st, "textcnn prod_gemm_f16d launch", g, wexp);
+        }
         switch (prod_precision_of(d)) {
             case RBR_PROD_BF16X3: return rbr::launch<prod_gemm_b16d_kernel<6, 8>, kB16Threads, 2>(grid_d, block, B16d<8>::kLds, st, "textcnn prod_gemm_b16d launch", g);
             case RBR_PROD_BF16X2: return rbr::launch<prod_gemm_b16d_kernel<3, 8>, kB16Threads, 2>(grid_d, block, B16d<8>::kLds, st, "textcnn prod_gemm_b16d launch", g);
@@ -946,7 +1141,12 @@ extern "C" void rbr_set_prod_precision(int32_t mode) {
 extern "C" int32_t rbr_get_prod_precision(void) { return rbr::prod_precision(); }
 extern "C" void rbr_textcnn_desc_stamp(rbr_textcnn_desc* d) {
     if (!d) return;
-    d->flags &= ~(RBR_CONV_CLASS_STAMPED | RBR_CONV_CLASS_T_BF16 | (0x3 << 16));
-    d->flags |= RBR_CONV_CLASS_STAMPED | ((rbr::prod_precision() & 0x3) << 16) | (rbr::b16_storage_setting() ? RBR_CONV_CLASS_T_BF16 : 0);
+    d->flags &= ~(RBR_CONV_CLASS_STAMPED | RBR_CONV_CLASS_T_BF16 | RBR_CONV_CLASS_SPLIT_BF16X3 | (0x3 << 16));
+    d->flags |= RBR_CONV_CLASS_STAMPED | ((rbr::prod_precision() & 0x3) << 16) | (rbr::b16_storage_setting() ? RBR_CONV_CLASS_T_BF16 : 0) |
+                (rbr::prod_split() == RBR_SPLIT_BF16X3 ? RBR_CONV_CLASS_SPLIT_BF16X3 : 0);
 }
+extern "C" void rbr_set_prod_split(int32_t split) {
+    rbr::g_prod_split = (split == RBR_SPLIT_F16X2S || split == RBR_SPLIT_BF16X3) ? split : -1;
+}
+extern "C" int32_t rbr_get_prod_split(void) { return rbr::prod_split(); }
 extern "C" void rbr_set_b16_storage(int32_t on) { rbr::g_b16_storage = (on == 0 || on == 1) ? on : -1; }

@@ -84,6 +84,21 @@ def get_prod_precision() -> str:
     return {v: k for k, v in _lib.PROD_PRECISIONS.items()}[mode]
 
 
+def set_prod_split(name: Optional[str]) -> None:
+    """Realisation of the "bf16x3" class on the forward GEMM's rows-in-registers route (rbr_set_prod_split; six or more
+    128-column groups, D >= 177): "f16x2s" (default: two scaled f16 planes, 3 plane products, the same f32-class accuracy) or
+    "bf16x3" (the six-product bf16 kernel: the A/B switch); None restores the default (env RBR_PROD_SPLIT).  Every other kernel
+    and class ignores it.  Set it between steps, like the precision."""
+    if name is not None and name not in _lib.PROD_SPLITS:
+        raise ValueError(f"unknown product split {name!r}; one of {sorted(_lib.PROD_SPLITS)}")
+    _lib.lib().rbr_set_prod_split(-1 if name is None else _lib.PROD_SPLITS[name])
+
+
+def get_prod_split() -> str:
+    split = _lib.lib().rbr_get_prod_split()
+    return {v: k for k, v in _lib.PROD_SPLITS.items()}[split]
+
+
 # --------------------------------------------------------------------------- id range check
 _ID_ERR: dict = {}       # per device: int64[4] error record of rbr_sanitize_ids (zero while clean)
 
