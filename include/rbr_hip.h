@@ -369,6 +369,35 @@ int rbr_textcnn_saliency(const rbr_textcnn_desc* d, const int64_t* ids, const ui
                          const float* table, const float* const* W, const float* feat, const int32_t* argmax,
                          const float* d_feat, float* sal, void* stream);
 
+/* Explaining a D-ATT score: per-position contributions of one tower THROUGH both attention gates.  d carries
+ * RBR_CONV_GATE_SPLIT(k): the banks [0, k) sit under the local gate gate_l[doc, t] = gate[0][doc][t], the rest under the global
+ * gate gate_g[doc] = gate[1][doc][0] (one scalar per document; its plane repeats it over L, as the forward reads it).  With
+ * x[t] = table[ids[doc, t]], g[c] = d_feat[doc,c] * act'(feat[doc,c]) and pos(p, j) as for rbr_textcnn_saliency:
+ *   raw_l[t]    = sum over banks w <  k, channels c, taps j with pos(argmax[doc,c], j) == t of g[c] * <x[t], W[w][c, :, j]>
+ *   raw_g[t]    = the same over banks w >= k
+ *   fixed[t]    = gate_l[t] * raw_l[t] + gate_g * raw_g[t]          gradient x input with the gates held constant
+ *   d_gate_l[t] = raw_l[t]                                          d score / d gate_l[t]
+ *   d_gate_g    = sum_t raw_g[t]                                    d score / d gate_g (fixed summation order)
+ *   dpre_l[s]   = d_gate_l[s] * gate_l[s] * (1 - gate_l[s]);  dpre_g = d_gate_g * gate_g * (1 - gate_g)
+ *   through[t]  = sum_{j < win} [0 <= s < L] dpre_l[s] * <x[t], w_l[:, j]>,  s = t - j + (win - 1) / 2
+ *               + dpre_g * <x[t], w_g[:, t]>
+ * so that fixed[t] + through[t] = <d score / d x[t], x[t]> exactly, with only the max-pool routing held fixed.  w_l [1, E, win]
+ * and w_g [1, E, L] are the gates' Conv1d weights (rbr_datt_local_gate_fwd / rbr_datt_global_gate_fwd); the gate biases play no
+ * part.  d_gate_* are raw sums, never fixed / gate: a saturated gate (exactly 0.0f or 1.0f) still reports its d_gate, and its
+ * share of `through` is exactly 0.  A tap outside [0, L) is the zero padding; an argmax outside the pooled range contributes
+ * nothing and is never used as an index; a token id outside [0, V) is never used as an index (its row counts as zero);
+ * padding_idx plays no part.
+ * fixed / through / d_gate_l [n_docs, L] and d_gate_g [n_docs] are OVERWRITTEN, every element once with a plain store, 0.0f where
+ * nothing lands.  Two launches on `stream`, no workspace (d_gate_* hand launch 1's sums to launch 2), no host synchronisation,
+ * no atomics: a document's rows have the same bits on every run and in every batch.  W is the HOST array of the torch-layout
+ * conv weights.  n_docs == 0 returns 0 without a launch.  RBR_ERR_BAD_ARG, with the cause in rbr_last_error(): a null pointer, a
+ * split outside 1 <= k < n_widths, win even or < 1; RBR_ERR_UNSUPPORTED: win > 9, a conv width > 9 -- nothing is launched.
+ * Reference counterpart: none (the reference computes both gates and has no attribution, models/dual_att/layers.py:43-89). */
+int rbr_datt_saliency(const rbr_textcnn_desc* d, const int64_t* ids, const float* gate, const float* table,
+                      const float* const* W, const float* feat, const int32_t* argmax, const float* d_feat, int32_t win,
+                      const float* w_l, const float* w_g, float* fixed, float* through, float* d_gate_l, float* d_gate_g,
+                      void* stream);
+
 /* ---- Rating head: LastFeat x2 + FM (deepconn/layers.py:156-165,189-209; narre.py:84-93,118-137)
  *   ul = u_feat @ Wu + bu + Eu[u_id];  il = i_feat @ Wi + bi + Ei[i_id]
  *   pred = (relu(ul*il) * drop) @ h + ub[u_id] + ib[i_id] + g

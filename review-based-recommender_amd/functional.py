@@ -1052,7 +1052,60 @@ def textcnn_saliency(table: torch.Tensor, ids: torch.Tensor, mask: Optional[torc
     return sal
 
 
-_HEAD_NAMES = ("Wu", "bu", "Eu", "Wi", "bi", "Ei", "h", "g", "ub", "ib")
+class DattSaliency(NamedTuple):
+    """datt_saliency: fixed / through / d_gate_l [n_docs, L], d_gate_g [n_docs]; fixed + through is gradient x input."""
+    fixed: torch.Tensor
+    through: torch.Tensor
+    d_gate_l: torch.Tensor
+    d_gate_g: torch.Tensor
+
+
+def datt_saliency(table: torch.Tensor, ids: torch.Tensor, gates, weights: Sequence[torch.Tensor], feat: torch.Tensor,
+                  argmax: torch.Tensor, d_feat: torch.Tensor, attn_weights, *, gate_split: int = 1, pad_mode: int = PAD_VALID,
+                  act: int = ACT_TANH) -> DattSaliency:
+    """What every token position of a D-ATT tower contributes to a score whose gradient on the tower's pooled features is
+    d_feat [n_docs, C], followed THROUGH both attention gates: fixed + through = <d score / d x[t], x[t]> for the embedded rows
+    x, with only the max-pool routing (feat / argmax [n_docs, C] as textcnn(return_argmax=True) returned them) held fixed;
+    rbr_datt_saliency in rbr_hip.h has the formula.
+    gates = (gate_l, gate_g) [n_docs, L] each, the planes the forward used (datt_gate), or the stacked [2, n_docs, L];
+    weights: the conv banks, the first gate_split of them under gate_l; attn_weights = (w_l [1, E, win], w_g [1, E, L]), the
+    gates' Conv1d weights.  Two launches, no autograd, no embedded rows are materialised; a document's rows are bit-identical
+    in every batch."""
+    if not (isinstance(attn_weights, (tuple, list)) and len(attn_weights) == 2):
+        raise RuntimeError("attn_weights must be (w_l [1, E, win], w_g [1, E, L])")
+    table_c, ids, _, ws, desc = _conv_operands(table, ids, None, weights, pad_mode, act, None, _lib.conv_gate_split(gate_split))
+    n_docs, L = ids.shape
+    E = table_c.shape[1]
+    Ctot = sum(int(w.shape[0]) for w in ws)
+    for w in ws:
+        if w.dim() != 3 or w.shape[1] != E:
+            raise RuntimeError(f"conv weights must be [C_w, D = {E}, kz_w], got {tuple(w.shape)}")
+    feat, argmax, d_feat = feat.detach().contiguous(), argmax.contiguous(), d_feat.detach().contiguous()
+    for t, name in ((feat, "feat"), (argmax, "argmax"), (d_feat, "d_feat")):
+        if tuple(t.shape) != (n_docs, Ctot):
+            raise RuntimeError(f"{name} must be [n_docs, C] = {(n_docs, Ctot)}, got {tuple(t.shape)}")
+    gate = torch.stack([gates[0], gates[1]]) if isinstance(gates, (tuple, list)) else gates
+    gate = gate.detach().contiguous()
+    if tuple(gate.shape) != (2, n_docs, L):
+        raise RuntimeError(f"gates must be two planes [n_docs, L] = {(n_docs, L)} each, got {tuple(gate.shape)}")
+    w_l, w_g = (w.detach().contiguous() for w in attn_weights)
+    if w_l.dim() != 3 or w_l.shape[0] != 1 or w_l.shape[1] != E:
+        raise RuntimeError(f"the local gate's weight must be [1, E = {E}, win], got {tuple(w_l.shape)}")
+    if tuple(w_g.shape) != (1, E, L):
+        raise RuntimeError(f"the global gate's weight must be [1, E, L] = {(1, E, L)}, got {tuple(w_g.shape)}")
+    ptrs = (dev_ptr(ids, I64, "ids"), dev_ptr(gate, F32, "gates"), dev_ptr(table_c.detach(), F32, "word table"),
+            ptr_array([w.detach() for w in ws], F32, "conv weight"), dev_ptr(feat, F32, "feat"), dev_ptr(argmax, I32, "argmax"),
+            dev_ptr(d_feat, F32, "d_feat"), int(w_l.shape[2]), dev_ptr(w_l, F32, "local gate weight"),
+            dev_ptr(w_g, F32, "global gate weight"))
+    dev = table_c.device
+    fixed, through, d_gate_l = (torch.empty(n_docs, L, dtype=F32, device=dev) for _ in range(3))
+    d_gate_g = torch.empty(n_docs, dtype=F32, device=dev)
+    _call("datt_saliency", _lib.lib().rbr_datt_saliency, C.byref(desc), *ptrs, dev_ptr(fixed, F32, "fixed"),
+          dev_ptr(through, F32, "through"), dev_ptr(d_gate_l, F32, "d_gate_l"), dev_ptr(d_gate_g, F32, "d_gate_g"), current_stream())
+    return DattSaliency(fixed, through, d_gate_l, d_gate_g)
+
+
+_HEAD_NAMES =("Wu", "bu", "Eu", "Wi", "bi", "Ei", "h", "g", "ub", "ib")
 _HEAD_ACC = ("Eu", "Ei", "ub", "ib")       # gradients accumulated with atomics (rows addressed by id)
 
 

@@ -29,14 +29,19 @@ class DualAtt(nn.Module):
         self.fc = nn.Sequential(nn.Linear(self.fc_input, hidden_size_1), nn.ReLU(), nn.Dropout(dropout),
                                 nn.Linear(hidden_size_1, hidden_size_2))
 
+    @staticmethod
+    def _merged_applies(local, table, docs, weights, pad):
+        """True when the tower's two gated convs run as ONE conv call of four banks under a split gate (_encode)."""
+        return (local.conv[0].kernel_size[0] == 1 and os.environ.get("RBR_DATT_MERGED", "1") != "0"
+                and RF.textcnn_product_applies(table, docs, weights, RF.PAD_VALID, RF.ACT_TANH, pad))
+
     def _encode(self, docs, local, glob, tabs):
         """`tabs`: four aliases of the word table (RF.table_fanout), one per table-consuming op of the tower."""
         pad = self.word_embeddings.padding_idx
         rows = RF.datt_token_rows(docs, tabs[0].shape[0])      # distinct-token maps, once per tower: both gates work on them
         convs = [local.conv[0], glob.conv1[0], glob.conv2[0], glob.conv3[0]]
         weights = [c.weight for c in convs]
-        if (local.conv[0].kernel_size[0] == 1 and os.environ.get("RBR_DATT_MERGED", "1") != "0"
-                and RF.textcnn_product_applies(tabs[1], docs, weights, RF.PAD_VALID, RF.ACT_TANH, pad)):
+        if self._merged_applies(local, tabs[1], docs, weights, pad):
             # The tower's two gated convs read the same tokens: as ONE conv call of four banks -- the 1-wide local conv ('same'
             # = 'valid' at width 1) under the local gate, the 2/3/4-wide global convs under the global gate
             # (RBR_CONV_GATE_SPLIT) -- they share the token list, the product-table GEMM, the gather launch, and in the
@@ -145,6 +150,53 @@ class DualAtt(nn.Module):
     def encode_items(self, i_docs):
         """The item tower's counterpart of encode_users (dual_att.py:52-57)."""
         return self._encode_side(i_docs, self.i_local_atten, self.i_global_atten)
+
+    # ---- why a pair scored as it did, through both gates (recommend.Recommender.attention)
+    def _attend_side(self, docs, d_latent, local, glob):
+        with RF.eval_mode(self):
+            pad = self.word_embeddings.padding_idx
+            if self.validate_ids:
+                (docs,) = RF.sanitize_ids([(docs, self.vocab_size, pad)])
+            docs, table = docs.contiguous(), self.word_embeddings.weight
+            rows = RF.datt_token_rows(docs, table.shape[0])
+            convs = [local.conv[0], glob.conv1[0], glob.conv2[0], glob.conv3[0]]
+            weights, biases = [c.weight for c in convs], [c.bias for c in convs]
+            runs = local.window_size <= 17
+            gate_l = RF.datt_gate(table, local.attn[0].weight, local.attn[0].bias, docs, is_global=False, padding_idx=pad, rows=rows)
+            gate_g = RF.datt_gate(table, glob.attn[0].weight, glob.attn[0].bias, docs, is_global=True, padding_idx=pad, rows=rows)
+            if self._merged_applies(local, table, docs, weights, pad):
+                feat, argmax = RF.textcnn(table, docs, None, weights, biases, gate=(gate_l, gate_g), gate_split=1,
+                                          pad_mode=RF.PAD_VALID, act=RF.ACT_TANH, padding_idx=pad, pad_runs=runs, return_argmax=True)
+            else:                                      # the two single-gate convs of the layers' encode, local channels first
+                f_l, a_l = RF.textcnn(table, docs, None, weights[:1], biases[:1], gate=gate_l, pad_mode=RF.PAD_SAME, act=RF.ACT_TANH,
+                                      padding_idx=pad, pad_runs=runs, return_argmax=True)
+                f_g, a_g = RF.textcnn(table, docs, None, weights[1:], biases[1:], gate=gate_g, pad_mode=RF.PAD_VALID,
+                                      act=RF.ACT_TANH, padding_idx=pad, pad_runs=True, return_argmax=True)
+                feat, argmax = torch.cat((f_l, f_g), 1), torch.cat((a_l, a_g), 1)
+            # the shared fc backwards: hid = relu(fc.0(feat)); d_feat = ((d_latent @ W2) * [hid > 0]) @ W1
+            hid = RF.linear(feat, self.fc[0].weight, self.fc[0].bias, relu=True)
+            d_hid = RF.linear(d_latent, self.fc[3].weight.t().contiguous()) * (hid > 0)
+            d_feat = RF.linear(d_hid, self.fc[0].weight.t().contiguous())
+            # a 1-wide 'same' conv is a 'valid' one: the four banks are one 'valid' conv for the saliency either way
+            s = RF.datt_saliency(table, docs, (gate_l, gate_g), weights, feat, argmax, d_feat,
+                                 (local.attn[0].weight, glob.attn[0].weight), gate_split=1, pad_mode=RF.PAD_VALID, act=RF.ACT_TANH)
+            text = d_feat * feat
+            k = local.out_size
+            return gate_l, gate_g[:, 0].contiguous(), s.fixed + s.through, s.fixed, text[:, :k].sum(1), text[:, k:].sum(1)
+
+    def attend_users(self, u_docs, d_latent):
+        """u_docs [n, doc_len] int64 and d_latent [n, hidden_size_2] = d score / d (the users' latent rows) -> (local_gate [n, L],
+        global_gate [n], tokens [n, L], tokens_fixed [n, L], local_text [n], global_text [n]) in eval semantics, no autograd.
+        The gates are the forward's.  tokens[n, t] = <d score / d x[t], x[t]> for the embedded row x[t], followed through the
+        shared fc, the four conv banks AND both gates, with only the max-pool routing held fixed (functional.datt_saliency);
+        tokens_fixed is the part that reaches x[t] with the gates held constant, so tokens - tokens_fixed is what runs through the
+        gates.  local_text / global_text = <d score / d feat, feat> over the local / global channels: what each half of the
+        tower's features adds to the score through the fc."""
+        return self._attend_side(u_docs, d_latent, self.u_local_atten, self.u_global_atten)
+
+    def attend_items(self, i_docs, d_latent):
+        """The item tower's counterpart of attend_users."""
+        return self._attend_side(i_docs, d_latent, self.i_local_atten, self.i_global_atten)
 
     def explain_users(self, *args, **kwargs):
         """Not covered: the token-level explanation reads the un-gated TextCNN's max-pool routing."""

@@ -19,6 +19,9 @@ With --explain N every line also carries "why", one entry per recommended item (
 the user's and of the item's text that moved the score most, as [position, token, weight] (words where meta.pkl's vocabulary is
 readable, else token ids; NARRE: position = review slot * rv_len + position in the review), and for NARRE the item's N
 weightiest reviews as [slot, id of the review's author, attention weight, contribution] (Recommender.explain).
+With --attention N (dual_att) every line carries "why" too, one entry per recommended item: the N entries of largest |weight| of
+the user's and of the item's document as [position, token, weight, local_gate], the weight followed through both attention gates
+(Recommender.attention).
 With --eval-split the (user, item) pairs of that split are ranked instead (as well, when --out is given too) and one JSON line of
 rank_metrics goes to --metrics-out, or to stdout.
 
@@ -60,6 +63,24 @@ class Explanation(NamedTuple):
     user_reviews: Optional[torch.Tensor] = None           # [B, rv_num] contribution of every review; sums to user_text
     item_review_weights: Optional[torch.Tensor] = None
     item_reviews: Optional[torch.Tensor] = None
+
+
+class Attention(NamedTuple):
+    """Recommender.attention (D-ATT): the two attention gates of each side of the pairs (u_ids[b], i_ids[b]) and what every token
+    adds to the score, followed through the fc, the convs AND both gates (DualAtt.attend_users has the fields' definitions)."""
+    score: torch.Tensor                   # [B] = Recommender.score
+    user_local_gate: torch.Tensor         # [B, doc_len] the local gate of every position
+    user_global_gate: torch.Tensor        # [B] the document's global gate
+    user_tokens: torch.Tensor             # [B, doc_len] gradient x input of every token, through the gates
+    user_tokens_fixed: torch.Tensor       # [B, doc_len] the part with the gates held constant
+    user_local_text: torch.Tensor         # [B] what the local half of the features adds to the score
+    user_global_text: torch.Tensor        # [B] the global half
+    item_local_gate: torch.Tensor
+    item_global_gate: torch.Tensor
+    item_tokens: torch.Tensor
+    item_tokens_fixed: torch.Tensor
+    item_local_text: torch.Tensor
+    item_global_text: torch.Tensor
 
 
 def top_tokens(tokens: torch.Tensor, docs: torch.Tensor, n: int):
@@ -273,6 +294,32 @@ class Recommender:
             return Explanation(score, ut, it, ux, ix)
         ut, ux, ua, ur, it, ix, ia, ir = cols
         return Explanation(score, ut, it, ux, ix, ua, ur, ia, ir)
+
+    def attention(self, u_ids: torch.Tensor, i_ids: torch.Tensor, chunk: int = 256) -> Attention:
+        """D-ATT's answer to "why": both attention gates of each side of the pairs (u_ids[b], i_ids[b]) and the per-token
+        contributions followed through them, `chunk` pairs at a time, from the latent tables and the cache rows; eval semantics, no
+        autograd, the model's mode is restored.  The score is the plain inner product of the latent rows, so d score / d (the
+        user's latent row) is the item's row and the reverse; each tower turns that gradient into its six fields
+        (DualAtt.attend_users / attend_items)."""
+        if self.kind != "dual_att":
+            raise ValueError(f"Recommender.attention covers D-ATT (DualAtt); {type(self.model).__name__} is not covered "
+                             "(DeepCoNN++ and NARRE: Recommender.explain)")
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
+            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+        ul, il = self._tables()
+        score = self.score(u_ids, i_ids)
+        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
+        with torch.no_grad():
+            d_i, d_u = RF.embedding(ul, u_ids, None), RF.embedding(il, i_ids, None)
+        c, m = self.cache, self.model
+        parts = []
+        for a in range(0, u_ids.shape[0], chunk):
+            u_docs = c.user.index_select(0, u_ids[a:a + chunk]).to(torch.int64).contiguous()
+            i_docs = c.item.index_select(0, i_ids[a:a + chunk]).to(torch.int64).contiguous()
+            parts.append(m.attend_users(u_docs, d_u[a:a + chunk]) + m.attend_items(i_docs, d_i[a:a + chunk]))
+        return Attention(score, *(torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts)))
 
     def evaluate(self, pairs, ks=(5, 10, 20), exclude=None, chunk: int = 4096) -> dict:
         """rank_metrics of held-out pairs: `pairs` is a dataset's examples (sequences starting (u_id, i_id, ...)) or the id
@@ -524,6 +571,8 @@ def parse_cli(argv=None):
     ap.add_argument("--metrics-out", help="file for the one JSON line of metrics of --eval-split (default: stdout)")
     ap.add_argument("--explain", type=int, metavar="N", help="with --out: add \"why\" to every line, the N weightiest tokens (and, "
                     "for NARRE, reviews) behind each recommended item; deepconn and narre only")
+    ap.add_argument("--attention", type=int, metavar="N", help="with --out: add \"why\" to every line, the N weightiest tokens of each "
+                    "side behind each recommended item with their local gates, followed through both attention gates; dual_att only")
     ap.add_argument("--chunk", type=int, default=256, help="ids encoded / users ranked per launch")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--reference-quirks", action="store_true", help="as for the trainer: kernel_sizes=[3] (NARRE hidden_dim=150)")
@@ -539,6 +588,13 @@ def parse_cli(argv=None):
             ap.error("--explain adds to the lines of --out: give --out")
         if a.model not in ("deepconn", "narre"):
             ap.error("--explain covers deepconn and narre")
+    if a.attention is not None:
+        if a.attention < 1:
+            ap.error("--attention must be at least 1")
+        if a.out is None:
+            ap.error("--attention adds to the lines of --out: give --out")
+        if a.model != "dual_att":
+            ap.error("--attention covers dual_att (deepconn and narre: --explain)")
     if a.eval_split is None:
         if a.out is None:
             ap.error("--out is required unless --eval-split is given")
@@ -596,6 +652,36 @@ def _why(rec, u_ids, items, n, words):
     return why
 
 
+def _why_attention(rec, u_ids, items, n, words):
+    """The "why" lists of --attention for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per item
+    the n entries of largest |tokens| on each side as [position, word, weight, local_gate]."""
+    dev = u_ids.device
+    keep = items >= 0
+    rows, cols = keep.nonzero(as_tuple=True)
+    why = [[None] * int(keep[r].sum()) for r in range(items.shape[0])]
+    if rows.numel() == 0:
+        return why
+    pu, pi = u_ids[rows.to(dev)], items[rows, cols].to(dev)
+    at = rec.attention(pu, pi)
+    c = rec.cache
+    word = (lambda t: words.get(int(t), int(t))) if words else int
+
+    def tops(tokens, gate, docs):
+        pos, tok, w = top_tokens(tokens, docs.to(torch.int64), n)
+        gl = torch.gather(gate, 1, pos).cpu()
+        pos, tok, w = pos.cpu(), tok.cpu(), w.cpu()
+        return [[[int(p), word(t), float(x), float(g)] for p, t, x, g in zip(*q) if x != 0.0] for q in zip(pos, tok, w, gl)]
+
+    ut = tops(at.user_tokens, at.user_local_gate, c.user.index_select(0, pu))
+    it = tops(at.item_tokens, at.item_local_gate, c.item.index_select(0, pi))
+    gu, gi = at.user_global_gate.cpu(), at.item_global_gate.cpu()
+    slot_of = keep.cumsum(1) - 1
+    for p, (r, k) in enumerate(zip(rows.tolist(), cols.tolist())):
+        why[r][int(slot_of[r, k])] = {"user_tokens": ut[p], "item_tokens": it[p], "user_global_gate": float(gu[p]),
+                                      "item_global_gate": float(gi[p])}
+    return why
+
+
 def main(argv=None) -> int:
     a = parse_cli(argv)
     from . import data as D
@@ -625,7 +711,7 @@ def main(argv=None) -> int:
     # AHN: sentence tables and the pair tail (AhnRecommender); a chunk of ids is chunk * R * S sentences through the encoder
     rec = AhnRecommender(model, cache).refresh(chunk=min(a.chunk, 32)) if a.model == "ahn" else Recommender(model, cache).refresh(chunk=a.chunk)
     seen = Recommender.seen_from(ds.examples, rec.n_users, dev) if a.exclude_train else None
-    words = _vocabulary(cfg.data_dir) if a.explain is not None else None
+    words = _vocabulary(cfg.data_dir) if a.explain is not None or a.attention is not None else None
     if a.out is not None:
         with open(a.out, "w") as f:
             for lo in range(1, rec.n_users, a.chunk):
@@ -633,6 +719,8 @@ def main(argv=None) -> int:
                 items, scores = rec.topk(u_ids, a.k, exclude=seen)
                 items, scores = items.cpu(), scores.cpu()
                 why = _why(rec, u_ids, items, a.explain, words) if a.explain is not None else None
+                if a.attention is not None:
+                    why = _why_attention(rec, u_ids, items, a.attention, words)
                 for r, u in enumerate(u_ids.tolist()):
                     keep = items[r] >= 0
                     line = {"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}
