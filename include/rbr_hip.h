@@ -398,6 +398,39 @@ int rbr_datt_saliency(const rbr_textcnn_desc* d, const int64_t* ids, const float
                       const float* w_l, const float* w_g, float* fixed, float* through, float* d_gate_l, float* d_gate_g,
                       void* stream);
 
+/* Explaining a SimpleSiamese score: per-token and per-review contributions of one tower, for n side rows (users or items) of R
+ * reviews x T tokens.  The tower (rbr_review_bag_fwd, rbr_linear_fwd with tanh, rbr_additive_attn_fwd) has no max-pool, so
+ * nothing is held fixed: gradient x input follows the transform AND the attention softmax.  With x_r = y[b,r,:] [F] the review
+ * vectors the attention read, s_r = a[b,r] its weights (both INPUTS, as the forward left them) and g [n, F] = d score / d (the
+ * pooled feature):
+ *   c_r            = <g, x_r>
+ *   reviews[b,r]   = s_r * c_r                                         the review's share with the attention held constant
+ *   cbar           = sum_r s_r * c_r
+ *   dl_r           = rev_mask[b,r] ? s_r * (c_r - cbar) : 0            d score / d logit_r (masked_fill blocks the gradient)
+ *   tp_r           = tanh(Wp x_r + bp)                                 [K], recomputed
+ *   q_r            = Wp^T (wi * (1 - tp_r^2))                          [F]  d logit_r / d x_r
+ *   gy_fixed_r     = s_r * g;          gy_thru_r = dl_r * q_r
+ *   gm_*_r         = Wt ? Wt^T (gy_*_r * (1 - x_r^2)) : gy_*_r         [E]  gradient on the review's averaged word row
+ *   inv_r          = 1 / (unmasked tokens of review r + 1e-8)          rbr_review_bag_fwd's expression
+ *   fixed[b,r,t]   = word_mask[b,r,t] ? inv_r * <gm_fixed_r, table[ids[b,r,t]]> : 0
+ *   through[b,r,t] = word_mask[b,r,t] ? inv_r * <gm_thru_r,  table[ids[b,r,t]]> : 0
+ * so that fixed + through = <d score / d (the token's embedded row), that row> exactly, and fixed alone is the reading with the
+ * attention weights held constant (NARRE's); without the transform sum_t fixed[b,r,t] = reviews[b,r] up to rounding.
+ * table [V, E]; ids [n, R, T]; word_mask [n, R, T] and rev_mask [n, R] may be NULL (all live); Wt [F, E] is the transform's
+ * weight, NULL without one (then F must equal E); Wp [K, F], bp [K], wi [K] the attention's parameters.  A masked token gets
+ * exactly 0.0f; a token id outside [0, V) is never used as an index (its row counts as zero); padding_idx plays no part.
+ * fixed / through [n, R, T] and reviews [n, R] are OVERWRITTEN, every element once with a plain store.  One launch, one workgroup
+ * per side row, no workspace, no atomics, a fixed summation order: a side row has the same bits on every run and in every batch.
+ * n == 0 returns 0 without a launch.  RBR_ERR_BAD_ARG, with the cause in rbr_last_error(): a non-positive dimension, E, F or K
+ * above 16384, R > 64, a null pointer, F != E without Wt; RBR_ERR_UNSUPPORTED: the LDS tiles (2 R F + R K + F, and 2 R E with Wt, floats) exceed 64 KiB
+ * -- nothing is launched.
+ * Reference counterpart: none (the reference computes the attention weights and returns None, None,
+ * models/simple_siamese/simple_siamese.py:87). */
+int rbr_siamese_saliency(int32_t n, int32_t R, int32_t T, int32_t V, int32_t E, int32_t F, int32_t K, const float* table,
+                         const int64_t* ids, const uint8_t* word_mask, const uint8_t* rev_mask, const float* y, const float* a,
+                         const float* g, const float* Wt, const float* Wp, const float* bp, const float* wi, float* fixed,
+                         float* through, float* reviews, void* stream);
+
 /* ---- Rating head: LastFeat x2 + FM (deepconn/layers.py:156-165,189-209; narre.py:84-93,118-137)
  *   ul = u_feat @ Wu + bu + Eu[u_id];  il = i_feat @ Wi + bi + Ei[i_id]
  *   pred = (relu(ul*il) * drop) @ h + ub[u_id] + ib[i_id] + g

@@ -162,6 +162,8 @@ SIGNATURES = {
     "rbr_textcnn_saliency": (C.c_int, [_DESC, c_i64p, c_u8p, c_f32p, c_f32p, _PP, c_f32p, c_i32p, c_f32p, c_f32p, c_stream]),
     "rbr_datt_saliency": (C.c_int, [_DESC, c_i64p, c_f32p, c_f32p, _PP, c_f32p, c_i32p, c_f32p, i32, c_f32p, c_f32p, c_f32p, c_f32p,
                                     c_f32p, c_f32p, c_stream]),
+    "rbr_siamese_saliency": (C.c_int, [i32, i32, i32, i32, i32, i32, i32, c_f32p, c_i64p, c_u8p, c_u8p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                       c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "rbr_datt_local_gate_prod_ws_bytes": (C.c_size_t, [i32, i32, i32, i32, i32]),
     "rbr_datt_local_gate_fwd_prod": (C.c_int, [i32, i32, i32, i32, i32, c_i64p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
                                                C.c_void_p, c_stream]),

@@ -3,7 +3,8 @@
 // wave_sum / wave_max: xor butterfly over groups of WIDTH consecutive lanes (WIDTH a power of two <= 64, the group aligned to
 // WIDTH): every lane of the group ends with the group's result.  The order of the additions is fixed -- partner WIDTH/2 first,
 // partner 1 last -- and the kernels whose results are tested for bit-reproducibility rely on exactly that order.
-// wave_sum_n: wave_sum for a group width that is a kernel argument (sentence_feed.hip).
+// wave_sum_n: wave_sum for a group width that is a kernel argument (sentence_feed.hip); also over an array of independent values
+// (siamese_saliency.hip).
 // wave_incl_scan: inclusive prefix sum over the 64 lanes (__shfl_up ladder); lane 63 holds the total.
 // The cross-wave step of a block reduction stays with its kernel: the sites add their four wave sums in different orders.
 //
@@ -39,6 +40,16 @@ template <typename T>
 __device__ __forceinline__ T wave_sum_n(T v, int width) {
     for (int o = width >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
+}
+
+// wave_sum_n of N independent values at once, each in the order of the scalar form: the N butterflies advance step by step together,
+// so that a step costs one shuffle latency instead of N (siamese_saliency.hip).  Every lane of the wave makes the call.
+template <int N, typename T>
+__device__ __forceinline__ void wave_sum_n(T (&v)[N], int width) {
+    for (int o = width >> 1; o > 0; o >>= 1) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], o);
+    }
 }
 
 template <int WIDTH = 64>

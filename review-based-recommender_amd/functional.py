@@ -2125,6 +2125,64 @@ def additive_attention(rev, mask, Wp, bp, wi, *, node_drop=None):
     return out, scores.unsqueeze(2)
 
 
+class SiameseSaliency(NamedTuple):
+    """siamese_saliency: fixed / through [n, R, T], reviews [n, R]; fixed + through is gradient x input of the token rows."""
+    fixed: torch.Tensor
+    through: torch.Tensor
+    reviews: torch.Tensor
+
+
+def siamese_saliency(table, ids, word_mask, rev_mask, y, a, g, Wt, Wp, bp, wi) -> SiameseSaliency:
+    """What every token and every review of a SimpleSiamese tower contributes to a score whose gradient on the tower's pooled
+    feature is g [n, F]: ids [n, R, T] over table [V, E], y [n, R, F] the review vectors the attention read and a [n, R] (or
+    [n, R, 1]) its weights, as review_bag / linear(tanh=True) / additive_attention left them; Wt [F, E] the latent transform's
+    weight or None; Wp [K, F], bp [K], wi [1, K] the attention's parameters.  fixed + through = <d score / d row, row> of every
+    token's embedded row, followed through the transform and the attention softmax; fixed holds the attention constant, and
+    reviews = a * <g, y>.  rbr_siamese_saliency in rbr_hip.h has the formula.  One launch, no autograd, no embedded rows are
+    materialised; a side row is bit-identical in every batch."""
+    if ids.dim() != 3:
+        raise RuntimeError(f"ids must be [n, R, T], got {tuple(ids.shape)}")
+    n, R, T = ids.shape
+    if table.dim() != 2:
+        raise RuntimeError(f"the word table must be [V, E], got {tuple(table.shape)}")
+    table_c = table.detach()
+    table_c = table_c if table_c.is_contiguous() else table_c.contiguous()
+    V, E = table_c.shape
+    ids = ids.contiguous()
+    wm8, rm8 = _mask_u8(word_mask), _mask_u8(rev_mask)
+    if wm8 is not None and wm8.shape != ids.shape:
+        raise RuntimeError(f"word_mask must be [n, R, T] = {tuple(ids.shape)}, got {tuple(wm8.shape)}")
+    if rm8 is not None and tuple(rm8.shape) != (n, R):
+        raise RuntimeError(f"rev_mask must be [n, R] = {(n, R)}, got {tuple(rm8.shape)}")
+    y, g = y.detach().contiguous(), g.detach().contiguous()
+    if y.dim() != 3 or tuple(y.shape[:2]) != (n, R):
+        raise RuntimeError(f"y must be [n, R, F] with [n, R] = {(n, R)}, got {tuple(y.shape)}")
+    F = y.shape[2]
+    if tuple(a.shape) not in ((n, R), (n, R, 1)):
+        raise RuntimeError(f"a must be [n, R] = {(n, R)} (or [n, R, 1]), got {tuple(a.shape)}")
+    a = a.detach().reshape(n, R).contiguous()
+    if tuple(g.shape) != (n, F):
+        raise RuntimeError(f"g must be [n, F] = {(n, F)}, got {tuple(g.shape)}")
+    Wp, bp, wi = Wp.detach().contiguous(), bp.detach().contiguous(), wi.detach().contiguous().view(-1)
+    K = Wp.shape[0]
+    if tuple(Wp.shape) != (K, F) or tuple(bp.shape) != (K,) or tuple(wi.shape) != (K,):
+        raise RuntimeError(f"the attention's parameters must be Wp [K, F = {F}], bp [K], wi [K], got {tuple(Wp.shape)} / "
+                           f"{tuple(bp.shape)} / {tuple(wi.shape)}")
+    if Wt is not None:
+        Wt = Wt.detach().contiguous()
+        if tuple(Wt.shape) != (F, E):
+            raise RuntimeError(f"the transform's weight must be [F, E] = {(F, E)}, got {tuple(Wt.shape)}")
+    dev = table_c.device
+    fixed, through = (torch.empty(n, R, T, dtype=F32, device=dev) for _ in range(2))
+    reviews = torch.empty(n, R, dtype=F32, device=dev)
+    _call("siamese_saliency", _lib.lib().rbr_siamese_saliency, n, R, T, V, E, F, K, dev_ptr(table_c, F32, "word table"),
+          dev_ptr(ids, I64, "ids"), dev_ptr(wm8, U8, "word_mask"), dev_ptr(rm8, U8, "rev_mask"), dev_ptr(y, F32, "y"),
+          dev_ptr(a, F32, "a"), dev_ptr(g, F32, "g"), dev_ptr(Wt, F32, "transform weight"), dev_ptr(Wp, F32, "proj weight"),
+          dev_ptr(bp, F32, "proj bias"), dev_ptr(wi, F32, "inner_product weight"), dev_ptr(fixed, F32, "fixed"),
+          dev_ptr(through, F32, "through"), dev_ptr(reviews, F32, "reviews"), current_stream())
+    return SiameseSaliency(fixed, through, reviews)
+
+
 # --------------------------------------------------------------------------- standalone embedding
 class _Embedding(torch.autograd.Function):
     @staticmethod

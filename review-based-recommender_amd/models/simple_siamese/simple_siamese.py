@@ -112,6 +112,45 @@ class SimpleSiamese(nn.Module):
 
     explain_items = explain_users
 
+    def _contribute_side(self, revs, word_masks, rev_masks, ids, last, d_latent):
+        with RF.eval_mode(self):
+            if self.validate_ids:
+                (revs,) = RF.sanitize_ids([(revs, self.vocab_size, 0)])
+            revs, word_masks, rev_masks = revs.contiguous(), word_masks.contiguous(), rev_masks.contiguous()
+            n, R, T = revs.shape
+            table = self.word_embedding.weight
+            # the forward values come from the ops _tower runs (eval: no dropout multipliers), so that the explanation belongs
+            # to the latent row the tables hold
+            y = RF.review_bag(table, revs.reshape(n * R, T), word_masks.reshape(n * R, T), drop=None,
+                              padding_idx=self.word_embedding.padding_idx)
+            Wt = None
+            if self.latent_transform:
+                lin = self.latent_transform_layer[0]
+                y, Wt = RF.linear(y, lin.weight, lin.bias, tanh=True), lin.weight
+            y = y.view(n, R, -1)
+            att = self.review_att_layer
+            _, a = att(y, rev_masks)
+            a = a.view(n, R)
+            g = RF.linear(d_latent, last.W)                                   # d score / d pooled = d_latent @ W^T  [n, F]
+            proj = att.proj_layer[0]
+            sal = RF.siamese_saliency(table, revs, word_masks, rev_masks, y, a, g, Wt, proj.weight, proj.bias,
+                                      att.inner_product.weight)
+            return sal.fixed + sal.through, sal.fixed, sal.reviews.sum(1), a, sal.reviews
+
+    def contribute_users(self, u_revs, u_rev_word_masks, u_rev_masks, u_ids, d_latent):
+        """encode_users' arguments plus d_latent [n, latent_dim] = d score / d (the users' latent rows) -> (tokens [n, rv_num,
+        rv_len], tokens_fixed [n, rv_num, rv_len], text [n], att [n, rv_num], reviews [n, rv_num]) in eval semantics, no autograd.
+        With g = d score / d (pooled feature): reviews[n, r] = att[n, r] * <g, review vector r> is the review's share with the
+        attention weights att held constant, text = reviews.sum(1); tokens[n, r, t] is gradient x input of the token's embedded
+        row followed through the whole tower -- the masked average, the tanh transform, and the attention softmax, which has no
+        max-pool to hold fixed -- and tokens_fixed the part of it with att held constant (functional.siamese_saliency).  Without
+        the transform tokens_fixed[n, r].sum() == reviews[n, r] up to rounding."""
+        return self._contribute_side(u_revs, u_rev_word_masks, u_rev_masks, u_ids, self.user_last_feat_layer, d_latent)
+
+    def contribute_items(self, i_revs, i_rev_word_masks, i_rev_masks, i_ids, d_latent):
+        """The item tower's counterpart of contribute_users."""
+        return self._contribute_side(i_revs, i_rev_word_masks, i_rev_masks, i_ids, self.item_last_feat_layer, d_latent)
+
     def score_mode_and_params(self):
         """(mode, h, g, ub, ib) of functional.pair_score*: FM, or FMWithoutUIBias (ub = ib = None) without use_ui_bias."""
         fm = self.fm

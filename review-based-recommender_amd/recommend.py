@@ -22,6 +22,10 @@ weightiest reviews as [slot, id of the review's author, attention weight, contri
 With --attention N (dual_att) every line carries "why" too, one entry per recommended item: the N entries of largest |weight| of
 the user's and of the item's document as [position, token, weight, local_gate], the weight followed through both attention gates
 (Recommender.attention).
+With --contributions N (simple_siamese) every line carries "why" too, one entry per recommended item: per side the N tokens of
+largest |weight| as [review slot * rv_len + position, token, weight], the weight followed through the review attention, and the N
+reviews of largest |contribution| as [slot, id of the review's counterpart (-1 where unknown), attention weight, contribution]
+(Recommender.contributions).
 With --eval-split the (user, item) pairs of that split are ranked instead (as well, when --out is given too) and one JSON line of
 rank_metrics goes to --metrics-out, or to stdout.
 
@@ -81,6 +85,22 @@ class Attention(NamedTuple):
     item_tokens_fixed: torch.Tensor
     item_local_text: torch.Tensor
     item_global_text: torch.Tensor
+
+
+class Contributions(NamedTuple):
+    """Recommender.contributions (SimpleSiamese): what every token and every review of each side of the pairs (u_ids[b],
+    i_ids[b]) adds to the score (SimpleSiamese.contribute_users has the fields' definitions)."""
+    score: torch.Tensor                   # [B] = Recommender.score
+    user_tokens: torch.Tensor             # [B, rv_num, rv_len] gradient x input of every token, through the attention softmax
+    item_tokens: torch.Tensor
+    user_tokens_fixed: torch.Tensor       # [B, rv_num, rv_len] the part with the attention weights held constant
+    item_tokens_fixed: torch.Tensor
+    user_text: torch.Tensor               # [B] what the user's text as a whole adds to the score
+    item_text: torch.Tensor
+    user_review_weights: torch.Tensor     # [B, rv_num] the forward attention weights
+    user_reviews: torch.Tensor            # [B, rv_num] contribution of every review under those weights; sums to user_text
+    item_review_weights: torch.Tensor
+    item_reviews: torch.Tensor
 
 
 def top_tokens(tokens: torch.Tensor, docs: torch.Tensor, n: int):
@@ -320,6 +340,40 @@ class Recommender:
             i_docs = c.item.index_select(0, i_ids[a:a + chunk]).to(torch.int64).contiguous()
             parts.append(m.attend_users(u_docs, d_u[a:a + chunk]) + m.attend_items(i_docs, d_i[a:a + chunk]))
         return Attention(score, *(torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts)))
+
+    def contributions(self, u_ids: torch.Tensor, i_ids: torch.Tensor, chunk: int = 256) -> Contributions:
+        """SimpleSiamese's answer to "why": per-token and per-review contributions of each side of the pairs (u_ids[b],
+        i_ids[b]), `chunk` pairs at a time, from the latent tables and the cache rows; eval semantics, no autograd, the model's
+        mode is restored.  The head is explain's -- d score / d zu = h * [zu * zi > 0] * zi, and zu for the item side -- and each
+        tower turns that gradient into its five fields (SimpleSiamese.contribute_users / contribute_items): the tower has no
+        max-pool, so *_tokens follow the attention softmax too, and *_tokens_fixed hold the weights constant."""
+        if self.kind != "simple_siamese":
+            raise ValueError(f"Recommender.contributions covers SimpleSiamese; {type(self.model).__name__} is not covered "
+                             "(DeepCoNN++ and NARRE: Recommender.explain, D-ATT: Recommender.attention)")
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
+            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+        ul, il = self._tables()
+        _, h, _, _, _ = self.model.score_mode_and_params()
+        score = self.score(u_ids, i_ids)
+        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
+        with torch.no_grad():
+            zu, zi = RF.embedding(ul, u_ids, None), RF.embedding(il, i_ids, None)
+            live = h.detach().view(1, -1) * (zu * zi > 0)
+            d_u, d_i = live * zi, live * zu
+        c, m = self.cache, self.model
+        parts = []
+        for a in range(0, u_ids.shape[0], chunk):
+            side = []
+            for docs, ids, d, fn in ((c.user, u_ids[a:a + chunk], d_u[a:a + chunk], m.contribute_users),
+                                     (c.item, i_ids[a:a + chunk], d_i[a:a + chunk], m.contribute_items)):
+                revs = docs.index_select(0, ids).to(torch.int64).contiguous()
+                word_masks = revs != PAD
+                side.append(fn(revs, word_masks, word_masks.any(-1), ids, d))     # masks as _encode derives them
+            parts.append(side[0] + side[1])
+        ut, uf, ux, ua, ur, it, if_, ix, ia, ir = (torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts))
+        return Contributions(score, ut, it, uf, if_, ux, ix, ua, ur, ia, ir)
 
     def evaluate(self, pairs, ks=(5, 10, 20), exclude=None, chunk: int = 4096) -> dict:
         """rank_metrics of held-out pairs: `pairs` is a dataset's examples (sequences starting (u_id, i_id, ...)) or the id
@@ -573,6 +627,8 @@ def parse_cli(argv=None):
                     "for NARRE, reviews) behind each recommended item; deepconn and narre only")
     ap.add_argument("--attention", type=int, metavar="N", help="with --out: add \"why\" to every line, the N weightiest tokens of each "
                     "side behind each recommended item with their local gates, followed through both attention gates; dual_att only")
+    ap.add_argument("--contributions", type=int, metavar="N", help="with --out: add \"why\" to every line, the N weightiest tokens and "
+                    "reviews of each side behind each recommended item, followed through the review attention; simple_siamese only")
     ap.add_argument("--chunk", type=int, default=256, help="ids encoded / users ranked per launch")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--reference-quirks", action="store_true", help="as for the trainer: kernel_sizes=[3] (NARRE hidden_dim=150)")
@@ -595,6 +651,13 @@ def parse_cli(argv=None):
             ap.error("--attention adds to the lines of --out: give --out")
         if a.model != "dual_att":
             ap.error("--attention covers dual_att (deepconn and narre: --explain)")
+    if a.contributions is not None:
+        if a.contributions < 1:
+            ap.error("--contributions must be at least 1")
+        if a.out is None:
+            ap.error("--contributions adds to the lines of --out: give --out")
+        if a.model != "simple_siamese":
+            ap.error("--contributions covers simple_siamese (deepconn and narre: --explain, dual_att: --attention)")
     if a.eval_split is None:
         if a.out is None:
             ap.error("--out is required unless --eval-split is given")
@@ -682,6 +745,40 @@ def _why_attention(rec, u_ids, items, n, words):
     return why
 
 
+def _why_contributions(rec, u_ids, items, n, words):
+    """The "why" lists of --contributions for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per
+    item and side the n tokens of largest |weight| as [slot-major position, word, weight] and the n reviews of largest
+    |contribution| as [slot, counterpart id (-1 where the cache has none), attention, contribution]."""
+    dev = u_ids.device
+    keep = items >= 0
+    rows, cols = keep.nonzero(as_tuple=True)
+    why = [[None] * int(keep[r].sum()) for r in range(items.shape[0])]
+    if rows.numel() == 0:
+        return why
+    pu, pi = u_ids[rows.to(dev)], items[rows, cols].to(dev)
+    co = rec.contributions(pu, pi)
+    c = rec.cache
+    word = (lambda t: words.get(int(t), int(t))) if words else int
+
+    def tops(tokens, docs):
+        pos, tok, w = (t.cpu() for t in top_tokens(tokens, docs.to(torch.int64), n))
+        return [[[int(p), word(t), float(x)] for p, t, x in zip(pr, tr, wr) if x != 0.0] for pr, tr, wr in zip(pos, tok, w)]
+
+    def revs(contrib, att, rids, ids):
+        rid = rids.index_select(0, ids).to(torch.int64) if rids is not None else torch.full_like(contrib, -1, dtype=torch.int64)
+        slot, rid, x = (t.cpu() for t in top_tokens(contrib, rid, n))
+        at = torch.gather(att.cpu(), 1, slot)
+        return [[[int(s), int(r), float(a), float(v)] for s, r, a, v in zip(*q) if v != 0.0] for q in zip(slot, rid, at, x)]
+
+    ut, it = tops(co.user_tokens, c.user.index_select(0, pu)), tops(co.item_tokens, c.item.index_select(0, pi))
+    ur = revs(co.user_reviews, co.user_review_weights, getattr(c, "user_rids", None), pu)
+    ir = revs(co.item_reviews, co.item_review_weights, getattr(c, "item_rids", None), pi)
+    slot_of = keep.cumsum(1) - 1
+    for p, (r, k) in enumerate(zip(rows.tolist(), cols.tolist())):
+        why[r][int(slot_of[r, k])] = {"user_tokens": ut[p], "item_tokens": it[p], "user_reviews": ur[p], "item_reviews": ir[p]}
+    return why
+
+
 def main(argv=None) -> int:
     a = parse_cli(argv)
     from . import data as D
@@ -711,7 +808,7 @@ def main(argv=None) -> int:
     # AHN: sentence tables and the pair tail (AhnRecommender); a chunk of ids is chunk * R * S sentences through the encoder
     rec = AhnRecommender(model, cache).refresh(chunk=min(a.chunk, 32)) if a.model == "ahn" else Recommender(model, cache).refresh(chunk=a.chunk)
     seen = Recommender.seen_from(ds.examples, rec.n_users, dev) if a.exclude_train else None
-    words = _vocabulary(cfg.data_dir) if a.explain is not None or a.attention is not None else None
+    words = _vocabulary(cfg.data_dir) if any(n is not None for n in (a.explain, a.attention, a.contributions)) else None
     if a.out is not None:
         with open(a.out, "w") as f:
             for lo in range(1, rec.n_users, a.chunk):
@@ -721,6 +818,8 @@ def main(argv=None) -> int:
                 why = _why(rec, u_ids, items, a.explain, words) if a.explain is not None else None
                 if a.attention is not None:
                     why = _why_attention(rec, u_ids, items, a.attention, words)
+                if a.contributions is not None:
+                    why = _why_contributions(rec, u_ids, items, a.contributions, words)
                 for r, u in enumerate(u_ids.tolist()):
                     keep = items[r] >= 0
                     line = {"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}
