@@ -1145,6 +1145,58 @@ int rbr_ahn_pair_attend_bwd(const rbr_ahn_shape* shape, int32_t B, int32_t G, co
                             const float* v, const int32_t* js, const int32_t* jr, const float* p, const float* dz, float* dX,
                             float* dXt, float* dKs, float* dKr, float* dbt_part, void* stream);
 
+/* ---- Why an AHN pair scored as it did, from the same cached tables (csrc/ahn_explain.hip): rbr_ahn_pair_score_ids' forward
+ *      (score, w, v with ITS bits; js [P, NU] / jr [P, Ru] int32, the item rows that attained the two maxima, with
+ *      rbr_ahn_pair_attend_fwd's bits, ties to the lowest index) and, behind it, gradient x input of every sentence and review,
+ *      reduced to scalars.  With xv[k] = z . VzT[k] + fm_u[k] + fm_i[k] the FM's gradients are closed forms:
+ *        dz[f] = sum_k xv[k] VzT[k, f] - z[f] vz2[f] + lz[f]
+ *        dq[f] = sum_k xv[k] VqT[k, f] - q[f] vq2[f] + lq[f]     q = sum_i beta[i] r'[i] the item's own pooled vector
+ *      (VqT [K, F], vq2 [F], lq [F]: block 2 of the FM as VzT, vz2, lz are block 0; r' [I, Ri, F] the items' transformed
+ *      reviews and beta [I, Ri] their review weights, in rbr_ahn_explain_rows).  User side, rbr_ahn_pair_attend_bwd's formulas
+ *      with every vector gradient replaced by its dot:
+ *        dv[r] = dz . p[r];  c = sum_r v[r] dv[r];  dt[r] = rev_mask[r] ? v[r] (dv[r] - c) : 0
+ *        da[r] = [p[r] > 0] (v[r] dz + dt[r] Kr[jr[r]]);  e[n] = da[r(n)] . Xt[n];  cs[r] = sum_s w[r, s] e[r, s]
+ *        ds[n] = sent_mask[n] ? w[n] (e[n] - cs[r]) : 0
+ *        user_sentences[n]       = w[n] e[n] + ds[n] s[n]          = <dX[n], X[n]> + <dXt[n], Xt[n]>
+ *        user_sentences_fixed[n] = w[n] <[p[r] > 0] v[r] dz, Xt[n]>     both attention weightings held constant
+ *        user_reviews[r] = v[r] dv[r];  user_text = dz . z = sum_r user_reviews[r]
+ *      item side through the user's attention (rows nobody matched are exactly 0; n, r ascending):
+ *        item_sentence_match[j] = sum_{n: js[n] = j} ds[n] s[n] = <dKs[j], Ks[j]>
+ *        item_review_match[k]   = sum_{r: jr[r] = k} dt[r] t[r] = <dKr[k], Kr[k]>
+ *      item side, own path, the item's attention weights held constant:
+ *        item_reviews[i] = beta[i] <dq, r'[i]>;  item_text = dq . q = sum_i item_reviews[i]
+ *      Outputs: score [P], w [P, NU], v [P, Ru], js [P, NU], jr [P, Ru], user_sentences / user_sentences_fixed [P, NU],
+ *      user_reviews [P, Ru], user_text [P], item_sentence_match [P, NJ], item_review_match [P, Ri], item_reviews [P, Ri],
+ *      item_text [P]; none may be NULL.  P, u_rows, i_rows, index_bits and err as in rbr_ahn_pair_score_ids.  ONE launch on
+ *      `stream` (256 threads, 4 pairs per workgroup), no workspace, no host synchronisation, no float atomics, no [P, rows, F]
+ *      gradient ever written; every sum has one order fixed by the shape: a pair has the same bits wherever it stands in the
+ *      launch and on every run.  Caps: those of rbr_ahn_pair_score_ids (dz [F] takes 8 KB of LDS beside the tail's 36 KB). ---- */
+typedef struct rbr_ahn_explain_rows {
+    const float* Rp;       /* [I, Ri, F] r': the items' transformed reviews */
+    const float* beta;     /* [I, Ri] item_review_weights */
+    const float* VqT;      /* [K, F] */
+    const float* vq2;      /* [F] */
+    const float* lq;       /* [F] */
+} rbr_ahn_explain_rows;
+typedef struct rbr_ahn_explain_out {
+    float* score;
+    float* w;
+    float* v;
+    int32_t* js;
+    int32_t* jr;
+    float* user_sentences;
+    float* user_sentences_fixed;
+    float* user_reviews;
+    float* user_text;
+    float* item_sentence_match;
+    float* item_review_match;
+    float* item_reviews;
+    float* item_text;
+} rbr_ahn_explain_out;
+int rbr_ahn_pair_explain_ids(const rbr_ahn_shape* shape, const rbr_ahn_user_state* user, const rbr_ahn_item_state* item,
+                             const rbr_ahn_head* head, const rbr_ahn_explain_rows* extra, int64_t P, const void* u_rows,
+                             const void* i_rows, int32_t index_bits, const rbr_ahn_explain_out* out, int64_t* err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,18 @@ class AhnHead(C.Structure):           # rbr_ahn_head
     _fields_ = [(n, C.c_void_p) for n in ("bt", "VzT", "vz2", "lz", "lin_b")]
 
 
+class AhnExplainRows(C.Structure):    # rbr_ahn_explain_rows
+    _fields_ = [(n, C.c_void_p) for n in ("Rp", "beta", "VqT", "vq2", "lq")]
+
+
+AHN_EXPLAIN_OUT = ("score", "w", "v", "js", "jr", "user_sentences", "user_sentences_fixed", "user_reviews", "user_text",
+                   "item_sentence_match", "item_review_match", "item_reviews", "item_text")
+
+
+class AhnExplainOut(C.Structure):     # rbr_ahn_explain_out
+    _fields_ = [(n, C.c_void_p) for n in AHN_EXPLAIN_OUT]
+
+
 _PP = C.POINTER(C.c_void_p)
 _DESC = C.POINTER(TextCNNDesc)
 i32 = C.c_int32
@@ -276,6 +288,9 @@ SIGNATURES = {
                                           c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, c_f32p, c_stream]),
     "rbr_ahn_pair_attend_bwd": (C.c_int, [C.POINTER(AhnShape), i32, i32, c_f32p, c_f32p, c_u8p, c_u8p, c_f32p, c_f32p, c_f32p,
                                           c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
+    "rbr_ahn_pair_explain_ids": (C.c_int, [C.POINTER(AhnShape), C.POINTER(AhnUserState), C.POINTER(AhnItemState), C.POINTER(AhnHead),
+                                           C.POINTER(AhnExplainRows), C.c_int64, C.c_void_p, C.c_void_p, i32,
+                                           C.POINTER(AhnExplainOut), c_i64p, c_stream]),
     "rbr_embedding_fwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, c_f32p, c_stream]),
     "rbr_embedding_bwd": (C.c_int, [C.c_int64, i32, c_i64p, c_f32p, i32, c_f32p, c_stream]),
     "rbr_hier_pool_fwd": (C.c_int, [i32, i32, i32, i32, c_i64p, c_u8p, c_f32p, i32, c_f32p, c_i32p, c_stream]),

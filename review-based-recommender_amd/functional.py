@@ -2971,6 +2971,67 @@ def ahn_pair_score_dense(user_state, item_state, head, u_rows=None):
     return out
 
 
+class AhnExplainRows(NamedTuple):
+    """What ahn_pair_explain reads beyond the score's operands (rbr_ahn_explain_rows): the item's own path into the FM.  Its
+    review weights beta are item_state.item_review_weights."""
+    Rp: torch.Tensor            # [I, Ri, F] r': the items' transformed reviews (AHN.item_reviews)
+    VqT: torch.Tensor           # [K, F] block 2 of fm.V, transposed (AHN.explain_head)
+    vq2: torch.Tensor           # [F]
+    lq: torch.Tensor            # [F]
+
+
+class AhnPairExplanation(NamedTuple):
+    """ahn_pair_explain's outputs for P pairs (include/rbr_hip.h has the formulas)."""
+    score: torch.Tensor                   # [P] ahn_pair_score's bits
+    user_sent_weights: torch.Tensor       # [P, Ru, Su] w
+    user_review_weights: torch.Tensor     # [P, Ru] v
+    user_match: torch.Tensor              # int32 [P, Ru, Su] js: the item sentence ri * Si + si each user sentence matched
+    review_match: torch.Tensor            # int32 [P, Ru] jr: the item review each user review matched
+    user_sentences: torch.Tensor          # [P, Ru, Su] gradient x input of every sentence vector, through both attentions
+    user_sentences_fixed: torch.Tensor    # [P, Ru, Su] the part with both attention weightings held constant
+    user_reviews: torch.Tensor            # [P, Ru]; sums to user_text
+    user_text: torch.Tensor               # [P]
+    item_sentence_match: torch.Tensor     # [P, Ri, Si] what an item sentence adds as the match of user sentences
+    item_review_match: torch.Tensor       # [P, Ri]
+    item_reviews: torch.Tensor            # [P, Ri] the item's own path, its weights held constant; sums to item_text
+    item_text: torch.Tensor               # [P]
+
+
+def ahn_pair_explain(user_state, item_state, head, extra, u_rows, i_rows) -> AhnPairExplanation:
+    """Why the pairs (u_rows[p], i_rows[p]) of ahn_pair_score scored as they did, in ONE launch (rbr_ahn_pair_explain_ids,
+    csrc/ahn_explain.hip): the score and the user's two weight arrays with ahn_pair_score's bits, the max routing with
+    ahn_pair_attend's, and what every user sentence, user review, matched item sentence / review and item review adds to the
+    score.  `extra`: an AhnExplainRows.  No autograd, no host synchronisation, no [P, rows, F] gradient.  A row outside its table
+    is explained as row 0 and recorded like sanitize_ids() records it (check_id_errors)."""
+    shape, c_user, c_item, c_head, keep = _ahn_operands(user_state, item_state, head)
+    dev = keep[0][0].device
+    Ru, Su, Ri, Si, F_, K = shape.Ru, shape.Su, shape.Ri, shape.Si, shape.F, shape.K
+    beta = item_state[4].detach().contiguous()
+    ex = [t.detach().contiguous() for t in extra]
+    want = {"extra.Rp": (ex[0], (c_item.rows, Ri, F_)), "extra.VqT": (ex[1], (K, F_)), "extra.vq2": (ex[2], (F_,)),
+            "extra.lq": (ex[3], (F_,)), "item_review_weights": (beta, (c_item.rows, Ri))}
+    for name, (t, shp) in want.items():
+        dev_ptr(t, F32, name)
+        if tuple(t.shape) != shp:
+            raise RuntimeError(f"AHN pair explain: {name} must be {shp}, got {tuple(t.shape)}")
+    u_rows, pu, bits = _ahn_rows(u_rows, "u_rows")
+    i_rows, pi, bits_i = _ahn_rows(i_rows, "i_rows")
+    if u_rows.shape != i_rows.shape or bits != bits_i:
+        raise RuntimeError(f"u_rows / i_rows must be [P] each of one dtype, got {tuple(u_rows.shape)} {u_rows.dtype} / "
+                           f"{tuple(i_rows.shape)} {i_rows.dtype}")
+    P = u_rows.shape[0]
+    f32 = lambda *s: torch.empty(P, *s, dtype=F32, device=dev)          # noqa: E731
+    i32 = lambda *s: torch.empty(P, *s, dtype=I32, device=dev)          # noqa: E731
+    res = AhnPairExplanation(f32(), f32(Ru, Su), f32(Ru), i32(Ru, Su), i32(Ru), f32(Ru, Su), f32(Ru, Su), f32(Ru), f32(), f32(Ri, Si),
+                             f32(Ri), f32(Ri), f32())
+    if P:
+        c_extra = _lib.AhnExplainRows(ex[0].data_ptr(), beta.data_ptr(), ex[1].data_ptr(), ex[2].data_ptr(), ex[3].data_ptr())
+        c_out = _lib.AhnExplainOut(*(dev_ptr(t, t.dtype, n) for n, t in zip(_lib.AHN_EXPLAIN_OUT, res)))
+        _call("ahn_pair_explain_ids", _lib.lib().rbr_ahn_pair_explain_ids, C.byref(shape), C.byref(c_user), C.byref(c_item),
+              C.byref(c_head), C.byref(c_extra), P, pu, pi, bits, C.byref(c_out), _id_err(dev).data_ptr(), current_stream())
+    return res
+
+
 class _AhnPairAttend(torch.autograd.Function):
     """rbr_ahn_pair_attend_fwd / rbr_ahn_pair_attend_bwd of rbr_hip.h: (z, w, v, js, jr), all but z non-differentiable."""
 

@@ -151,6 +151,16 @@ class AHN(nn.Module):
             fm = self._fm_partial(q, Vb[2], lb[2]) + self._fm_partial(self.item_embeddigns(ids), Vb[3], lb[3])
         return RF.AhnItemState(Ks.view(n, r_num * s_num, F_), Kr.view(n, r_num, F_), fm, sent_w, rev_w)
 
+    def item_reviews(self, item_sents, sent_masks) -> torch.Tensor:
+        """The transformed item reviews r' [n, Ri, F] of the sentence vectors [n, Ri, Si, F] item_state is given: what its Kr
+        (= r' @ Wr^T) and the pooled item q (= sum_i item_review_weights[i] r'[i]) are made of, by the same modules.  The item's
+        own path into the FM, for functional.ahn_pair_explain."""
+        n, r_num, s_num, F_ = item_sents.shape
+        with RF.eval_mode(self):
+            r, _, _ = self.unbalanced_sentence_aggregator.item_aggregator(item_sents.detach().reshape(n * r_num, s_num, F_),
+                                                                          sent_masks.reshape(n * r_num, s_num).bool())
+            return self.item_review_trans_layer(r).detach().view(n, r_num, F_)
+
     def encode_users(self, reviews, sent_masks, sent_lens, rev_masks, ids, t_out) -> "RF.AhnUserState":
         """Word ids [n, Ru, Su, W], sentence masks / lengths [n, Ru, Su], review masks [n, Ru], user ids [n] and the side's fixed
         output length t_out (device int32 [1], functional.lstm_t_out) -> the per-user state of the pair tail; eval semantics."""
@@ -171,6 +181,12 @@ class AHN(nn.Module):
         Vb, lb = self._fm_blocks()
         return RF.AhnPairHead(self.user_review_trans_layer[0].bias.detach().clone(), Vb[0].t().contiguous(),
                               (Vb[0] * Vb[0]).sum(1).contiguous(), lb[0].contiguous().clone(), self.fm.lin.bias.detach().clone())
+
+    def explain_head(self):
+        """(VqT [K, F], vq2 [F], lq [F]): the FM's block of the item's pooled vector q, cut as pair_head cuts z's block.  A
+        snapshot, like the tables; with AHN.item_reviews the rest of functional.AhnExplainRows."""
+        Vb, lb = self._fm_blocks()
+        return Vb[2].t().contiguous(), (Vb[2] * Vb[2]).sum(1).contiguous(), lb[2].contiguous().clone()
 
     def aggregate(self, user_sents, item_sents, user_sent_masks, item_sent_masks, user_review_masks, item_review_masks,
                   user_ids, item_ids):

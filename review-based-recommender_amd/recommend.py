@@ -32,6 +32,13 @@ rank_metrics goes to --metrics-out, or to stdout.
 --model ahn: AHN's towers attend to each other, so it has no latent tables -- but only the user side depends on the pair, and the
 encoder on the id alone.  `AhnRecommender` keeps per-id SENTENCE tables and scores a pair by the co-attention tail in one HIP launch
 per block (csrc/ahn_pair.hip); same flags and JSON lines, sentence split instead of the doc / review split, --explain refused.
+With --sentences N (ahn) every line carries "why", one entry per recommended item: "user_sentences", the N sentences of the user
+of largest |contribution| as [review slot, sentence slot, attention weight, contribution, matched item review slot, matched item
+sentence slot] -- the contribution followed through both softmaxes and both max-similarities, the match being the item sentence
+the co-attention paired it with -- plus, where meta.pkl's vocabulary is readable, the sentence's words and the matched item
+sentence's words; "item_sentences", the N matched item sentences of largest |match contribution| as [review slot, sentence slot,
+item_sent_weight, match contribution]; "user_reviews" and "item_reviews" as [slot, attention weight, contribution]
+(AhnRecommender.sentences, csrc/ahn_explain.hip: one launch per block of pairs).
 """
 from __future__ import annotations
 
@@ -101,6 +108,26 @@ class Contributions(NamedTuple):
     user_reviews: torch.Tensor            # [B, rv_num] contribution of every review under those weights; sums to user_text
     item_review_weights: torch.Tensor
     item_reviews: torch.Tensor
+
+
+class SentenceContributions(NamedTuple):
+    """AhnRecommender.sentences: what every sentence and review of the pairs (u_ids[b], i_ids[b]) adds to AHN's score, and which
+    item sentence each user sentence matched (functional.ahn_pair_explain and include/rbr_hip.h have the definitions)."""
+    score: torch.Tensor                   # [B] = AhnRecommender.score
+    user_sent_weights: torch.Tensor       # [B, Ru, Su] the four weight arrays of AhnRecommender.attention
+    item_sent_weights: torch.Tensor       # [B, Ri, Si]
+    user_review_weights: torch.Tensor     # [B, Ru]
+    item_review_weights: torch.Tensor     # [B, Ri]
+    user_sentences: torch.Tensor          # [B, Ru, Su] gradient x input of every sentence vector, through both softmaxes and maxima
+    user_sentences_fixed: torch.Tensor    # [B, Ru, Su] the part with both attention weightings held constant
+    user_reviews: torch.Tensor            # [B, Ru] contribution of every user review; sums to user_text
+    user_text: torch.Tensor               # [B] what the user's text as a whole adds to the score
+    user_match: torch.Tensor              # int64 [B, Ru, Su] the flat item sentence ri * Si + si each user sentence matched
+    review_match: torch.Tensor            # int64 [B, Ru] the item review each user review matched
+    item_sentence_match: torch.Tensor     # [B, Ri, Si] what an item sentence adds as the match of user sentences; 0 where unmatched
+    item_review_match: torch.Tensor       # [B, Ri] the same for the item's reviews
+    item_reviews: torch.Tensor            # [B, Ri] the item's own path, its attention weights held constant; sums to item_text
+    item_text: torch.Tensor               # [B]
 
 
 def top_tokens(tokens: torch.Tensor, docs: torch.Tensor, n: int):
@@ -490,6 +517,8 @@ class AhnRecommender:
     vectors X and X @ Wt^T with the masks, and per item the pre-multiplied keys Ks, Kr and its own attention weights; a score
     is then the pair tail alone, one HIP launch per block (functional.ahn_pair_score*, csrc/ahn_pair.hip).  In f32 that is
     2 * Ru * Su * F * 4 bytes per user and (Ri * Si + Ri) * F * 4 per item: about 240 KB and 120 KB at the default shape.
+    refresh() also keeps the items' transformed reviews r' (`item_rows` [I, Ri, F], from the same sentence vectors: the encoder
+    still runs once per id) for sentences(): Ri * F * 4 bytes more per item, about 12 KB on top of the 120 KB.
 
     `cache`: a data.DeviceSentenceCache of the sentence split, or pass `user` / `item` = per-id word-id tensors [N, R, S, W] on
     the model's device (row 0 = the padding id).  The tables are read by the PLAIN rule: the first rv_num slots of an id's row, as
@@ -521,6 +550,7 @@ class AhnRecommender:
         self.n_users, self.n_items = user.shape[0], item.shape[0]
         self.item_lo = 1                     # the padding id 0 is never recommended
         self.user_state = self.item_state = self.head = None
+        self.item_rows = self.explain_head = None      # r' [I, Ri, F] and the FM's q block: what sentences() reads beyond the score's
         self._versions = None
 
     # ------------------------------------------------------------------ the tables
@@ -533,7 +563,7 @@ class AhnRecommender:
         m = self.model
         states = []
         with RF.eval_mode(m):
-            for docs, n, enc in ((self.user, self.n_users, m.encode_users), (self.item, self.n_items, m.encode_items)):
+            for docs, n, state_of in ((self.user, self.n_users, m.user_state), (self.item, self.n_items, m.item_state)):
                 if not docs.is_cuda:
                     raise RuntimeError(f"the per-id sentence tables must live on a HIP device (got {docs.device}); there is no CPU path")
                 t_out = RF.lstm_t_out(D.sentence_masks(docs, PAD)[0].reshape(-1), docs.shape[-1])
@@ -542,14 +572,17 @@ class AhnRecommender:
                     revs = docs[a:a + chunk].to(torch.int64).contiguous()
                     lens, sent_masks, rev_masks = D.sentence_masks(revs, PAD)
                     ids = torch.arange(a, a + revs.shape[0], dtype=torch.int64, device=revs.device)
-                    rows = enc(revs, sent_masks, lens, rev_masks, ids, t_out)
+                    sents = m._encode_side(revs, lens, t_out)      # the encoder runs once per id: the state and r' both come from it
+                    rows = state_of(sents, sent_masks, rev_masks, ids)
+                    extra = [m.item_reviews(sents, sent_masks)] if state_of == m.item_state else []
                     if fields is None:
-                        fields = [torch.empty(n, *t.shape[1:], dtype=t.dtype, device=t.device) for t in rows]
-                    for dst, t in zip(fields, rows):
+                        fields = [torch.empty(n, *t.shape[1:], dtype=t.dtype, device=t.device) for t in (*rows, *extra)]
+                    for dst, t in zip(fields, (*rows, *extra)):
                         dst[a:a + t.shape[0]] = t
-                states.append(type(rows)(*fields))
+                states.append(type(rows)(*fields[:len(rows)]))
             self.user_state, self.item_state = states
-            self.head = m.pair_head()
+            self.item_rows = fields[-1]
+            self.head, self.explain_head = m.pair_head(), m.explain_head()
         self._versions = [p._version for p in m.parameters()]
         return self
 
@@ -581,6 +614,28 @@ class AhnRecommender:
         u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
         _, w, v = RF.ahn_pair_score(us, its, head, u_ids, i_ids, weights=True)
         return w, its.item_sent_weights.index_select(0, i_ids), v, its.item_review_weights.index_select(0, i_ids)
+
+    def sentences(self, u_ids: torch.Tensor, i_ids: torch.Tensor, chunk: int = 256) -> SentenceContributions:
+        """AHN's answer to "why": for the pairs (u_ids[b], i_ids[b]), `chunk` pairs per launch, from the tables alone
+        (functional.ahn_pair_explain, csrc/ahn_explain.hip) -- the score and the four weight arrays, what every user sentence and
+        review adds to the score (gradient x input of the sentence vector, followed through both softmaxes and both
+        max-similarities; *_fixed holds the attention weightings constant), WHICH item sentence each user sentence matched and
+        which item review each user review, what the matched item sentences / reviews add through that match, and the item's own
+        reviews under its own weights (held constant, as NARRE's are in Recommender.explain).  The id embeddings and the biases
+        are the part of the score no text explains; no encoder runs and no autograd."""
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        us, its, head = self._tables()
+        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
+            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
+        extra = RF.AhnExplainRows(self.item_rows, *self.explain_head)
+        parts = [RF.ahn_pair_explain(us, its, head, extra, u_ids[a:a + chunk], i_ids[a:a + chunk]) for a in range(0, u_ids.shape[0], chunk)]
+        ex = RF.AhnPairExplanation(*(torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts)))
+        return SentenceContributions(ex.score, ex.user_sent_weights, its.item_sent_weights.index_select(0, i_ids), ex.user_review_weights,
+                                     its.item_review_weights.index_select(0, i_ids), ex.user_sentences, ex.user_sentences_fixed,
+                                     ex.user_reviews, ex.user_text, ex.user_match.to(torch.int64), ex.review_match.to(torch.int64),
+                                     ex.item_sentence_match, ex.item_review_match, ex.item_reviews, ex.item_text)
 
     def topk(self, u_ids: torch.Tensor, k: int, exclude=None):
         """Recommender.topk over score_all's block (select_topk)."""
@@ -629,6 +684,9 @@ def parse_cli(argv=None):
                     "side behind each recommended item with their local gates, followed through both attention gates; dual_att only")
     ap.add_argument("--contributions", type=int, metavar="N", help="with --out: add \"why\" to every line, the N weightiest tokens and "
                     "reviews of each side behind each recommended item, followed through the review attention; simple_siamese only")
+    ap.add_argument("--sentences", type=int, metavar="N", help="with --out: add \"why\" to every line, the N weightiest user sentences "
+                    "behind each recommended item with the item sentence each matched, the matched item sentences and both sides' "
+                    "reviews; ahn only")
     ap.add_argument("--chunk", type=int, default=256, help="ids encoded / users ranked per launch")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--reference-quirks", action="store_true", help="as for the trainer: kernel_sizes=[3] (NARRE hidden_dim=150)")
@@ -658,6 +716,13 @@ def parse_cli(argv=None):
             ap.error("--contributions adds to the lines of --out: give --out")
         if a.model != "simple_siamese":
             ap.error("--contributions covers simple_siamese (deepconn and narre: --explain, dual_att: --attention)")
+    if a.sentences is not None:
+        if a.sentences < 1:
+            ap.error("--sentences must be at least 1")
+        if a.out is None:
+            ap.error("--sentences adds to the lines of --out: give --out")
+        if a.model != "ahn":
+            ap.error("--sentences covers ahn (deepconn and narre: --explain, dual_att: --attention, simple_siamese: --contributions)")
     if a.eval_split is None:
         if a.out is None:
             ap.error("--out is required unless --eval-split is given")
@@ -779,6 +844,55 @@ def _why_contributions(rec, u_ids, items, n, words):
     return why
 
 
+def _why_sentences(rec, u_ids, items, n, words):
+    """The "why" lists of --sentences for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per item
+    the n user sentences of largest |contribution| as [review slot, sentence slot, weight, contribution, matched item review
+    slot, matched item sentence slot] (with a vocabulary: + the sentence's words and the matched item sentence's words, token 0
+    dropped), the n matched item sentences of largest |match contribution| as [review slot, sentence slot, item_sent_weight,
+    match contribution], and both sides' n reviews of largest |contribution| as [slot, weight, contribution]."""
+    dev = u_ids.device
+    keep = items >= 0
+    rows, cols = keep.nonzero(as_tuple=True)
+    why = [[None] * int(keep[r].sum()) for r in range(items.shape[0])]
+    if rows.numel() == 0:
+        return why
+    pu, pi = u_ids[rows.to(dev)], items[rows, cols].to(dev)
+    sc = rec.sentences(pu, pi)
+    Su, Si = sc.user_sentences.shape[2], sc.item_sentence_match.shape[2]
+
+    def sent_words(table, ids, pos):
+        if not words:
+            return None
+        sents = table.index_select(0, ids).to(torch.int64)
+        sents = sents.reshape(sents.shape[0], -1, sents.shape[-1])
+        picked = torch.gather(sents, 1, pos.view(*pos.shape, 1).expand(-1, -1, sents.shape[-1])).cpu()
+        return [[[words.get(int(t), int(t)) for t in s if int(t) != PAD] for s in row] for row in picked.tolist()]
+
+    pos, wgt, x = top_tokens(sc.user_sentences, sc.user_sent_weights, n)
+    hit = torch.gather(sc.user_match.reshape(pos.shape[0], -1), 1, pos)
+    uw, iw = sent_words(rec.user, pu, pos), sent_words(rec.item, pi, hit)
+    pos, wgt, x, hit = pos.cpu(), wgt.cpu(), x.cpu(), hit.cpu()
+    us = []
+    for p in range(pos.shape[0]):
+        row = []
+        for k, (q, a, c, h) in enumerate(zip(pos[p].tolist(), wgt[p].tolist(), x[p].tolist(), hit[p].tolist())):
+            if c != 0.0:
+                row.append([q // Su, q % Su, a, c, h // Si, h % Si] + ([uw[p][k], iw[p][k]] if words else []))
+        us.append(row)
+
+    def tops(contrib, weights, width=None):
+        q, a, c = (t.cpu() for t in top_tokens(contrib, weights, n))
+        slot = (lambda s: [s]) if width is None else (lambda s: [s // width, s % width])
+        return [[slot(s) + [w, v] for s, w, v in zip(*r) if v != 0.0] for r in zip(q.tolist(), a.tolist(), c.tolist())]
+
+    isent = tops(sc.item_sentence_match, sc.item_sent_weights, Si)
+    ur, ir = tops(sc.user_reviews, sc.user_review_weights), tops(sc.item_reviews, sc.item_review_weights)
+    slot_of = keep.cumsum(1) - 1
+    for p, (r, k) in enumerate(zip(rows.tolist(), cols.tolist())):
+        why[r][int(slot_of[r, k])] = {"user_sentences": us[p], "user_reviews": ur[p], "item_sentences": isent[p], "item_reviews": ir[p]}
+    return why
+
+
 def main(argv=None) -> int:
     a = parse_cli(argv)
     from . import data as D
@@ -808,7 +922,7 @@ def main(argv=None) -> int:
     # AHN: sentence tables and the pair tail (AhnRecommender); a chunk of ids is chunk * R * S sentences through the encoder
     rec = AhnRecommender(model, cache).refresh(chunk=min(a.chunk, 32)) if a.model == "ahn" else Recommender(model, cache).refresh(chunk=a.chunk)
     seen = Recommender.seen_from(ds.examples, rec.n_users, dev) if a.exclude_train else None
-    words = _vocabulary(cfg.data_dir) if any(n is not None for n in (a.explain, a.attention, a.contributions)) else None
+    words = _vocabulary(cfg.data_dir) if any(n is not None for n in (a.explain, a.attention, a.contributions, a.sentences)) else None
     if a.out is not None:
         with open(a.out, "w") as f:
             for lo in range(1, rec.n_users, a.chunk):
@@ -820,6 +934,8 @@ def main(argv=None) -> int:
                     why = _why_attention(rec, u_ids, items, a.attention, words)
                 if a.contributions is not None:
                     why = _why_contributions(rec, u_ids, items, a.contributions, words)
+                if a.sentences is not None:
+                    why = _why_sentences(rec, u_ids, items, a.sentences, words)
                 for r, u in enumerate(u_ids.tolist()):
                     keep = items[r] >= 0
                     line = {"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}
