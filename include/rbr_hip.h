@@ -1057,6 +1057,21 @@ int rbr_lstm_seq_fwd(int32_t N, int32_t T, int32_t Hh, const float* xproj, const
 int rbr_lstm_seq_bwd(int32_t N, int32_t T, int32_t Hh, const float* w_hh_fwd, const float* w_hh_rev, const int64_t* lengths,
                      const void* saved, const float* d_out, const float* d_pooled, const int32_t* argmax, float* d_xproj,
                      float* d_w_hh_fwd, float* d_w_hh_rev, void* ws, void* stream);
+/* Word saliency through the recurrence: gradient x input of every step's input, per direction, without d_xproj.  The input
+ * projection is linear, so <d s / d x_t, x_t> = <W_ih^T dpre_t, x_t> = <dpre_t, W_ih x_t>: the backward's loop forms that dot
+ * in place of the d_xproj store.
+ *   saved      the state rbr_lstm_seq_fwd wrote for the same N, T, Hh, lengths and weights (gates, c and the tile order are read,
+ *              h_{t-1} is not; nothing is modified: rbr_lstm_seq_bwd may follow on the same state)
+ *   xw [N, T, 8 Hh]   the BIAS-FREE input projection x W_ih^T of both directions, xproj's layout
+ *   d_pooled [N, 2 Hh], argmax [N, 2 Hh]   as in rbr_lstm_seq_bwd: a unit with argmax -1 takes no gradient
+ *   words_out [N, T, 2]   OVERWRITTEN: per step and direction the sum over the four gates and the Hh units of dpre * xw; 0.0f at
+ *              t >= len and in empty rows.  The two directions of a step add up to gradient x input of x_t.
+ * The sum over the units is a butterfly inside each wave, then the waves of a sentence in wave order: no atomics, no
+ * workspace, and a step's bits depend on its sequence alone -- not on the batch around it or on the run.
+ * Sizes and refusals are rbr_lstm_seq_bwd's; N == 0 returns 0 without a launch. */
+int rbr_lstm_seq_saliency(int32_t N, int32_t T, int32_t Hh, const float* w_hh_fwd, const float* w_hh_rev, const int64_t* lengths,
+                          const void* saved, const float* xw, const float* d_pooled, const int32_t* argmax, float* words_out,
+                          void* stream);
 
 /* ---- AHN's pair-dependent tail from cached per-id sentence tables (csrc/ahn_pair.hip).  AHN's co-attention is asymmetric
  *      (models/ahn/ahn_layers.py:562-660): the item side is pooled by GatedAttention alone, only the user side looks at the pair.

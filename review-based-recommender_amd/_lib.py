@@ -302,6 +302,8 @@ SIGNATURES = {
                                    c_stream]),
     "rbr_lstm_seq_bwd": (C.c_int, [i32, i32, i32, c_f32p, c_f32p, c_i64p, C.c_void_p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p,
                                    c_f32p, C.c_void_p, c_stream]),
+    "rbr_lstm_seq_saliency": (C.c_int, [i32, i32, i32, c_f32p, c_f32p, c_i64p, C.c_void_p, c_f32p, c_f32p, c_i32p, c_f32p,
+                                        c_stream]),
 }
 
 _lib = None

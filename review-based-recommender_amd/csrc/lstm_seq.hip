@@ -1,6 +1,7 @@
 // lstm_seq.hip -- one-layer bidirectional LSTM over N padded sequences of at most T steps, forward and backward:
 // rbr_lstm_seq_fwd / rbr_lstm_seq_bwd (AHN's shared sentence encoder, models/ahn/ahn_layers.py:249-312, and the max over
-// the words that follows it, ahn_model.py:62-67).
+// the words that follows it, ahn_model.py:62-67), and rbr_lstm_seq_saliency: gradient x input of every step through the
+// backward's loop, without d_xproj (lstm_saliency_kernel, below the backward).
 //
 // The input projection xproj = x W_ih^T + b_ih + b_hh of BOTH directions is a plain GEMM over [N * T, E] and is done by
 // rbr_linear_* in front of this file; what is left is the recurrence  gates_t = xproj_t + h_{t-1} W_hh^T  (gate order i, f, g, o),
@@ -199,6 +200,49 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(const LstmArgs A, const f
     }
 }
 
+// d pre-activations of one unit at one step from the saved gate activations, c_t (ct), c_{t-1} (cp; 0 at the sentence's first
+// step) and dh = d h_t; dc_rec, the d c carried from the later step, becomes this step's.  The ONE statement of this arithmetic:
+// the backward and the word saliency both inline it, so the two see the same d pre-activations bit for bit.
+struct LstmDpre { float ai, af, ag, ao; };
+__device__ __forceinline__ LstmDpre lstm_dpre(float gi, float gf, float gg, float go, float ct, float cp, float dh, float& dc_rec) {
+    const float tc = tanhf(ct);
+    const float dc = fmaf(dh * go, 1.f - tc * tc, dc_rec);
+    LstmDpre d;
+    d.ai = dc * gg * gi * (1.f - gi);
+    d.af = dc * cp * gf * (1.f - gf);
+    d.ag = dc * gi * (1.f - gg * gg);
+    d.ao = dh * tc * go * (1.f - go);
+    dc_rec = dc * gf;
+    return d;
+}
+
+// d h_{t-1}[j] of the RS sentences of a thread = sum over the 4 Hh gate rows of d_gates[row] * W_hh[row][j], d_gates of the
+// thread's sentence group (tile rows row0 .. row0 + RS - 1 of dg) read from LDS, W_hh in the torch layout (lanes along k).
+template <int RS>
+__device__ __forceinline__ void lstm_dh_prev(int Hh, int G4, int j, const float* __restrict__ w, const float* dg, int row0,
+                                             float (&dh_rec)[RS]) {
+    float acc[RS];
+#pragma unroll
+    for (int r = 0; r < RS; ++r) acc[r] = 0.f;
+    for (int q4 = 0; q4 < G4; q4 += 4) {
+        float wv[4];
+#pragma unroll
+        for (int qq = 0; qq < 4; ++qq) wv[qq] = w[(long)(q4 + qq) * Hh + j];
+#pragma unroll
+        for (int r = 0; r < RS; ++r) {
+            const float4 d = *reinterpret_cast<const float4*>(dg + (row0 + r) * G4 + q4);
+            float a = acc[r];
+            a = fmaf(d.x, wv[0], a);
+            a = fmaf(d.y, wv[1], a);
+            a = fmaf(d.z, wv[2], a);
+            a = fmaf(d.w, wv[3], a);
+            acc[r] = a;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RS; ++r) dh_rec[r] = acc[r];
+}
+
 template <int RS>
 __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs A, const float* __restrict__ w0, const float* __restrict__ w1,
                                                        const long long* __restrict__ lengths, const int* __restrict__ perm,
@@ -245,44 +289,17 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs A, const f
                     float dh = dh_rec[r];
                     if (d_out != nullptr) dh += d_out[pos * 2L * Hh + dir * Hh + j];
                     if (amx[r] == t) dh += dpl[r];
-                    const float tc = tanhf(ct);
-                    const float dc = fmaf(dh * go, 1.f - tc * tc, dc_rec[r]);
-                    const float dai = dc * gg * gi * (1.f - gi);
-                    const float daf = dc * cp * gf * (1.f - gf);
-                    const float dag = dc * gi * (1.f - gg * gg);
-                    const float dao = dh * tc * go * (1.f - go);
-                    dc_rec[r] = dc * gf;
+                    const LstmDpre d = lstm_dpre(gi, gf, gg, go, ct, cp, dh, dc_rec[r]);
                     float* dx = d_xproj + pos * 8L * Hh + (long)dir * 4 * Hh + j;
-                    dx[0] = dai; dx[Hh] = daf; dx[2 * Hh] = dag; dx[3 * Hh] = dao;
-                    dgr[0] = dai; dgr[Hh] = daf; dgr[2 * Hh] = dag; dgr[3 * Hh] = dao;
+                    dx[0] = d.ai; dx[Hh] = d.af; dx[2 * Hh] = d.ag; dx[3 * Hh] = d.ao;
+                    dgr[0] = d.ai; dgr[Hh] = d.af; dgr[2 * Hh] = d.ag; dgr[3 * Hh] = d.ao;
                 } else {
                     dgr[0] = 0.f; dgr[Hh] = 0.f; dgr[2 * Hh] = 0.f; dgr[3 * Hh] = 0.f;
                 }
             }
         }
         __syncthreads();
-        if (jv && s > 0) {                     // d h_{t-1}[j] = sum over the 4 Hh gate rows of d_gates[row] * W_hh[row][j]
-            float acc[RS];
-#pragma unroll
-            for (int r = 0; r < RS; ++r) acc[r] = 0.f;
-            for (int q4 = 0; q4 < G4; q4 += 4) {
-                float wv[4];
-#pragma unroll
-                for (int qq = 0; qq < 4; ++qq) wv[qq] = w[(long)(q4 + qq) * Hh + j];
-#pragma unroll
-                for (int r = 0; r < RS; ++r) {
-                    const float4 d = *reinterpret_cast<const float4*>(dg + (sg * RS + r) * G4 + q4);
-                    float a = acc[r];
-                    a = fmaf(d.x, wv[0], a);
-                    a = fmaf(d.y, wv[1], a);
-                    a = fmaf(d.z, wv[2], a);
-                    a = fmaf(d.w, wv[3], a);
-                    acc[r] = a;
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < RS; ++r) dh_rec[r] = acc[r];
-        }
+        if (jv && s > 0) lstm_dh_prev<RS>(Hh, G4, j, w, dg, sg * RS, dh_rec);
         __syncthreads();
     }
     if (!jv) return;
@@ -295,6 +312,95 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const LstmArgs A, const f
             float* dx = d_xproj + (n * T + t) * 8L * Hh + (long)dir * 4 * Hh + j;
             dx[0] = 0.f; dx[Hh] = 0.f; dx[2 * Hh] = 0.f; dx[3 * Hh] = 0.f;
         }
+    }
+}
+
+// Word saliency: lstm_bwd_kernel's loop -- the same tiling, tile_lengths, trip count and d h_{t-1} through LDS -- that stores no
+// d_xproj.  The input projection is linear, so gradient x input of a word needs no dx:
+//     <d score / d x_t, x_t> = <W_ih^T dpre_t, x_t> = <dpre_t, W_ih x_t> = <dpre_t, xw_t>       (xw: the BIAS-FREE projection)
+// and each step reduces a thread's four products dpre * xw over the hidden-unit lanes: the xor butterfly of rbr_wave.h inside a
+// wave (lanes j >= Hh and ended sentences add 0.0f), lane 0 of each wave leaves the sums of its RS sentences in LDS in front of the
+// step's first barrier, and behind it thread `slot` adds the JW / 64 wave sums of its sentence in wave order and stores
+// words_out[n, t, dir].  `red` is written again only behind the step's second barrier.  The order of every addition depends on
+// Hh alone: a word's bits depend on its sentence, not on the tile slot, the batch or the run.  No atomics, no workspace.
+template <int RS>
+__global__ __launch_bounds__(256) void lstm_saliency_kernel(const LstmArgs A, const float* __restrict__ w0, const float* __restrict__ w1,
+                                                            const long long* __restrict__ lengths, const int* __restrict__ perm,
+                                                            const float* __restrict__ gates, const float* __restrict__ cs,
+                                                            const float* __restrict__ xw, const float* __restrict__ d_pooled,
+                                                            const int* __restrict__ argmax, float* __restrict__ words_out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* dg = reinterpret_cast<float*>(smem);                                     // [TS][4 Hh] d pre-activations of the step
+    int* s_len = reinterpret_cast<int*>(smem + (size_t)A.TS * 4 * A.Hh * sizeof(float));
+    int* s_n = s_len + A.TS;
+    float* red = reinterpret_cast<float*>(s_n + A.TS);                              // [waves][RS] wave sums of the step
+    const int tid = threadIdx.x, dir = blockIdx.y, tile = blockIdx.x;
+    const int Hh = A.Hh, T = A.T, G4 = 4 * A.Hh;
+    const int j = tid % A.JW, sg = tid / A.JW;
+    const int lane = tid & 63, wave = tid >> 6, wpg = A.JW >> 6;                    // wpg: waves per sentence group
+    const bool jv = j < Hh;
+    const int lmax = tile_lengths(A, lengths, perm, tile, s_len, s_n);
+    const int* my_n = s_n + sg * RS;
+    const float* __restrict__ w = dir ? w1 : w0;                                    // [4 Hh][Hh]
+    float dh_rec[RS], dc_rec[RS], dpl[RS];
+    int amx[RS];
+#pragma unroll
+    for (int r = 0; r < RS; ++r) {
+        dh_rec[r] = 0.f; dc_rec[r] = 0.f; dpl[r] = 0.f; amx[r] = -1;
+        const long n = my_n[r];
+        if (jv && n >= 0) {
+            amx[r] = argmax[n * 2L * Hh + dir * Hh + j];
+            dpl[r] = d_pooled[n * 2L * Hh + dir * Hh + j];
+        }
+    }
+
+    for (int s = lmax - 1; s >= 0; --s) {
+        float p[RS];
+#pragma unroll
+        for (int r = 0; r < RS; ++r) p[r] = 0.f;
+        if (jv) {
+#pragma unroll
+            for (int r = 0; r < RS; ++r) {
+                const int len = s_len[sg * RS + r];
+                float* dgr = dg + (sg * RS + r) * G4 + j;
+                if (s < len) {
+                    const int t = dir ? len - 1 - s : s;
+                    const long pos = (long)my_n[r] * T + t;
+                    const float* gp = gates + pos * 8L * Hh + (long)dir * 4 * Hh + j;
+                    const float gi = gp[0], gf = gp[Hh], gg = gp[2 * Hh], go = gp[3 * Hh];
+                    const float ct = cs[pos * 2L * Hh + dir * Hh + j];
+                    const float cp = (s > 0) ? cs[(pos + (dir ? 1 : -1)) * 2L * Hh + dir * Hh + j] : 0.f;
+                    float dh = dh_rec[r];
+                    if (amx[r] == t) dh += dpl[r];
+                    const LstmDpre d = lstm_dpre(gi, gf, gg, go, ct, cp, dh, dc_rec[r]);
+                    const float* xp = xw + pos * 8L * Hh + (long)dir * 4 * Hh + j;
+                    p[r] = fmaf(d.ao, xp[3 * Hh], fmaf(d.ag, xp[2 * Hh], fmaf(d.af, xp[Hh], d.ai * xp[0])));
+                    dgr[0] = d.ai; dgr[Hh] = d.af; dgr[2 * Hh] = d.ag; dgr[3 * Hh] = d.ao;
+                } else {
+                    dgr[0] = 0.f; dgr[Hh] = 0.f; dgr[2 * Hh] = 0.f; dgr[3 * Hh] = 0.f;
+                }
+            }
+        }
+        wave_sum_n(p, 64);                      // every lane of every wave is here: lmax is the workgroup's
+        if (lane == 0) {
+#pragma unroll
+            for (int r = 0; r < RS; ++r) red[wave * RS + r] = p[r];
+        }
+        __syncthreads();
+        if (tid < A.TS && s < s_len[tid]) {     // sentence slot tid = group tid / RS, row tid % RS: its waves in wave order
+            const float* rp = red + (tid / RS) * wpg * RS + tid % RS;
+            float v = rp[0];
+            for (int k = 1; k < wpg; ++k) v += rp[k * RS];
+            const int len = s_len[tid];
+            words_out[((long)s_n[tid] * T + (dir ? len - 1 - s : s)) * 2 + dir] = v;
+        }
+        if (jv && s > 0) lstm_dh_prev<RS>(Hh, G4, j, w, dg, sg * RS, dh_rec);
+        __syncthreads();
+    }
+    for (int e = tid; e < A.TS * T; e += blockDim.x) {                    // behind the sentence's end (and empty rows): zeros
+        const int slot = e / T, t = e % T;
+        const long n = s_n[slot];
+        if (n >= 0 && t >= s_len[slot]) words_out[(n * T + t) * 2 + dir] = 0.f;
     }
 }
 
@@ -413,5 +519,31 @@ extern "C" int rbr_lstm_seq_bwd(int32_t N, int32_t T, int32_t Hh, const float* w
                                  dir ? d_w_hh_rev : d_w_hh_fwd, Hh, part, st))
             return e;
     }
+    return 0;
+}
+
+extern "C" int rbr_lstm_seq_saliency(int32_t N, int32_t T, int32_t Hh, const float* w_hh_fwd, const float* w_hh_rev, const int64_t* lengths,
+                                     const void* saved, const float* xw, const float* d_pooled, const int32_t* argmax, float* words_out,
+                                     void* stream) {
+    LstmArgs A;
+    int rs;
+    if (!lstm_args("rbr_lstm_seq_saliency", N, T, Hh, A, rs)) return RBR_ERR_BAD_ARG;
+    if (int e = lstm_refuse("rbr_lstm_seq_saliency", T, Hh)) return e;
+    if (N == 0) return 0;
+    if (!w_hh_fwd || !w_hh_rev || !lengths || !saved || !xw || !d_pooled || !argmax || !words_out) {
+        set_error("rbr_lstm_seq_saliency: null pointer");
+        return RBR_ERR_BAD_ARG;
+    }
+    if ((long)N * T > 0x7fffffffL / (8L * Hh)) { set_error("rbr_lstm_seq_saliency: N * T * 8 Hh exceeds 2^31 elements"); return RBR_ERR_UNSUPPORTED; }
+    LstmSaved S = lstm_saved(const_cast<void*>(saved), N, T, Hh);
+    const dim3 grid((unsigned)((N + A.TS - 1) / A.TS), 2), block((unsigned)(A.JW * A.nsg));
+    // the backward's tile and tile lists, and one wave sum per wave and sentence row behind them
+    const size_t lds = (size_t)A.TS * 4 * Hh * sizeof(float) + (size_t)2 * A.TS * sizeof(int) + (size_t)(block.x / 64) * rs * sizeof(float);
+    const long long* len64 = reinterpret_cast<const long long*>(lengths);
+    if (rs == 16)
+        hipLaunchKernelGGL(lstm_saliency_kernel<16>, grid, block, lds, (hipStream_t)stream, A, w_hh_fwd, w_hh_rev, len64, S.perm, S.gates, S.cs, xw, d_pooled, argmax, words_out);
+    else
+        hipLaunchKernelGGL(lstm_saliency_kernel<8>, grid, block, lds, (hipStream_t)stream, A, w_hh_fwd, w_hh_rev, len64, S.perm, S.gates, S.cs, xw, d_pooled, argmax, words_out);
+    RBR_CHECK_LAUNCH("lstm word saliency launch");
     return 0;
 }

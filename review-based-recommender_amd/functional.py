@@ -3113,43 +3113,51 @@ def lstm_t_out(lengths: torch.Tensor, T: int) -> torch.Tensor:
     return lengths.clamp(1, min(int(T), LSTM_MAX_LEN)).max().to(I32).view(1)
 
 
+def _lstm_seq_fwd(xproj, w_f, w_r, lengths, t_out, pool):
+    """The checks and the one rbr_lstm_seq_fwd call shared by _LstmSeq.forward and lstm_seq_states -> (out, pooled, argmax, saved,
+    and the contiguous w_f, w_r, lengths the call read)."""
+    if xproj.dim() != 3 or xproj.shape[2] % 8:
+        raise RuntimeError(f"lstm_seq: xproj must be [N, T, 8 * Hh], got {tuple(xproj.shape)}")
+    N, T, H8 = xproj.shape
+    Hh = H8 // 8
+    if tuple(w_f.shape) != (4 * Hh, Hh) or tuple(w_r.shape) != (4 * Hh, Hh):
+        raise RuntimeError(f"lstm_seq: w_hh must be [{4 * Hh}, {Hh}] for both directions")
+    if lengths.dtype != I64 or lengths.numel() != N:
+        raise RuntimeError("lstm_seq: lengths must be int64 [N]")
+    L_ = _lib.lib()
+    dev = xproj.device
+    xproj, w_f, w_r, lengths = xproj.contiguous(), w_f.contiguous(), w_r.contiguous(), lengths.contiguous().view(-1)
+    per_seq = 0
+    if pool:
+        if t_out is None:
+            t_out = lstm_t_out(lengths, T)
+        t_out = t_out.contiguous().view(-1)
+        if t_out.numel() not in (1, N):
+            raise RuntimeError("lstm_seq: t_out must hold one value, or one per sequence")
+        per_seq = int(t_out.numel() == N and N > 1)
+    saved = torch.empty(L_.rbr_lstm_seq_ws_bytes(N, T, Hh), dtype=U8, device=dev)
+    out = pooled = argmax = None
+    if pool:
+        pooled = torch.empty(N, 2 * Hh, dtype=F32, device=dev)
+        argmax = torch.empty(N, 2 * Hh, dtype=I32, device=dev)
+    else:
+        out = torch.empty(N, T, 2 * Hh, dtype=F32, device=dev)
+    _call("lstm_seq_fwd", L_.rbr_lstm_seq_fwd, N, T, Hh, dev_ptr(xproj, F32, "xproj"), dev_ptr(w_f, F32, "w_hh_fwd"),
+          dev_ptr(w_r, F32, "w_hh_rev"), dev_ptr(lengths, I64, "lengths"), dev_ptr(t_out if pool else None, I32, "t_out"), per_seq,
+          dev_ptr(out, F32, "out"), dev_ptr(pooled, F32, "pooled"), dev_ptr(argmax, I32, "argmax"),
+          saved.data_ptr() if saved.numel() else None, current_stream())
+    return out, pooled, argmax, saved, w_f, w_r, lengths
+
+
 class _LstmSeq(torch.autograd.Function):
     """rbr_lstm_seq_fwd / rbr_lstm_seq_bwd of rbr_hip.h: the recurrence over xproj, returning out [N, T, 2 Hh] or the fused
     (pooled [N, 2 Hh], argmax int32 [N, 2 Hh])."""
 
     @staticmethod
     def forward(ctx, xproj, w_f, w_r, lengths, t_out, pool):
-        if xproj.dim() != 3 or xproj.shape[2] % 8:
-            raise RuntimeError(f"lstm_seq: xproj must be [N, T, 8 * Hh], got {tuple(xproj.shape)}")
+        out, pooled, argmax, saved, w_f, w_r, lengths = _lstm_seq_fwd(xproj, w_f, w_r, lengths, t_out, pool)
         N, T, H8 = xproj.shape
-        Hh = H8 // 8
-        if tuple(w_f.shape) != (4 * Hh, Hh) or tuple(w_r.shape) != (4 * Hh, Hh):
-            raise RuntimeError(f"lstm_seq: w_hh must be [{4 * Hh}, {Hh}] for both directions")
-        if lengths.dtype != I64 or lengths.numel() != N:
-            raise RuntimeError("lstm_seq: lengths must be int64 [N]")
-        L_ = _lib.lib()
-        dev = xproj.device
-        xproj, w_f, w_r, lengths = xproj.contiguous(), w_f.contiguous(), w_r.contiguous(), lengths.contiguous().view(-1)
-        per_seq = 0
-        if pool:
-            if t_out is None:
-                t_out = lstm_t_out(lengths, T)
-            t_out = t_out.contiguous().view(-1)
-            if t_out.numel() not in (1, N):
-                raise RuntimeError("lstm_seq: t_out must hold one value, or one per sequence")
-            per_seq = int(t_out.numel() == N and N > 1)
-        saved = torch.empty(L_.rbr_lstm_seq_ws_bytes(N, T, Hh), dtype=U8, device=dev)
-        out = pooled = argmax = None
-        if pool:
-            pooled = torch.empty(N, 2 * Hh, dtype=F32, device=dev)
-            argmax = torch.empty(N, 2 * Hh, dtype=I32, device=dev)
-        else:
-            out = torch.empty(N, T, 2 * Hh, dtype=F32, device=dev)
-        _call("lstm_seq_fwd", L_.rbr_lstm_seq_fwd, N, T, Hh, dev_ptr(xproj, F32, "xproj"), dev_ptr(w_f, F32, "w_hh_fwd"),
-              dev_ptr(w_r, F32, "w_hh_rev"), dev_ptr(lengths, I64, "lengths"), dev_ptr(t_out if pool else None, I32, "t_out"), per_seq,
-              dev_ptr(out, F32, "out"), dev_ptr(pooled, F32, "pooled"), dev_ptr(argmax, I32, "argmax"),
-              saved.data_ptr() if saved.numel() else None, current_stream())
-        ctx.job = (N, T, Hh, bool(pool))
+        ctx.job = (N, T, H8 // 8, bool(pool))
         ctx.save_for_backward(w_f, w_r, lengths, saved, *([argmax] if pool else []))
         if pool:
             ctx.mark_non_differentiable(argmax)
@@ -3196,3 +3204,77 @@ def bilstm_encode(x, lstm_params, lengths, *, pool: bool, t_out=None):
     b = torch.cat([b_ih_f + b_hh_f, b_ih_r + b_hh_r], dim=0)
     xproj = linear(x.reshape(N * T, E), W, b).view(N, T, W.shape[0])
     return lstm_seq(xproj, w_hh_f, w_hh_r, lengths, pool=pool, t_out=t_out)
+
+
+class LstmState(NamedTuple):
+    """lstm_seq_states' handle: the forward's saved state (gate activations, cell states, the tile order) kept alive outside
+    autograd, with the shape it belongs to.  Read by lstm_seq_word_saliency; never modified."""
+    saved: torch.Tensor       # uint8 [rbr_lstm_seq_ws_bytes(N, T, Hh)]
+    N: int
+    T: int
+    Hh: int
+
+
+def lstm_seq_states(xproj, w_hh_fwd, w_hh_rev, lengths, t_out):
+    """lstm_seq(..., pool=True, t_out=t_out) outside autograd -> (pooled [N, 2 Hh], argmax int32 [N, 2 Hh], state): the same
+    launch, so pooled and argmax have lstm_seq's bits, and `state` keeps what the forward saved for lstm_seq_word_saliency.
+    Nothing here is differentiable: the inputs' autograd history is ignored."""
+    with torch.no_grad():
+        _, pooled, argmax, saved, _, _, _ = _lstm_seq_fwd(xproj.detach(), w_hh_fwd.detach(), w_hh_rev.detach(), lengths, t_out, True)
+    N, T, H8 = xproj.shape
+    return pooled, argmax, LstmState(saved, N, T, H8 // 8)
+
+
+def lstm_seq_word_saliency(state: LstmState, xw, w_hh_fwd, w_hh_rev, lengths, d_pooled, argmax) -> torch.Tensor:
+    """rbr_lstm_seq_saliency of rbr_hip.h: gradient x input of every step through the recurrence, per direction, from the state of
+    lstm_seq_states -> [N, T, 2] f32.  xw [N, T, 8 Hh] is the BIAS-FREE input projection x W_ih^T (xproj's layout), d_pooled
+    [N, 2 Hh] the gradient of whatever is explained with respect to `pooled`, argmax the forward's.  out[n, t, d] = sum over
+    direction d's four gates and Hh units of d pre-activation * xw = <d / d x_t, x_t> restricted to direction d; exactly 0 at
+    t >= len and in empty rows.  No d_xproj, no weight gradient, no workspace; the same inputs give the same bits, and a
+    sequence's values do not depend on the batch around it.  w_hh_*, lengths: what the forward was given."""
+    N, T, Hh = state.N, state.T, state.Hh
+    if tuple(xw.shape) != (N, T, 8 * Hh):
+        raise RuntimeError(f"lstm_seq_word_saliency: xw must be [{N}, {T}, {8 * Hh}] like the forward's xproj, got {tuple(xw.shape)}")
+    if tuple(w_hh_fwd.shape) != (4 * Hh, Hh) or tuple(w_hh_rev.shape) != (4 * Hh, Hh):
+        raise RuntimeError(f"lstm_seq_word_saliency: w_hh must be [{4 * Hh}, {Hh}] for both directions")
+    if lengths.dtype != I64 or lengths.numel() != N:
+        raise RuntimeError("lstm_seq_word_saliency: lengths must be int64 [N]")
+    if tuple(d_pooled.shape) != (N, 2 * Hh) or tuple(argmax.shape) != (N, 2 * Hh):
+        raise RuntimeError(f"lstm_seq_word_saliency: d_pooled and argmax must be [{N}, {2 * Hh}]")
+    L_ = _lib.lib()
+    if state.saved.numel() != L_.rbr_lstm_seq_ws_bytes(N, T, Hh):
+        raise RuntimeError("lstm_seq_word_saliency: the state does not belong to this shape")
+    xw, d_pooled, argmax = xw.detach().contiguous(), d_pooled.detach().contiguous(), argmax.contiguous()
+    w_f, w_r, lengths = w_hh_fwd.detach().contiguous(), w_hh_rev.detach().contiguous(), lengths.contiguous().view(-1)
+    # the pointer checks come first: a CPU tensor is refused before anything is allocated on a device
+    ptrs = (dev_ptr(w_f, F32, "w_hh_fwd"), dev_ptr(w_r, F32, "w_hh_rev"), dev_ptr(lengths, I64, "lengths"),
+            dev_ptr(state.saved, U8, "state") if N else None, dev_ptr(xw, F32, "xw"), dev_ptr(d_pooled, F32, "d_pooled"),
+            dev_ptr(argmax, I32, "argmax"))
+    words = torch.empty(N, T, 2, dtype=F32, device=xw.device)
+    _call("lstm_seq_saliency", L_.rbr_lstm_seq_saliency, N, T, Hh, *ptrs, dev_ptr(words, F32, "words_out"), current_stream())
+    return words
+
+
+def bilstm_encode_states(x, lstm_params, lengths, *, t_out):
+    """bilstm_encode(x, lstm_params, lengths, pool=True, t_out=t_out) outside autograd, keeping what the word saliency reads ->
+    (xw [N, T, 8 Hh], pooled, argmax, state).  The input projection runs once WITHOUT the bias (xw = x W_ih^T, the saliency's
+    second operand) and the recurrence reads xproj = xw + (b_ih + b_hh): the MFMA `linear` adds its bias to the finished sum,
+    so pooled has bilstm_encode's bits for the same rows."""
+    w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r = (p.detach() for p in lstm_params)
+    N, T, E = x.shape
+    with torch.no_grad():
+        W = torch.cat([w_ih_f, w_ih_r], dim=0)
+        b = torch.cat([b_ih_f + b_hh_f, b_ih_r + b_hh_r], dim=0)
+        xw = linear(x.detach().reshape(N * T, E), W, None).view(N, T, W.shape[0])
+        pooled, argmax, state = lstm_seq_states(xw + b, w_hh_f, w_hh_r, lengths, t_out)
+    return xw, pooled, argmax, state
+
+
+def bilstm_word_saliency(x, lstm_params, lengths, d_pooled_of, *, t_out):
+    """Gradient x input of every word of x [N, T, E] through bilstm_encode(x, lstm_params, lengths, pool=True, t_out=t_out), for
+    the scalar whose gradient with respect to the pooled vectors the caller supplies: d_pooled_of(pooled [N, 2 Hh]) -> [N, 2 Hh].
+    Returns (pooled, argmax, words [N, T, 2]); words.sum(-1)[n, t] = <d scalar / d x[n, t], x[n, t]>: bilstm_encode_states, the
+    caller's gradient, lstm_seq_word_saliency.  The biases take no share (they are not part of x W_ih^T)."""
+    xw, pooled, argmax, state = bilstm_encode_states(x, lstm_params, lengths, t_out=t_out)
+    words = lstm_seq_word_saliency(state, xw, lstm_params[1], lstm_params[5], lengths, d_pooled_of(pooled), argmax)
+    return pooled, argmax, words

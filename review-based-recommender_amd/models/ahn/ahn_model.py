@@ -115,6 +115,57 @@ class AHN(nn.Module):
         rows = RF.embedding(self.word_embeddings.weight, reviews.reshape(n * r_num * s_num, w_num), self.word_embeddings.padding_idx)
         return self.word_encoder.encode_max(rows, sent_lens.reshape(-1).to(torch.int64), t_out=t_out).view(n, r_num, s_num, self.hidden_dim)
 
+    def word_contributions(self, user_reviews, item_reviews, user_sent_masks, item_sent_masks, user_sent_lengths, item_sent_lenghts,
+                           user_review_masks, item_review_masks, user_ids, item_ids, t_out_user, t_out_item):
+        """forward()'s ten arguments for n pairs plus each side's fixed output length (device int32 [1], as _encode_side takes it)
+        -> (score [n], user_words [n, Ru, Su, W, 2], item_words [n, Ri, Si, W, 2], user_sentences [n, Ru, Su], item_sentences
+        [n, Ri, Si], user_sents [n, Ru, Su, F], item_sents [n, Ri, Si, F]); eval semantics.
+
+        Both sides' sentences are re-encoded with the encoder's state kept (functional.bilstm_encode_states; one batch when the
+        word widths agree, each sentence with its own side's t_out, as in encode_sentences), aggregate() runs under autograd on
+        the DETACHED sentence vectors, pair by pair, and each score is differentiated for d score / d sentence vector of both
+        sides -- the item's through its match AND its own GatedAttention path -- and functional.lstm_seq_word_saliency takes each
+        gradient down to the words: *_words[..., w, d] = <d score / d x_w, x_w> through direction d of the BiLSTM, x_w the
+        word's embedding.  *_sentences = <d score / d sentence vector, sentence vector>."""
+        n, ur_num, us_num, uw_num = user_reviews.shape
+        _, ir_num, is_num, iw_num = item_reviews.shape
+        n_u, n_i = n * ur_num * us_num, n * ir_num * is_num
+        F_ = self.hidden_dim
+        table, pad = self.word_embeddings.weight, self.word_embeddings.padding_idx
+        u_len, i_len = user_sent_lengths.reshape(n_u).to(torch.int64), item_sent_lenghts.reshape(n_i).to(torch.int64)
+        params = self.word_encoder.lstm_params()
+        with RF.eval_mode(self):
+            if uw_num == iw_num:
+                sides = [(torch.cat([user_reviews.reshape(n_u, uw_num), item_reviews.reshape(n_i, iw_num)], dim=0),
+                          torch.cat([u_len, i_len]), torch.cat([t_out_user.expand(n_u), t_out_item.expand(n_i)]))]
+            else:
+                sides = [(user_reviews.reshape(n_u, uw_num), u_len, t_out_user), (item_reviews.reshape(n_i, iw_num), i_len, t_out_item)]
+            enc = [RF.bilstm_encode_states(RF.embedding(table, ids, pad), params, lens, t_out=t_out) for ids, lens, t_out in sides]
+            pooled = torch.cat([e[1] for e in enc], dim=0)
+            xu, xi = pooled[:n_u].view(n, ur_num, us_num, F_), pooled[n_u:].view(n, ir_num, is_num, F_)
+            score, gu, gi = [], [], []
+            with torch.enable_grad():
+                # one pair at a time: torch picks its product kernels by the batch's size, and a pair's bits must not depend on
+                # the pairs explained beside it (the tail is a few hundred rows; the encoder above is the arithmetic)
+                for b in range(n):
+                    s = slice(b, b + 1)
+                    xu_b, xi_b = xu[s].detach().requires_grad_(True), xi[s].detach().requires_grad_(True)
+                    sc = self.aggregate(xu_b, xi_b, user_sent_masks[s], item_sent_masks[s], user_review_masks[s],
+                                        item_review_masks[s], user_ids[s], item_ids[s])[0]
+                    g = torch.autograd.grad(sc.sum(), (xu_b, xi_b))
+                    score.append(sc.detach())
+                    gu.append(g[0])
+                    gi.append(g[1])
+            score, gu, gi = torch.cat(score), torch.cat(gu), torch.cat(gi)
+            d_pooled = torch.cat([gu.reshape(n_u, F_), gi.reshape(n_i, F_)], dim=0)
+            words, a = [], 0
+            for (_, lens, _), (xw, _, argmax, state) in zip(sides, enc):
+                words.append(RF.lstm_seq_word_saliency(state, xw, params[1], params[5], lens, d_pooled[a:a + state.N], argmax))
+                a += state.N
+            words = [words[0][:n_u], words[0][n_u:]] if len(words) == 1 else words
+            return (score, words[0].reshape(n, ur_num, us_num, uw_num, 2), words[1].reshape(n, ir_num, is_num, iw_num, 2),
+                    (gu * xu).sum(-1), (gi * xi).sum(-1), xu, xi)
+
     def _fm_blocks(self):
         """fm.V and fm.lin.weight cut into the four blocks of final_features = [z, e_u, q, e_i]."""
         F_ = self.hidden_dim

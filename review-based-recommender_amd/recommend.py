@@ -39,6 +39,9 @@ the co-attention paired it with -- plus, where meta.pkl's vocabulary is readable
 sentence's words; "item_sentences", the N matched item sentences of largest |match contribution| as [review slot, sentence slot,
 item_sent_weight, match contribution]; "user_reviews" and "item_reviews" as [slot, attention weight, contribution]
 (AhnRecommender.sentences, csrc/ahn_explain.hip: one launch per block of pairs).
+With --words N beside --sentences every entry of "user_sentences" and "item_sentences" ends with the sentence's N words of largest
+|contribution| as [position, word, contribution], the contribution followed through the BiLSTM and everything behind it, the
+item's through its own attention path as well as its matches (AhnRecommender.words, csrc/lstm_seq.hip: the encoder runs again).
 """
 from __future__ import annotations
 
@@ -128,6 +131,18 @@ class SentenceContributions(NamedTuple):
     item_review_match: torch.Tensor       # [B, Ri] the same for the item's reviews
     item_reviews: torch.Tensor            # [B, Ri] the item's own path, its attention weights held constant; sums to item_text
     item_text: torch.Tensor               # [B]
+
+
+class WordContributions(NamedTuple):
+    """AhnRecommender.words: what every WORD of the pairs (u_ids[b], i_ids[b]) adds to AHN's score -- gradient x input of the
+    word's embedding, followed through the BiLSTM, the max over the words and everything behind it (AHN.word_contributions)."""
+    score: torch.Tensor                   # [B] = AhnRecommender.score
+    user_words: torch.Tensor              # [B, Ru, Su, W] = user_words_dir.sum(-1)
+    item_words: torch.Tensor              # [B, Ri, Si, W] through the item's FULL path: as the match of user sentences and its own
+    user_sentences: torch.Tensor          # [B, Ru, Su] <d score / d sentence vector, sentence vector> = sentences().user_sentences
+    item_sentences: torch.Tensor          # [B, Ri, Si] the same for the item's sentences, full path
+    user_words_dir: torch.Tensor          # [B, Ru, Su, W, 2] the split by BiLSTM direction (forward, reverse)
+    item_words_dir: torch.Tensor          # [B, Ri, Si, W, 2]
 
 
 def top_tokens(tokens: torch.Tensor, docs: torch.Tensor, n: int):
@@ -551,6 +566,7 @@ class AhnRecommender:
         self.item_lo = 1                     # the padding id 0 is never recommended
         self.user_state = self.item_state = self.head = None
         self.item_rows = self.explain_head = None      # r' [I, Ri, F] and the FM's q block: what sentences() reads beyond the score's
+        self.t_out = None                    # (user, item): each side's fixed output length, device int32 [1] (words() re-encodes with it)
         self._versions = None
 
     # ------------------------------------------------------------------ the tables
@@ -561,12 +577,13 @@ class AhnRecommender:
             raise ValueError("chunk must be at least 1")
         from . import data as D
         m = self.model
-        states = []
+        states, t_outs = [], []
         with RF.eval_mode(m):
             for docs, n, state_of in ((self.user, self.n_users, m.user_state), (self.item, self.n_items, m.item_state)):
                 if not docs.is_cuda:
                     raise RuntimeError(f"the per-id sentence tables must live on a HIP device (got {docs.device}); there is no CPU path")
                 t_out = RF.lstm_t_out(D.sentence_masks(docs, PAD)[0].reshape(-1), docs.shape[-1])
+                t_outs.append(t_out)
                 fields = None
                 for a in range(0, n, chunk):
                     revs = docs[a:a + chunk].to(torch.int64).contiguous()
@@ -583,6 +600,7 @@ class AhnRecommender:
             self.user_state, self.item_state = states
             self.item_rows = fields[-1]
             self.head, self.explain_head = m.pair_head(), m.explain_head()
+            self.t_out = tuple(t_outs)
         self._versions = [p._version for p in m.parameters()]
         return self
 
@@ -637,6 +655,41 @@ class AhnRecommender:
                                      ex.user_reviews, ex.user_text, ex.user_match.to(torch.int64), ex.review_match.to(torch.int64),
                                      ex.item_sentence_match, ex.item_review_match, ex.item_reviews, ex.item_text)
 
+    def words(self, u_ids: torch.Tensor, i_ids: torch.Tensor, chunk: int = 8) -> WordContributions:
+        """sentences() one level down: what every word of both sides' text adds to the score of the pairs (u_ids[b], i_ids[b]).
+        Unlike sentences() this runs the encoder again: per chunk of pairs the pairs' word ids are gathered from the per-id
+        tables, both sides are re-encoded with the TABLES' own t_out per side (so the sentence vectors are the tables' X), the
+        tail runs under autograd on the detached sentence vectors, and the two sentence gradients go through the recurrence's
+        word-saliency kernel (AHN.word_contributions, functional.lstm_seq_word_saliency; csrc/lstm_seq.hip) -- one launch for
+        both sides when their word widths agree.  The item's words are explained through its full path: as the match of user
+        sentences and through its own attention pooling.  Padding words, masked sentences and masked reviews hold exactly 0.
+
+        NOT attributed: the biases (the LSTM's b_ih + b_hh are no part of x W_ih^T, and the linear layers' and the FM's are no
+        part of any word), the id embeddings, and the dependence of the attention on routing ties -- each max (over the words,
+        and both max-similarities) passes its gradient to the one candidate the forward picked, so where two candidates tie a
+        word's share depends on which was picked, and the zero candidate of the max over the words takes no gradient.
+
+        `chunk` pairs are encoded at a time.  The encoder's state, the bias-free projection and the projection the recurrence
+        reads come to 28 * Hh * W * 4 bytes per sentence ((8 + 2 + 2) Hh floats of state and twice 8 Hh per word): about
+        336 KB per sentence and 67 MB per pair of 200 sentences at the default shape (Hh 150, W 20).  The default of 8 pairs
+        keeps a chunk near half of the 1 GiB that the input projection's operands may span (15 would still fit; the
+        embedded words and the autograd tail need room too)."""
+        if chunk < 1:
+            raise ValueError("chunk must be at least 1")
+        self._tables()
+        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
+            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+        from . import data as D
+        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
+        parts = []
+        for a in range(0, u_ids.shape[0], chunk):
+            pu, pi = u_ids[a:a + chunk], i_ids[a:a + chunk]
+            ur, ir = self.user.index_select(0, pu).to(torch.int64), self.item.index_select(0, pi).to(torch.int64)
+            (ul, usm, urm), (il, ism, irm) = D.sentence_masks(ur, PAD), D.sentence_masks(ir, PAD)
+            parts.append(self.model.word_contributions(ur, ir, usm, ism, ul, il, urm, irm, pu, pi, *self.t_out)[:5])
+        score, uw, iw, us_, is_ = (torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts))
+        return WordContributions(score, uw.sum(-1), iw.sum(-1), us_, is_, uw, iw)
+
     def topk(self, u_ids: torch.Tensor, k: int, exclude=None):
         """Recommender.topk over score_all's block (select_topk)."""
         scores = self.score_all(u_ids)
@@ -687,6 +740,8 @@ def parse_cli(argv=None):
     ap.add_argument("--sentences", type=int, metavar="N", help="with --out: add \"why\" to every line, the N weightiest user sentences "
                     "behind each recommended item with the item sentence each matched, the matched item sentences and both sides' "
                     "reviews; ahn only")
+    ap.add_argument("--words", type=int, metavar="N", help="with --sentences: every user and item sentence of \"why\" also carries "
+                    "its N weightiest words with their contributions, followed through the BiLSTM; ahn only")
     ap.add_argument("--chunk", type=int, default=256, help="ids encoded / users ranked per launch")
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--reference-quirks", action="store_true", help="as for the trainer: kernel_sizes=[3] (NARRE hidden_dim=150)")
@@ -723,6 +778,13 @@ def parse_cli(argv=None):
             ap.error("--sentences adds to the lines of --out: give --out")
         if a.model != "ahn":
             ap.error("--sentences covers ahn (deepconn and narre: --explain, dual_att: --attention, simple_siamese: --contributions)")
+    if a.words is not None:
+        if a.words < 1:
+            ap.error("--words must be at least 1")
+        if a.model != "ahn":
+            ap.error("--words covers ahn (it adds to --sentences)")
+        if a.sentences is None:
+            ap.error("--words adds to the sentences of --sentences: give --sentences")
     if a.eval_split is None:
         if a.out is None:
             ap.error("--out is required unless --eval-split is given")
@@ -844,12 +906,14 @@ def _why_contributions(rec, u_ids, items, n, words):
     return why
 
 
-def _why_sentences(rec, u_ids, items, n, words):
+def _why_sentences(rec, u_ids, items, n, words, n_words=None):
     """The "why" lists of --sentences for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per item
     the n user sentences of largest |contribution| as [review slot, sentence slot, weight, contribution, matched item review
     slot, matched item sentence slot] (with a vocabulary: + the sentence's words and the matched item sentence's words, token 0
     dropped), the n matched item sentences of largest |match contribution| as [review slot, sentence slot, item_sent_weight,
-    match contribution], and both sides' n reviews of largest |contribution| as [slot, weight, contribution]."""
+    match contribution], and both sides' n reviews of largest |contribution| as [slot, weight, contribution].  With n_words
+    (--words) every user and item sentence entry ends with its n_words words of largest |contribution| as [position, word,
+    contribution] (AhnRecommender.words; the item's through its full path), zeros dropped."""
     dev = u_ids.device
     keep = items >= 0
     rows, cols = keep.nonzero(as_tuple=True)
@@ -868,24 +932,44 @@ def _why_sentences(rec, u_ids, items, n, words):
         picked = torch.gather(sents, 1, pos.view(*pos.shape, 1).expand(-1, -1, sents.shape[-1])).cpu()
         return [[[words.get(int(t), int(t)) for t in s if int(t) != PAD] for s in row] for row in picked.tolist()]
 
+    wc = rec.words(pu, pi) if n_words is not None else None
+    word = (lambda t: words.get(int(t), int(t))) if words else int
+
+    def top_words(contrib, table, ids, pos):
+        """per pair and picked sentence (pos: flat sentence slots [P, n']) its n_words weightiest words"""
+        if wc is None:
+            return None
+        width = contrib.shape[-1]
+        at = pos.view(*pos.shape, 1).expand(-1, -1, width)
+        c = torch.gather(contrib.reshape(contrib.shape[0], -1, width), 1, at)
+        toks = torch.gather(table.index_select(0, ids).to(torch.int64).reshape(contrib.shape[0], -1, width), 1, at)
+        t = c.abs().topk(min(n_words, width), dim=-1).indices
+        c, toks, t = torch.gather(c, 2, t).cpu().tolist(), torch.gather(toks, 2, t).cpu().tolist(), t.cpu().tolist()
+        return [[[[q, word(k), v] for q, k, v in zip(*sent) if v != 0.0] for sent in zip(*row)] for row in zip(t, toks, c)]
+
     pos, wgt, x = top_tokens(sc.user_sentences, sc.user_sent_weights, n)
     hit = torch.gather(sc.user_match.reshape(pos.shape[0], -1), 1, pos)
     uw, iw = sent_words(rec.user, pu, pos), sent_words(rec.item, pi, hit)
+    utop = top_words(wc.user_words, rec.user, pu, pos) if wc is not None else None
     pos, wgt, x, hit = pos.cpu(), wgt.cpu(), x.cpu(), hit.cpu()
     us = []
     for p in range(pos.shape[0]):
         row = []
         for k, (q, a, c, h) in enumerate(zip(pos[p].tolist(), wgt[p].tolist(), x[p].tolist(), hit[p].tolist())):
             if c != 0.0:
-                row.append([q // Su, q % Su, a, c, h // Si, h % Si] + ([uw[p][k], iw[p][k]] if words else []))
+                row.append([q // Su, q % Su, a, c, h // Si, h % Si] + ([uw[p][k], iw[p][k]] if words else [])
+                           + ([utop[p][k]] if utop is not None else []))
         us.append(row)
 
-    def tops(contrib, weights, width=None):
-        q, a, c = (t.cpu() for t in top_tokens(contrib, weights, n))
+    def tops(contrib, weights, width=None, word_table=None):
+        q, a, c = top_tokens(contrib, weights, n)
+        top = top_words(wc.item_words, word_table, pi, q) if word_table is not None and wc is not None else None
+        q, a, c = q.cpu().tolist(), a.cpu().tolist(), c.cpu().tolist()
         slot = (lambda s: [s]) if width is None else (lambda s: [s // width, s % width])
-        return [[slot(s) + [w, v] for s, w, v in zip(*r) if v != 0.0] for r in zip(q.tolist(), a.tolist(), c.tolist())]
+        return [[slot(s) + [w, v] + ([top[p][k]] if top is not None else []) for k, (s, w, v) in enumerate(zip(*r)) if v != 0.0]
+                for p, r in enumerate(zip(q, a, c))]
 
-    isent = tops(sc.item_sentence_match, sc.item_sent_weights, Si)
+    isent = tops(sc.item_sentence_match, sc.item_sent_weights, Si, rec.item)
     ur, ir = tops(sc.user_reviews, sc.user_review_weights), tops(sc.item_reviews, sc.item_review_weights)
     slot_of = keep.cumsum(1) - 1
     for p, (r, k) in enumerate(zip(rows.tolist(), cols.tolist())):
@@ -935,7 +1019,7 @@ def main(argv=None) -> int:
                 if a.contributions is not None:
                     why = _why_contributions(rec, u_ids, items, a.contributions, words)
                 if a.sentences is not None:
-                    why = _why_sentences(rec, u_ids, items, a.sentences, words)
+                    why = _why_sentences(rec, u_ids, items, a.sentences, words, a.words)
                 for r, u in enumerate(u_ids.tolist()):
                     keep = items[r] >= 0
                     line = {"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}
