@@ -193,6 +193,46 @@ def rank_metrics(rank: torch.Tensor, n_cand: torch.Tensor, ks) -> dict:
     return out
 
 
+def _check_pairs(u_ids, i_ids, chunk, tables=None):
+    """The pair arguments of explain / attention / contributions / sentences / words: chunk >= 1 and two id vectors [B], B >= 1.
+    `tables` (AhnRecommender._tables) runs between the two checks: AHN's entry points report missing tables before a bad shape."""
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    if tables is not None:
+        tables()
+    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
+        raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+
+
+def _cat_chunks(parts, empty=None):
+    """The columns of the per-chunk result tuples `parts`, each concatenated over the chunks; a single chunk's columns are
+    returned as they are (no launch), and no chunk at all gives `empty`."""
+    if not parts:
+        return empty
+    return [torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts)]
+
+
+def _evaluate(rec, pairs, ks, exclude, chunk) -> dict:
+    """Recommender.evaluate and AhnRecommender.evaluate: rec.rank over `chunk` pairs at a time, one rank_metrics call."""
+    if chunk < 1:
+        raise ValueError("chunk must be at least 1")
+    dev = rec._device()
+    if len(pairs) == 2 and all(torch.is_tensor(t) for t in pairs):
+        u_ids, i_ids = (t.to(dev, torch.int64) for t in pairs)
+    else:
+        u_ids = torch.tensor([int(e[0]) for e in pairs], dtype=torch.int64, device=dev)
+        i_ids = torch.tensor([int(e[1]) for e in pairs], dtype=torch.int64, device=dev)
+    parts = [rec.rank(u_ids[a:a + chunk], i_ids[a:a + chunk], exclude) for a in range(0, u_ids.shape[0], chunk)]
+    rank, n_cand = _cat_chunks(parts, empty=[torch.empty(0, dtype=torch.int32, device=dev)] * 2)
+    return rank_metrics(rank, n_cand, ks)
+
+
+# what each tower's explain_* / attend_* / contribute_* returns per side: the result's field names less user_ / item_
+_SIDE_FIELDS = {"deepconn": ("tokens", "text"), "narre": ("tokens", "text", "review_weights", "reviews"),
+                "dual_att": ("local_gate", "global_gate", "tokens", "tokens_fixed", "local_text", "global_text"),
+                "simple_siamese": ("tokens", "tokens_fixed", "text", "review_weights", "reviews")}
+
+
 class Recommender:
     """Latent tables of a trained model over a whole catalogue, and the queries on them.
 
@@ -227,19 +267,23 @@ class Recommender:
         self._versions = None
 
     # ------------------------------------------------------------------ the tables
-    def _encode(self, side: str, a: int, b: int) -> torch.Tensor:
-        c, m = self.cache, self.model
-        docs = (c.user if side == "user" else c.item)[a:b].to(torch.int64).contiguous()
-        ids = torch.arange(a, b, dtype=torch.int64, device=docs.device)
-        enc = m.encode_users if side == "user" else m.encode_items
-        if self.kind == "deepconn":
-            return enc(docs, docs != PAD, ids)
+    def _tower_args(self, side: str, ids: torch.Tensor, take):
+        """The positional arguments this kind's towers read for the ids `ids` of a side; `take` selects those ids' rows from a
+        cache table (refresh: a slice, the pair driver: a gather)."""
+        c = self.cache
+        docs = take(getattr(c, side)).to(torch.int64).contiguous()
         if self.kind == "dual_att":
-            return enc(docs)
-        if self.kind == "narre":
-            return enc(docs, docs != PAD, ids, (c.user_rids if side == "user" else c.item_rids)[a:b])
+            return (docs,)
         word_masks = docs != PAD
-        return enc(docs, word_masks, word_masks.any(-1), ids)      # review masks: the reviews that hold any token
+        if self.kind == "deepconn":
+            return docs, word_masks, ids
+        if self.kind == "narre":
+            return docs, word_masks, ids, take(getattr(c, f"{side}_rids"))
+        return docs, word_masks, word_masks.any(-1), ids           # review masks: the reviews that hold any token
+
+    def _encode(self, side: str, a: int, b: int) -> torch.Tensor:
+        ids = torch.arange(a, b, dtype=torch.int64, device=getattr(self.cache, side).device)
+        return getattr(self.model, f"encode_{side}s")(*self._tower_args(side, ids, lambda t: t[a:b]))
 
     def refresh(self, chunk: int = 256) -> "Recommender":
         """Encodes all users and all items, `chunk` ids at a time, into the latent tables (eval semantics, no autograd; the
@@ -314,15 +358,30 @@ class Recommender:
             exclude = (exclude.off, exclude.items, u_ids)
         return RF.pair_score_rank(mode, rows, il, i_ids, h, g, ub_rows, ib, item_lo=self.item_lo, exclude=exclude)
 
-    def _explain_side(self, side: str, ids: torch.Tensor, d_latent: torch.Tensor):
-        """The model's explain_users / explain_items on the cache rows of `ids` (checked ids), read as _encode reads them."""
-        c, m = self.cache, self.model
-        docs = (c.user if side == "user" else c.item).index_select(0, ids).to(torch.int64).contiguous()
-        fn = m.explain_users if side == "user" else m.explain_items
-        if self.kind == "deepconn":
-            return fn(docs, docs != PAD, ids, d_latent)
-        rids = (c.user_rids if side == "user" else c.item_rids).index_select(0, ids)
-        return fn(docs, docs != PAD, ids, rids, d_latent)
+    def _explain_pairs(self, result, verb: str, u_ids: torch.Tensor, i_ids: torch.Tensor, chunk: int):
+        """The driver of explain / attention / contributions: the score, the head's gradient on both latent rows, and per chunk
+        of pairs the towers' `verb`_users / `verb`_items on the pairs' cache rows, read as _encode reads them; `result` is
+        built by field name from the towers' _SIDE_FIELDS."""
+        _check_pairs(u_ids, i_ids, chunk)
+        ul, il = self._tables()
+        mode, h, _, _, _ = self.model.score_mode_and_params()
+        score = self.score(u_ids, i_ids)
+        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
+        with torch.no_grad():
+            zu, zi = RF.embedding(ul, u_ids, None), RF.embedding(il, i_ids, None)
+            if mode == "fm":                 # score = relu(zu * zi) . h + biases
+                live = h.detach().view(1, -1) * (zu * zi > 0)
+                d_u, d_i = live * zi, live * zu
+            else:                            # the inner product: each side's gradient is the other side's row
+                d_u, d_i = zi, zu
+
+        def tower(side, ids, d_latent):
+            return getattr(self.model, f"{verb}_{side}s")(*self._tower_args(side, ids, lambda t: t.index_select(0, ids)), d_latent)
+
+        cols = _cat_chunks([tower("user", u_ids[a:a + chunk], d_u[a:a + chunk]) + tower("item", i_ids[a:a + chunk], d_i[a:a + chunk])
+                            for a in range(0, u_ids.shape[0], chunk)])
+        names = [f"{side}_{field}" for side in ("user", "item") for field in _SIDE_FIELDS[self.kind]]
+        return result(score=score, **dict(zip(names, cols)))
 
     def explain(self, u_ids: torch.Tensor, i_ids: torch.Tensor, chunk: int = 256) -> Explanation:
         """Why the pairs (u_ids[b], i_ids[b]) scored as they did (DeepCoNN++ and NARRE, CNN arch), `chunk` pairs at a time, from
@@ -334,28 +393,7 @@ class Recommender:
         part of the score no text explains."""
         if self.kind not in ("deepconn", "narre"):
             raise ValueError(f"Recommender.explain covers DeepCoNN++ and NARRE with arch='CNN'; {type(self.model).__name__} is not covered")
-        if chunk < 1:
-            raise ValueError("chunk must be at least 1")
-        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
-            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
-        ul, il = self._tables()
-        _, h, _, _, _ =self.model.score_mode_and_params()
-        score = self.score(u_ids, i_ids)
-        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
-        with torch.no_grad():
-            zu, zi = RF.embedding(ul, u_ids, None), RF.embedding(il, i_ids, None)
-            live = h.detach().view(1, -1) * (zu * zi > 0)
-            d_u, d_i = live * zi, live * zu
-        parts = []
-        for a in range(0, u_ids.shape[0], chunk):
-            parts.append(self._explain_side("user", u_ids[a:a + chunk], d_u[a:a + chunk]) +
-                         self._explain_side("item", i_ids[a:a + chunk], d_i[a:a + chunk]))
-        cols = [torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts)]
-        if self.kind == "deepconn":
-            ut, ux, it, ix = cols
-            return Explanation(score, ut, it, ux, ix)
-        ut, ux, ua, ur, it, ix, ia, ir = cols
-        return Explanation(score, ut, it, ux, ix, ua, ur, ia, ir)
+        return self._explain_pairs(Explanation, "explain", u_ids, i_ids, chunk)
 
     def attention(self, u_ids: torch.Tensor, i_ids: torch.Tensor, chunk: int = 256) -> Attention:
         """D-ATT's answer to "why": both attention gates of each side of the pairs (u_ids[b], i_ids[b]) and the per-token
@@ -366,22 +404,7 @@ class Recommender:
         if self.kind != "dual_att":
             raise ValueError(f"Recommender.attention covers D-ATT (DualAtt); {type(self.model).__name__} is not covered "
                              "(DeepCoNN++ and NARRE: Recommender.explain)")
-        if chunk < 1:
-            raise ValueError("chunk must be at least 1")
-        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
-            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
-        ul, il = self._tables()
-        score = self.score(u_ids, i_ids)
-        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
-        with torch.no_grad():
-            d_i, d_u = RF.embedding(ul, u_ids, None), RF.embedding(il, i_ids, None)
-        c, m = self.cache, self.model
-        parts = []
-        for a in range(0, u_ids.shape[0], chunk):
-            u_docs = c.user.index_select(0, u_ids[a:a + chunk]).to(torch.int64).contiguous()
-            i_docs = c.item.index_select(0, i_ids[a:a + chunk]).to(torch.int64).contiguous()
-            parts.append(m.attend_users(u_docs, d_u[a:a + chunk]) + m.attend_items(i_docs, d_i[a:a + chunk]))
-        return Attention(score, *(torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts)))
+        return self._explain_pairs(Attention, "attend", u_ids, i_ids, chunk)
 
     def contributions(self, u_ids: torch.Tensor, i_ids: torch.Tensor, chunk: int = 256) -> Contributions:
         """SimpleSiamese's answer to "why": per-token and per-review contributions of each side of the pairs (u_ids[b],
@@ -392,47 +415,16 @@ class Recommender:
         if self.kind != "simple_siamese":
             raise ValueError(f"Recommender.contributions covers SimpleSiamese; {type(self.model).__name__} is not covered "
                              "(DeepCoNN++ and NARRE: Recommender.explain, D-ATT: Recommender.attention)")
-        if chunk < 1:
-            raise ValueError("chunk must be at least 1")
-        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
-            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
-        ul, il = self._tables()
-        _, h, _, _, _ = self.model.score_mode_and_params()
-        score = self.score(u_ids, i_ids)
-        u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
-        with torch.no_grad():
-            zu, zi = RF.embedding(ul, u_ids, None), RF.embedding(il, i_ids, None)
-            live = h.detach().view(1, -1) * (zu * zi > 0)
-            d_u, d_i = live * zi, live * zu
-        c, m = self.cache, self.model
-        parts = []
-        for a in range(0, u_ids.shape[0], chunk):
-            side = []
-            for docs, ids, d, fn in ((c.user, u_ids[a:a + chunk], d_u[a:a + chunk], m.contribute_users),
-                                     (c.item, i_ids[a:a + chunk], d_i[a:a + chunk], m.contribute_items)):
-                revs = docs.index_select(0, ids).to(torch.int64).contiguous()
-                word_masks = revs != PAD
-                side.append(fn(revs, word_masks, word_masks.any(-1), ids, d))     # masks as _encode derives them
-            parts.append(side[0] + side[1])
-        ut, uf, ux, ua, ur, it, if_, ix, ia, ir = (torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts))
-        return Contributions(score, ut, it, uf, if_, ux, ix, ua, ur, ia, ir)
+        return self._explain_pairs(Contributions, "contribute", u_ids, i_ids, chunk)
+
+    def _device(self):
+        return self._tables()[0].device
 
     def evaluate(self, pairs, ks=(5, 10, 20), exclude=None, chunk: int = 4096) -> dict:
         """rank_metrics of held-out pairs: `pairs` is a dataset's examples (sequences starting (u_id, i_id, ...)) or the id
         tensors (u_ids, i_ids) themselves.  Ranked `chunk` pairs at a time, one rank_metrics call over all of them; `exclude`: a
         SeenItems (the CLI's --exclude-train: the training split's seen_from) or None."""
-        if chunk < 1:
-            raise ValueError("chunk must be at least 1")
-        dev = self._tables()[0].device
-        if len(pairs) == 2 and all(torch.is_tensor(t) for t in pairs):
-            u_ids, i_ids = (t.to(dev, torch.int64) for t in pairs)
-        else:
-            u_ids = torch.tensor([int(e[0]) for e in pairs], dtype=torch.int64, device=dev)
-            i_ids = torch.tensor([int(e[1]) for e in pairs], dtype=torch.int64, device=dev)
-        parts = [self.rank(u_ids[a:a + chunk], i_ids[a:a + chunk], exclude) for a in range(0, u_ids.shape[0], chunk)]
-        rank = torch.cat([p[0] for p in parts]) if parts else torch.empty(0, dtype=torch.int32, device=dev)
-        n_cand = torch.cat([p[1] for p in parts]) if parts else torch.empty(0, dtype=torch.int32, device=dev)
-        return rank_metrics(rank, n_cand, ks)
+        return _evaluate(self, pairs, ks, exclude, chunk)
 
     @staticmethod
     def seen_from(examples, n_users: int, device=None) -> SeenItems:
@@ -612,6 +604,9 @@ class AhnRecommender:
             raise RuntimeError("AhnRecommender.refresh() has not been called: there are no sentence tables yet")
         return self.user_state, self.item_state, self.head
 
+    def _device(self):
+        return self._tables()[0].X.device
+
     # ------------------------------------------------------------------ the queries
     def score(self, u_ids: torch.Tensor, i_ids: torch.Tensor) -> torch.Tensor:
         """Predicted ratings [B] of the pairs (u_ids[b], i_ids[b]): the pair tail over the tables, one launch."""
@@ -641,15 +636,12 @@ class AhnRecommender:
         which item review each user review, what the matched item sentences / reviews add through that match, and the item's own
         reviews under its own weights (held constant, as NARRE's are in Recommender.explain).  The id embeddings and the biases
         are the part of the score no text explains; no encoder runs and no autograd."""
-        if chunk < 1:
-            raise ValueError("chunk must be at least 1")
+        _check_pairs(u_ids, i_ids, chunk, self._tables)
         us, its, head = self._tables()
-        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
-            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
         u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
         extra = RF.AhnExplainRows(self.item_rows, *self.explain_head)
-        parts = [RF.ahn_pair_explain(us, its, head, extra, u_ids[a:a + chunk], i_ids[a:a + chunk]) for a in range(0, u_ids.shape[0], chunk)]
-        ex = RF.AhnPairExplanation(*(torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts)))
+        ex = RF.AhnPairExplanation(*_cat_chunks([RF.ahn_pair_explain(us, its, head, extra, u_ids[a:a + chunk], i_ids[a:a + chunk])
+                                                 for a in range(0, u_ids.shape[0], chunk)]))
         return SentenceContributions(ex.score, ex.user_sent_weights, its.item_sent_weights.index_select(0, i_ids), ex.user_review_weights,
                                      its.item_review_weights.index_select(0, i_ids), ex.user_sentences, ex.user_sentences_fixed,
                                      ex.user_reviews, ex.user_text, ex.user_match.to(torch.int64), ex.review_match.to(torch.int64),
@@ -674,11 +666,7 @@ class AhnRecommender:
         336 KB per sentence and 67 MB per pair of 200 sentences at the default shape (Hh 150, W 20).  The default of 8 pairs
         keeps a chunk near half of the 1 GiB that the input projection's operands may span (15 would still fit; the
         embedded words and the autograd tail need room too)."""
-        if chunk < 1:
-            raise ValueError("chunk must be at least 1")
-        self._tables()
-        if u_ids.dim() != 1 or u_ids.shape != i_ids.shape or u_ids.shape[0] == 0:
-            raise ValueError(f"u_ids / i_ids must be [B] each with B >= 1, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+        _check_pairs(u_ids, i_ids, chunk, self._tables)
         from . import data as D
         u_ids, i_ids = RF.sanitize_ids([(u_ids, self.n_users, PAD), (i_ids, self.n_items, PAD)])
         parts = []
@@ -687,7 +675,7 @@ class AhnRecommender:
             ur, ir = self.user.index_select(0, pu).to(torch.int64), self.item.index_select(0, pi).to(torch.int64)
             (ul, usm, urm), (il, ism, irm) = D.sentence_masks(ur, PAD), D.sentence_masks(ir, PAD)
             parts.append(self.model.word_contributions(ur, ir, usm, ism, ul, il, urm, irm, pu, pi, *self.t_out)[:5])
-        score, uw, iw, us_, is_ = (torch.cat(col) if len(parts) > 1 else col[0] for col in zip(*parts))
+        score, uw, iw, us_, is_ = _cat_chunks(parts)
         return WordContributions(score, uw.sum(-1), iw.sum(-1), us_, is_, uw, iw)
 
     def topk(self, u_ids: torch.Tensor, k: int, exclude=None):
@@ -704,21 +692,158 @@ class AhnRecommender:
 
     def evaluate(self, pairs, ks=(5, 10, 20), exclude=None, chunk: int = 256) -> dict:
         """Recommender.evaluate: rank_metrics of held-out pairs, ranked `chunk` pairs (chunk x I scores) at a time."""
-        if chunk < 1:
-            raise ValueError("chunk must be at least 1")
-        dev = self._tables()[0].X.device
-        if len(pairs) == 2 and all(torch.is_tensor(t) for t in pairs):
-            u_ids, i_ids = (t.to(dev, torch.int64) for t in pairs)
-        else:
-            u_ids = torch.tensor([int(e[0]) for e in pairs], dtype=torch.int64, device=dev)
-            i_ids = torch.tensor([int(e[1]) for e in pairs], dtype=torch.int64, device=dev)
-        parts = [self.rank(u_ids[a:a + chunk], i_ids[a:a + chunk], exclude) for a in range(0, u_ids.shape[0], chunk)]
-        rank = torch.cat([p[0] for p in parts]) if parts else torch.empty(0, dtype=torch.int32, device=dev)
-        n_cand = torch.cat([p[1] for p in parts]) if parts else torch.empty(0, dtype=torch.int32, device=dev)
-        return rank_metrics(rank, n_cand, ks)
+        return _evaluate(self, pairs, ks, exclude, chunk)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the "why" lists
+def _vocabulary(data_dir):
+    """token id -> word from meta.pkl's indexlizer (_vocab._token2id), or None where it cannot be read."""
+    from . import data as D
+    try:
+        ix = D.load_pickle(os.path.join(data_dir, "meta.pkl"))["indexlizer"]
+        t2i = getattr(getattr(ix, "_vocab", ix), "_token2id", None)
+        return {int(i): str(t) for t, i in t2i.items()} if isinstance(t2i, dict) else None
+    except Exception:
+        return None
+
+
+def _kept_pairs(u_ids, items):
+    """For the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): the kept pairs (pu, pi) on u_ids' device,
+    each pair's place (row, slot) in the output, and the empty "why" skeleton -- per user one None per kept item."""
+    keep = items >= 0
+    rows, cols = keep.nonzero(as_tuple=True)
+    why = [[None] * int(keep[r].sum()) for r in range(items.shape[0])]
+    places = list(zip(rows.tolist(), (keep.cumsum(1) - 1)[rows, cols].tolist()))
+    return u_ids[rows.to(u_ids.device)], items[rows, cols].to(u_ids.device), places, why
+
+
+def _fill(why, places, **cols):
+    """Writes one entry per pair, {name: cols[name][p]}, to the pair's place in the skeleton."""
+    for p, (r, slot) in enumerate(places):
+        why[r][slot] = {name: col[p] for name, col in cols.items()}
+    return why
+
+
+def _entries(top, word=None, mid=(), tail=(), width=None):
+    """The JSON entries of every pair from top_tokens' (position, id, weight) [P, n']: per kept position
+    [position] + [id] + mid + [weight] + tail, entries of weight 0.0 dropped.  width: the position splits into [position //
+    width, position % width]; word: id -> what stands for it; mid / tail: further columns [P, n'], tensors or nested lists."""
+    pos, ids, weight = (t.cpu().tolist() for t in top)
+    mid, tail = ([c.cpu().tolist() if torch.is_tensor(c) else c for c in cols] for cols in (mid, tail))
+    place = (lambda q: [q]) if width is None else (lambda q: [q // width, q % width])
+    return [[place(q) + [word(t) if word else t] + [c[p][k] for c in mid] + [x] + [c[p][k] for c in tail]
+             for k, (q, t, x) in enumerate(zip(pos[p], ids[p], weight[p])) if x != 0.0] for p in range(len(pos))]
+
+
+def _word_of(words):
+    return (lambda t: words.get(t, t)) if words else None
+
+
+def _token_entries(tokens, table, ids, n, words, gate=None):
+    """Per pair the n tokens of largest |weight| as [position, word, weight] (+ [gate at the position])."""
+    top = top_tokens(tokens, table.index_select(0, ids).to(torch.int64), n)
+    return _entries(top, _word_of(words), tail=() if gate is None else [torch.gather(gate, 1, top[0])])
+
+
+def _review_entries(contrib, att, rids, ids, n):
+    """Per pair the n reviews of largest |contribution| as [slot, counterpart id (-1 where the cache has none), attention,
+    contribution]."""
+    rid = rids.index_select(0, ids).to(torch.int64) if rids is not None else torch.full_like(contrib, -1, dtype=torch.int64)
+    top = top_tokens(contrib, rid, n)
+    return _entries(top, mid=[torch.gather(att, 1, top[0])])
+
+
+def _why(rec, u_ids, items, n, words):
+    """The "why" lists of --explain for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill)."""
+    pu, pi, places, why = _kept_pairs(u_ids, items)
+    if not places:
+        return why
+    ex, c = rec.explain(pu, pi), rec.cache
+    cols = {"user_tokens": _token_entries(ex.user_tokens, c.user, pu, n, words),
+            "item_tokens": _token_entries(ex.item_tokens, c.item, pi, n, words)}
+    if ex.item_reviews is not None:
+        cols["item_reviews"] = _review_entries(ex.item_reviews, ex.item_review_weights, c.item_rids, pi, n)
+    return _fill(why, places, **cols)
+
+
+def _why_attention(rec, u_ids, items, n, words):
+    """The "why" lists of --attention for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per item
+    the n entries of largest |tokens| on each side as [position, word, weight, local_gate]."""
+    pu, pi, places, why = _kept_pairs(u_ids, items)
+    if not places:
+        return why
+    at, c = rec.attention(pu, pi), rec.cache
+    return _fill(why, places, user_tokens=_token_entries(at.user_tokens, c.user, pu, n, words, at.user_local_gate),
+                 item_tokens=_token_entries(at.item_tokens, c.item, pi, n, words, at.item_local_gate),
+                 user_global_gate=at.user_global_gate.cpu().tolist(), item_global_gate=at.item_global_gate.cpu().tolist())
+
+
+def _why_contributions(rec, u_ids, items, n, words):
+    """The "why" lists of --contributions for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per
+    item and side the n tokens of largest |weight| as [slot-major position, word, weight] and the n reviews of largest
+    |contribution| as [slot, counterpart id (-1 where the cache has none), attention, contribution]."""
+    pu, pi, places, why = _kept_pairs(u_ids, items)
+    if not places:
+        return why
+    co, c = rec.contributions(pu, pi), rec.cache
+    return _fill(why, places, user_tokens=_token_entries(co.user_tokens, c.user, pu, n, words),
+                 item_tokens=_token_entries(co.item_tokens, c.item, pi, n, words),
+                 user_reviews=_review_entries(co.user_reviews, co.user_review_weights, getattr(c, "user_rids", None), pu, n),
+                 item_reviews=_review_entries(co.item_reviews, co.item_review_weights, getattr(c, "item_rids", None), pi, n))
+
+
+def _why_sentences(rec, u_ids, items, n, words, n_words=None):
+    """The "why" lists of --sentences for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per item
+    the n user sentences of largest |contribution| as [review slot, sentence slot, weight, contribution, matched item review
+    slot, matched item sentence slot] (with a vocabulary: + the sentence's words and the matched item sentence's words, token 0
+    dropped), the n matched item sentences of largest |match contribution| as [review slot, sentence slot, item_sent_weight,
+    match contribution], and both sides' n reviews of largest |contribution| as [slot, weight, contribution].  With n_words
+    (--words) every user and item sentence entry ends with its n_words words of largest |contribution| as [position, word,
+    contribution] (AhnRecommender.words; the item's through its full path), zeros dropped."""
+    pu, pi, places, why = _kept_pairs(u_ids, items)
+    if not places:
+        return why
+    sc = rec.sentences(pu, pi)
+    wc = rec.words(pu, pi) if n_words is not None else None
+    Su, Si = sc.user_sentences.shape[2], sc.item_sentence_match.shape[2]
+
+    def picked(t, pos):
+        """the rows [P, n', width] of the flat sentence slots pos [P, n'] out of t [P, R, S, width]"""
+        return torch.gather(t.reshape(t.shape[0], -1, t.shape[-1]), 1, pos.view(*pos.shape, 1).expand(-1, -1, t.shape[-1]))
+
+    def sent_words(table, ids, pos):
+        """per pair and picked sentence its words, token 0 dropped"""
+        sents = picked(table.index_select(0, ids).to(torch.int64), pos).cpu().tolist()
+        return [[[words.get(t, t) for t in s if t != PAD] for s in row] for row in sents]
+
+    def top_words(contrib, table, ids, pos):
+        """per pair and picked sentence its n_words weightiest words as [position, word, contribution]"""
+        c, toks = picked(contrib, pos), picked(table.index_select(0, ids).to(torch.int64), pos)
+        t = c.abs().topk(min(n_words, c.shape[-1]), dim=-1).indices
+        flat = _entries([x.flatten(0, 1) for x in (t, torch.gather(toks, 2, t), torch.gather(c, 2, t))], _word_of(words))
+        return [flat[p * pos.shape[1]:(p + 1) * pos.shape[1]] for p in range(pos.shape[0])]
+
+    top = top_tokens(sc.user_sentences, sc.user_sent_weights, n)
+    hit = torch.gather(sc.user_match.reshape(top[0].shape[0], -1), 1, top[0])                 # the matched flat item sentence
+    tail = [hit.cpu() // Si, hit.cpu() % Si]
+    if words:
+        tail += [sent_words(rec.user, pu, top[0]), sent_words(rec.item, pi, hit)]
+    if wc is not None:
+        tail.append(top_words(wc.user_words, rec.user, pu, top[0]))
+    user_sentences = _entries(top, width=Su, tail=tail)
+    top = top_tokens(sc.item_sentence_match, sc.item_sent_weights, n)
+    item_sentences = _entries(top, width=Si, tail=[top_words(wc.item_words, rec.item, pi, top[0])] if wc is not None else ())
+    return _fill(why, places, user_sentences=user_sentences,
+                 user_reviews=_entries(top_tokens(sc.user_reviews, sc.user_review_weights, n)), item_sentences=item_sentences,
+                 item_reviews=_entries(top_tokens(sc.item_reviews, sc.item_review_weights, n)))
 
 
 # ---------------------------------------------------------------------------------------------------------------- CLI
+# the flags that add "why" to every line of --out: the models each covers, and the function of its lists
+_WHY_FLAGS = {"explain": (("deepconn", "narre"), _why), "attention": (("dual_att",), _why_attention),
+              "contributions": (("simple_siamese",), _why_contributions), "sentences": (("ahn",), _why_sentences)}
+
+
 def parse_cli(argv=None):
     ap = argparse.ArgumentParser(prog="python -m review_based_recommender_amd.recommend",
                                  description="top-K recommendations of a trained model for every user of its dataset")
@@ -750,34 +875,15 @@ def parse_cli(argv=None):
         ap.error("--k must be in 1..128")
     if a.chunk < 1:
         ap.error("--chunk must be at least 1")
-    if a.explain is not None:
-        if a.explain < 1:
-            ap.error("--explain must be at least 1")
+    for flag, (models, _) in _WHY_FLAGS.items():
+        if getattr(a, flag) is None:
+            continue
+        if getattr(a, flag) < 1:
+            ap.error(f"--{flag} must be at least 1")
         if a.out is None:
-            ap.error("--explain adds to the lines of --out: give --out")
-        if a.model not in ("deepconn", "narre"):
-            ap.error("--explain covers deepconn and narre")
-    if a.attention is not None:
-        if a.attention < 1:
-            ap.error("--attention must be at least 1")
-        if a.out is None:
-            ap.error("--attention adds to the lines of --out: give --out")
-        if a.model != "dual_att":
-            ap.error("--attention covers dual_att (deepconn and narre: --explain)")
-    if a.contributions is not None:
-        if a.contributions < 1:
-            ap.error("--contributions must be at least 1")
-        if a.out is None:
-            ap.error("--contributions adds to the lines of --out: give --out")
-        if a.model != "simple_siamese":
-            ap.error("--contributions covers simple_siamese (deepconn and narre: --explain, dual_att: --attention)")
-    if a.sentences is not None:
-        if a.sentences < 1:
-            ap.error("--sentences must be at least 1")
-        if a.out is None:
-            ap.error("--sentences adds to the lines of --out: give --out")
-        if a.model != "ahn":
-            ap.error("--sentences covers ahn (deepconn and narre: --explain, dual_att: --attention, simple_siamese: --contributions)")
+            ap.error(f"--{flag} adds to the lines of --out: give --out")
+        if a.model not in models:
+            ap.error(f"--{flag} covers {' and '.join(models)} ({a.model}: --{next(f for f, (m, _) in _WHY_FLAGS.items() if a.model in m)})")
     if a.words is not None:
         if a.words < 1:
             ap.error("--words must be at least 1")
@@ -797,184 +903,6 @@ def parse_cli(argv=None):
     if any(not 1 <= k < 2 ** 31 for k in a.ks):
         ap.error("every K of --ks must be in 1..2^31-1")
     return a
-
-
-def _vocabulary(data_dir):
-    """token id -> word from meta.pkl's indexlizer (_vocab._token2id), or None where it cannot be read."""
-    from . import data as D
-    try:
-        ix = D.load_pickle(os.path.join(data_dir, "meta.pkl"))["indexlizer"]
-        t2i = getattr(getattr(ix, "_vocab", ix), "_token2id", None)
-        return {int(i): str(t) for t, i in t2i.items()} if isinstance(t2i, dict) else None
-    except Exception:
-        return None
-
-
-def _why(rec, u_ids, items, n, words):
-    """The "why" lists of --explain for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill)."""
-    dev = u_ids.device
-    keep = items >= 0
-    rows, cols = keep.nonzero(as_tuple=True)
-    why = [[None] * int(keep[r].sum()) for r in range(items.shape[0])]
-    if rows.numel() == 0:
-        return why
-    pu, pi = u_ids[rows.to(dev)], items[rows, cols].to(dev)
-    ex = rec.explain(pu, pi)
-    c = rec.cache
-    word = (lambda t: words.get(int(t), int(t))) if words else int
-
-    def tops(tokens, docs):
-        pos, tok, w = (t.cpu() for t in top_tokens(tokens, docs.to(torch.int64), n))
-        return [[[int(p), word(t), float(x)] for p, t, x in zip(pr, tr, wr) if x != 0.0] for pr, tr, wr in zip(pos, tok, w)]
-
-    ut, it = tops(ex.user_tokens, c.user.index_select(0, pu)), tops(ex.item_tokens, c.item.index_select(0, pi))
-    rv = None
-    if ex.item_reviews is not None:
-        slot, rid, contrib = (t.cpu() for t in top_tokens(ex.item_reviews, c.item_rids.index_select(0, pi), n))
-        att = torch.gather(ex.item_review_weights.cpu(), 1, slot)
-        rv = [[[int(s), int(r), float(a), float(x)] for s, r, a, x in zip(*q) if x != 0.0] for q in zip(slot, rid, att, contrib)]
-    slot_of = keep.cumsum(1) - 1
-    for p, (r, k) in enumerate(zip(rows.tolist(), cols.tolist())):
-        entry = {"user_tokens": ut[p], "item_tokens": it[p]}
-        if rv is not None:
-            entry["item_reviews"] = rv[p]
-        why[r][int(slot_of[r, k])] = entry
-    return why
-
-
-def _why_attention(rec, u_ids, items, n, words):
-    """The "why" lists of --attention for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per item
-    the n entries of largest |tokens| on each side as [position, word, weight, local_gate]."""
-    dev = u_ids.device
-    keep = items >= 0
-    rows, cols = keep.nonzero(as_tuple=True)
-    why = [[None] * int(keep[r].sum()) for r in range(items.shape[0])]
-    if rows.numel() == 0:
-        return why
-    pu, pi = u_ids[rows.to(dev)], items[rows, cols].to(dev)
-    at = rec.attention(pu, pi)
-    c = rec.cache
-    word = (lambda t: words.get(int(t), int(t))) if words else int
-
-    def tops(tokens, gate, docs):
-        pos, tok, w = top_tokens(tokens, docs.to(torch.int64), n)
-        gl = torch.gather(gate, 1, pos).cpu()
-        pos, tok, w = pos.cpu(), tok.cpu(), w.cpu()
-        return [[[int(p), word(t), float(x), float(g)] for p, t, x, g in zip(*q) if x != 0.0] for q in zip(pos, tok, w, gl)]
-
-    ut = tops(at.user_tokens, at.user_local_gate, c.user.index_select(0, pu))
-    it = tops(at.item_tokens, at.item_local_gate, c.item.index_select(0, pi))
-    gu, gi = at.user_global_gate.cpu(), at.item_global_gate.cpu()
-    slot_of = keep.cumsum(1) - 1
-    for p, (r, k) in enumerate(zip(rows.tolist(), cols.tolist())):
-        why[r][int(slot_of[r, k])] = {"user_tokens": ut[p], "item_tokens": it[p], "user_global_gate": float(gu[p]),
-                                      "item_global_gate": float(gi[p])}
-    return why
-
-
-def _why_contributions(rec, u_ids, items, n, words):
-    """The "why" lists of --contributions for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per
-    item and side the n tokens of largest |weight| as [slot-major position, word, weight] and the n reviews of largest
-    |contribution| as [slot, counterpart id (-1 where the cache has none), attention, contribution]."""
-    dev = u_ids.device
-    keep = items >= 0
-    rows, cols = keep.nonzero(as_tuple=True)
-    why = [[None] * int(keep[r].sum()) for r in range(items.shape[0])]
-    if rows.numel() == 0:
-        return why
-    pu, pi = u_ids[rows.to(dev)], items[rows, cols].to(dev)
-    co = rec.contributions(pu, pi)
-    c = rec.cache
-    word = (lambda t: words.get(int(t), int(t))) if words else int
-
-    def tops(tokens, docs):
-        pos, tok, w = (t.cpu() for t in top_tokens(tokens, docs.to(torch.int64), n))
-        return [[[int(p), word(t), float(x)] for p, t, x in zip(pr, tr, wr) if x != 0.0] for pr, tr, wr in zip(pos, tok, w)]
-
-    def revs(contrib, att, rids, ids):
-        rid = rids.index_select(0, ids).to(torch.int64) if rids is not None else torch.full_like(contrib, -1, dtype=torch.int64)
-        slot, rid, x = (t.cpu() for t in top_tokens(contrib, rid, n))
-        at = torch.gather(att.cpu(), 1, slot)
-        return [[[int(s), int(r), float(a), float(v)] for s, r, a, v in zip(*q) if v != 0.0] for q in zip(slot, rid, at, x)]
-
-    ut, it = tops(co.user_tokens, c.user.index_select(0, pu)), tops(co.item_tokens, c.item.index_select(0, pi))
-    ur = revs(co.user_reviews, co.user_review_weights, getattr(c, "user_rids", None), pu)
-    ir = revs(co.item_reviews, co.item_review_weights, getattr(c, "item_rids", None), pi)
-    slot_of = keep.cumsum(1) - 1
-    for p, (r, k) in enumerate(zip(rows.tolist(), cols.tolist())):
-        why[r][int(slot_of[r, k])] = {"user_tokens": ut[p], "item_tokens": it[p], "user_reviews": ur[p], "item_reviews": ir[p]}
-    return why
-
-
-def _why_sentences(rec, u_ids, items, n, words, n_words=None):
-    """The "why" lists of --sentences for the users u_ids [n_u] and their recommended items [n_u, k] (CPU, -1 = fill): per item
-    the n user sentences of largest |contribution| as [review slot, sentence slot, weight, contribution, matched item review
-    slot, matched item sentence slot] (with a vocabulary: + the sentence's words and the matched item sentence's words, token 0
-    dropped), the n matched item sentences of largest |match contribution| as [review slot, sentence slot, item_sent_weight,
-    match contribution], and both sides' n reviews of largest |contribution| as [slot, weight, contribution].  With n_words
-    (--words) every user and item sentence entry ends with its n_words words of largest |contribution| as [position, word,
-    contribution] (AhnRecommender.words; the item's through its full path), zeros dropped."""
-    dev = u_ids.device
-    keep = items >= 0
-    rows, cols = keep.nonzero(as_tuple=True)
-    why = [[None] * int(keep[r].sum()) for r in range(items.shape[0])]
-    if rows.numel() == 0:
-        return why
-    pu, pi = u_ids[rows.to(dev)], items[rows, cols].to(dev)
-    sc = rec.sentences(pu, pi)
-    Su, Si = sc.user_sentences.shape[2], sc.item_sentence_match.shape[2]
-
-    def sent_words(table, ids, pos):
-        if not words:
-            return None
-        sents = table.index_select(0, ids).to(torch.int64)
-        sents = sents.reshape(sents.shape[0], -1, sents.shape[-1])
-        picked = torch.gather(sents, 1, pos.view(*pos.shape, 1).expand(-1, -1, sents.shape[-1])).cpu()
-        return [[[words.get(int(t), int(t)) for t in s if int(t) != PAD] for s in row] for row in picked.tolist()]
-
-    wc = rec.words(pu, pi) if n_words is not None else None
-    word = (lambda t: words.get(int(t), int(t))) if words else int
-
-    def top_words(contrib, table, ids, pos):
-        """per pair and picked sentence (pos: flat sentence slots [P, n']) its n_words weightiest words"""
-        if wc is None:
-            return None
-        width = contrib.shape[-1]
-        at = pos.view(*pos.shape, 1).expand(-1, -1, width)
-        c = torch.gather(contrib.reshape(contrib.shape[0], -1, width), 1, at)
-        toks = torch.gather(table.index_select(0, ids).to(torch.int64).reshape(contrib.shape[0], -1, width), 1, at)
-        t = c.abs().topk(min(n_words, width), dim=-1).indices
-        c, toks, t = torch.gather(c, 2, t).cpu().tolist(), torch.gather(toks, 2, t).cpu().tolist(), t.cpu().tolist()
-        return [[[[q, word(k), v] for q, k, v in zip(*sent) if v != 0.0] for sent in zip(*row)] for row in zip(t, toks, c)]
-
-    pos, wgt, x = top_tokens(sc.user_sentences, sc.user_sent_weights, n)
-    hit = torch.gather(sc.user_match.reshape(pos.shape[0], -1), 1, pos)
-    uw, iw = sent_words(rec.user, pu, pos), sent_words(rec.item, pi, hit)
-    utop = top_words(wc.user_words, rec.user, pu, pos) if wc is not None else None
-    pos, wgt, x, hit = pos.cpu(), wgt.cpu(), x.cpu(), hit.cpu()
-    us = []
-    for p in range(pos.shape[0]):
-        row = []
-        for k, (q, a, c, h) in enumerate(zip(pos[p].tolist(), wgt[p].tolist(), x[p].tolist(), hit[p].tolist())):
-            if c != 0.0:
-                row.append([q // Su, q % Su, a, c, h // Si, h % Si] + ([uw[p][k], iw[p][k]] if words else [])
-                           + ([utop[p][k]] if utop is not None else []))
-        us.append(row)
-
-    def tops(contrib, weights, width=None, word_table=None):
-        q, a, c = top_tokens(contrib, weights, n)
-        top = top_words(wc.item_words, word_table, pi, q) if word_table is not None and wc is not None else None
-        q, a, c = q.cpu().tolist(), a.cpu().tolist(), c.cpu().tolist()
-        slot = (lambda s: [s]) if width is None else (lambda s: [s // width, s % width])
-        return [[slot(s) + [w, v] + ([top[p][k]] if top is not None else []) for k, (s, w, v) in enumerate(zip(*r)) if v != 0.0]
-                for p, r in enumerate(zip(q, a, c))]
-
-    isent = tops(sc.item_sentence_match, sc.item_sent_weights, Si, rec.item)
-    ur, ir = tops(sc.user_reviews, sc.user_review_weights), tops(sc.item_reviews, sc.item_review_weights)
-    slot_of = keep.cumsum(1) - 1
-    for p, (r, k) in enumerate(zip(rows.tolist(), cols.tolist())):
-        why[r][int(slot_of[r, k])] = {"user_sentences": us[p], "user_reviews": ur[p], "item_sentences": isent[p], "item_reviews": ir[p]}
-    return why
 
 
 def main(argv=None) -> int:
@@ -1006,20 +934,17 @@ def main(argv=None) -> int:
     # AHN: sentence tables and the pair tail (AhnRecommender); a chunk of ids is chunk * R * S sentences through the encoder
     rec = AhnRecommender(model, cache).refresh(chunk=min(a.chunk, 32)) if a.model == "ahn" else Recommender(model, cache).refresh(chunk=a.chunk)
     seen = Recommender.seen_from(ds.examples, rec.n_users, dev) if a.exclude_train else None
-    words = _vocabulary(cfg.data_dir) if any(n is not None for n in (a.explain, a.attention, a.contributions, a.sentences)) else None
+    flag = next((f for f in _WHY_FLAGS if getattr(a, f) is not None), None)        # at most one: each covers other models
+    words = _vocabulary(cfg.data_dir) if flag is not None else None
     if a.out is not None:
         with open(a.out, "w") as f:
             for lo in range(1, rec.n_users, a.chunk):
                 u_ids = torch.arange(lo, min(lo + a.chunk, rec.n_users), dtype=torch.int64, device=dev)
                 items, scores = rec.topk(u_ids, a.k, exclude=seen)
                 items, scores = items.cpu(), scores.cpu()
-                why = _why(rec, u_ids, items, a.explain, words) if a.explain is not None else None
-                if a.attention is not None:
-                    why = _why_attention(rec, u_ids, items, a.attention, words)
-                if a.contributions is not None:
-                    why = _why_contributions(rec, u_ids, items, a.contributions, words)
-                if a.sentences is not None:
-                    why = _why_sentences(rec, u_ids, items, a.sentences, words, a.words)
+                why = None
+                if flag is not None:
+                    why = _WHY_FLAGS[flag][1](rec, u_ids, items, getattr(a, flag), words, *([a.words] if a.words is not None else []))
                 for r, u in enumerate(u_ids.tolist()):
                     keep = items[r] >= 0
                     line = {"user": u, "items": items[r][keep].tolist(), "scores": scores[r][keep].tolist()}

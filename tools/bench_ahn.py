@@ -20,53 +20,21 @@ Device events, medians over --repeats blocks of --iters calls after --warmup cal
 The process ends itself after --limit seconds (SIGALRM); run it under `timeout` as above."""
 from __future__ import annotations
 
-import argparse
-import contextlib
-import io
 import json
-import os
-import signal
-import statistics
-import sys
 
 import torch
 from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+from benchlib import arm, parser, quiet, rounded_ms as timed_ms
 
 DEV = "cuda:0"
 BZ, RV, SN, WN, E, HH = 32, 10, 10, 20, 300, 150
 
 
-def timed_ms(fn, iters, warmup, repeats):
-    """Median over `repeats` blocks of `iters` calls (device events around each block), per call."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return [round(statistics.median(out), 4), round(min(out), 4), round(max(out), 4)]
-
-
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--limit", type=int, default=540, help="seconds after which the process ends itself")
+    ap = parser(__doc__, repeats=5, iters=10, warmup=3, limit=540)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_ahn.py needs an MI355X: there is no CPU fallback and no CPU timing")
-    signal.alarm(a.limit)
+    arm("bench_ahn.py", a.limit)
     from review_based_recommender_amd import _lib
     from review_based_recommender_amd import functional as RF
     from review_based_recommender_amd.models.ahn.ahn_model import AHN
@@ -125,8 +93,7 @@ def main():
 
     # the whole model's training step
     V, U, I, K = 20000, 1000, 1000, 10
-    with contextlib.redirect_stdout(io.StringIO()):
-        model = AHN(E, 2 * HH, K, U, I, V, None, rnn_dropout=0.0, dropout=0.5, item_review_num=RV).to(DEV)
+    model = quiet(AHN, E, 2 * HH, K, U, I, V, None, rnn_dropout=0.0, dropout=0.5, item_review_num=RV).to(DEV)
     lens = lengths.view(2, BZ, RV, SN)
     ids = torch.randint(1, V, (2, BZ, RV, SN, WN), generator=g) * (torch.arange(WN) < lens.unsqueeze(-1))
     sm = lens > 0

@@ -17,57 +17,24 @@ random pairs.  Device events, medians over --repeats blocks of --iters calls aft
 The process ends itself after --limit seconds (SIGALRM); run it under `timeout` as above."""
 from __future__ import annotations
 
-import argparse
-import contextlib
-import io
 import json
-import os
-import signal
-import statistics
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from benchlib import arm, parser, quiet, rounded_ms as timed_ms
 
-import ahn_explain_ref as E_REF  # noqa: E402
+import ahn_explain_ref as E_REF  # noqa: E402  (benchlib set the path)
 
 DEV = "cuda:0"
 RV, SN, WN, E, K = 10, 10, 20, 300, 10
 N_IDS, V, PAIRS = 1001, 20000, 256
 
 
-def timed_ms(fn, iters, warmup, repeats):
-    """Median over `repeats` blocks of `iters` calls (device events around each block), per call."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return [round(statistics.median(out), 4), round(min(out), 4), round(max(out), 4)]
-
-
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--limit", type=int, default=540, help="seconds after which the process ends itself")
+    ap = parser(__doc__, repeats=5, iters=10, warmup=3, limit=540)
     ap.add_argument("--out", help="also write the JSON line to this file")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_ahn_sentences.py needs an MI355X: there is no CPU fallback and no CPU timing")
-    signal.alarm(a.limit)
+    arm("bench_ahn_sentences.py", a.limit)
     from review_based_recommender_amd import functional as RF
     from review_based_recommender_amd.models.ahn.ahn_model import AHN
     from review_based_recommender_amd.recommend import AhnRecommender
@@ -82,8 +49,7 @@ def main():
         return t.to(torch.int32).to(DEV)
 
     user, item = table(), table()
-    with contextlib.redirect_stdout(io.StringIO()):
-        model = AHN(E, E, K, N_IDS, N_IDS, V, None, rnn_dropout=0.0, dropout=0.5, item_review_num=RV).to(DEV).eval()
+    model = quiet(AHN, E, E, K, N_IDS, N_IDS, V, None, rnn_dropout=0.0, dropout=0.5, item_review_num=RV).to(DEV).eval()
     rec = AhnRecommender(model, user=user, item=item).refresh()
     pu = torch.randint(1, N_IDS, (PAIRS,), generator=g).to(DEV)
     pi = torch.randint(1, N_IDS, (PAIRS,), generator=g).to(DEV)

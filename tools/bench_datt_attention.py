@@ -21,46 +21,19 @@ What the op has to move and compute, from the shapes (code below), and the floor
 The process ends itself after --limit seconds (SIGALRM); run it under `timeout` as above."""
 from __future__ import annotations
 
-import argparse
-import contextlib
-import io
 import json
-import os
-import signal
-import statistics
-import sys
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests", "golden")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from benchlib import arm, parser, quiet, timed_ms
 
-import synth  # noqa: E402
+import synth  # noqa: E402  (benchlib set the path)
 
 DEV = "cuda:0"
 N_IDS, PAIRS = 1001, 256
 GATHER_TBPS = 8.6          # random rows out of the Infinity Cache, chip-wide
-
-
-def timed_ms(fn, iters, warmup, repeats):
-    """Median over `repeats` blocks of `iters` calls (device events around each block), per call."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return statistics.median(out), min(out), max(out)
 
 
 def recommender():
@@ -69,8 +42,7 @@ def recommender():
     from review_based_recommender_amd.recommend import Recommender
     rng = np.random.default_rng(5)
     c = synth.DATT_CFGS["cfg4"]
-    with contextlib.redirect_stdout(io.StringIO()):
-        m = DualAtt(c["V"], c["L"], c["win"], c["l_out"], c["g_out"], c["E"], c["h1"], c["h2"], 0.5, None)
+    m = quiet(DualAtt, c["V"], c["L"], c["win"], c["l_out"], c["g_out"], c["E"], c["h1"], c["h2"], 0.5, None)
     m.load_state_dict(synth.datt_params(c, 0))
     docs = [torch.from_numpy(synth._docs(rng, N_IDS, c["L"], c["V"])) for _ in range(2)]
     for d in docs:
@@ -101,15 +73,9 @@ def composed_tokens(m, docs, d_latent):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--limit", type=int, default=540, help="seconds after which the process ends itself")
+    ap = parser(__doc__, repeats=5, iters=20, warmup=3, limit=540)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_datt_attention.py needs an MI355X: there is no CPU fallback and no CPU timing")
-    signal.alarm(a.limit)
+    arm("bench_datt_attention.py", a.limit)
     from review_based_recommender_amd import functional as RF
     m, rec, u_ids, i_ids, c = recommender()
     at = rec.attention(u_ids, i_ids)

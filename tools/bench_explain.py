@@ -18,48 +18,16 @@ Per shape, device events, medians over --repeats blocks of --iters calls after -
 The process ends itself after --limit seconds (SIGALRM); run it under `timeout` as above."""
 from __future__ import annotations
 
-import argparse
-import contextlib
-import io
 import json
-import os
-import signal
-import statistics
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests", "golden")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from benchlib import arm, parser, quiet, timed_ms
 
-import synth  # noqa: E402
+import synth  # noqa: E402  (benchlib set the path)
 
 DEV = "cuda:0"
-
-
-def timed_ms(fn, iters, warmup, repeats):
-    """Median over `repeats` blocks of `iters` calls (device events around each block), per call."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return statistics.median(out), min(out), max(out)
-
-
-def _quiet(fn, *a):
-    with contextlib.redirect_stdout(io.StringIO()):
-        return fn(*a)
 
 
 def recommender(kind):
@@ -69,14 +37,14 @@ def recommender(kind):
     if kind == "cfg2":
         from review_based_recommender_amd.models.deepconn.deepconn import DeepCoNNpp
         c = synth.DEEPCONN_CFGS["cfg2"]
-        m = _quiet(DeepCoNNpp, c["U"], c["I"], c["V"], c["kz"], c["D"], c["H"], c["K"], c["L"], None, 0.5)
+        m = quiet(DeepCoNNpp, c["U"], c["I"], c["V"], c["kz"], c["D"], c["H"], c["K"], c["L"], None, 0.5)
         m.load_state_dict(synth.deepconn_params(c, 0))
         docs = [torch.from_numpy(synth._docs(rng, n, c["L"], c["V"])) for n in (c["U"], c["I"])]
         extra = {}
     else:
         from review_based_recommender_amd.models.narre.narre import NARRE
         c = synth.NARRE_CFGS["cfg3"]
-        m = _quiet(NARRE, c["U"], c["I"], c["V"], c["kz"], c["H"], c["D"], c["A"], c["K"], c["R"], c["T"], 0.5, 0, 0, 0, None, "CNN")
+        m = quiet(NARRE, c["U"], c["I"], c["V"], c["kz"], c["H"], c["D"], c["A"], c["K"], c["R"], c["T"], 0.5, 0, 0, 0, None, "CNN")
         m.load_state_dict(synth.narre_params(c, 0))
         docs = [torch.from_numpy(synth._docs(rng, n * c["R"], c["T"], c["V"])).view(n, c["R"], c["T"]) for n in (c["U"], c["I"])]
         rids = [torch.from_numpy(rng.integers(1, n, size=(k, c["R"])).astype(np.int64)) for k, n in ((c["U"], c["I"]), (c["I"], c["U"]))]
@@ -150,15 +118,9 @@ def bench_shape(kind, a):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--limit", type=int, default=540, help="seconds after which the process ends itself")
+    ap = parser(__doc__, repeats=5, iters=20, warmup=3, limit=540)
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_explain.py needs an MI355X: there is no CPU fallback and no CPU timing")
-    signal.alarm(a.limit)
+    arm("bench_explain.py", a.limit)
     res = {"bench": "explain", "device": torch.cuda.get_device_name(0), "repeats": a.repeats, "iters": a.iters}
     for kind in ("cfg2", "cfg3"):
         res.update(bench_shape(kind, a))

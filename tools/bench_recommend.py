@@ -17,44 +17,17 @@ The process ends itself after --limit seconds (SIGALRM); run it under `timeout` 
 """
 from __future__ import annotations
 
-import argparse
-import contextlib
-import io
 import json
-import os
-import signal
-import statistics
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for p in (ROOT, os.path.join(ROOT, "tests", "golden")):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+from benchlib import arm, parser, quiet, timed_ms
 
-import synth  # noqa: E402
+import synth  # noqa: E402  (benchlib set the path)
 
 LANE_OPS_PER_S = 256 * 4 * 16 * 2.4e9        # 39.3e12 unpacked fp32 lane-operations per second (an fma counts 2 FLOP and is issued
                                              # for 64 lanes over 4 cycles on a 16-lane pipe: 157.3 TFLOP/s)
-
-
-def timed_ms(fn, iters, warmup, repeats):
-    """Median over `repeats` blocks of `iters` calls (device events around each block), per call."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(repeats):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return statistics.median(out), min(out), max(out)
 
 
 def torch_topk(ul, il, h, g, ub, ib, k, item_lo, budget_bytes=1 << 30):
@@ -102,8 +75,7 @@ def s1_tables(a, res):
     from review_based_recommender_amd.models.deepconn.deepconn import DeepCoNNpp
     from review_based_recommender_amd.recommend import Recommender
     cfg = synth.DEEPCONN_CFGS["cfg2"]
-    with contextlib.redirect_stdout(io.StringIO()):
-        m = DeepCoNNpp(cfg["U"], cfg["I"], cfg["V"], cfg["kz"], cfg["D"], cfg["H"], cfg["K"], cfg["L"], None, 0.5)
+    m = quiet(DeepCoNNpp, cfg["U"], cfg["I"], cfg["V"], cfg["kz"], cfg["D"], cfg["H"], cfg["K"], cfg["L"], None, 0.5)
     m.load_state_dict(synth.deepconn_params(cfg, 0))
     m.validate_ids = False
     m.to("cuda:0").eval()
@@ -124,16 +96,10 @@ def s1_tables(a, res):
 
 
 def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--limit", type=int, default=840, help="seconds after which the process ends itself")
+    ap = parser(__doc__, repeats=5, iters=20, warmup=3, limit=840)
     ap.add_argument("--only", choices=["all", "topk"], default="all", help="topk: skip the encode timing (profiler runs)")
     a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench_recommend.py needs an MI355X: there is no CPU fallback and no CPU timing")
-    signal.alarm(a.limit)
+    arm("bench_recommend.py", a.limit)
     res = {"bench": "recommend", "device": torch.cuda.get_device_name(0), "repeats": a.repeats, "iters": a.iters}
     res.update(bench_shape("S1", *s1_tables(a, res), 10, a))
     gen = torch.Generator().manual_seed(0)
