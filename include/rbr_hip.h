@@ -969,7 +969,10 @@ int rbr_hier_pool_bwd(int32_t n_docs, int32_t L, int32_t D, int32_t k, const int
  *        x = node_drop[b,r] * rev[b,r,:];  t = tanh(x Wp^T + bp);  s = softmax_r(masked_fill(<t, wi>, ~mask, -1e8));
  *        out[b,:] = sum_r s[r] x[r,:].   rev [B,R,H], mask [B,R] or NULL, node_drop [B,R] or NULL, Wp [K,H], bp [K],
  *        wi [K]; scores [B,R] and t_out [B,R,K] are kept for the backward, which overwrites d_rev, d_Wp, d_bp, d_wi.
- *        R <= 64; ws: rbr_additive_attn_bwd_ws_floats(B,R,H,K) floats.                                     ---- */
+ *        ws: rbr_additive_attn_bwd_ws_floats(B,R,H,K) floats (d_pre [B,R,K] first, then x [B,R,H]).
+ *        Shapes: B, R, H, K >= 1; R <= 64; and the kernels' 64 KiB of dynamic LDS: K + H <= 256 (64 rows of d_pre and x in
+ *        the d_Wp kernel) and R*(H+K+2) + H <= 16384 floats (x, d_pre, two R-vectors and d_out in the backward).  A shape
+ *        outside returns RBR_ERR_BAD_ARG from both entry points before anything is launched.                  ---- */
 int rbr_review_bag_fwd(int32_t n_rev, int32_t T, int32_t D, const int64_t* ids, const uint8_t* mask, const float* table,
                        const float* drop, float* out, float* inv_len, void* stream);
 size_t rbr_review_bag_bwd_ws_bytes(int32_t n_rev, int32_t T);

@@ -2120,7 +2120,9 @@ class _AdditiveAttn(torch.autograd.Function):
 
 
 def additive_attention(rev, mask, Wp, bp, wi, *, node_drop=None):
-    """AddictiveAttention over the reviews (+ NodeDropout multiplier [B,R]).  Returns (out [B,H], scores [B,R,1])."""
+    """AddictiveAttention over the reviews (+ NodeDropout multiplier [B,R]).  Returns (out [B,H], scores [B,R,1]).
+    rev [B,R,H], Wp [K,H]: B, R, H, K >= 1, R <= 64 and, for the kernels' 64 KiB of LDS, K + H <= 256 and
+    R * (H + K + 2) + H <= 16384; a shape outside is refused by the library (RBR_ERR_BAD_ARG) and raises RuntimeError."""
     out, scores = _AdditiveAttn.apply(rev, mask, node_drop, Wp, bp, wi)
     return out, scores.unsqueeze(2)
 

@@ -1,6 +1,7 @@
 """Plain float64 restatements, with per-element error bounds, of the ops the edge tests of the rating head, nn.Linear,
-clip + Adam and the SimpleSiamese review bag compare the HIP kernels with (tests/test_pair_head_edges_gpu.py,
-test_linear_edges_gpu.py, test_clip_adam_edges_gpu.py, test_review_bag_edges_gpu.py).
+clip + Adam, the SimpleSiamese review bag and SimpleSiamese's additive attention compare the HIP kernels with
+(tests/test_pair_head_edges_gpu.py, test_linear_edges_gpu.py, test_clip_adam_edges_gpu.py, test_review_bag_edges_gpu.py,
+test_additive_attn_edges_gpu.py).
 tests/test_edge_refs_host.py checks every formula here against torch autograd / torch.optim.Adam in float64 on the CPU.
 
 Every function takes f32 (or already float64) CPU tensors and computes in float64.  Beside each value it returns `Abs`, the same
@@ -10,7 +11,9 @@ result by
     bound = (n + 4) * EPS * Abs,   EPS = 2^-24,   n = number of terms behind the element
 
 (n - 1 additions in any order; the 4 covers the roundings inside one term).  An element with Abs == 0 has no terms: it must be
-exactly 0, or bit-equal to the base it is accumulated onto.
+exactly 0, or bit-equal to the base it is accumulated onto.  Where one stage feeds the next (adam_step, additive_attention) the
+bound is propagated: every stage adds its own (n + 4) * EPS * Abs to what its inputs carry, and the function returns
+(value, bound) per tensor.
 """
 import math
 
@@ -230,3 +233,111 @@ def adam_step(p, m, v, g, coef, t, lr, betas=(0.9, 0.999), eps=1e-8):
     p1 = p - u
     b_p = b_u + EPS * (p.abs() + u.abs())
     return {"gc": (gc, b_gc), "m": (m1, b_m), "v": (v1, rel_v * v1), "p": (p1, b_p)}
+
+
+# --------------------------------------------------------------------------------------------------------- additive attention
+TINY = 2.0 ** -126        # smallest normal f32: covers a result in the subnormal range, rounded there or flushed to 0
+
+
+def _addatt_inputs(rev, mask, node_drop):
+    rev = f64(rev)
+    B, R, _ = rev.shape
+    nd = torch.ones(B, R, dtype=torch.float64) if node_drop is None else f64(node_drop)
+    m = torch.ones(B, R, dtype=torch.bool) if mask is None else mask.detach().cpu().bool()
+    return rev, nd, m, nd.unsqueeze(2) * rev
+
+
+def additive_attention_fwd(rev, mask, node_drop, Wp, bp, wi):
+    """SimpleSiamese's NodeDropout + AddictiveAttention -> {name: (value, bound)} for pre, t [B,R,K], logit, scores [B,R], out [B,H].
+      x = node_drop * rev                       its one rounding is one of the 4 of every (n + 4) it enters
+      pre = x Wp^T + bp                         (H + 1 + 4) EPS (|x| |Wp|^T + |bp|)
+      t = tanh(pre)                             bound(pre) (tanh is 1-Lipschitz) + 4 EPS for tanhf, a value <= 1
+      logit = <t, wi>                           sum_k |wi_k| bound(t_k) + (K + 4) EPS sum_k |t_k wi_k|
+      s = softmax_r(masked_fill(logit, ~mask, -1e8)), as the kernel has it: e_r = expf(logit_r - max), s_r = e_r * (1 / sum e).
+        Logits moved by at most delta move s_r by at most a factor exp(2 delta): numerator and denominator by exp(delta) each.
+        delta = max over the row's valid reviews of bound(logit_r) + EPS |logit_r - max| (the rounding of the subtraction).
+        The roundings after it are relative, nothing cancels in a sum of positive terms: expf 4 EPS on the numerator and 4 EPS on
+        the denominator's terms, R - 1 additions, 4 EPS for the division, 1 for the product: (R + 12) EPS.  Together
+            bound(s_r) = s_r * expm1(2 delta + (R + 12) EPS) + 2 TINY
+        (expf's and the division's 4 EPS are relative to a value <= 1 here, so inside the absolute 4 EPS that the other edge
+        tests give a transcendental of magnitude <= 1; 2 TINY: e_r or s_r in the subnormal range, max e = 1 so sum e >= 1).
+        A masked review in a row with a valid one: expf(-1e8 - max) = 0, s_r == 0 exactly, bound 0.
+        A row without a valid review: every e_r = expf(0) = 1, their sum R is exact, s_r = 1/R to the division: 4 EPS / R.
+      out = sum_r s_r x_r                       sum_r bound(s_r) |x_r| + (R + 4) EPS sum_r s_r |x_r|"""
+    rev, nd, m, x = _addatt_inputs(rev, mask, node_drop)
+    Wp, bp, wi = f64(Wp), f64(bp), f64(wi).reshape(-1)
+    B, R, H = rev.shape
+    K = Wp.shape[0]
+    pre = x @ Wp.t() + bp
+    b_pre = bound_of(H + 1, x.abs() @ Wp.abs().t() + bp.abs())
+    t = torch.tanh(pre)
+    b_t = b_pre + 4 * EPS
+    logit = t @ wi
+    b_logit = b_t @ wi.abs() + bound_of(K, t.abs() @ wi.abs())
+    filled = torch.where(m, logit, torch.full_like(logit, -1e8))
+    s = torch.softmax(filled, dim=1)
+    mx = filled.max(1, keepdim=True).values
+    zero = torch.zeros_like(logit)
+    delta = torch.where(m, b_logit + EPS * (logit - mx).abs(), zero).max(1, keepdim=True).values
+    b_s = s * torch.expm1(2 * delta + (R + 12) * EPS) + 2 * TINY
+    any_valid = m.any(1, keepdim=True)
+    b_s = torch.where(any_valid, torch.where(m, b_s, zero), torch.full_like(s, 4 * EPS / R))
+    assert bool((s[any_valid.expand(B, R) & ~m] == 0).all())
+    out = (s.unsqueeze(2) * x).sum(1)
+    b_out = (b_s.unsqueeze(2) * x.abs()).sum(1) + bound_of(R, (s.unsqueeze(2) * x.abs()).sum(1))
+    return {"pre": (pre, b_pre), "t": (t, b_t), "logit": (logit, b_logit), "scores": (s, b_s), "out": (out, b_out)}
+
+
+def additive_attention_bwd(rev, mask, node_drop, Wp, wi, scores, t, d_out):
+    """The backward of additive_attention_fwd from the SAVED scores [B,R] and t [B,R,K] (the kernel consumes what the forward
+    kept, so the forward's error is no part of these bounds) -> {name: (value, bound)}.  With x = node_drop * rev, N = B * R:
+      dsr_r = <d_out, x_r>                      (H + 4) EPS A_r,   A_r = <|d_out|, |x_r|>
+      dot = sum_r s_r dsr_r                     sum_r s_r bound(dsr_r) + (R + 4) EPS sum_r s_r A_r
+      dl_r = mask_r ? s_r (dsr_r - dot) : 0     s_r (bound(dsr_r) + bound(dot)) + 4 EPS Abs,  Abs = s_r (A_r + sum_j s_j A_j):
+                                                the difference cancels, its roundings are relative to the operands' magnitudes
+      d_pre = dl wi (1 - t^2)                   one term.  f32's 1 - t^2 is off by at most EPS (1 + t^2) ABSOLUTE (a saturated
+                                                unit: most of what is left of it), so
+                                                |wi| (bound(dl) (1 - t^2) + 4 EPS (|dl| + bound(dl)) (1 + t^2))
+      d_wi = sum_{b,r} dl t                     sum bound(dl) |t| + (N + 4) EPS sum |dl t|          (atomics: any order)
+      d_bp = sum_{b,r} d_pre                    sum bound(d_pre) + (N + 4) EPS sum |d_pre|
+      d_Wp = d_pre^T x                          sum bound(d_pre) |x| + (N + 4) EPS sum |d_pre| |x|
+      d_rev = node_drop (s d_out + d_pre Wp)    |node_drop| (sum_k bound(d_pre) |Wp| + (K + 1 + 4) EPS (s |d_out| + |d_pre| |Wp|))
+    Bound 0, exact zeros: dl and the d_pre row of every masked review; the d_rev row of a masked review whose row has a valid
+    one (s == 0 there) and of every review with node_drop == 0.  In a row WITHOUT a valid review s = 1/R and d_rev = node_drop *
+    s * d_out: the masked_fill blocks the gradient of the logits, not the weighted sum's."""
+    rev, nd, m, x = _addatt_inputs(rev, mask, node_drop)
+    Wp, wi, s, t, dy = f64(Wp), f64(wi).reshape(-1), f64(scores).reshape(rev.shape[:2]), f64(t), f64(d_out)
+    B, R, H = rev.shape
+    K = Wp.shape[0]
+    N = B * R
+    dsr, adsr = torch.einsum("bh,brh->br", dy, x), torch.einsum("bh,brh->br", dy.abs(), x.abs())
+    b_dsr = bound_of(H, adsr)
+    dot, adot = (s * dsr).sum(1, keepdim=True), (s * adsr).sum(1, keepdim=True)
+    b_dot = (s * b_dsr).sum(1, keepdim=True) + bound_of(R, adot)
+    mf = m.double()
+    dl = mf * s * (dsr - dot)
+    b_dl = mf * s * (b_dsr + b_dot) + 4 * EPS * mf * s * (adsr + adot)
+    f, af, w = 1 - t * t, 1 + t * t, wi.abs()
+    d_pre = dl.unsqueeze(2) * wi * f
+    b_dpre = w * (b_dl.unsqueeze(2) * f + 4 * EPS * (dl.abs() + b_dl).unsqueeze(2) * af)
+    d_wi = torch.einsum("br,brk->k", dl, t)
+    b_dwi = torch.einsum("br,brk->k", b_dl, t.abs()) + bound_of(N, torch.einsum("br,brk->k", dl.abs(), t.abs()))
+    d_bp = d_pre.sum((0, 1))
+    b_dbp = b_dpre.sum((0, 1)) + bound_of(N, d_pre.abs().sum((0, 1)))
+    d_Wp = torch.einsum("brk,brh->kh", d_pre, x)
+    b_dWp = torch.einsum("brk,brh->kh", b_dpre, x.abs()) + bound_of(N, torch.einsum("brk,brh->kh", d_pre.abs(), x.abs()))
+    core = s.unsqueeze(2) * dy.unsqueeze(1) + d_pre @ Wp
+    acore = s.unsqueeze(2) * dy.abs().unsqueeze(1) + d_pre.abs() @ Wp.abs()
+    d_rev = nd.unsqueeze(2) * core
+    b_drev = nd.abs().unsqueeze(2) * (b_dpre @ Wp.abs() + bound_of(K + 1, acore))
+    return {"dl": (dl, b_dl), "d_pre": (d_pre, b_dpre), "d_wi": (d_wi, b_dwi), "d_bp": (d_bp, b_dbp), "d_Wp": (d_Wp, b_dWp),
+            "d_rev": (d_rev, b_drev)}
+
+
+def additive_attention(rev, mask, node_drop, Wp, bp, wi, d_out, scores=None, t=None):
+    """Forward and backward in one dict {name: (value, bound)}.  `scores`, `t`: what the forward under test saved (the backward
+    starts from them); None: the restatement's own float64 ones, for the comparison with autograd."""
+    ref = additive_attention_fwd(rev, mask, node_drop, Wp, bp, wi)
+    ref.update(additive_attention_bwd(rev, mask, node_drop, Wp, wi, ref["scores"][0] if scores is None else scores,
+                                      ref["t"][0] if t is None else t, d_out))
+    return ref

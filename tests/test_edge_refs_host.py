@@ -1,7 +1,7 @@
 """The float64 formulas of tests/edge_refs.py -- the references of the GPU edge tests of the rating head, nn.Linear,
-clip + Adam and the review bag -- against torch on the CPU: the head backward, the linear activation backward from a saved
-output and the review bag against autograd, the one-step Adam against clip_grad_norm_ + torch.optim.Adam, all in float64 to
-1e-12 relative.  Then the bound formulas on an f32 CPU computation of the same ops: the reference alone must stay inside them."""
+clip + Adam, the review bag and the additive attention -- against torch on the CPU: the head backward, the linear activation
+backward from a saved output, the review bag and the additive attention (through oracle.ref_cpu.additive_attention) against
+autograd, the one-step Adam against clip_grad_norm_ + torch.optim.Adam, all in float64 to 1e-12 relative.  Then the bound formulas on an f32 CPU computation of the same ops: the reference alone must stay inside them."""
 import numpy as np
 import pytest
 import torch
@@ -144,6 +144,70 @@ def test_review_bag_reference_matches_autograd(name):
     assert out32.dtype == dt32.dtype == torch.float32
     for k, got in (("out", out32), ("dtable", dt32)):
         R.check("host-bag", f"{name} {k}", got, ref[k][0], R.bound_of(ref[k][2], ref[k][1]))
+
+
+# --------------------------------------------------------------------------------------------------------- additive attention
+def _att_cases():
+    import test_additive_attn_edges_gpu as G
+    return G
+
+
+def _additive_attention_f32(inp):
+    """NodeDropout + AddictiveAttention and its backward in f32 on the CPU, operation by operation in the kernels' order: the
+    softmax as max, exp, sum, one reciprocal, products; the backward from the saved f32 scores and t."""
+    rev, mask, nd, Wp, bp, d_out = (inp[k] for k in ("rev", "mask", "node_drop", "Wp", "bp", "d_out"))
+    wi = inp["wi"].reshape(-1)
+    B, R_, H = rev.shape
+    K = Wp.shape[0]
+    m = torch.ones(B, R_, dtype=torch.bool) if mask is None else mask
+    x = rev if nd is None else rev * nd.unsqueeze(2)
+    t = torch.tanh(x @ Wp.t() + bp)
+    lg = torch.where(m, t @ wi, torch.tensor(-1e8))
+    e = torch.exp(lg - lg.max(1, keepdim=True).values)
+    s = e * (1.0 / e.sum(1, keepdim=True))
+    out = (s.unsqueeze(2) * x).sum(1)
+    dsr = torch.einsum("bh,brh->br", d_out, x)
+    dot = (s * dsr).sum(1, keepdim=True)
+    dl = torch.where(m, s * (dsr - dot), torch.tensor(0.0))
+    d_pre = dl.unsqueeze(2) * wi * (1.0 - t * t)
+    d_rev = s.unsqueeze(2) * d_out.unsqueeze(1) + d_pre @ Wp
+    if nd is not None:
+        d_rev = d_rev * nd.unsqueeze(2)
+    got = {"t": t, "scores": s, "out": out, "d_pre": d_pre, "d_wi": torch.einsum("br,brk->k", dl, t), "d_bp": d_pre.sum((0, 1)),
+           "d_Wp": d_pre.reshape(B * R_, K).t() @ x.reshape(B * R_, H), "d_rev": d_rev}
+    assert all(v.dtype == torch.float32 for v in got.values())
+    return got
+
+
+@pytest.mark.parametrize("name", list(_att_cases().CASES))
+def test_additive_attention_reference_matches_autograd(name):
+    """Every case of tests/test_additive_attn_edges_gpu.py: the restatement (its backward fed its own float64 scores and t)
+    against float64 autograd through oracle.ref_cpu.additive_attention on node_drop * rev, forward and all five gradients; then
+    its bounds on an f32 evaluation, whose backward starts from ITS saved scores and t, as the kernels' does."""
+    from oracle import ref_cpu as O
+    inp = _att_cases().inputs(name)
+    B, R_, H = inp["rev"].shape
+    m = torch.ones(B, R_, dtype=torch.bool) if inp["mask"] is None else inp["mask"]
+    leaves = {k: inp[k].double().clone().requires_grad_(True) for k in ("rev", "Wp", "bp", "wi")}
+    x = leaves["rev"] if inp["node_drop"] is None else leaves["rev"] * inp["node_drop"].double().unsqueeze(2)
+    out, scores = O.additive_attention(x, m, leaves["Wp"], leaves["bp"], leaves["wi"])
+    (out * inp["d_out"].double()).sum().backward()
+    args = (inp["rev"], inp["mask"], inp["node_drop"], inp["Wp"], inp["bp"], inp["wi"], inp["d_out"])
+    ref = R.additive_attention(*args)
+    _close("out", ref["out"][0], out.detach())
+    _close("scores", ref["scores"][0], scores.detach())
+    for k, leaf in (("d_rev", "rev"), ("d_Wp", "Wp"), ("d_bp", "bp"), ("d_wi", "wi")):
+        _close(k, ref[k][0], leaves[leaf].grad)
+    # d_pre, the gradient of the pre-activation: autograd's through the same graph, cut at pre
+    pre = (x.detach() @ leaves["Wp"].detach().t() + leaves["bp"].detach()).requires_grad_(True)
+    lg = torch.tanh(pre) @ leaves["wi"].detach().reshape(-1)
+    s = torch.softmax(torch.masked_fill(lg, ~m, -1e8), dim=1)
+    ((s.unsqueeze(2) * x.detach()).sum(1) * inp["d_out"].double()).sum().backward()
+    _close("d_pre", ref["d_pre"][0], pre.grad)
+    got = _additive_attention_f32(inp)
+    ref32 = R.additive_attention(*args, scores=got["scores"], t=got["t"])
+    for k, v in got.items():
+        R.check("host-additive-attn", f"{name} {k}", v, *ref32[k])
 
 
 # ----------------------------------------------------------------------------------------------------------------- clip + Adam
