@@ -455,6 +455,26 @@ def _review_tables(reviews, rids, n: int, slots: int, T):
     return torch.from_numpy(tab), torch.from_numpy(rid)
 
 
+def _resident_tables(ds, side: str, slots: int, T, pad: int, device):
+    """One side's ("user" / "item") resident pair for an id feed: int32 (reviews [N, slots, *T], rids [N, slots]) on `device` from
+    meta's ragged lists (_review_tables), tokens range-checked against the vocabulary and rids against the other side's id count,
+    row 0 all pad."""
+    n_other = ds.item_num if side == "user" else ds.user_num
+    tab, rid = _review_tables(getattr(ds, f"{side}_reviews"), getattr(ds, f"{side}_rids"), getattr(ds, f"{side}_num"), slots, T)
+    _check_range(tab, ds.vocab_size, f"meta.pkl {side}_reviews tokens")
+    _check_range(rid, n_other, f"meta.pkl {side}_rids")
+    tab[0] = pad                            # id 0 is the padding id: the row a bad id is replaced by
+    rid[0] = 0
+    return tab.to(torch.int32).to(device), rid.to(torch.int32).to(device)
+
+
+def _deliver(got, given, required: int):
+    """The cpu restatement's results `got` under the gathers' output convention, `given` being what the caller passed for each: a
+    tensor is copied into; the first `required` are handed over on None; the others on True and left out on None / False."""
+    return tuple(dst.copy_(val) if torch.is_tensor(dst) else (val if dst is True or (dst is None and n < required) else None)
+                 for n, (dst, val) in enumerate(zip(given, got)))
+
+
 def _slots_torch(own, other, tab, rid, n_other: int, leave_one_out: bool):
     """The id feeds' rule on the host, one side: for own ids [B] with counterparts `other`, over the tables tab [N, R+1, ...] /
     rid [N, R+1], d = the FIRST j < R with rid[own][j] == other (leave_one_out and 0 < other < n_other; else R) and output slot q
@@ -481,7 +501,52 @@ def sentence_masks(revs: torch.Tensor, pad: int = 0):
     return lens, sent_masks, sent_masks.any(-1)
 
 
-class DeviceDocCache:
+class _IdFeed:
+    """The id-feed protocol -- what GraphedTrainStep.from_ids / GraphedForward.from_ids, the trainer, NegativeFeed and InBatchFeed
+    take: empty_inputs / gather / inputs for a batch of (u_ids, i_ids).  A feed states `order` (the names of its model's arguments,
+    each a (user, item) pair), `like` ({name: (shape behind the batch dimension, dtype)}), `optional` (the names its cache
+    produces only when asked), `kind` (its model, for messages) and _gather(u_ids, i_ids, **outputs) -> {name: stacked [2B, ...] or
+    None}, how its cache's one launch is called: `outputs` gives per name a stacked tensor to write into, True (an optional output to
+    allocate) or None (an optional output to leave out)."""
+
+    optional = ("rev_masks", "rids", "ids")
+
+    def _order(self, with_ids: bool = True):
+        """`order` for DeviceDocCache's parameter `with_ids`: a feed bound to its model ignores it."""
+        return self.order
+
+    def _outputs(self, out, order):
+        """_gather's `outputs` for the arguments `order`: allocated, or the stacked views of `out`; nothing else is produced."""
+        if out is None:
+            asked = {k: True for k in order if k in self.optional}
+        elif len(out) != 2 * len(order):
+            raise RuntimeError(f"out must be the {2 * len(order)} arguments of {self.kind}")
+        else:
+            asked = {k: _adjacent(out[2 * n], out[2 * n + 1]) for n, k in enumerate(order)}
+        return {**dict.fromkeys(self.optional), **asked}
+
+    def _gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, **outputs):
+        """A feed over a `cache` with NAMES and gather(u_ids, i_ids, leave_one_out, **outputs); every other feed states its own."""
+        return dict(zip(self.cache.NAMES, self.cache.gather(u_ids, i_ids, self.leave_one_out, **outputs)))
+
+    def empty_inputs(self, B: int, with_ids: bool = True):
+        """Zeroed tensors of inputs()' shapes and dtypes for B pairs (what a recorded step lays its input block out by)."""
+        return tuple(torch.zeros((B, *self.like[k][0]), dtype=self.like[k][1], device=self.device)
+                     for k in self._order(with_ids) for _ in range(2))
+
+    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None, **kw):
+        """The pairs' batch, stacked ({name: [2B, ...]}, user rows first).  `out`: the model's arguments to write into instead, each
+        (user, item) pair adjacent in one allocation -- the input views of a recorded step."""
+        return self._gather(u_ids, i_ids, **self._outputs(out, self._order()), **kw)
+
+    def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
+        """The model's arguments for the pairs, in its own order -- views of one gather."""
+        B, order = u_ids.shape[0], self._order(with_ids)
+        got = self._gather(u_ids, i_ids, **self._outputs(None, order))
+        return tuple(half for k in order for half in (got[k][:B], got[k][B:]))
+
+
+class DeviceDocCache(_IdFeed):
     """All user / item documents resident on the GPU, so a batch is a pair of id vectors gathered ON DEVICE
     instead of 2 x doc_len token ids per pair shipped from the DataLoader workers.
 
@@ -494,6 +559,8 @@ class DeviceDocCache:
     rebuilds those from ids; this cache holds the first rv_num reviews per id, the valid / test rule.)"""
 
     PAD = 0          # get_mask's padding id (utils.py:30-42)
+    optional = ("masks", "ids")
+    kind = "the doc split"
 
     def __init__(self, ds, device):
         self.device = torch.device(device)
@@ -511,7 +578,20 @@ class DeviceDocCache:
             self.user = user.to(torch.int32).to(self.device)
             self.item = item.to(torch.int32).to(self.device)
             self.user_rids = self.item_rids = None
-            self.doc_len = self.user.shape[1]
+            self.doc_len = L = self.user.shape[1]
+            self.like = {"docs": ((L,), torch.int64), "masks": ((L,), torch.bool), "ids": ((), torch.int64)}
+
+    def _order(self, with_ids: bool = True):
+        """(u_docs, i_docs, u_masks, i_masks, u_ids, i_ids) for DeepCoNN++, (u_docs, i_docs) for D-ATT (with_ids=False)."""
+        return ("docs", "masks", "ids") if with_ids else ("docs",)
+
+    def _gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, **outputs):
+        from . import functional as RF
+        if self.user_rids is not None:
+            raise RuntimeError("gather is the doc split's id feed (the review split's is DeviceReviewCache.feed)")
+        u_ids = u_ids.to(self.device, non_blocking=True)
+        i_ids = i_ids.to(self.device, non_blocking=True)
+        return dict(zip(("docs", "masks", "ids"), RF.doc_gather(u_ids, i_ids, self.user, self.item, self.PAD, 0, **outputs)))
 
     def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None, masks: bool = True, ids: bool = True):
         """The documents of the pairs (u_ids[b], i_ids[b]) on the device (functional.doc_gather, one launch): stacked
@@ -519,36 +599,15 @@ class DeviceDocCache:
         write into instead -- (u_docs, i_docs) or (u_docs, i_docs, u_masks, i_masks, u_ids, i_ids), each pair adjacent in one
         allocation (the input views of a recorded step); its length decides masks / ids.  An id outside its table gets the
         all-pad row 0 and an IndexError at functional.check_id_errors()."""
-        from . import functional as RF
-        if self.user_rids is not None:
-            raise RuntimeError("gather is the doc split's id feed (the review split's is DeviceReviewCache.feed)")
-        u_ids = u_ids.to(self.device, non_blocking=True)
-        i_ids = i_ids.to(self.device, non_blocking=True)
-        if out is None:
-            return RF.doc_gather(u_ids, i_ids, self.user, self.item, self.PAD, 0, masks=masks, ids=ids)
-        if len(out) not in (2, 6):
+        if out is not None and len(out) not in (2, 6):
             raise RuntimeError("out must be (u_docs, i_docs) or (u_docs, i_docs, u_masks, i_masks, u_ids, i_ids)")
-        stacked = [_adjacent(out[k], out[k + 1]) for k in range(0, len(out), 2)] + [None, None]
-        return RF.doc_gather(u_ids, i_ids, self.user, self.item, self.PAD, 0, docs=stacked[0], masks=stacked[1], ids=stacked[2])
+        outputs = dict(masks=masks, ids=ids) if out is None else self._outputs(out, self._order(len(out) == 6))
+        return tuple(self._gather(u_ids, i_ids, **outputs).values())
 
-    def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
-        """The model's doc-fed arguments for the pairs: (u_docs, i_docs, u_masks, i_masks, u_ids, i_ids) for DeepCoNN++, or
-        (u_docs, i_docs) for D-ATT (with_ids=False) -- views of one gather."""
-        B = u_ids.shape[0]
-        docs, masks, ids = self.gather(u_ids, i_ids, masks=with_ids, ids=with_ids)
-        if not with_ids:
-            return docs[:B], docs[B:]
-        return docs[:B], docs[B:], masks[:B], masks[B:], ids[:B], ids[B:]
-
-    def empty_inputs(self, B: int, with_ids: bool = True):
-        """Zeroed tensors of inputs()' shapes and dtypes for B pairs (what a recorded step lays its input block out by)."""
-        L = self.user.shape[1]
-        docs = [torch.zeros(B, L, dtype=torch.int64, device=self.device) for _ in range(2)]
-        if not with_ids:
-            return tuple(docs)
-        masks = [torch.zeros(B, L, dtype=torch.bool, device=self.device) for _ in range(2)]
-        ids = [torch.zeros(B, dtype=torch.int64, device=self.device) for _ in range(2)]
-        return (*docs, *masks, *ids)
+    def feed(self, with_ids: bool) -> "_DocFeed":
+        """The cache bound to its model's form -- with_ids=True: DeepCoNN++'s six arguments, False: D-ATT's two -- as
+        DeviceReviewCache.feed binds a review cache: the feed's methods ignore the with_ids they are passed."""
+        return _DocFeed(self, with_ids)
 
     def doc_batch(self, u_ids: torch.Tensor, i_ids: torch.Tensor):
         if self.device.type != "cuda":
@@ -562,6 +621,17 @@ class DeviceDocCache:
         u, i = self.user.index_select(0, u_ids), self.item.index_select(0, i_ids)
         return (u, i, get_mask(u), get_mask(i), u_ids, i_ids, self.user_rids.index_select(0, u_ids),
                 self.item_rids.index_select(0, i_ids))
+
+
+class _DocFeed(_IdFeed):
+    """A DeviceDocCache bound to with_ids (DeviceDocCache.feed): the cache's launch under one model's argument order."""
+
+    optional = DeviceDocCache.optional
+
+    def __init__(self, cache: DeviceDocCache, with_ids: bool):
+        self.cache, self.with_ids, self.device = cache, bool(with_ids), cache.device
+        self.kind = "deepconn" if with_ids else "dual_att"
+        self.order, self.like, self._gather = cache._order(with_ids), cache.like, cache._gather
 
 
 class DeviceReviewCache:
@@ -581,6 +651,7 @@ class DeviceReviewCache:
     bytes: the plain tables, gather and feed read the first R + 1 slots only."""
 
     PAD = 0
+    NAMES = ("revs", "word_masks", "rev_masks", "rids", "ids")                # gather's outputs; sample_gather adds "slots"
     ORDER = {"narre": ("revs", "word_masks", "ids", "rids"), "simple_siamese": ("revs", "word_masks", "rev_masks", "ids")}
     MAX_POOL = 63        # one lane of a wave per table slot (csrc/review_sample.hip)
 
@@ -592,14 +663,8 @@ class DeviceReviewCache:
             raise ValueError(f"pool must be an integer in [rv_num = {R}, {self.MAX_POOL}], got {pool!r}")
         self.pool = R if pool is None else pool
         tabs = {}
-        for side, revs, rids, n, n_other in (("user", ds.user_reviews, ds.user_rids, ds.user_num, ds.item_num),
-                                             ("item", ds.item_reviews, ds.item_rids, ds.item_num, ds.user_num)):
-            tab, rid = _review_tables(revs, rids, n, self.pool + 1, self.rv_len)
-            _check_range(tab, ds.vocab_size, f"meta.pkl {side}_reviews tokens")
-            _check_range(rid, n_other, f"meta.pkl {side}_rids")
-            tab[0] = self.PAD                   # id 0 is the padding id: the row a bad id is replaced by
-            rid[0] = 0
-            wide = (tab.to(torch.int32).to(self.device), rid.to(torch.int32).to(self.device))
+        for side in ("user", "item"):
+            wide = _resident_tables(ds, side, self.pool + 1, self.rv_len, self.PAD, self.device)
             # the plain gather takes contiguous [N, R + 1, ..] tables: with a wider pool, its own copies of the leading slots
             tabs[side] = wide + (wide if self.pool == R else (wide[0][:, :R + 1].contiguous(), wide[1][:, :R + 1].contiguous()))
         (self.user_pool_table, self.user_pool_rid_table, self.user_table, self.user_rid_table) = tabs["user"]
@@ -618,14 +683,7 @@ class DeviceReviewCache:
             return RF.review_gather(u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table, self.item_rid_table,
                                     leave_one_out, self.PAD, 0, revs=revs, word_masks=word_masks, rev_masks=rev_masks, rids=rids,
                                     ids=ids)
-        got = self._gather_torch(u_ids, i_ids, leave_one_out)
-        outs = []
-        for n, (val, dst) in enumerate(zip(got, (revs, word_masks, rev_masks, rids, ids))):
-            if torch.is_tensor(dst):
-                outs.append(dst.copy_(val))
-            else:                               # revs / word_masks: None allocates; the others: True allocates, None / False omits
-                outs.append(val if dst is True or (dst is None and n < 2) else None)
-        return tuple(outs)
+        return _deliver(self._gather_torch(u_ids, i_ids, leave_one_out), (revs, word_masks, rev_masks, rids, ids), 2)
 
     def _gather_torch(self, u_ids, i_ids, leave_one_out: bool):
         u = _slots_torch(u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table.shape[0], leave_one_out)
@@ -658,13 +716,7 @@ class DeviceReviewCache:
                                            rev_masks=rev_masks, rids=rids, ids=ids, slots=slots)
         got = self._sample_gather_host(u_ids, i_ids, n_user, n_item, seed, int(state[0]))
         state[0] += 1
-        outs = []
-        for n, (val, dst) in enumerate(zip(got, (revs, word_masks, rev_masks, rids, ids, slots))):
-            if torch.is_tensor(dst):
-                outs.append(dst.copy_(val))
-            else:
-                outs.append(val if dst is True or (dst is None and n < 2) else None)
-        return tuple(outs)
+        return _deliver(got, (revs, word_masks, rev_masks, rids, ids, slots), 2)
 
     def _sample_gather_host(self, u_ids, i_ids, n_user: int, n_item: int, seed: int, call: int):
         """THE DRAW of include/rbr_hip.h (rbr_review_sample_gather) in numpy, for call number `call`."""
@@ -718,7 +770,17 @@ def _philox4x32_10(quad, call: int, seed: int):
     return c0, c1, c2, c3
 
 
-class ReviewFeed:
+class _Reseed:
+    """reseed() of a feed that draws: `seed` and `state` (int64 [2] on the feed's device, [call number, ticket])."""
+
+    def reseed(self, seed: int, call: int = 0) -> None:
+        """The next draw is call number `call` under `seed` (no host synchronisation: one small copy on the current stream).
+        A recorded step holds the seed it was recorded with: reseed it with that seed, to move the call number only."""
+        self.seed = int(seed)
+        self.state.copy_(torch.tensor([int(call), 0], dtype=torch.int64), non_blocking=True)
+
+
+class ReviewFeed(_IdFeed):
     """One model's view of a DeviceReviewCache under one rule: empty_inputs / gather / inputs with DeviceDocCache's meaning, in
     the model's own argument order --
       narre          (u_revs, i_revs, u_word_masks, i_word_masks, u_ids, i_ids, u_rids, i_rids)
@@ -730,41 +792,12 @@ class ReviewFeed:
         self.cache, self.kind, self.leave_one_out = cache, kind, bool(leave_one_out)
         self.order = cache.ORDER[kind]
         self.device = cache.device
-
-    def empty_inputs(self, B: int, with_ids: bool = True):
-        """Zeroed tensors of inputs()' shapes and dtypes for B pairs (what a recorded step lays its input block out by).
-        `with_ids` is DeviceDocCache's parameter: both review models take their ids, so it changes nothing here."""
-        R, T, dev = self.cache.rv_num, self.cache.rv_len, self.device
-        like = {"revs": ((B, R, T), torch.int64), "word_masks": ((B, R, T), torch.bool), "rev_masks": ((B, R), torch.bool),
-                "rids": ((B, R), torch.int64), "ids": ((B,), torch.int64)}
-        return tuple(torch.zeros(like[k][0], dtype=like[k][1], device=dev) for k in self.order for _ in range(2))
-
-    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None):
-        """The pairs' batch, stacked ({name: [2B, ...]} in the model's order).  `out`: the model's eight arguments to write into
-        instead, each (user, item) pair adjacent in one allocation -- the input views of a recorded step."""
-        got = self.cache.gather(u_ids, i_ids, self.leave_one_out, **self._outputs(out))
-        return dict(zip(("revs", "word_masks", "rev_masks", "rids", "ids"), got))
-
-    def _outputs(self, out):
-        """The cache's output arguments for `out`: the model's own outputs (allocated, or the stacked views of `out`), no others."""
-        if out is None:
-            kw = {k: True for k in self.order if k not in ("revs", "word_masks")}
-        else:
-            if len(out) != 2 * len(self.order):
-                raise RuntimeError(f"out must be the {2 * len(self.order)} arguments of {self.kind}")
-            kw = {k: _adjacent(out[2 * n], out[2 * n + 1]) for n, k in enumerate(self.order)}
-        for k in ("rev_masks", "rids", "ids"):
-            kw.setdefault(k, None)
-        return kw
-
-    def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
-        """The model's arguments for the pairs -- views of one gather."""
-        B = u_ids.shape[0]
-        got = self.gather(u_ids, i_ids)
-        return tuple(half for k in self.order for half in (got[k][:B], got[k][B:]))
+        R, T = cache.rv_num, cache.rv_len
+        self.like = {"revs": ((R, T), torch.int64), "word_masks": ((R, T), torch.bool), "rev_masks": ((R,), torch.bool),
+                     "rids": ((R,), torch.int64), "ids": ((), torch.int64)}
 
 
-class SampledReviewFeed(ReviewFeed):
+class SampledReviewFeed(_Reseed, ReviewFeed):
     """ReviewFeed under the train rule with the reference's review sampling (trainer/train_simple_siamese.py:346-368,
     sample_train_review): every gather keeps n_user / n_item (the reference's u_rv_num / i_rv_num; None: rv_num) of each row's
     non-empty candidate reviews, a fresh uniform random subset in random order, and pads to rv_num slots with empty reviews.  The
@@ -786,18 +819,11 @@ class SampledReviewFeed(ReviewFeed):
         self.seed = int(seed)
         self.state = torch.zeros(2, dtype=torch.int64, device=self.device)
 
-    def reseed(self, seed: int, call: int = 0) -> None:
-        """The next draw is call number `call` under `seed` (no host synchronisation: one small copy on the current stream).
-        A recorded step holds the seed it was recorded with: reseed it with that seed, to move the call number only."""
-        self.seed = int(seed)
-        self.state.copy_(torch.tensor([int(call), 0], dtype=torch.int64), non_blocking=True)
-
-    def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, out=None, slots=None):
-        """ReviewFeed.gather with the draw of the feed's next call number; `slots`: True / an int32 [2B, R] tensor for the table
-        slot behind every output slot (-1: empty)."""
-        got = self.cache.sample_gather(u_ids, i_ids, self.n_user, self.n_item, self.seed, self.state, slots=slots,
-                                       **self._outputs(out))
-        return dict(zip(("revs", "word_masks", "rev_masks", "rids", "ids", "slots"), got))
+    def _gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, slots=None, **outputs):
+        """ReviewFeed's with the draw of the feed's next call number; `slots` (gather(slots=...)): True / an int32 [2B, R] tensor for
+        the table slot behind every output slot (-1: empty)."""
+        got = self.cache.sample_gather(u_ids, i_ids, self.n_user, self.n_item, self.seed, self.state, slots=slots, **outputs)
+        return dict(zip(self.cache.NAMES + ("slots",), got))
 
 
 class DeviceSentenceCache:
@@ -813,16 +839,9 @@ class DeviceSentenceCache:
     def __init__(self, ds, device):
         self.device = torch.device(device)
         self.rv_num, self.sent_num, self.word_num = int(ds.rv_num), int(ds.sent_num), int(ds.word_num)
-        tabs = {}
-        for side, revs, rids, n, n_other in (("user", ds.user_reviews, ds.user_rids, ds.user_num, ds.item_num),
-                                             ("item", ds.item_reviews, ds.item_rids, ds.item_num, ds.user_num)):
-            tab, rid = _review_tables(revs, rids, n, self.rv_num + 1, (self.sent_num, self.word_num))
-            _check_range(tab, ds.vocab_size, f"meta.pkl {side}_reviews tokens")
-            _check_range(rid, n_other, f"meta.pkl {side}_rids")
-            tab[0] = self.PAD                   # id 0 is the padding id: the row a bad id is replaced by
-            rid[0] = 0
-            tabs[side] = (tab.to(torch.int32).to(self.device), rid.to(torch.int32).to(self.device))
-        (self.user_table, self.user_rid_table), (self.item_table, self.item_rid_table) = tabs["user"], tabs["item"]
+        (self.user_table, self.user_rid_table), (self.item_table, self.item_rid_table) = (
+            _resident_tables(ds, side, self.rv_num + 1, (self.sent_num, self.word_num), self.PAD, self.device)
+            for side in ("user", "item"))
 
     def gather(self, u_ids: torch.Tensor, i_ids: torch.Tensor, leave_one_out: bool, rids=True, ids=True, **out):
         """functional.sentence_gather over the tables: (revs, sent_lens, sent_masks, rev_masks, rids, ids), stacked, user rows first
@@ -833,16 +852,8 @@ class DeviceSentenceCache:
             from . import functional as RF
             return RF.sentence_gather(u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table, self.item_rid_table,
                                       leave_one_out, self.PAD, 0, rids=rids, ids=ids, **out)
-        got = dict(zip(self.NAMES, self._gather_torch(u_ids, i_ids, leave_one_out)))
         out.update(rids=rids, ids=ids)
-        res = []
-        for name in self.NAMES:
-            dst = out.get(name)
-            if torch.is_tensor(dst):
-                res.append(dst.copy_(got[name]))
-            else:                               # the first four: None allocates; rids / ids: True allocates, None / False omits
-                res.append(None if name in ("rids", "ids") and dst is not True else got[name])
-        return tuple(res)
+        return _deliver(self._gather_torch(u_ids, i_ids, leave_one_out), [out.get(name) for name in self.NAMES], 4)
 
     def _gather_torch(self, u_ids, i_ids, leave_one_out: bool):
         u = _slots_torch(u_ids, i_ids, self.user_table, self.user_rid_table, self.item_table.shape[0], leave_one_out)
@@ -855,32 +866,23 @@ class DeviceSentenceCache:
         return SentenceFeed(self, leave_one_out)
 
 
-class SentenceFeed:
+class SentenceFeed(_IdFeed):
     """AHN's view of a DeviceSentenceCache under one rule: the model's ten forward arguments (models/ahn/ahn_model.py) --
     (u_revs, i_revs, u_sent_masks, i_sent_masks, u_sent_lens, i_sent_lens, u_rev_masks, i_rev_masks, u_ids, i_ids)."""
 
-    ORDER = ("revs", "sent_masks", "sent_lens", "rev_masks", "ids")
+    ORDER = order = ("revs", "sent_masks", "sent_lens", "rev_masks", "ids")
+    optional = ("rids", "ids")
+    kind = "ahn"
 
     def __init__(self, cache: DeviceSentenceCache, leave_one_out: bool):
         self.cache, self.leave_one_out = cache, bool(leave_one_out)
         self.device = cache.device
-
-    def empty_inputs(self, B: int, with_ids: bool = True):
-        """Zeroed tensors of inputs()' shapes and dtypes for B pairs."""
-        c, dev = self.cache, self.device
-        R, S, W = c.rv_num, c.sent_num, c.word_num
-        like = {"revs": ((B, R, S, W), torch.int64), "sent_masks": ((B, R, S), torch.bool), "sent_lens": ((B, R, S), torch.int64),
-                "rev_masks": ((B, R), torch.bool), "ids": ((B,), torch.int64)}
-        return tuple(torch.zeros(like[k][0], dtype=like[k][1], device=dev) for k in self.ORDER for _ in range(2))
-
-    def inputs(self, u_ids: torch.Tensor, i_ids: torch.Tensor, with_ids: bool = True):
-        """The model's arguments for the pairs -- views of one gather.  `with_ids` is DeviceDocCache's parameter: AHN takes its ids."""
-        B = u_ids.shape[0]
-        got = dict(zip(self.cache.NAMES, self.cache.gather(u_ids, i_ids, self.leave_one_out, rids=False)))
-        return tuple(half for k in self.ORDER for half in (got[k][:B], got[k][B:]))
+        R, S, W = cache.rv_num, cache.sent_num, cache.word_num
+        self.like = {"revs": ((R, S, W), torch.int64), "sent_masks": ((R, S), torch.bool), "sent_lens": ((R, S), torch.int64),
+                     "rev_masks": ((R,), torch.bool), "ids": ((), torch.int64)}
 
 
-class NegativeFeed:
+class NegativeFeed(_Reseed):
     """An id feed (DeviceDocCache, ReviewFeed) behind a negative sampler, for a pairwise objective (train_step.BprObjective): a
     batch of B observed pairs becomes (1 + n_neg) * B pairs -- rows [0, B) the pairs themselves, rows [(j+1)B, (j+2)B) each
     pair's j-th negative, an item of [item_lo, n_items) its user has not rated (functional.sample_negatives; `seen`: the training
@@ -917,12 +919,6 @@ class NegativeFeed:
         self._buffers = {}
         self._last = None
         self._tables = None          # (mode, ul, il, h, g, ub, ib) of set_tables: ul / il the feed's own copies
-
-    def reseed(self, seed: int, call: int = 0) -> None:
-        """The next draw is call number `call` under `seed` (no host synchronisation: one small copy on the current stream).
-        A recorded step holds the seed it was recorded with: reseed it with that seed, to move the call number only."""
-        self.seed = int(seed)
-        self.state.copy_(torch.tensor([int(call), 0], dtype=torch.int64), non_blocking=True)
 
     def set_tables(self, mode, ul, il, h=None, g=None, ub=None, ib=None) -> None:
         """The latent tables ul [U, K] / il [n_items, K] and the head (`mode`, h, g, ub, ib: model.score_mode_and_params()) that

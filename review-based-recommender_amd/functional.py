@@ -182,6 +182,48 @@ def dedup_rows(u_ids: torch.Tensor, i_ids: torch.Tensor, user_size: int, item_si
     return first, out.view(torch.bool)
 
 
+def _pair_batch(u_ids: torch.Tensor, i_ids: torch.Tensor) -> int:
+    """B of a gather's id vectors, which must be [B] each."""
+    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
+        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
+    return u_ids.shape[0]
+
+
+def _check_review_tables(user_revs, user_rids, item_revs, item_rids, dims: str) -> None:
+    """The resident (reviews, rids) pair of both sides: reviews [U, *dims] / [I, *dims] with equal `dims` (their names for the
+    message: "R+1, T", "R+1, S, W") and at least two slots, rids [U, slots] / [I, slots]."""
+    nd = 2 + dims.count(",")
+    if user_revs.dim() != nd or item_revs.dim() != nd or user_revs.shape[1:] != item_revs.shape[1:] or user_revs.shape[1] < 2:
+        raise RuntimeError(f"review tables must be [U, {dims}] / [I, {dims}], got {tuple(user_revs.shape)} / "
+                           f"{tuple(item_revs.shape)}")
+    n = user_revs.shape[1]
+    if user_rids.shape != (user_revs.shape[0], n) or item_rids.shape != (item_revs.shape[0], n):
+        raise RuntimeError(f"rid tables must be [U, {n}] / [I, {n}], got {tuple(user_rids.shape)} / {tuple(item_rids.shape)}")
+
+
+def _gather_outputs(dev, rows: int, spec, given):
+    """The stacked outputs of a gather.  spec: (name, trailing shape, dtype, optional) per output; `given`: what the caller passed
+    for each.  A tensor is written into and must be contiguous, [rows, *trailing] and of that dtype; a required output is
+    allocated on None; an optional one is allocated on True and left out (None) on None / False."""
+    outs = []
+    for (name, tail, dtype, optional), t in zip(spec, given):
+        shape = (rows, *tail)
+        if optional and (t is None or t is False):
+            t = None
+        elif t is (True if optional else None):
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+            raise RuntimeError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}, got {t.dtype} {list(t.shape)}")
+        outs.append(t)
+    return outs
+
+
+def _review_outputs(R: int, T: int):
+    """_gather_outputs' spec of the review split's five outputs."""
+    return (("revs", (R, T), I64, False), ("word_masks", (R, T), torch.bool, False), ("rev_masks", (R,), torch.bool, True),
+            ("rids", (R,), I64, True), ("ids", (), I64, True))
+
+
 def doc_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_docs: torch.Tensor, item_docs: torch.Tensor, pad_token: int = 0,
                replace_id: int = 0, docs: Optional[torch.Tensor] = None, masks=True, ids=True):
     """The id-fed doc-split batch (rbr_doc_gather, one launch): returns (docs2 [2B, L] int64, masks2 [2B, L] bool or None,
@@ -194,26 +236,12 @@ def doc_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_docs: torch.Tensor
 
     `docs` / `masks` / `ids`: stacked output tensors to write into (a recorded step's input views), True to allocate, or
     None / False to leave out (masks / ids; D-ATT takes the documents only).  No autograd, no sync: graph-capturable."""
-    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
-        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
-    B, L = u_ids.shape[0], user_docs.shape[1]
-    if user_docs.dim() != 2 or item_docs.dim() != 2 or item_docs.shape[1] != L:
+    B = _pair_batch(u_ids, i_ids)
+    if user_docs.dim() != 2 or item_docs.dim() != 2 or item_docs.shape[1] != user_docs.shape[1]:
         raise RuntimeError(f"tables must be [U, L] / [I, L], got {tuple(user_docs.shape)} / {tuple(item_docs.shape)}")
-    dev = u_ids.device
-    if docs is None:
-        docs = torch.empty(2 * B, L, dtype=I64, device=dev)
-    if masks is True:
-        masks = torch.empty(2 * B, L, dtype=torch.bool, device=dev)
-    elif masks is False:
-        masks = None
-    if ids is True:
-        ids = torch.empty(2 * B, dtype=I64, device=dev)
-    elif ids is False:
-        ids = None
-    if docs.shape != (2 * B, L) or (masks is not None and masks.shape != (2 * B, L)) or (ids is not None and ids.shape != (2 * B,)):
-        raise RuntimeError(f"outputs must be docs [{2 * B}, {L}], masks [{2 * B}, {L}], ids [{2 * B}]")
-    if masks is not None and masks.dtype != torch.bool:
-        raise RuntimeError(f"masks must be bool, got {masks.dtype}")
+    L, dev = user_docs.shape[1], u_ids.device
+    docs, masks, ids = _gather_outputs(dev, 2 * B, (("docs", (L,), I64, False), ("masks", (L,), torch.bool, True),
+                                                    ("ids", (), I64, True)), (docs, masks, ids))
     if B == 0:
         return docs, masks, ids
     _call(None, _lib.lib().rbr_doc_gather, B, L, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),
@@ -239,26 +267,11 @@ def review_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_revs: torch.Ten
 
     `revs` / `word_masks`: stacked tensors to write into, or None to allocate; `rev_masks` / `rids` / `ids`: a stacked tensor,
     True to allocate, None / False to leave out.  No autograd, no sync: graph-capturable."""
-    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
-        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
-    if user_revs.dim() != 3 or item_revs.dim() != 3 or user_revs.shape[1:] != item_revs.shape[1:] or user_revs.shape[1] < 2:
-        raise RuntimeError(f"review tables must be [U, R+1, T] / [I, R+1, T], got {tuple(user_revs.shape)} / {tuple(item_revs.shape)}")
-    B, R, T = u_ids.shape[0], user_revs.shape[1] - 1, user_revs.shape[2]
-    if user_rids.shape != (user_revs.shape[0], R + 1) or item_rids.shape != (item_revs.shape[0], R + 1):
-        raise RuntimeError(f"rid tables must be [U, {R + 1}] / [I, {R + 1}], got {tuple(user_rids.shape)} / {tuple(item_rids.shape)}")
-    dev = u_ids.device
-    if revs is None:
-        revs = torch.empty(2 * B, R, T, dtype=I64, device=dev)
-    if word_masks is None:
-        word_masks = torch.empty(2 * B, R, T, dtype=torch.bool, device=dev)
-    rev_masks = torch.empty(2 * B, R, dtype=torch.bool, device=dev) if rev_masks is True else (None if rev_masks is False else rev_masks)
-    rids = torch.empty(2 * B, R, dtype=I64, device=dev) if rids is True else (None if rids is False else rids)
-    ids = torch.empty(2 * B, dtype=I64, device=dev) if ids is True else (None if ids is False else ids)
-    for name, t, shape, dtype in (("revs", revs, (2 * B, R, T), I64), ("word_masks", word_masks, (2 * B, R, T), torch.bool),
-                                  ("rev_masks", rev_masks, (2 * B, R), torch.bool), ("rids", rids, (2 * B, R), I64),
-                                  ("ids", ids, (2 * B,), I64)):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
-            raise RuntimeError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}, got {t.dtype} {list(t.shape)}")
+    B = _pair_batch(u_ids, i_ids)
+    _check_review_tables(user_revs, user_rids, item_revs, item_rids, "R+1, T")
+    R, T, dev = user_revs.shape[1] - 1, user_revs.shape[2], u_ids.device
+    revs, word_masks, rev_masks, rids, ids = _gather_outputs(dev, 2 * B, _review_outputs(R, T),
+                                                             (revs, word_masks, rev_masks, rids, ids))
     if B == 0:
         return revs, word_masks, rev_masks, rids, ids
     _call(None, _lib.lib().rbr_review_gather, B, R, T, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),
@@ -282,31 +295,14 @@ def sentence_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_revs: torch.T
 
     `revs` / `sent_lens` / `sent_masks` / `rev_masks`: stacked tensors to write into, or None to allocate; `rids` / `ids`: a stacked
     tensor, True to allocate, None / False to leave out.  No autograd, no sync: graph-capturable."""
-    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
-        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
-    if user_revs.dim() != 4 or item_revs.dim() != 4 or user_revs.shape[1:] != item_revs.shape[1:] or user_revs.shape[1] < 2:
-        raise RuntimeError(f"review tables must be [U, R+1, S, W] / [I, R+1, S, W], got {tuple(user_revs.shape)} / "
-                           f"{tuple(item_revs.shape)}")
-    B, R, S, W = u_ids.shape[0], user_revs.shape[1] - 1, user_revs.shape[2], user_revs.shape[3]
-    if user_rids.shape != (user_revs.shape[0], R + 1) or item_rids.shape != (item_revs.shape[0], R + 1):
-        raise RuntimeError(f"rid tables must be [U, {R + 1}] / [I, {R + 1}], got {tuple(user_rids.shape)} / {tuple(item_rids.shape)}")
+    B = _pair_batch(u_ids, i_ids)
+    _check_review_tables(user_revs, user_rids, item_revs, item_rids, "R+1, S, W")
+    R, S, W = user_revs.shape[1] - 1, user_revs.shape[2], user_revs.shape[3]
     dev = u_ids.device
-    if revs is None:
-        revs = torch.empty(2 * B, R, S, W, dtype=I64, device=dev)
-    if sent_lens is None:
-        sent_lens = torch.empty(2 * B, R, S, dtype=I64, device=dev)
-    if sent_masks is None:
-        sent_masks = torch.empty(2 * B, R, S, dtype=torch.bool, device=dev)
-    if rev_masks is None:
-        rev_masks = torch.empty(2 * B, R, dtype=torch.bool, device=dev)
-    rids = torch.empty(2 * B, R, dtype=I64, device=dev) if rids is True else (None if rids is False else rids)
-    ids = torch.empty(2 * B, dtype=I64, device=dev) if ids is True else (None if ids is False else ids)
-    for name, t, shape, dtype in (("revs", revs, (2 * B, R, S, W), I64), ("sent_lens", sent_lens, (2 * B, R, S), I64),
-                                  ("sent_masks", sent_masks, (2 * B, R, S), torch.bool),
-                                  ("rev_masks", rev_masks, (2 * B, R), torch.bool), ("rids", rids, (2 * B, R), I64),
-                                  ("ids", ids, (2 * B,), I64)):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
-            raise RuntimeError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}, got {t.dtype} {list(t.shape)}")
+    revs, sent_lens, sent_masks, rev_masks, rids, ids = _gather_outputs(
+        dev, 2 * B, (("revs", (R, S, W), I64, False), ("sent_lens", (R, S), I64, False), ("sent_masks", (R, S), torch.bool, False),
+                     ("rev_masks", (R,), torch.bool, False), ("rids", (R,), I64, True), ("ids", (), I64, True)),
+        (revs, sent_lens, sent_masks, rev_masks, rids, ids))
     if B == 0:
         return revs, sent_lens, sent_masks, rev_masks, rids, ids
     _call(None, _lib.lib().rbr_sentence_gather, B, R, S, W, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),
@@ -336,31 +332,16 @@ def review_sample_gather(u_ids: torch.Tensor, i_ids: torch.Tensor, user_revs: to
     tensors to write into or None to allocate; `rev_masks` / `rids` / `ids`: a tensor, True to allocate, None / False to leave out);
     slots2 int32 [2B, R] -- the table slot each output slot was copied from, -1 for an empty one -- under the same convention
     (default: left out).  No autograd, no sync: graph-capturable."""
-    if u_ids.dim() != 1 or u_ids.shape != i_ids.shape:
-        raise RuntimeError(f"u_ids / i_ids must be [B] each, got {tuple(u_ids.shape)} / {tuple(i_ids.shape)}")
-    if user_revs.dim() != 3 or item_revs.dim() != 3 or user_revs.shape[1:] != item_revs.shape[1:] or user_revs.shape[1] < 2:
-        raise RuntimeError(f"review tables must be [U, P+1, T] / [I, P+1, T], got {tuple(user_revs.shape)} / {tuple(item_revs.shape)}")
-    B, P, T, R = u_ids.shape[0], user_revs.shape[1] - 1, user_revs.shape[2], int(R)
-    if user_rids.shape != (user_revs.shape[0], P + 1) or item_rids.shape != (item_revs.shape[0], P + 1):
-        raise RuntimeError(f"rid tables must be [U, {P + 1}] / [I, {P + 1}], got {tuple(user_rids.shape)} / {tuple(item_rids.shape)}")
+    B = _pair_batch(u_ids, i_ids)
+    _check_review_tables(user_revs, user_rids, item_revs, item_rids, "P+1, T")
+    P, T, R = user_revs.shape[1] - 1, user_revs.shape[2], int(R)
     if state.shape != (2,) or state.dtype != I64:
         raise RuntimeError(f"state must be int64 [2], got {state.dtype} {tuple(state.shape)}")
     if R < 1:
         raise RuntimeError(f"R must be >= 1, got {R}")
     dev = u_ids.device
-    if revs is None:
-        revs = torch.empty(2 * B, R, T, dtype=I64, device=dev)
-    if word_masks is None:
-        word_masks = torch.empty(2 * B, R, T, dtype=torch.bool, device=dev)
-    rev_masks = torch.empty(2 * B, R, dtype=torch.bool, device=dev) if rev_masks is True else (None if rev_masks is False else rev_masks)
-    rids = torch.empty(2 * B, R, dtype=I64, device=dev) if rids is True else (None if rids is False else rids)
-    ids = torch.empty(2 * B, dtype=I64, device=dev) if ids is True else (None if ids is False else ids)
-    slots = torch.empty(2 * B, R, dtype=I32, device=dev) if slots is True else (None if slots is False else slots)
-    for name, t, shape, dtype in (("revs", revs, (2 * B, R, T), I64), ("word_masks", word_masks, (2 * B, R, T), torch.bool),
-                                  ("rev_masks", rev_masks, (2 * B, R), torch.bool), ("rids", rids, (2 * B, R), I64),
-                                  ("ids", ids, (2 * B,), I64), ("slots", slots, (2 * B, R), I32)):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous()):
-            raise RuntimeError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)}, got {t.dtype} {list(t.shape)}")
+    revs, word_masks, rev_masks, rids, ids, slots = _gather_outputs(
+        dev, 2 * B, _review_outputs(R, T) + (("slots", (R,), I32, True),), (revs, word_masks, rev_masks, rids, ids, slots))
     if B == 0:
         return revs, word_masks, rev_masks, rids, ids, slots
     _call(None, _lib.lib().rbr_review_sample_gather, B, R, T, P, dev_ptr(u_ids, I64, "u_ids"), dev_ptr(i_ids, I64, "i_ids"),

@@ -474,6 +474,50 @@ def _flat_views(flat: torch.Tensor, layout, like):
     return [flat[o:o + t.numel() * t.element_size()].view(t.dtype).view(t.shape) for o, t in zip(layout, like)]
 
 
+class _InputBlock:
+    """`tensors` in ONE block: `flat` (uint8, _flat_layout) and `views` of it with the tensors' shapes and dtypes, initialised from
+    them -- so a loader hands a batch over with a single copy, and the two towers' inputs are neighbours that the models stack
+    as a view.  `mismatch`: the error text for a packed block of another layout."""
+    __slots__ = ("layout", "flat", "views", "mismatch")
+
+    def __init__(self, tensors, device, mismatch: str):
+        tensors = list(tensors)
+        self.layout, self.mismatch = _flat_layout(tensors), mismatch
+        self.flat = torch.empty(self.layout[-1], dtype=torch.uint8, device=device)
+        self.views = tuple(_flat_views(self.flat, self.layout, tensors))
+        for v, src in zip(self.views, tensors):
+            v.copy_(src)
+
+    def matches(self, batch) -> bool:
+        """True when `batch` has the views' shapes and dtypes."""
+        return len(batch) == len(self.views) and all(a.shape == b.shape and a.dtype == b.dtype for a, b in zip(batch, self.views))
+
+    def pack(self, tensors, device=None) -> torch.Tensor:
+        """`tensors` as one block of this layout, on the block's device (or on `device`)."""
+        tensors = list(tensors)
+        blob = torch.empty(self.flat.shape, dtype=torch.uint8, device=device or self.flat.device)
+        for v, src in zip(_flat_views(blob, self.layout, tensors), tensors):
+            v.copy_(src)
+        return blob
+
+    def load(self, tensors=None, packed: torch.Tensor | None = None, pack_on_host: bool = False) -> None:
+        """Copies into the block on the current stream: `packed` (pack()'s blob) with one copy; `tensors` (one per view, None: leave
+        that view) with one copy per tensor that is not already its view -- or, with pack_on_host and all of them in host memory,
+        packed there and sent with ONE host-to-device copy."""
+        if packed is not None:
+            if packed.shape != self.flat.shape or packed.dtype != torch.uint8:
+                raise RuntimeError(self.mismatch)
+            self.flat.copy_(packed, non_blocking=True)
+        if tensors is None:
+            return
+        if pack_on_host and all(t is not None and not t.is_cuda for t in tensors):
+            self.flat.copy_(self.pack(tensors, "cpu"), non_blocking=True)
+            return
+        for dst, src in zip(self.views, tensors):
+            if src is not None and dst is not src:
+                dst.copy_(src, non_blocking=True)
+
+
 def _lib_mod():
     from . import _lib
     return _lib
@@ -506,20 +550,14 @@ class GraphedForward:
             raise RuntimeError("GraphedForward needs HIP tensors")
         self.model = model
         self._feed, self._with_ids = feed, with_ids
+        mismatch = "packed batch does not match the forward's input layout (use GraphedForward.pack)"
+        # `_staged` is the block a caller's batch is copied into: the model's inputs, or with a feed the (u_ids, i_ids) block
+        self._staged = block = _InputBlock(batch, batch[0].device, mismatch)
         self.ids = None
         if feed is not None:
-            self._id_layout = _flat_layout(batch)
-            self._id_flat = torch.empty(self._id_layout[-1], dtype=torch.uint8, device=batch[0].device)
-            self.ids = tuple(_flat_views(self._id_flat, self._id_layout, batch))
-            for v, src in zip(self.ids, batch):
-                v.copy_(src)
-            batch = list(feed.empty_inputs(batch[0].shape[0], with_ids))
-        self._layout = _flat_layout(batch)
-        self._flat = torch.empty(self._layout[-1], dtype=torch.uint8, device=batch[0].device)
-        views = _flat_views(self._flat, self._layout, batch)
-        for v, src in zip(views, batch):
-            v.copy_(src)
-        self.batch = tuple(views)
+            self.ids = block.views
+            block = _InputBlock(feed.empty_inputs(batch[0].shape[0], with_ids), batch[0].device, mismatch)
+        self.batch = block.views
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.no_grad():      # warm-up off the default stream (allocator, lazy module state)
@@ -546,33 +584,19 @@ class GraphedForward:
         if self._feed is not None:
             self._feed.gather(self.ids[0], self.ids[1], out=self.batch)
 
-    def _inputs(self):
-        return (self.ids, self._id_flat, self._id_layout) if self._feed is not None else (self.batch, self._flat, self._layout)
-
     def matches(self, batch) -> bool:
         """True when `batch` has the shapes and dtypes the graph was recorded with (a ragged last batch does not)."""
-        ref = self._inputs()[0]
-        return len(batch) == len(ref) and all(a.shape == b.shape and a.dtype == b.dtype for a, b in zip(batch, ref))
+        return self._staged.matches(batch)
 
     def pack(self, batch) -> torch.Tensor:
-        _, flat, layout = self._inputs()
-        blob = torch.empty_like(flat)
-        for v, src in zip(_flat_views(blob, layout, list(batch)), batch):
-            v.copy_(src)
-        return blob
+        return self._staged.pack(batch)
 
     def __call__(self, batch=None, packed: torch.Tensor | None = None) -> torch.Tensor:
-        dsts, flat, _ = self._inputs()
-        if packed is not None:
-            if packed.shape != flat.shape or packed.dtype != torch.uint8:
-                raise RuntimeError("packed batch does not match the forward's input layout (use GraphedForward.pack)")
-            flat.copy_(packed, non_blocking=True)
+        self._staged.load(packed=packed)
         if batch is not None:
             if not self.matches(batch):
                 raise RuntimeError("batch shapes differ from the recorded forward's (run ragged batches eagerly)")
-            for dst, src in zip(dsts, batch):
-                if dst is not src:
-                    dst.copy_(src, non_blocking=True)
+            self._staged.load(batch)
         self.graph.replay()
         return self.pred
 
@@ -598,8 +622,9 @@ def _count_kernel_nodes(graph: torch.cuda.CUDAGraph) -> int:
 
 
 class _StepSlot:
-    """One input block of a GraphedTrainStep and the graph(s) recorded over it."""
-    __slots__ = ("flat", "batch", "ratings", "ids", "id_flat", "g_fwd_bwd", "g_update", "static_grads", "loss", "gnorm", "pred")
+    """One input slot of a GraphedTrainStep -- `block`: the model's inputs, `staged`: the block a loader writes (the same one, or
+    with a feed the id block) -- and the graph(s) recorded over it."""
+    __slots__ = ("block", "staged", "batch", "ratings", "ids", "g_fwd_bwd", "g_update", "static_grads", "loss", "gnorm", "pred")
 
 
 class GraphedTrainStep:
@@ -641,33 +666,19 @@ class GraphedTrainStep:
         self.model, self.optimizer, self.grad_sync, self.max_grad_norm = model, optimizer, grad_sync, max_grad_norm
         self._keep_graph = bool(keep_graph)      # keeps the hipGraph_t behind the executable: kernel_launches() can count its nodes
         self._feed, self._with_ids = feed, with_ids
-        id_block = None
-        if feed is not None:          # the loader's block is (u_ids, i_ids, ratings); the documents are gathered on the device
-            id_block = list(batch) + [ratings]
-            self._id_layout = _flat_layout(id_block)
-            inputs = list(feed.empty_inputs(batch[0].shape[0], with_ids))
-        else:
-            inputs = list(batch) + [ratings]
-        # every input of the step lives in ONE block (`flat`): a loader hands over a batch with a single device-to-device
-        # (or host-to-device) copy, and the two towers' inputs are neighbours, so the models stack them as a view
-        self._layout = _flat_layout(inputs)
         self._slots = []
         for _ in range(slots):
+            # what a loader stages -- the batch and its ratings -- lives in ONE block; with a feed that is (u_ids, i_ids, ratings),
+            # and the documents are gathered on the device into a block of their own
             sl = _StepSlot()
-            sl.flat = torch.empty(self._layout[-1], dtype=torch.uint8, device=ratings.device)
-            views = _flat_views(sl.flat, self._layout, inputs)
-            for v, src in zip(views, inputs):
-                v.copy_(src)
-            if id_block is None:
-                sl.batch, sl.ratings = tuple(views[:-1]), views[-1]
-                sl.ids = sl.id_flat = None
-            else:
-                sl.batch = tuple(views)
-                sl.id_flat = torch.empty(self._id_layout[-1], dtype=torch.uint8, device=ratings.device)
-                idv = _flat_views(sl.id_flat, self._id_layout, id_block)
-                for v, src in zip(idv, id_block):
-                    v.copy_(src)
-                sl.ids, sl.ratings = tuple(idv[:-1]), idv[-1]
+            sl.staged = sl.block = _InputBlock(list(batch) + [ratings], ratings.device, "packed batch does not match the step's "
+                                               "input layout (use GraphedTrainStep.pack)" if feed is None else
+                                               "packed ids do not match the step's id block (use GraphedTrainStep.pack)")
+            sl.batch, sl.ratings, sl.ids = sl.staged.views[:-1], sl.staged.views[-1], None
+            if feed is not None:
+                sl.ids = sl.batch
+                sl.block = _InputBlock(feed.empty_inputs(batch[0].shape[0], with_ids), ratings.device, sl.staged.mismatch)
+                sl.batch = sl.block.views
             sl.g_update = sl.static_grads = None
             self._slots.append(sl)
         first = self._slots[0]
@@ -751,7 +762,7 @@ class GraphedTrainStep:
     pred = property(lambda self: self._slots[0].pred)
     g_fwd_bwd = property(lambda self: self._slots[0].g_fwd_bwd)
     g_update = property(lambda self: self._slots[0].g_update)
-    _flat = property(lambda self: self._slots[0].flat)
+    _flat = property(lambda self: self._slots[0].block.flat)
 
     @property
     def slots(self) -> int:
@@ -769,10 +780,8 @@ class GraphedTrainStep:
     def slot_inputs(self, slot: int = 0):
         """(batch views, ratings view, the whole block as uint8) of input slot `slot`: what a loader writes into.  With an id
         feed: ((u_ids, i_ids) views, ratings view, the id block) -- slot_batch() has the gathered documents."""
-        sl = self._slots[slot]
-        if self._feed is not None:
-            return sl.ids, sl.ratings, sl.id_flat
-        return sl.batch, sl.ratings, sl.flat
+        st = self._slots[slot].staged
+        return st.views[:-1], st.views[-1], st.flat
 
     def slot_batch(self, slot: int = 0):
         """The model's input views of slot `slot` (with an id feed: what the recorded gather writes)."""
@@ -781,47 +790,16 @@ class GraphedTrainStep:
     def pack(self, batch, ratings: torch.Tensor) -> torch.Tensor:
         """`batch` + `ratings` as one block in the layout of the step's input buffers (what a loader would stage on the
         device); hand it to __call__(packed=...).  With an id feed `batch` is (u_ids, i_ids) and the block is the id block."""
-        flat, layout = (self._slots[0].id_flat, self._id_layout) if self._feed is not None else (self._slots[0].flat, self._layout)
-        blob = torch.empty_like(flat)
-        for v, src in zip(_flat_views(blob, layout, list(batch) + [ratings]), list(batch) + [ratings]):
-            v.copy_(src)
-        return blob
+        return self._slots[0].staged.pack(list(batch) + [ratings])
 
     def stage(self, slot: int, batch=None, ratings: torch.Tensor | None = None, packed: torch.Tensor | None = None) -> None:
         """Copies a batch into input slot `slot` on the current stream (no replay).  With an id feed `batch` is (u_ids, i_ids):
         host tensors together with host ratings go over in ONE host-to-device copy of the id block."""
-        sl = self._slots[slot]
-        if self._feed is not None:
-            return self._stage_ids(sl, batch, ratings, packed)
-        if packed is not None:
-            if packed.shape != sl.flat.shape or packed.dtype != torch.uint8:
-                raise RuntimeError("packed batch does not match the step's input layout (use GraphedTrainStep.pack)")
-            sl.flat.copy_(packed, non_blocking=True)      # one copy launch for all inputs
-        if batch is not None:
-            for dst, src in zip(sl.batch, batch):
-                if dst is not src:
-                    dst.copy_(src, non_blocking=True)
-        if ratings is not None and ratings is not sl.ratings:
-            sl.ratings.copy_(ratings, non_blocking=True)
-
-    def _stage_ids(self, sl, batch, ratings, packed) -> None:
-        if packed is not None:
-            if packed.shape != sl.id_flat.shape or packed.dtype != torch.uint8:
-                raise RuntimeError("packed ids do not match the step's id block (use GraphedTrainStep.pack)")
-            sl.id_flat.copy_(packed, non_blocking=True)
-        if batch is not None and ratings is not None and not ratings.is_cuda and not any(t.is_cuda for t in batch):
-            blob = torch.empty(sl.id_flat.shape, dtype=torch.uint8)       # packed on the host: one copy
-            srcs = list(batch) + [ratings]
-            for v, src in zip(_flat_views(blob, self._id_layout, srcs), srcs):
-                v.copy_(src)
-            sl.id_flat.copy_(blob, non_blocking=True)
-            return
-        if batch is not None:
-            for dst, src in zip(sl.ids, batch):
-                if dst is not src:
-                    dst.copy_(src, non_blocking=True)
-        if ratings is not None and ratings is not sl.ratings:
-            sl.ratings.copy_(ratings, non_blocking=True)
+        st = self._slots[slot].staged
+        tensors = None
+        if batch is not None or ratings is not None:
+            tensors = (list(batch) if batch is not None else [None] * (len(st.views) - 1)) + [ratings]
+        st.load(tensors, packed, pack_on_host=self._feed is not None)
 
     def __call__(self, batch=None, ratings: torch.Tensor | None = None, packed: torch.Tensor | None = None, slot: int = 0):
         """Runs one step on `batch` / `packed` (None: the batch already in the slot's input block).  Returns the slot's

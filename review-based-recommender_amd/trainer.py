@@ -359,18 +359,25 @@ class ReviewExperiment:
         self.best_rmse = 1e3
         self.patience = 0
         self.grad_sync = None
+        self._graphed_eval = None            # the recorded eval forward; False once the runtime has refused its capture
+        self._towers = None                  # the one Recommender (_negative_towers)
+        self._seen = None                    # the training split's seen-items CSR
+        self._table_bytes_logged = False
+        self.last_rank_metrics = None
 
         review_split = kind in ("narre", "simple_siamese", "ahn")
         cls = D.SentenceDataset if kind == "ahn" else D.ReviewDataset if review_split else D.DocDataset
-        kw = {} if review_split else {"with_ids": kind == "deepconn"}
-        if args.device_cache or args.device_reviews:
-            kw["feed"] = "ids"
-        self.train_set = cls(args.data_dir, "train", **kw)
-        self.valid_set = cls(args.data_dir, "valid", **kw)
+        form = () if review_split else (kind == "deepconn",)      # DocDataset: do the loader's batches carry the ids (D-ATT's do not)
+        kw = {"feed": "ids"} if args.device_cache or args.device_reviews else {}
+        self.train_set = cls(args.data_dir, "train", *form, **kw)
+        self.valid_set = cls(args.data_dir, "valid", *form, **kw)
         # device_cache: meta.pkl's documents resident on this GPU (train and valid share meta.pkl, so one cache serves both)
-        self.cache = D.DeviceDocCache(self.train_set, self.device) if args.device_cache else None
-        self.train_feed = self.eval_feed = self.cache     # what rebuilds a batch from its ids
-        if args.device_reviews and kind == "ahn":
+        self.cache = self.train_feed = self.eval_feed = None
+        if args.device_cache:
+            self.cache = D.DeviceDocCache(self.train_set, self.device)
+            # what rebuilds a batch from its ids, in the model's form: D-ATT takes the documents only
+            self.train_feed = self.eval_feed = self.cache.feed(kind != "dual_att")
+        elif args.device_reviews and kind == "ahn":
             # the sentence split's reviews resident on this GPU: the same two rules, lengths and masks made by the same launch
             self.cache = D.DeviceSentenceCache(self.train_set, self.device)
             self.train_feed, self.eval_feed = self.cache.feed(True), self.cache.feed(False)
@@ -569,20 +576,27 @@ class ReviewExperiment:
         loss, gnorm, _ = self._graphed(slot=0)
         return loss.clone(), gnorm.clone(), self._graphed.ratings
 
+    def _replay(self, key, record, *batch):
+        """`fast_step`: the step recorded for the batch shape `key` replayed on `batch` -- record() makes it at first use --, as
+        (loss, gnorm) copies (the graph's outputs are overwritten by the next replay); None: a batch of another shape (the
+        ragged last one), or graphs are off, and the caller steps eagerly."""
+        if not self._record:
+            return None
+        if self._graphed is None:
+            self._graphed, self._graphed_key = record(), key
+        if key != self._graphed_key:
+            return None
+        loss, gnorm, _ = self._graphed(*batch)
+        return loss.clone(), gnorm.clone()
+
     def _step(self, inputs, ratings):
         """One optimisation step; with `fast_step` the step recorded for this batch shape is replayed (a ragged last
         batch, or a batch of another shape, runs eagerly)."""
         a = self.args
-        if self._record:
-            key = tuple((t.shape, t.dtype) for t in inputs) + ((ratings.shape, ratings.dtype),)
-            if self._graphed is None:
-                self._graphed = GraphedTrainStep(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync)
-                self._graphed_key = key
-            if key == self._graphed_key:
-                loss, gnorm, _ = self._graphed(inputs, ratings)
-                return loss.clone(), gnorm.clone()          # the graph's outputs are overwritten by the next replay
-        loss, gnorm, _ = train_step(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync)
-        return loss, gnorm
+        key = tuple((t.shape, t.dtype) for t in inputs) + ((ratings.shape, ratings.dtype),)
+        done = self._replay(key, lambda: GraphedTrainStep(self.model, self.optimizer, inputs, ratings, a.max_grad_norm,
+                                                          self.grad_sync), inputs, ratings)
+        return done or train_step(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync)[:2]
 
     def _id_step(self, batch):
         """device_cache / device_reviews: one step on a (u_ids, i_ids, ratings) batch.  With `fast_step` the id-fed step recorded
@@ -590,64 +604,44 @@ class ReviewExperiment:
         eagerly and train_step runs on them."""
         a = self.args
         u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
-        with_ids = self.kind != "dual_att"
-        if self._record:
-            key = tuple((t.shape, t.dtype) for t in batch)
-            if self._graphed is None:
-                # recording runs warm-up steps: they must not use up the draws of the negative sampler or the review sampler
-                states = _feed_states(self.train_feed)
-                calls = [t.clone() for t in states]
-                self._graphed = GraphedTrainStep.from_ids(self.model, self.optimizer, self.train_feed, u_ids, i_ids, ratings,
-                                                          a.max_grad_norm, self.grad_sync, with_ids=with_ids,
-                                                          objective=self.objective)
-                for t, c in zip(states, calls):
-                    t.copy_(c)
-                self._graphed_key = key
-            if key == self._graphed_key:
-                loss, gnorm, _ = self._graphed((u_ids, i_ids), ratings)
-                return loss.clone(), gnorm.clone(), ratings
-        inputs = self.train_feed.inputs(u_ids, i_ids, with_ids=with_ids)
-        loss, gnorm, _ = train_step(self.model, self.optimizer, inputs, ratings, a.max_grad_norm, self.grad_sync,
-                                    objective=self.objective)
-        return loss, gnorm, ratings
 
-    def _eval_forward_ids(self, u_ids, i_ids):
-        """device_cache / device_reviews: the eval forward of an id batch -- gather + forward replayed from a hipGraph for the
-        loader's regular batch shape with `fast_step`, eager otherwise."""
-        with_ids = self.kind != "dual_att"
-        if self._record:
-            g = getattr(self, "_graphed_eval", None)
-            if g is None:
-                try:
-                    g = self._graphed_eval = GraphedForward.from_ids(self.model, self.eval_feed, u_ids, i_ids, with_ids=with_ids)
-                except Exception as e:          # a capture the runtime refuses costs the speed-up, not the validation
-                    self.print_write_to_log(f"eval forward not graphed ({type(e).__name__}: {str(e)[:100]})")
-                    g = self._graphed_eval = False
-            if g and g.matches((u_ids, i_ids)):
-                return g((u_ids, i_ids))
-        out = self.model(*self.eval_feed.inputs(u_ids, i_ids, with_ids=with_ids))
-        return out[0] if isinstance(out, tuple) else out
+        def record():
+            # recording runs warm-up steps: they must not use up the draws of the negative sampler or the review sampler
+            states = _feed_states(self.train_feed)
+            calls = [t.clone() for t in states]
+            graphed = GraphedTrainStep.from_ids(self.model, self.optimizer, self.train_feed, u_ids, i_ids, ratings,
+                                                a.max_grad_norm, self.grad_sync, objective=self.objective)
+            for t, c in zip(states, calls):
+                t.copy_(c)
+            return graphed
 
-    def _eval_forward(self, inputs):
-        """The eval forward: replayed from a hipGraph for the loader's regular batch shape (recorded at first use; the
-        parameters are read in place, so training steps in between need no re-recording), eager for any other shape
+        done = self._replay(tuple((t.shape, t.dtype) for t in batch), record, (u_ids, i_ids), ratings)
+        if done is None:
+            done = train_step(self.model, self.optimizer, self.train_feed.inputs(u_ids, i_ids), ratings, a.max_grad_norm,
+                              self.grad_sync, objective=self.objective)[:2]
+        return (*done, ratings)
+
+    def _eval_forward(self, inputs, feed=None):
+        """The eval forward of `inputs` -- the model's arguments, or with `feed` (device_cache / device_reviews) the batch's
+        (u_ids, i_ids), gathered in front of it: replayed from a hipGraph for the loader's regular batch shape (recorded at first
+        use; the parameters are read in place, so training steps in between need no re-recording), eager for any other shape
         (the ragged last batch) and when graphs are off."""
         if self._record and inputs and inputs[0].is_cuda:
-            g = getattr(self, "_graphed_eval", None)
+            g = self._graphed_eval
             if g is None:
                 try:
-                    g = self._graphed_eval = GraphedForward(self.model, inputs)
+                    g = self._graphed_eval = GraphedForward(self.model, inputs, feed=feed)
                 except Exception as e:          # a capture the runtime refuses costs the speed-up, not the validation
                     self.print_write_to_log(f"eval forward not graphed ({type(e).__name__}: {str(e)[:100]})")
                     g = self._graphed_eval = False
             if g and g.matches(inputs):
                 return g(inputs)
-        out = self.model(*inputs)
+        out = self.model(*(inputs if feed is None else feed.inputs(*inputs)))
         return out[0] if isinstance(out, tuple) else out
 
     def _negative_towers(self):
         """The one Recommender of this experiment: the validation's latent tables, and with neg_candidates > 1 the sampler's."""
-        if getattr(self, "_towers", None) is None:
+        if self._towers is None:
             from .recommend import AhnRecommender, Recommender
             # AHN (ahn_tables): per-id sentence tables and the fused pair tail speak the same protocol
             self._towers = (AhnRecommender if self.kind == "ahn" else Recommender)(self.model, self.cache)
@@ -676,7 +670,7 @@ class ReviewExperiment:
             # pair is two row gathers and the head's arithmetic instead of two document encodes (recommend.Recommender)
             towers = self._negative_towers()
             towers.refresh()
-            if self.kind == "ahn" and not getattr(self, "_table_bytes_logged", False):
+            if self.kind == "ahn" and not self._table_bytes_logged:
                 self._table_bytes_logged = True      # ahn_tables is a memory opt-in: say once what it costs
                 nbytes = sum(t.numel() * t.element_size() for st in (towers.user_state, towers.item_state) for t in st)
                 self.print_write_to_log("ahn_tables: {:,d} bytes of per-id sentence tables ({} users, {} items)".format(
@@ -684,7 +678,7 @@ class ReviewExperiment:
             if self.args.neg_candidates > 1:
                 self._hand_tables_to_feed(towers)          # the next epoch's candidates are scored from this pass's tables
         ranks = []
-        if self.args.rank_metrics and getattr(self, "_seen", None) is None:
+        if self.args.rank_metrics and self._seen is None:
             # what a validation item competes against: every item its user has not rated in the training split
             self._seen = towers.seen_from(self.train_set.examples, towers.n_users, self.device)
         with torch.no_grad():
@@ -696,7 +690,7 @@ class ReviewExperiment:
                         ranks.append(towers.rank(u_ids, i_ids, exclude=self._seen))
                 elif self.cache is not None:
                     u_ids, i_ids, ratings = [t.to(self.device, non_blocking=True) for t in batch]
-                    pred = self._eval_forward_ids(u_ids, i_ids)
+                    pred = self._eval_forward((u_ids, i_ids), self.eval_feed)
                 else:
                     inputs, ratings = self._to_device(batch)
                     pred = self._eval_forward(inputs)
@@ -715,12 +709,8 @@ class ReviewExperiment:
         RF.check_id_errors(self.device)
         if self.select_metric is not None:
             self.best_rmse = min(self.best_rmse, rmse)        # reported; the model is selected below, by its rank metric
-        elif rmse < self.best_rmse:
-            self.best_rmse = rmse
-            self.save("best_model.pt")
-            self.patience = 0
         else:
-            self.patience += 1
+            self.best_rmse = -self._selected(-rmse, -self.best_rmse)      # lower is better: selected by its negative
         self.print_write_to_log("valid loss: {:.3f}, valid rmse: {:.3f}, best rmse: {:.3f}".format(
             float(loss_sum) / max(steps, 1), rmse, self.best_rmse))
         if ranks:
@@ -730,17 +720,21 @@ class ReviewExperiment:
             keys = [f"{name}@{k}" for k in self.args.rank_metrics for name in ("hr", "ndcg")] + ["mrr"]
             line = "valid " + ", ".join("{}: {:.3f}".format(k, m[k]) for k in keys)
             if self.select_metric is not None:
-                score = m[self.select_metric]
-                if score is not None and score > self.best_score:
-                    self.best_score = score
-                    self.save("best_model.pt")
-                    self.patience = 0
-                else:
-                    self.patience += 1
+                self.best_score = self._selected(m[self.select_metric], self.best_score)
                 line += ", best {}: {:.3f}".format(self.select_metric, self.best_score)
             self.print_write_to_log(line)
         if self.patience >= self.args.patience:
             raise EarlyStop("early stop")
+
+    def _selected(self, score, best):
+        """Model selection by a score where higher is better: a `score` above `best` saves best_model.pt and resets the patience;
+        anything else (None: the metric had no pair to rank) uses one up.  Returns the best score so far."""
+        if score is not None and score > best:
+            self.save("best_model.pt")
+            self.patience = 0
+            return score
+        self.patience += 1
+        return best
 
     def train(self):
         self.print_write_to_log("start training ...")

@@ -190,6 +190,35 @@ def test_sentence_gather_refuses_bad_arguments():
         RF.sentence_gather(u, i, cache.user_table, cache.user_rid_table, cache.item_table, cache.item_rid_table, True, 0, 7)
 
 
+@pytest.mark.parametrize("W", [5, 8])                            # one word per unit; four words (16 bytes) per unit
+@pytest.mark.parametrize("loo", [True, False])
+def test_feed_gathers_into_the_views_of_an_input_block(W, loo):
+    """SentenceFeed.gather(out=...) -- the feed protocol's form for a recorded step: the ten views of a block laid out by
+    empty_inputs(B) receive what inputs() returns, the bytes of the block outside the views keep their 0xA5, rids are not made."""
+    from review_based_recommender_amd.train_step import _flat_layout, _flat_views
+    B, R, S = 3, 2, 3
+    cache, _, train, valid = _split(R, S, W, 30)
+    feed = cache.feed(loo)
+    want = _collate((train if loo else valid)[:B], R, S, W)
+    like = list(feed.empty_inputs(B))
+    layout, guard = _flat_layout(like), 256
+    flat = torch.full((layout[-1] + 2 * guard,), 0xA5, dtype=torch.uint8, device=DEV)
+    views = _flat_views(flat[guard:guard + layout[-1]], layout, like)
+    assert len(views) == 10 and views[0].data_ptr() % 16 == 0
+    got = feed.gather(want["u_ids"], want["i_ids"], out=views)
+    torch.cuda.synchronize()
+    assert got["rids"] is None and got["revs"].data_ptr() == views[0].data_ptr()
+    args = feed.inputs(want["u_ids"], want["i_ids"])
+    assert len(args) == 10
+    for k, (v, a) in enumerate(zip(views, args)):
+        assert v.dtype == a.dtype and v.shape == a.shape and torch.equal(v, a), k
+        assert torch.equal(v.cpu(), want[feed.order[k // 2]][(k % 2) * B:(k % 2 + 1) * B]), k
+    covered = torch.zeros(flat.numel(), dtype=torch.bool)
+    for o, t in zip(layout, like):
+        covered[guard + o:guard + o + t.numel() * t.element_size()] = True
+    assert not bool(covered.all()) and bool((flat.cpu()[~covered] == 0xA5).all())
+
+
 # ------------------------------------------------------------------------------------------------ 2. trainer
 def _cfg(tmp_path, data_dir, tag, **extra):
     cfg = {"data_dir": data_dir, "dataset": "synthetic", "log_dir": str(tmp_path / "logs"), "log": True, "log_idx": 2,

@@ -222,6 +222,32 @@ def test_cpu_cache_gather_equals_the_examples_collate(split, set_name):
         cache.gather(torch.tensor([1]), torch.tensor([-1]), loo)
 
 
+@pytest.mark.parametrize("set_name", ["train", "valid"])
+def test_cpu_feed_gathers_into_the_views_of_an_input_block(split, set_name):
+    """SentenceFeed.gather(out=...): the ten views of a block laid out by empty_inputs(B) receive what inputs() returns, the bytes
+    of the block outside the views keep their 0xA5, rids are not made."""
+    from review_based_recommender_amd import data as D
+    from review_based_recommender_amd.train_step import _flat_layout, _flat_views
+    d, _ = split
+    ds = D.SentenceDataset(d, set_name)
+    feed = D.DeviceSentenceCache(ds, "cpu").feed(set_name == "train")
+    b = ds.collate_fn([ds[k] for k in range(5)])
+    like = list(feed.empty_inputs(5))
+    layout = _flat_layout(like)
+    flat = torch.full((layout[-1],), 0xA5, dtype=torch.uint8)
+    views = _flat_views(flat, layout, like)
+    got = feed.gather(b[2], b[3], out=views)
+    assert got["rids"] is None and got["revs"].data_ptr() == views[0].data_ptr()
+    args = feed.inputs(b[2], b[3])
+    assert len(views) == len(args) == 10 and torch.equal(args[0], b[0]) and torch.equal(args[1], b[1])
+    for k, (v, a) in enumerate(zip(views, args)):
+        assert v.dtype == a.dtype and v.shape == a.shape and torch.equal(v, a), k
+    covered = torch.zeros(flat.numel(), dtype=torch.bool)
+    for o, t in zip(layout, like):
+        covered[o:o + t.numel() * t.element_size()] = True
+    assert not bool(covered.all()) and bool((flat[~covered] == 0xA5).all())
+
+
 def test_sentence_masks_count_words_wherever_they_stand():
     from review_based_recommender_amd import data as D
     revs = torch.tensor([[[[0, 5, 0, 7], [0, 0, 0, 0], [9, 0, 0, 0]], [[0, 0, 0, 0]] * 3]])
